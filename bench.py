@@ -9,7 +9,12 @@ ComputeFlow over the whole pyramid (40 levels x (40 x (phi/ksi + 5 sweeps)) + wa
 The reference's own timer sits before the upload and after the download (optical_flow_e.cpp:169,579); that rate is
 reported beside it as `host_inclusive` (page-locked host volumes -> H2D -> solve -> D2H) and is never `value`.
 
-One JSON line on stdout carries the metric plus
+A plain run sets up, warms up, times `--steps` solves and prints one JSON line on stdout with the metric (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall milliseconds of one timed step, ...).  `--dump-outputs DIR` then also
+writes the (u, v, w) of the last timed step to DIR/*.npy (float32; a fixed seeded sample of the voxels of a large volume, the
+flat indices in DIR/sample_index.npy); the inputs are the same on every run with the same arguments, so two builds can be
+compared output for output.  With `--full` the line also carries `parity` (the result
+against the committed digest), `host_inclusive` and
   roofline     : the dominant kernel (the fused pair of solver sweeps, 2 x 52 algorithmic B/voxel) timed live with HIP
                  events on the library stream over the timed region, against the 8 TB/s HBM peak; `traffic` is the HBM
                  byte count of one finest-level launch from the committed PMC passes (omitted when they were collected on
@@ -21,11 +26,12 @@ One JSON line on stdout carries the metric plus
   cpu_baseline : the same numerics (the oracle, a scalar-per-voxel C port with OpenMP over planes) run on the box's own
                  host cores on BASELINE config 2 (128^3, full default pyramid), timed fully.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--no-cpu] [--no-extra]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--dump-outputs DIR] [--full [--no-cpu] [--no-extra]]
 For N > 1 the SAME volume (512^3 by default, like N = 1: one size per sweep) is z-slab partitioned over one rank per GPU; the line
-then carries both exchange orders timed in this one invocation (`exchange_orders`; `value` = the faster), the measured microseconds
-per exchange (`exchange_us`), the unsplit single-GPU solve of the same volume on rank 0's device (`single_gpu_same_size`) and the
-`speedup` over it, and -- unless --no-config5 / --no-extra -- the same record for BASELINE config 5 (1024^3) under `config5`.  Two ways
+then carries both exchange orders timed in this one invocation (`exchange_orders`; `value` = the faster) and, with --full, the
+measured microseconds per exchange (`exchange_us`), the unsplit single-GPU solve of the same volume on rank 0's device
+(`single_gpu_same_size`) and the `speedup` over it, and -- unless --no-config5 / --no-extra -- the same record for BASELINE config 5
+(1024^3) under `config5`.  Two ways
 in: under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` (RANK / WORLD_SIZE in the environment), or
 bare -- `python bench.py --gpus N` starts the N rank processes itself (launch_ranks: the parent never loads the native
 library or touches the GPU, forwards rank 0's JSON line, and exits non-zero if any rank fails or hangs).
@@ -301,6 +307,47 @@ def parity_record(size, digest):
             "digest": digest, "golden": want, "match": (digest == want) if want else None}
 
 
+DUMP_MAX_WHOLE = 4 << 20     # voxels per component written whole (3 x 16 MB of float32)
+DUMP_SAMPLE = 2 << 20        # voxels per component in the fixed sample of a larger volume (3 x 8 MB + 16 MB of indices)
+DUMP_SEED = 20240607
+
+
+def dump_sample_index(shape):
+    """the flat (z, y, x) indices of the voxels written for a volume of `shape`: all of them up to DUMP_MAX_WHOLE voxels,
+    otherwise DUMP_SAMPLE distinct ones drawn with a fixed seed, ascending -- the same set for every run of the same size"""
+    import numpy as np
+    total = int(np.prod(shape))
+    if total <= DUMP_MAX_WHOLE:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(total, DUMP_SAMPLE, replace=False))
+
+
+def output_sample(flow, index, z_lo=0, z_hi=None):
+    """what --dump-outputs writes of planes z_lo <= z < z_hi of (u, v, w): the planes whole when `index` is None, otherwise the
+    voxels of the fixed sample that lie in them (one ascending run of `index`)"""
+    import numpy as np
+    depth, height, width = flow[0].shape
+    z_hi = depth if z_hi is None else z_hi
+    if index is None:
+        return [np.ascontiguousarray(vol[z_lo:z_hi]) for vol in flow]
+    a, b = np.searchsorted(index, [z_lo * height * width, z_hi * height * width])
+    return [vol.reshape(-1)[index[a:b]] for vol in flow]
+
+
+def write_outputs(directory, arrays, index):
+    """--dump-outputs DIR: the (u, v, w) of the timed path's last step -- the arrays a caller of ComputeFlow receives -- as
+    DIR/u.npy, DIR/v.npy, DIR/w.npy (float32).  Volumes above DUMP_MAX_WHOLE voxels are written as the fixed sample of
+    dump_sample_index, whose flat indices go to DIR/sample_index.npy (float64, exact), so that the files stay under 64 MB."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    if index is not None:
+        np.save(os.path.join(directory, "sample_index.npy"), index.astype(np.float64))
+    for name, vol in zip(("u", "v", "w"), arrays):
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(vol, dtype=np.float32))
+    log(f"[bench] outputs of the last timed step written to {directory} ("
+        + ("whole volumes" if index is None else f"a fixed sample of {index.size} voxels per component") + ")")
+
+
 def run_single(args):
     pkg = importlib.import_module("cuda-flow3d_amd")
     S = args.size
@@ -311,21 +358,22 @@ def run_single(args):
     flow.upload(f0, f1)
     del f0, f1
     hip = pkg.hip()
-    events = not profiler_attached()
+    events = args.full and not profiler_attached()
 
     for i in range(args.warmup):
         t = flow.compute_resident(silent=True)
         log(f"[bench] warmup {i}: {t:.3f} s")
 
-    # Timed region: HIP events around every launch of the DOMINANT kernel only (the fused pair, kernel id 2; the single
+    # Timed region.  --full: HIP events around every launch of the DOMINANT kernel only (the fused pair, kernel id 2; the single
     # sweep when fusion is off).  Events on all 6400 solver launches of a solve cost ~2 % of it; the other two solver kernels
-    # are timed in one extra, untimed step afterwards.
+    # are timed in one extra, untimed step afterwards.  A plain run has no events in it.
     # kernel ids (include/f3d.h): 0 phi/ksi, 1 one sweep, 2 two fused sweeps, 3 sweep + next phi/ksi fused, 4 three fused sweeps,
     # 5 two sweeps + next phi/ksi fused (the three-stage launches of the small and mid-size levels)
     dominant = 2 if os.environ.get("F3D_FUSED_SWEEPS", "1") != "0" else 1
-    hip.f3d_prof_reset()
-    hip.f3d_prof_select(1 << dominant)
-    hip.f3d_prof_enable(1 if events else 0)
+    if args.full:
+        hip.f3d_prof_reset()
+        hip.f3d_prof_select(1 << dominant)
+        hip.f3d_prof_enable(1 if events else 0)
     pkg.sync()
     t0 = time.perf_counter()
     dev_s = 0.0
@@ -333,7 +381,38 @@ def run_single(args):
         dev_s += flow.compute_resident(silent=True)
     pkg.sync()
     wall = time.perf_counter() - t0
-    hip.f3d_prof_enable(0)
+    if args.full:
+        hip.f3d_prof_enable(0)
+    if args.dump_outputs:
+        index = dump_sample_index((S, S, S))
+        write_outputs(args.dump_outputs, output_sample(flow.download(), index), index)
+    ms_per_step = wall / args.steps * 1e3
+    whole = TOTAL_BYTES.get(S)
+    out = {
+        "metric": "Mvoxels/s full pyramid solve", "value": round(S ** 3 * args.steps / wall / 1e6, 4),
+        "unit": "Mvoxels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{S}^3 synthetic translated-Gaussian float32 pair (BASELINE config "
+                               f"{4 if S == 512 else 5 if S == 1024 else 'size ' + str(S)}), full coarse-to-fine pyramid "
+                               "(40 levels x 40 outer x 5 inner, alpha 7.5, median 5^3, Gaussian sigma 2), "
+                               "frames resident in HBM (value = device-resident rate"
+                               + ("; host_inclusive beside it)" if args.full else ")"),
+                   "parallelism": "1 GPU"},
+        "device_ms_per_step": round(dev_s / args.steps * 1e3, 3),
+        "whole_run_roofline_frac": round(whole / (wall / args.steps) / 1e9 / HBM_PEAK_GBS, 4) if whole else None,
+    }
+    if not args.full:
+        flow.destroy()
+        print(json.dumps(out), flush=True)
+        return
+    full_record(args, pkg, hip, flow, S, events, dominant, out)
+
+
+def full_record(args, pkg, hip, flow, S, events, dominant, out):
+    """--full: everything the line carries beyond the headline -- the per-kernel roofline of the timed region, the parity of
+    the result against the committed digest, the host-inclusive rate, and (unless --no-extra) the fixed sample, BASELINE
+    configs 2 and 3 and the host-CPU legs"""
     if events and not args.no_extra:
         hip.f3d_prof_select(0x3f & ~(1 << dominant))
         hip.f3d_prof_enable(1)
@@ -394,54 +473,39 @@ def run_single(args):
     # every solver launch priced at its algorithmic bytes: 52 B per voxel-sweep, 40 B per voxel of phi/ksi
     all_sweeps = gbs(1.0, SWEEP_BYTES_PER_VOXEL * (s1_vox + 2 * s2_vox + sp_vox + 3 * t3_vox + 2 * tp_vox) +
                      PHI_KSI_BYTES_PER_VOXEL * (sp_vox + pk_vox + tp_vox), s1_ms + s2_ms + sp_ms + pk_ms + t3_ms + tp_ms)
-    ms_per_step = wall / args.steps * 1e3
-    whole = TOTAL_BYTES.get(S)
-    out = {
-        "metric": "Mvoxels/s full pyramid solve", "value": round(S ** 3 * args.steps / wall / 1e6, 4),
-        "unit": "Mvoxels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{S}^3 synthetic translated-Gaussian float32 pair (BASELINE config "
-                               f"{4 if S == 512 else 5 if S == 1024 else 'size ' + str(S)}), full coarse-to-fine pyramid "
-                               "(40 levels x 40 outer x 5 inner, alpha 7.5, median 5^3, Gaussian sigma 2), "
-                               "frames resident in HBM (value = device-resident rate; host_inclusive beside it)",
-                   "parallelism": "1 GPU"},
-        "device_ms_per_step": round(dev_s / args.steps * 1e3, 3),
-        "host_inclusive": inclusive,
-        "parity": parity,
-        "whole_run_roofline_frac": round(whole / (wall / args.steps) / 1e9 / HBM_PEAK_GBS, 4) if whole else None,
-        "roofline": {
-            "bound": "hbm", "kernel": dom_name,
-            "algorithmic_bytes_per_voxel_per_launch": dom_b,
-            "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-            "traffic": None, "launches": dom_n, "avg_launch_us": round(dom_ms / dom_n * 1e3, 3) if dom_n else None,
-            "avg_voxels_per_launch": round(dom_vox / dom_n, 1) if dom_n else None,
-            "finest_level": {"achieved": round(finest, 1), "frac": round(finest / HBM_PEAK_GBS, 4), "launches": fin_n,
-                             "avg_launch_us": round(fin_ms / fin_n * 1e3, 3) if fin_n else None,
-                             "note": "algorithmic bytes of TWO sweeps per launch (SURVEY.md 8d) over a launch that moves the bytes of one: "
-                                     "this fraction is not bounded by 1; hbm_frac below prices the same launch in the bytes the memory "
-                                     "system moved"},
-            "all_solver_launches": {"achieved": round(all_sweeps, 1), "frac": round(all_sweeps / HBM_PEAK_GBS, 4),
-                                    "note": "every solver launch at its algorithmic bytes (52 B per voxel-sweep, 40 B per voxel of "
-                                            "phi/ksi), fused or not; the non-dominant kernels are timed in one extra untimed step"},
-            "sweep_phi_ksi": {"kernel": "k_pair8 (last sweep + next phi/ksi, f3d_solve_sweep_phi_ksi)",
-                              "achieved": round(gbs(SWEEP_BYTES_PER_VOXEL + PHI_KSI_BYTES_PER_VOXEL, sp_vox, sp_ms), 1),
-                              "launches": sp_n,
-                              "finest_level": {"achieved": round(gbs(SWEEP_BYTES_PER_VOXEL + PHI_KSI_BYTES_PER_VOXEL, spf_vox, spf_ms), 1),
-                                               "frac": round(gbs(SWEEP_BYTES_PER_VOXEL + PHI_KSI_BYTES_PER_VOXEL, spf_vox, spf_ms) / HBM_PEAK_GBS, 4),
-                                               "launches": spf_n,
-                                               "avg_launch_us": round(spf_ms / spf_n * 1e3, 3) if spf_n else None}},
-            "three_stage": {"kernel": "k_tri (three sweeps: f3d_solve_sweep3; two sweeps + next phi/ksi: f3d_solve_sweep2_phi_ksi) on the "
-                                      "levels up to ~144^3",
-                            "three_sweeps": {"achieved": round(gbs(3 * SWEEP_BYTES_PER_VOXEL, t3_vox, t3_ms), 1), "launches": t3_n,
-                                             "avg_launch_us": round(t3_ms / t3_n * 1e3, 3) if t3_n else None},
-                            "two_sweeps_phi_ksi": {"achieved": round(gbs(2 * SWEEP_BYTES_PER_VOXEL + PHI_KSI_BYTES_PER_VOXEL, tp_vox, tp_ms), 1),
-                                                   "launches": tp_n, "avg_launch_us": round(tp_ms / tp_n * 1e3, 3) if tp_n else None}},
-            "single_sweep": {"kernel": "k_sweep6", "achieved": round(gbs(SWEEP_BYTES_PER_VOXEL, s1_vox, s1_ms), 1),
-                             "launches": s1_n},
-            "phi_ksi": {"kernel": "k_phiksi6", "achieved": round(gbs(PHI_KSI_BYTES_PER_VOXEL, pk_vox, pk_ms), 1),
-                        "frac": round(gbs(PHI_KSI_BYTES_PER_VOXEL, pk_vox, pk_ms) / HBM_PEAK_GBS, 4), "launches": pk_n},
-        },
+    out["host_inclusive"] = inclusive
+    out["parity"] = parity
+    out["roofline"] = {
+        "bound": "hbm", "kernel": dom_name,
+        "algorithmic_bytes_per_voxel_per_launch": dom_b,
+        "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+        "traffic": None, "launches": dom_n, "avg_launch_us": round(dom_ms / dom_n * 1e3, 3) if dom_n else None,
+        "avg_voxels_per_launch": round(dom_vox / dom_n, 1) if dom_n else None,
+        "finest_level": {"achieved": round(finest, 1), "frac": round(finest / HBM_PEAK_GBS, 4), "launches": fin_n,
+                         "avg_launch_us": round(fin_ms / fin_n * 1e3, 3) if fin_n else None,
+                         "note": "algorithmic bytes of TWO sweeps per launch (SURVEY.md 8d) over a launch that moves the bytes of one: "
+                                 "this fraction is not bounded by 1; hbm_frac below prices the same launch in the bytes the memory "
+                                 "system moved"},
+        "all_solver_launches": {"achieved": round(all_sweeps, 1), "frac": round(all_sweeps / HBM_PEAK_GBS, 4),
+                                "note": "every solver launch at its algorithmic bytes (52 B per voxel-sweep, 40 B per voxel of "
+                                        "phi/ksi), fused or not; the non-dominant kernels are timed in one extra untimed step"},
+        "sweep_phi_ksi": {"kernel": "k_pair8 (last sweep + next phi/ksi, f3d_solve_sweep_phi_ksi)",
+                          "achieved": round(gbs(SWEEP_BYTES_PER_VOXEL + PHI_KSI_BYTES_PER_VOXEL, sp_vox, sp_ms), 1),
+                          "launches": sp_n,
+                          "finest_level": {"achieved": round(gbs(SWEEP_BYTES_PER_VOXEL + PHI_KSI_BYTES_PER_VOXEL, spf_vox, spf_ms), 1),
+                                           "frac": round(gbs(SWEEP_BYTES_PER_VOXEL + PHI_KSI_BYTES_PER_VOXEL, spf_vox, spf_ms) / HBM_PEAK_GBS, 4),
+                                           "launches": spf_n,
+                                           "avg_launch_us": round(spf_ms / spf_n * 1e3, 3) if spf_n else None}},
+        "three_stage": {"kernel": "k_tri (three sweeps: f3d_solve_sweep3; two sweeps + next phi/ksi: f3d_solve_sweep2_phi_ksi) on the "
+                                  "levels up to ~144^3",
+                        "three_sweeps": {"achieved": round(gbs(3 * SWEEP_BYTES_PER_VOXEL, t3_vox, t3_ms), 1), "launches": t3_n,
+                                         "avg_launch_us": round(t3_ms / t3_n * 1e3, 3) if t3_n else None},
+                        "two_sweeps_phi_ksi": {"achieved": round(gbs(2 * SWEEP_BYTES_PER_VOXEL + PHI_KSI_BYTES_PER_VOXEL, tp_vox, tp_ms), 1),
+                                               "launches": tp_n, "avg_launch_us": round(tp_ms / tp_n * 1e3, 3) if tp_n else None}},
+        "single_sweep": {"kernel": "k_sweep6", "achieved": round(gbs(SWEEP_BYTES_PER_VOXEL, s1_vox, s1_ms), 1),
+                         "launches": s1_n},
+        "phi_ksi": {"kernel": "k_phiksi6", "achieved": round(gbs(PHI_KSI_BYTES_PER_VOXEL, pk_vox, pk_ms), 1),
+                    "frac": round(gbs(PHI_KSI_BYTES_PER_VOXEL, pk_vox, pk_ms) / HBM_PEAK_GBS, 4), "launches": pk_n},
     }
     if not events:
         out["roofline"]["note"] = "a profiler is attached: no HIP-event bracket in this run, kernel times come from its trace"
@@ -479,7 +543,7 @@ ORDERS = (("per_outer_iteration", False, "once per outer iteration: K + 1 = 6 pl
           ("per_stage", True, "after every solver stage: 2 / 1 / 3 planes, stages on the slab itself"))
 
 
-def measure_multi(pkg, dist, torch, rank, world, S, steps, warmup, args):
+def measure_multi(pkg, dist, torch, rank, world, S, steps, warmup, args, dump=None):
     """One size of the multi-GPU sweep: the SAME S^3 volume on `world` z-slabs (strong scaling), BOTH exchange orders timed in this
     one invocation (bit-identical; which wins is a property of the machine's exchange latency), then -- outside every timed
     region -- one solve per order with HIP events around the exchanges (microseconds per exchange) and, on rank 0's device, the
@@ -517,9 +581,10 @@ def measure_multi(pkg, dist, torch, rank, world, S, steps, warmup, args):
             if rank == 0:
                 log(f"[bench] {S}^3 {name} warmup {i}: {tsec:.3f} s")
         before = pkg.comm_info()
-        hip.f3d_prof_reset()
-        hip.f3d_prof_select(0x6)   # events on the sweep kernels only (ids 1 and 2): they are what the roofline line reports
-        hip.f3d_prof_enable(1)
+        if args.full:
+            hip.f3d_prof_reset()
+            hip.f3d_prof_select(0x6)   # events on the sweep kernels only (ids 1 and 2): they are what the roofline line reports
+            hip.f3d_prof_enable(1)
         pkg.sync()
         dist.barrier()
         t0 = time.perf_counter()
@@ -528,11 +593,32 @@ def measure_multi(pkg, dist, torch, rank, world, S, steps, warmup, args):
         pkg.sync()
         dist.barrier()
         wall = time.perf_counter() - t0
-        hip.f3d_prof_enable(0)
         tw = torch.tensor([wall], dtype=torch.float64)
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
         wall = tw.item()
         after = pkg.comm_info()
+        mine_comm = {"rank": after["rank"], "device": after["device"], "sent_bytes": after["sent_bytes"] - before["sent_bytes"],
+                     "exchanges": after["exchanges"] - before["exchanges"]}
+        comms = [None] * world if rank == 0 else None
+        dist.gather_object(mine_comm, comms, dst=0)
+        result = flow.download() if args.full or (dump and name == orders[-1][0]) else None
+        if dump and name == orders[-1][0]:
+            # --dump-outputs: every rank hands rank 0 its share of what the last timed step computed
+            index = dump_sample_index((S, S, S))
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(output_sample(result, index, lo, hi), parts, dst=0)
+            if rank == 0:
+                write_outputs(dump, [np.concatenate([p[c] for p in parts]) for c in range(3)], index)
+        if rank == 0:
+            record = {"exchange_order": what, "ms_per_step": round(wall / steps * 1e3, 3), "value": round(S ** 3 * steps / wall / 1e6, 4),
+                      "comm": {"per_rank": comms, "halo_GB_sent_per_step": round(sum(c["sent_bytes"] for c in comms) / 1e9 / steps, 4),
+                               "exchanges_per_step_rank0": comms[0]["exchanges"] // max(1, steps)}}
+            measured[name] = record
+            if not args.full:
+                log(f"[bench] {S}^3 {name}: {wall / steps * 1e3:.1f} ms per step")
+        if not args.full:
+            continue
+        hip.f3d_prof_enable(0)
         tot_ms, tot_bytes, launches = 0.0, 0.0, 0
         per_kernel = {}
         for kid, bpv in ((1, SWEEP_BYTES_PER_VOXEL), (2, 2 * SWEEP_BYTES_PER_VOXEL)):
@@ -543,13 +629,9 @@ def measure_multi(pkg, dist, torch, rank, world, S, steps, warmup, args):
             launches += n.value
             per_kernel[kid] = (ms.value, n.value, vox.value)
         # outside the timed region: every rank hashes the planes it owns, rank 0 compares the whole with the single-GPU digest
-        mine = pkg.flow_plane_digests(flow.download(), lo, hi)
+        mine = pkg.flow_plane_digests(result, lo, hi)
         gathered = [None] * world if rank == 0 else None
         dist.gather_object(mine, gathered, dst=0)
-        mine_comm = {"rank": after["rank"], "device": after["device"], "sent_bytes": after["sent_bytes"] - before["sent_bytes"],
-                     "exchanges": after["exchanges"] - before["exchanges"]}
-        comms = [None] * world if rank == 0 else None
-        dist.gather_object(mine_comm, comms, dst=0)
         # one more solve, untimed, with events around every exchange: what an exchange costs on THIS machine
         pkg.comm_timing(True)
         flow.compute_resident()
@@ -562,23 +644,20 @@ def measure_multi(pkg, dist, torch, rank, world, S, steps, warmup, args):
             log(f"[bench] {S}^3 {name}: {wall / steps * 1e3:.1f} ms per step; digest {parity['digest'][:16]}... matches the committed "
                 f"single-GPU one: {parity['match']}")
             achieved = tot_bytes / (tot_ms * 1e-3) / 1e9 if tot_ms else 0.0
-            measured[name] = {
-                "exchange_order": what, "ms_per_step": round(wall / steps * 1e3, 3), "value": round(S ** 3 * steps / wall / 1e6, 4),
+            record.update({
                 "parity": parity, "rank0_solver_sweeps_GBs": round(achieved, 1), "rank0_sweep_launches": launches,
                 "_per_kernel": per_kernel,
-                "comm": {"per_rank": comms, "halo_GB_sent_per_step": round(sum(c["sent_bytes"] for c in comms) / 1e9 / steps, 4),
-                         "exchanges_per_step_rank0": comms[0]["exchanges"] // max(1, steps)},
                 # microseconds per exchange, measured (HIP events: pack -> grouped send / recv -> unpack on the library stream; the
                 # transfer alone on the stream it was posted to): per rank, from one untimed solve
                 "exchange_us": {"rank0": timings[0],
                                 "worst_rank_mean_us_blocking": max((x["blocking_exchange"]["mean_us"] or 0.0) for x in timings),
                                 "worst_rank_mean_us_transfer_alone": max((x["grouped_send_recv_alone"]["mean_us"] or 0.0) for x in timings)},
-            }
+            })
     comm = pkg.comm_info()
     flow.destroy()
     # the unsplit solve of the same volume on rank 0's device (the others wait): every multi-GPU line carries its own baseline
     single = None
-    if rank == 0 and not args.no_single:
+    if rank == 0 and args.full and not args.no_single:
         log(f"[bench] single-GPU solve of the same {S}^3 volume on rank 0's device ...")
         g0, g1 = pkg.synth_pair(S, S, S)
         one = pkg.OpticalFlow()
@@ -604,6 +683,30 @@ def measure_multi(pkg, dist, torch, rank, world, S, steps, warmup, args):
     best = min(measured, key=lambda k: measured[k]["ms_per_step"])
     b = measured[best]
     whole = TOTAL_BYTES.get(S)
+    shm = os.environ.get("F3D_COMM_BACKEND") == "shm"
+    out = {
+        "metric": "Mvoxels/s full pyramid solve", "value": b["value"],
+        "unit": "Mvoxels/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": b["ms_per_step"], "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{S}^3 synthetic translated-Gaussian float32 pair"
+                               + (" (BASELINE config 4: the size the metric is quoted on)" if S == 512 else
+                                  " (BASELINE config 5, the z-slab scaling workload)" if S == 1024 else "")
+                               + ", full coarse-to-fine pyramid (40 levels x 40 outer x 5 inner, alpha 7.5, median 5^3, Gaussian "
+                                 "sigma 2), frames resident in HBM; the SAME volume at every N (strong scaling)",
+                   "parallelism": f"z-slab decomposition over {world} GPUs, halo exchange on RCCL, {b['exchange_order']}"
+                                  + (" -- REHEARSAL: shared-memory transport, ranks share devices" if shm else "")},
+        # both bit-identical exchange orders (DESIGN.md section 5) were timed in this invocation: `value` is the faster one
+        "exchange_order": best, "exchange_orders": measured,
+        "launched_by": "bench.py itself (one child process per rank)" if os.environ.get("F3D_BENCH_LAUNCHED") == "1"
+                       else "an external launcher (RANK / WORLD_SIZE were set)",
+        # the communicator as the transport reports it: `rccl_ranks` is ncclCommCount's answer on rank 0, not WORLD_SIZE
+        "rccl_ranks": comm["ranks"], "comm_backend": comm["backend"],
+        "comm": b["comm"],
+        "whole_run_roofline_frac": round(whole / (b["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS / world, 4) if whole else None,
+    }
+    if not args.full:
+        return out
     achieved = b["rank0_solver_sweeps_GBs"]
     roof = {"bound": "hbm", "kernel": "k_pair8 + k_sweep6 (all solver sweeps, 52 B per voxel-sweep) on rank 0's slab incl. widened "
                                       "windows", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -622,33 +725,12 @@ def measure_multi(pkg, dist, torch, rank, world, S, steps, warmup, args):
                      "hbm_frac_scope": f"the {n2} two-sweep launches of rank 0 at the measured {per_voxel:.1f} B per voxel"})
     for m in measured.values():
         m.pop("_per_kernel")
-    shm = os.environ.get("F3D_COMM_BACKEND") == "shm"
-    out = {
-        "metric": "Mvoxels/s full pyramid solve", "value": b["value"],
-        "unit": "Mvoxels/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-        "ms_per_step": b["ms_per_step"], "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "parity": b["parity"],
-        "config": {"workload": f"{S}^3 synthetic translated-Gaussian float32 pair"
-                               + (" (BASELINE config 4: the size the metric is quoted on)" if S == 512 else
-                                  " (BASELINE config 5, the z-slab scaling workload)" if S == 1024 else "")
-                               + ", full coarse-to-fine pyramid (40 levels x 40 outer x 5 inner, alpha 7.5, median 5^3, Gaussian "
-                                 "sigma 2), frames resident in HBM; the SAME volume at every N (strong scaling)",
-                   "parallelism": f"z-slab decomposition over {world} GPUs, halo exchange on RCCL, {b['exchange_order']}"
-                                  + (" -- REHEARSAL: shared-memory transport, ranks share devices" if shm else "")},
-        # both bit-identical exchange orders (DESIGN.md section 5) were timed in this invocation: `value` is the faster one
-        "exchange_order": best, "exchange_orders": measured,
-        # the unsplit solve of the same volume on rank 0's device and what the N GPUs make of it
-        "single_gpu_same_size": single,
-        "speedup": round(b["value"] / single["value"], 4) if single else None,
-        "launched_by": "bench.py itself (one child process per rank)" if os.environ.get("F3D_BENCH_LAUNCHED") == "1"
-                       else "an external launcher (RANK / WORLD_SIZE were set)",
-        # the communicator as the transport reports it: `rccl_ranks` is ncclCommCount's answer on rank 0, not WORLD_SIZE
-        "rccl_ranks": comm["ranks"], "comm_backend": comm["backend"],
-        "comm": b["comm"],
-        "exchange_us": b["exchange_us"],
-        "whole_run_roofline_frac": round(whole / (b["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS / world, 4) if whole else None,
-        "roofline": roof,
-    }
+    out["parity"] = b["parity"]
+    # the unsplit solve of the same volume on rank 0's device and what the N GPUs make of it
+    out["single_gpu_same_size"] = single
+    out["speedup"] = round(b["value"] / single["value"], 4) if single else None
+    out["exchange_us"] = b["exchange_us"]
+    out["roofline"] = roof
     return out
 
 
@@ -680,15 +762,15 @@ def run_multi(args):
     dist.broadcast_object_list(box, src=0)
     pkg.comm_init(box[0], rank, world, device=device)
 
-    out = measure_multi(pkg, dist, torch, rank, world, args.size, args.steps, args.warmup, args)
-    if args.size == 512 and not args.no_extra and not args.no_config5:
+    out = measure_multi(pkg, dist, torch, rank, world, args.size, args.steps, args.warmup, args, dump=args.dump_outputs)
+    if args.size == 512 and args.full and not args.no_extra and not args.no_config5:
         # BASELINE config 5 in the same invocation, bounded: one warm-up and two steps per exchange order
         c5 = measure_multi(pkg, dist, torch, rank, world, 1024, min(args.steps, 2), 1, args)
         if rank == 0:
             out["config5"] = c5
     pkg.comm_destroy()
     if rank == 0:
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             # the legs of the one-GPU line that do not depend on N, so that every line of a scaling run is self-contained: the
             # like-for-like sample on rank 0's device and the host-CPU baseline (the other ranks wait at the barrier below)
             log("[bench] fixed sample on rank 0's GPU (phi/ksi + 5 sweeps on a 512^3 level) ...")
@@ -785,8 +867,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--size", type=int, default=0, help="volume edge; default 512 for every N (BASELINE config 4: the size the metric "
                                                       "is quoted on); with several GPUs the 1024^3 leg (config 5) is appended")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: roofline of the timed kernels, parity of the "
+                                                       "result, host-inclusive rate, fixed sample, configs 2/3, CPU legs (--gpus N > 1: "
+                                                       "also exchange timings, the single-GPU solve and config 5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write (u, v, w) of the last timed step to DIR/*.npy (float32; a fixed "
+                                                          "seeded sample of voxels above 4 Mi voxels, indices in sample_index.npy)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the host-CPU legs (cpu_baseline, fixed_sample.cpu)")
-    ap.add_argument("--no-extra", action="store_true", help="only the timed steps: no host-inclusive step, fixed sample, "
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no host-inclusive step, fixed sample, "
                                                            "configs 2/3 or CPU legs (profiling runs)")
     ap.add_argument("--no-config5", action="store_true", help="--gpus N > 1: do not append the 1024^3 leg (BASELINE config 5) to the 512^3 line")
     ap.add_argument("--no-single", action="store_true", help="--gpus N > 1: skip the single-GPU solve of the same volume on rank 0 "
@@ -795,6 +882,8 @@ def main():
     ap.add_argument("--launch-timeout", type=int, default=3300, help="--gpus N started bare: seconds the launcher waits for the "
                                                                      "ranks before it ends them")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         # started bare (the way `--gpus 1` is): become the launcher -- before anything loads the native library
         sys.exit(launch_ranks(args, sys.argv[1:]))

@@ -121,7 +121,7 @@ def test_bench_gpus_2_started_bare_equals_one_gpu(f3d):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     env["F3D_COMM_BACKEND"] = "shm"       # two ranks on the one GPU of the box; never a reported number
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--size", str(S), "--steps", "1", "--warmup", "0", "--no-extra"],
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--size", str(S), "--steps", "1", "--warmup", "0", "--full", "--no-extra"],
                        env=env, capture_output=True, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
@@ -153,3 +153,61 @@ def test_bench_gpus_2_started_bare_equals_one_gpu(f3d):
     assert single["digest_equals_the_slab_runs"] is True and single["value"] > 0
     assert line["speedup"] == pytest.approx(line["value"] / single["value"], rel=1e-3)
     assert "config5" not in line          # only the 512^3 sweep takes the 1024^3 leg along
+
+
+def _bench_on_the_host_stand_in(tmp_path, *extra):
+    """bench.py --gpus 1 on the host-memory stand-in of the device library (tests/cpu_device): the whole script, a tiny volume"""
+    subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "cpu_device"), "all", "-j4"], check=True, stdout=subprocess.DEVNULL)
+    env = dict(os.environ, F3D_LIBDIR=os.path.join(ROOT, "tests", "cpu_device", "_build", "plain"), OMP_NUM_THREADS="4")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "F3D_BENCH_FORCE_SLAB"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--size", "24", "--warmup", "1"] + list(extra), env=env,
+                       capture_output=True, timeout=600, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run carries the headline (ms_per_step = one timed step, --steps of them) and nothing that takes runs of its own;
+    --dump-outputs writes the flow of the last timed step, the same on every run, and --full adds the rest of the record."""
+    import numpy as np
+    line = _bench_on_the_host_stand_in(tmp_path, "--steps", "2", "--dump-outputs", str(tmp_path / "a"))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 2 and line["unit"] == "Mvoxels/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] == pytest.approx(24 ** 3 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3, abs=1e-4)   # value: 4 decimals
+    for key in ("roofline", "parity", "host_inclusive", "fixed_sample", "configs", "cpu_baseline"):
+        assert key not in line, key
+    again = _bench_on_the_host_stand_in(tmp_path, "--steps", "1", "--dump-outputs", str(tmp_path / "b"))
+    assert again["steps"] == 1
+    want = _bench_on_the_host_stand_in(tmp_path, "--steps", "1", "--full", "--no-extra")
+    assert "roofline" in want and want["parity"]["digest"]
+    got = [np.load(str(tmp_path / "a" / (n + ".npy"))) for n in "uvw"]
+    assert all(g.dtype == np.float32 and g.shape == (24, 24, 24) and np.isfinite(g).all() for g in got)
+    assert all(np.array_equal(g, np.load(str(tmp_path / "b" / (n + ".npy")))) for g, n in zip(got, "uvw"))
+    sys.path.insert(0, ROOT)
+    import importlib
+    f3d = importlib.import_module("cuda-flow3d_amd")
+    assert f3d.combine_plane_digests(f3d.flow_plane_digests(got)) == want["parity"]["digest"]
+
+
+def test_dumped_sample_of_a_large_volume_is_fixed_and_small():
+    """above 4 Mi voxels --dump-outputs writes a seeded sample: the same voxels on every run, at most 64 MB in all, and the
+    shares of the z-slabs of a multi-GPU run put together give the single-GPU sample"""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    S = 512
+    index = bench.dump_sample_index((S, S, S))
+    assert np.array_equal(index, bench.dump_sample_index((S, S, S))) and np.all(np.diff(index) > 0)
+    assert index[0] >= 0 and index[-1] < S ** 3 and index.size * (3 * 4 + 8) <= 64 << 20
+    assert bench.dump_sample_index((161, 161, 161)) is None
+    flow = [np.arange(S ** 3, dtype=np.float32).reshape(S, S, S) * k for k in (1, -1, 2)]
+    whole = bench.output_sample(flow, index)
+    assert all(np.array_equal(w, f.reshape(-1)[index]) for w, f in zip(whole, flow))
+    parts = [bench.output_sample(flow, index, lo, hi) for lo, hi in ((0, 170), (170, 171), (171, 512))]
+    assert all(np.array_equal(np.concatenate([p[c] for p in parts]), whole[c]) for c in range(3))

@@ -6,7 +6,7 @@ R=$(pwd)   # the tree the command was started in (a staged copy under tools/gpu_
 O=${F3D_OUT:-$R/gpurun_out}/round
 mkdir -p $O
 cd $R
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -1 $O/bench_default.json
 cd /tmp && export TMPDIR=/tmp
 KB=${F3D_KBENCH_KERNELS:-all}   # every solver kernel: the fused launches on frames and on frame derivatives (what the resident operator runs)
