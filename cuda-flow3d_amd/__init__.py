@@ -205,6 +205,9 @@ def host():
         "f3d_flow_set_level_stats": [C.c_void_p, C.c_int], "f3d_flow_level_stat_count": [C.c_void_p, C.POINTER(_sz)],
         "f3d_flow_level_stat": [C.c_void_p, _sz, C.POINTER(LevelStat)],
         "f3d_flow_final_residual": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+        "f3d_flow_trajectory_begin": [C.c_void_p], "f3d_flow_trajectory_append": [C.c_void_p],
+        "f3d_flow_trajectory_download": [C.c_void_p, _fp, _fp, _fp, C.POINTER(C.c_ulonglong)],
+        "f3d_flow_trajectory_end": [C.c_void_p],
         "f3d_op_create": [C.POINTER(C.c_void_p), C.c_char_p], "f3d_op_initialize": [C.c_void_p, C.POINTER(Size4)],
         "f3d_op_execute": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), _sz],
         "f3d_op_execute_batch": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(_sz), _sz],
@@ -265,6 +268,9 @@ def host():
     L.f3d_volume_data.restype = C.c_void_p
     L.f3d_piecemeal_budget_bytes.argtypes = []
     L.f3d_piecemeal_budget_bytes.restype = _sz
+    if hasattr(L, "f3d_host_last_error"):
+        L.f3d_host_last_error.argtypes = []
+        L.f3d_host_last_error.restype = C.c_char_p
     _host = L
     return L
 
@@ -289,6 +295,55 @@ def check(status, what="f3d call"):
     if status != 0:
         msg = hip().f3d_last_error()
         raise F3dError(f"{what} failed: {msg.decode() if msg else 'status %d' % status}")
+
+
+def _host_check(status, what):
+    """check() for the calls that can fail in the host library itself (f3d_host_last_error describes those)"""
+    if status != 0:
+        msg = host().f3d_host_last_error()
+        raise F3dError(f"{what} failed: {msg.decode() if msg else 'status %d' % status}")
+
+
+def _compose_entry():
+    """f3d_compose_flow of the device library, declared on first use: it is not in hip()'s table, so that a library without it
+    (an older build, the host-memory stand-in of the tests) still loads; using it there raises."""
+    L = hip()
+    try:
+        fn = L.f3d_compose_flow
+    except AttributeError:
+        raise F3dError(f"{os.path.join(_LIBDIR, 'libf3d_hip.so')} has no f3d_compose_flow: this device library cannot compose "
+                       "flows into a trajectory") from None
+    fn.argtypes = [_dp] * 6 + [_sz] * 3 + [C.POINTER(C.c_ulonglong)]
+    fn.restype = C.c_int
+    return fn
+
+
+def compose_flow(acc, inc):
+    """One trajectory step on the device (include/f3d.h, f3d_compose_flow) for flows from anywhere: acc = (u, v, w) displacement of
+    every voxel of frame 0 so far, inc = (u, v, w) flow of the next pair (numpy [z, y, x] float32, voxel units).  Returns
+    (u, v, w, lost): acc + inc sampled trilinearly at x + acc, NaN where the point has left the volume, and the number of voxels
+    whose u is NaN.  The inputs are not modified."""
+    fn = _compose_entry()
+    acc = [np.ascontiguousarray(a, dtype=np.float32) for a in acc]
+    inc = [np.ascontiguousarray(a, dtype=np.float32) for a in inc]
+    if len(acc) != 3 or len(inc) != 3 or any(a.ndim != 3 or a.shape != acc[0].shape for a in acc + inc):
+        raise ValueError("acc and inc must be three [z, y, x] volumes of one shape each")
+    d, h, w = acc[0].shape
+    box = Containers(w, h, d)
+    previous = Size4()
+    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
+    try:
+        pa = [box.new(a) for a in acc]
+        pi = [box.new(a) for a in inc]
+        box.set_current()
+        lost = C.c_ulonglong()
+        check(fn(*pa, *pi, w, h, d, C.byref(lost)), "f3d_compose_flow")
+        out = tuple(box.download(p, (w, h, d)) for p in pa)
+    finally:
+        if previous.pitch:   # the geometry of whoever set one before (a driver on this lane)
+            hip().f3d_set_container(C.byref(previous))
+        box.free()
+    return out + (int(lost.value),)
 
 
 def _f32(a):
@@ -757,6 +812,53 @@ class OpticalFlow:
         a, b = (C.c_double * 3)(), (C.c_double * 3)()
         check(host().f3d_flow_final_residual(self._h, a, b), "f3d_flow_final_residual")
         return tuple(a), tuple(b)
+
+    # ---- trajectory of a frame sequence (include/f3d_host.h, f3d_flow_trajectory_*) ----
+    def trajectory_begin(self):
+        """start (or restart) the cumulative displacement at zero; allocates three containers on first use"""
+        _host_check(host().f3d_flow_trajectory_begin(self._h), "f3d_flow_trajectory_begin")
+
+    def trajectory_append(self):
+        """compose the flow of the last compute_resident() into the displacement, on the device"""
+        _host_check(host().f3d_flow_trajectory_append(self._h), "f3d_flow_trajectory_append")
+
+    def trajectory_download(self):
+        """(u, v, w, lost): the displacement of every voxel of frame 0 (frame 0's grid, voxel units; NaN where the point has left
+        the volume) and the number of voxels whose u is NaN"""
+        w, h, d = self.dims
+        u, v, ww = (np.empty((d, h, w), np.float32) for _ in range(3))
+        lost = C.c_ulonglong()
+        _host_check(host().f3d_flow_trajectory_download(self._h, u.ctypes.data_as(_fp), v.ctypes.data_as(_fp),
+                                                        ww.ctypes.data_as(_fp), C.byref(lost)), "f3d_flow_trajectory_download")
+        return u, v, ww, int(lost.value)
+
+    def trajectory_end(self):
+        _host_check(host().f3d_flow_trajectory_end(self._h), "f3d_flow_trajectory_end")
+
+    def compute_sequence(self, frames, cumulative=False, silent=True, **kw):
+        """Generator over the consecutive pairs of `frames` (an iterable of [z, y, x] volumes): yields (k, (u, v, w), disp) for
+        pair k (frame k -> k+1), where disp is None, or with cumulative=True the trajectory_download() tuple (u, v, w, lost) of
+        the displacement frame 0 -> frame k+1.  Each pair is uploaded and solved with compute_resident()."""
+        previous = None
+        k = 0
+        if cumulative:
+            self.trajectory_begin()
+        try:
+            for frame in frames:
+                if previous is not None:
+                    self.upload(previous, frame)
+                    self.compute_resident(silent=silent, **kw)
+                    flow = self.download()
+                    disp = None
+                    if cumulative:
+                        self.trajectory_append()
+                        disp = self.trajectory_download()
+                    yield k, flow, disp
+                    k += 1
+                previous = frame
+        finally:
+            if cumulative and self._h:
+                self.trajectory_end()
 
     def destroy(self):
         if self._h:

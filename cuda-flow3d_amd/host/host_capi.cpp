@@ -16,6 +16,7 @@
 struct f3d_flow_s {
   OpticalFlowE driver;
   bool device_ready = false;
+  bool trajectory_started = false;
 };
 
 struct f3d_slabflow_s {
@@ -38,6 +39,15 @@ struct f3d_op_s {
 };
 
 namespace {
+
+// message of the last failed call of this thread that failed in the host library itself (f3d_host_last_error)
+thread_local std::string g_host_error;
+
+int HostFail(const char* what)
+{
+  g_host_error = what ? what : "unknown error";
+  return 1;
+}
 
 void FillBag(OperationParameters& bag, f3d_flow_params& p)
 {
@@ -183,6 +193,46 @@ int f3d_flow_final_residual(f3d_flow flow, double registered[3], double unregist
   unregistered[0] = b.rms; unregistered[1] = b.mean_abs; unregistered[2] = b.max_abs;
   return 0;
 }
+
+int f3d_flow_trajectory_begin(f3d_flow flow)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_trajectory_begin: null driver");
+  if (!flow->driver.ResetTrajectory()) return HostFail(flow->driver.TrajectoryError().c_str());
+  flow->trajectory_started = true;
+  return 0;
+}
+
+int f3d_flow_trajectory_append(f3d_flow flow)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_trajectory_append: null driver");
+  if (!flow->trajectory_started) return HostFail("f3d_flow_trajectory_append: f3d_flow_trajectory_begin has not been called");
+  if (!flow->driver.ComposeTrajectory()) return HostFail(flow->driver.TrajectoryError().c_str());
+  return 0;
+}
+
+int f3d_flow_trajectory_download(f3d_flow flow, float* u, float* v, float* w, unsigned long long* lost)
+{
+  g_host_error.clear();
+  if (!flow || !u || !v || !w) return HostFail("f3d_flow_trajectory_download: null argument");
+  if (!flow->trajectory_started) return HostFail("f3d_flow_trajectory_download: f3d_flow_trajectory_begin has not been called");
+  const DataSize4& c = flow->driver.ContainerSize();
+  Data3D fu(u, c.width, c.height, c.depth), fv(v, c.width, c.height, c.depth), fw(w, c.width, c.height, c.depth);
+  if (!flow->driver.DownloadTrajectory(fu, fv, fw, lost)) return HostFail(flow->driver.TrajectoryError().c_str());
+  return 0;
+}
+
+int f3d_flow_trajectory_end(f3d_flow flow)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_trajectory_end: null driver");
+  flow->driver.ReleaseTrajectory();
+  flow->trajectory_started = false;
+  return 0;
+}
+
+const char* f3d_host_last_error(void) { return g_host_error.empty() ? f3d_last_error() : g_host_error.c_str(); }
 
 int f3d_flow_destroy(f3d_flow flow)
 {

@@ -4,7 +4,7 @@
 // the nine-key parameter bag, write flow-u/v/w as RAW float32), with the compile-time constants turned into
 // flags:  flow3d --dims W H D --frames f0.raw f1.raw [f2.raw ...] [--f32] [--out prefix] [--levels N] [--scale s]
 //                [--outer N] [--inner N] [--alpha a] [--eps-smooth e] [--eps-data e] [--median r] [--sigma s]
-//                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N]
+//                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -14,6 +14,10 @@
 // own stream and container geometry), pair k going to thread k mod N.  Pair k+1 does not depend on pair k, and a small volume
 // (up to ~128^3) is a chain of dependent launches of 10-20 us that leaves most of the chip idle: two such chains side by side
 // nearly double the pairs per second.  Large volumes fill the chip by themselves and gain nothing.
+// --cumulative (resident driver, pairs in order) also composes every pair's flow into the displacement of each voxel of frame 0 on
+// the device (f3d_compose_flow) and writes <prefix>_<k>_disp-{u,v,w}-W-H-D.raw: frame 0 -> frame k+1 on frame 0's grid, NaN where
+// the point has left the volume.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,7 +39,7 @@ static void Usage()
   std::printf("usage: flow3d --dims W H D (--frames f0.raw f1.raw [f2.raw ...] [--f32] | --synthetic) [--out prefix]\n"
               "              [--levels N] [--scale s] [--outer N] [--inner N] [--alpha a] [--eps-smooth e]\n"
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
-              "              [--concurrent N]\n");
+              "              [--concurrent N] [--cumulative]\n");
 }
 
 int main(int argc, char** argv)
@@ -44,7 +48,7 @@ int main(int argc, char** argv)
   std::vector<std::string> files;
   std::string prefix = "flow3d";
   bool f32_input = false, synthetic = false, write_vtk = false, silent_mode = false, print_stats = false;
-  bool use_partial_gpu = false, partial_full = false;
+  bool use_partial_gpu = false, partial_full = false, cumulative = false;
   size_t concurrent = 1;
 
   // defaults of src/main.cpp:77-85
@@ -90,10 +94,16 @@ int main(int argc, char** argv)
     else if (a == "--full") partial_full = true;
     else if (a == "--budget-mb") { need(1); setenv("F3D_P_BUDGET_MB", argv[++i], 1); }
     else if (a == "--concurrent") { need(1); concurrent = std::strtoull(argv[++i], nullptr, 10); }
+    else if (a == "--cumulative") cumulative = true;
     else { Usage(); return 64; }
   }
   if (width == 0 || height == 0 || depth == 0 || (!synthetic && files.size() < 2)) {
     Usage();
+    return 64;
+  }
+  if (cumulative && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--cumulative needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
     return 64;
   }
 
@@ -252,6 +262,23 @@ int main(int argc, char** argv)
     w.WriteRAWToFileF32((tag + "_flow-w" + suffix).c_str());
     if (write_vtk) Data3D::WriteFlowToFileVTK((tag + "_flow.vtk").c_str(), u, v, w);
   };
+  // --cumulative: the displacement frame 0 -> frame k+1 and how many points have left the volume (NaN)
+  Data3D disp[3];
+  if (cumulative)
+    for (Data3D& d : disp)
+      if (!d.Allocate(width, height, depth)) return 2;
+  auto write_disp = [&](size_t k) {
+    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
+    disp[0].WriteRAWToFileF32((tag + "_disp-u" + suffix).c_str());
+    disp[1].WriteRAWToFileF32((tag + "_disp-v" + suffix).c_str());
+    disp[2].WriteRAWToFileF32((tag + "_disp-w" + suffix).c_str());
+    if (write_vtk) Data3D::WriteFlowToFileVTK((tag + "_disp.vtk").c_str(), disp[0], disp[1], disp[2]);
+    const float* u = disp[0].DataPtr();
+    const size_t n = width * height * depth;
+    size_t lost = 0;
+    for (size_t i = 0; i < n; ++i) lost += std::isnan(u[i]) ? 1 : 0;
+    std::printf("displacement frame 0 -> frame %zu: %zu of %zu voxels have left the volume\n", k + 1, lost, n);
+  };
 
   if (pairs == 1) {
     if (!synthetic && !load(frame_1, files[1])) return 2;
@@ -260,6 +287,12 @@ int main(int argc, char** argv)
     if (print_stats) report();
     optical_flow_e.DownloadFlow(flow_u, flow_v, flow_w);
     write_pair(0, flow_u, flow_v, flow_w);
+    if (cumulative) {
+      if (!optical_flow_e.ResetTrajectory() || !optical_flow_e.ComposeTrajectory() ||
+          !optical_flow_e.DownloadTrajectory(disp[0], disp[1], disp[2], nullptr))
+        return 3;
+      write_disp(0);
+    }
   } else {
     // Sequence: pair k solves on the device while the host reads frame k+2 and uploads it on one copy queue, and downloads and
     // writes the flow of pair k-1 on another -- from and to page-locked buffers (the reference's ALLOCATE_PINNED_MEMORY switch,
@@ -283,6 +316,8 @@ int main(int argc, char** argv)
     for (Data3D& f : host_frame) pin(f);
     for (auto& set : host_flow)
       for (Data3D& f : set) pin(f);
+    if (cumulative)
+      for (Data3D& d : disp) pin(d);
     f3d_queue up = nullptr, down = nullptr;
     f3d_event uploaded[3] = {nullptr, nullptr, nullptr};
     if (CheckDeviceError(f3d_queue_create(&up)) || CheckDeviceError(f3d_queue_create(&down))) return 3;
@@ -297,6 +332,14 @@ int main(int argc, char** argv)
       return true;
     };
     if (!upload(0) || !upload(1)) return 2;
+    // --cumulative: displacement k is composed on the library stream after pair k and goes down on `down` beside the next solve.
+    // Two device-side dependencies: the download of displacement k waits for compose k (`composed`), and compose k+1, which
+    // rewrites the same containers in place, waits for that download to finish (`disp_down`).
+    f3d_event composed = nullptr, disp_down = nullptr;
+    if (cumulative) {
+      if (CheckDeviceError(f3d_event_create(&composed)) || CheckDeviceError(f3d_event_create(&disp_down))) return 3;
+      if (!optical_flow_e.ResetTrajectory()) return 3;
+    }
     DevicePtr taken[3] = {0, 0, 0};
     bool pending_output = false;
     const bool serial_sequence = std::getenv("F3D_SEQ_SERIAL") && std::atoi(std::getenv("F3D_SEQ_SERIAL")) != 0;
@@ -313,6 +356,7 @@ int main(int argc, char** argv)
         CheckDeviceError(f3d_queue_sync(down));
         optical_flow_e.GiveResultBack(taken);
         write_pair(k - 1, host_flow[(k - 1) & 1][0], host_flow[(k - 1) & 1][1], host_flow[(k - 1) & 1][2]);
+        if (cumulative) write_disp(k - 1);
         pending_output = false;
       }
       optical_flow_e.EndComputeFlowResident();
@@ -322,11 +366,26 @@ int main(int argc, char** argv)
       for (int i = 0; i < 3; ++i)
         CheckDeviceError(f3d_copy_planes_d2h_on(down, host_flow[k & 1][i].DataPtr(), width, height, width, height, depth, taken[i],
                                                 c.pitch, c.height, 0));
+      if (cumulative) {
+        if (k > 0) CheckDeviceError(f3d_queue_wait_event(nullptr, disp_down));
+        if (!optical_flow_e.ComposeTrajectory(taken)) return 3;
+        CheckDeviceError(f3d_event_record(composed));
+        CheckDeviceError(f3d_queue_wait_event(down, composed));
+        for (int i = 0; i < 3; ++i)
+          CheckDeviceError(f3d_copy_planes_d2h_on(down, disp[i].DataPtr(), width, height, width, height, depth,
+                                                  optical_flow_e.TrajectoryContainer(i), c.pitch, c.height, 0));
+        CheckDeviceError(f3d_event_record_on(disp_down, down));
+      }
       pending_output = true;
     }
     CheckDeviceError(f3d_queue_sync(down));
     optical_flow_e.GiveResultBack(taken);
     write_pair(pairs - 1, host_flow[(pairs - 1) & 1][0], host_flow[(pairs - 1) & 1][1], host_flow[(pairs - 1) & 1][2]);
+    if (cumulative) {
+      write_disp(pairs - 1);
+      f3d_event_destroy(composed);
+      f3d_event_destroy(disp_down);
+    }
     CheckDeviceError(f3d_queue_sync(up));
     for (f3d_event e : uploaded) f3d_event_destroy(e);
     f3d_queue_destroy(up);

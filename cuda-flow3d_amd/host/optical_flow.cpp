@@ -12,6 +12,12 @@
 #include "operator_calls.h"
 #include "hip_utils.h"
 
+// Declared weak: the host library keeps loading against a device library that lacks the entry (the address is then null and the
+// trajectory calls fail with a message instead of the whole library failing to load).
+extern "C" int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr acc_w, f3d_devptr inc_u, f3d_devptr inc_v,
+                                f3d_devptr inc_w, size_t width, size_t height, size_t depth, unsigned long long* lost)
+    __attribute__((weak));
+
 // ---- base --------------------------------------------------------------------------------------------------
 
 size_t OpticalFlowBase::GetMaxWarpLevel(size_t width, size_t height, size_t depth, float scale_factor)
@@ -377,6 +383,94 @@ bool OpticalFlowE::FinalResidual(Residual& registered, Residual& unregistered)
   return ok;
 }
 
+// ---- trajectory of a frame sequence ------------------------------------------------------------------------------------------
+
+bool OpticalFlowE::TrajectoryFail(const char* what)
+{
+  trajectory_error_ = std::string("'") + GetName() + "': " + what;
+  std::printf("Error: %s\n", trajectory_error_.c_str());
+  return false;
+}
+
+bool OpticalFlowE::AllocateTrajectory()
+{
+  trajectory_error_.clear();
+  if (!f3d_compose_flow) return TrajectoryFail("the device library has no f3d_compose_flow (trajectory composition)");
+  if (!initialized_) return TrajectoryFail("the driver was not initialized");
+  if (trajectory_[0]) return true;
+  const size_t rows = dev_container_size_.height * dev_container_size_.depth;
+  for (DevicePtr& p : trajectory_) {
+    size_t pitch = 0;
+    if (f3d_alloc_pitched(&p, &pitch, dev_container_size_.width * sizeof(float), rows) != 0) p = 0;
+    if (!p || pitch != dev_container_size_.pitch) {
+      ReleaseTrajectory();
+      return TrajectoryFail("the three trajectory containers do not fit beside the driver's on the device");
+    }
+  }
+  return true;
+}
+
+bool OpticalFlowE::ResetTrajectory()
+{
+  if (!AllocateTrajectory()) return false;
+  const size_t rows = dev_container_size_.height * dev_container_size_.depth;
+  for (DevicePtr p : trajectory_)
+    if (CheckDeviceError(f3d_memset2d(p, dev_container_size_.pitch, 0, dev_container_size_.width * sizeof(float), rows)))
+      return TrajectoryFail(f3d_last_error());
+  return true;
+}
+
+bool OpticalFlowE::ComposeTrajectory()
+{
+  if (!result_flow_[0]) {
+    trajectory_error_.clear();
+    return TrajectoryFail("no flow is held on the device (ComputeFlowResident first)");
+  }
+  const DevicePtr flow[3] = {result_flow_[0], result_flow_[1], result_flow_[2]};
+  return ComposeTrajectory(flow);
+}
+
+bool OpticalFlowE::ComposeTrajectory(const DevicePtr (&flow)[3])
+{
+  trajectory_error_.clear();
+  if (!f3d_compose_flow) return TrajectoryFail("the device library has no f3d_compose_flow (trajectory composition)");
+  if (!trajectory_[0]) return TrajectoryFail("the trajectory was not started (ResetTrajectory first)");
+  if (!flow[0] || !flow[1] || !flow[2]) return TrajectoryFail("no flow to compose");
+  const f3d_size4 c = {dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, dev_container_size_.pitch};
+  if (CheckDeviceError(f3d_set_container(&c)) ||
+      CheckDeviceError(f3d_compose_flow(trajectory_[0], trajectory_[1], trajectory_[2], flow[0], flow[1], flow[2],
+                                        dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, nullptr)))
+    return TrajectoryFail(f3d_last_error());
+  return true;
+}
+
+bool OpticalFlowE::DownloadTrajectory(Data3D& u, Data3D& v, Data3D& w, unsigned long long* lost)
+{
+  trajectory_error_.clear();
+  if (!trajectory_[0]) return TrajectoryFail("the trajectory was not started (ResetTrajectory first)");
+  Data3D* out[3] = {&u, &v, &w};
+  for (int c = 0; c < 3; ++c)
+    if (CheckDeviceError(f3d_copy3d_d2h(out[c]->DataPtr(), out[c]->Width(), out[c]->Height(), out[c]->Depth(), trajectory_[c],
+                                        dev_container_size_.pitch, dev_container_size_.height, 0)))
+      return TrajectoryFail(f3d_last_error());
+  if (lost) {
+    const float* p = u.DataPtr();
+    const size_t n = u.Width() * u.Height() * u.Depth();
+    unsigned long long count = 0;
+    for (size_t i = 0; i < n; ++i) count += std::isnan(p[i]) ? 1 : 0;
+    *lost = count;
+  }
+  return true;
+}
+
+void OpticalFlowE::ReleaseTrajectory()
+{
+  for (DevicePtr& p : trajectory_) {
+    if (p) CheckDeviceError(f3d_free(p));
+    p = 0;
+  }
+}
+
 // The coarse-to-fine solve on two frames that are already on the device (optical_flow_e.cpp:208-533 is the sequence of operator
 // calls this reproduces: pre-blur; per level frames from the originals, flow from the level before, registration, solve, update,
 // median).  Containers are named by what they hold:
@@ -541,6 +635,7 @@ void OpticalFlowE::Destroy()
 {
   for (CudaOperationBase* cuop : cuda_operations_) cuop->Destroy();
   ReleaseResult();
+  ReleaseTrajectory();
   size_t freed = 0;
   while (!free_containers_.empty()) {
     CheckDeviceError(f3d_free(free_containers_.back()));

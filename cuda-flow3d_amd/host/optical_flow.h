@@ -3,6 +3,7 @@
 #ifndef F3D_HOST_OPTICAL_FLOW_H_
 #define F3D_HOST_OPTICAL_FLOW_H_
 
+#include <string>
 #include <vector>
 
 #include "data_types.h"
@@ -100,6 +101,20 @@ class OpticalFlowE : public OpticalFlowBase {
   // original frame_0, and the same difference without any flow.  Needs the resident raw frames and a computed flow.
   bool FinalResidual(Residual& registered, Residual& unregistered);
 
+  // Trajectory of a frame sequence: the displacement of every voxel of frame 0 to the frame the sequence has reached (Lagrangian,
+  // frame 0's grid, voxel units), kept in three containers of its own that are allocated on request and freed by Destroy().  Each
+  // pair's flow is composed into it on the device (f3d_compose_flow: acc += flow sampled at x + acc; a point that leaves the
+  // volume becomes NaN and stays NaN).  Compose enqueues on the library stream and does not wait.  Every call returns false with
+  // TrajectoryError() set when it cannot run -- among other reasons when the device library lacks f3d_compose_flow.
+  bool AllocateTrajectory();                                        // three containers; false with a message when they do not fit
+  bool ResetTrajectory();                                           // allocates on first use, then zero
+  bool ComposeTrajectory();                                         // with the flow ComputeFlowResident() left on the device
+  bool ComposeTrajectory(const DevicePtr (&flow)[3]);               // with three given containers (TakeResult's)
+  bool DownloadTrajectory(Data3D& u, Data3D& v, Data3D& w, unsigned long long* lost);  // lost: voxels whose u is NaN
+  DevicePtr TrajectoryContainer(int component) const { return trajectory_[component]; }
+  void ReleaseTrajectory();
+  const std::string& TrajectoryError() const { return trajectory_error_; }
+
  private:
   static constexpr size_t kContainers = 15;  // optical_flow_e.h:40
 
@@ -118,6 +133,9 @@ class OpticalFlowE : public OpticalFlowBase {
   f3d_event ev_begin_ = nullptr, ev_end_ = nullptr;
   DevicePtr result_flow_[3] = {0, 0, 0};
   float last_device_seconds_ = 0.f;
+  DevicePtr trajectory_[3] = {0, 0, 0};
+  std::string trajectory_error_;
+  bool TrajectoryFail(const char* what);
   std::vector<LevelStatistics> level_stats_;
   bool ResidualOf(DevicePtr frame_0, DevicePtr warped, const DataSize4& size, Residual& out);
 

@@ -424,6 +424,18 @@ int f3d_flow_stats(f3d_devptr flow_u, f3d_devptr flow_v, f3d_devptr flow_w, size
 int f3d_residual_stats(f3d_devptr frame_0, f3d_devptr frame_1_warped, size_t width, size_t height, size_t depth,
                        const f3d_slab* slab, double* sum_squares, double* sum_abs, float* max_abs);
 
+/* Trajectory step (no reference counterpart: the reference writes the flow of each consecutive pair, src/main.cpp:132-185).
+ * acc = (acc_u, acc_v, acc_w) is the displacement of every voxel of frame 0 so far (frame 0's grid, voxel units); inc is the flow
+ * of the next pair, defined on the grid of the frame the points have reached.  For every voxel (x, y, z), in place:
+ *   p = (x + acc_u, y + acc_v, z + acc_w)            (one float add per axis)
+ *   p NaN, or outside [0, width-1] x [0, height-1] x [0, depth-1]:  acc = (NaN, NaN, NaN)   (the point is lost and stays lost)
+ *   else:  acc += inc sampled trilinearly at p       (f3d_warp's sample, src/kernels/registration_3d.cu:66-79, same order)
+ * Starting from acc = 0 the first step gives inc back exactly.  Geometry from the current container (f3d_set_container), whole
+ * volume, library stream.  No acc component may be an inc component.  lost (nullable): the number of voxels whose acc_u is NaN
+ * after the step; asking for it waits for the stream, passing NULL does not. */
+int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr acc_w, f3d_devptr inc_u, f3d_devptr inc_v,
+                     f3d_devptr inc_w, size_t width, size_t height, size_t depth, unsigned long long* lost);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,22 @@ int f3d_flow_level_stat(f3d_flow flow, size_t index, f3d_level_stat* out);  /* i
 /* residual of the ORIGINAL frame_1 registered with the flow on the device (h = 1) against the original frame_0, and of the pair
  * as it stands; values: rms, mean |.|, max |.| each.  Needs f3d_flow_upload + f3d_flow_compute_resident. */
 int f3d_flow_final_residual(f3d_flow flow, double registered[3], double unregistered[3]);
+/* Trajectory of a frame sequence (the displacement of every voxel of frame 0 to the frame the sequence has reached: frame 0's grid,
+ * voxel units; f3d_compose_flow of include/f3d.h is the step).  Per pair: f3d_flow_upload + f3d_flow_compute_resident, then
+ * f3d_flow_trajectory_append composes the flow the driver holds into the trajectory on the device.  f3d_flow_compute releases its
+ * result, so it is no source.
+ *   begin     allocates three containers on first use (fails when they do not fit), then sets the trajectory to zero
+ *   append    an error before begin or when no flow is held; enqueues and returns
+ *   download  u, v, w receive width*height*depth floats; lost (nullable) the number of voxels whose u is NaN (left the volume)
+ *   end       frees the three containers (f3d_flow_destroy does too)
+ * A device library without f3d_compose_flow still loads; then every call fails.  Failures of these calls are described by
+ * f3d_host_last_error(). */
+int f3d_flow_trajectory_begin(f3d_flow flow);
+int f3d_flow_trajectory_append(f3d_flow flow);
+int f3d_flow_trajectory_download(f3d_flow flow, float* u, float* v, float* w, unsigned long long* lost);
+int f3d_flow_trajectory_end(f3d_flow flow);
+/* message of this thread's last call that failed in the host library itself; f3d_last_error() when there is none */
+const char* f3d_host_last_error(void);
 int f3d_flow_destroy(f3d_flow flow);
 
 /* name: "add" | "convolution" | "median" | "registration" | "resample" | "solve" */
