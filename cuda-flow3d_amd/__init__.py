@@ -42,6 +42,14 @@ class LevelStat(C.Structure):  # f3d_level_stat
                 ("flow_min", C.c_float), ("flow_max", C.c_float), ("flow_avg", C.c_float)]
 
 
+class StrainStats(C.Structure):  # f3d_strain_stats
+    _fields_ = [("defined", C.c_ulonglong), ("folded", C.c_ulonglong), ("vol_min", C.c_float), ("vol_max", C.c_float),
+                ("eq_max", C.c_float), ("vol_sum", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class FlowParams(C.Structure):  # f3d_flow_params
     _fields_ = [
         ("warp_levels_count", C.c_size_t), ("warp_scale_factor", C.c_float),
@@ -208,6 +216,8 @@ def host():
         "f3d_flow_trajectory_begin": [C.c_void_p], "f3d_flow_trajectory_append": [C.c_void_p],
         "f3d_flow_trajectory_download": [C.c_void_p, _fp, _fp, _fp, C.POINTER(C.c_ulonglong)],
         "f3d_flow_trajectory_end": [C.c_void_p],
+        "f3d_flow_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(StrainStats)],
+        "f3d_flow_strain_end": [C.c_void_p],
         "f3d_op_create": [C.POINTER(C.c_void_p), C.c_char_p], "f3d_op_initialize": [C.c_void_p, C.POINTER(Size4)],
         "f3d_op_execute": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), _sz],
         "f3d_op_execute_batch": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(_sz), _sz],
@@ -344,6 +354,68 @@ def compose_flow(acc, inc):
             hip().f3d_set_container(C.byref(previous))
         box.free()
     return out + (int(lost.value),)
+
+
+# the eight outputs of f3d_flow_strain in ABI order, and the F3D_STRAIN_* group of each
+STRAIN_NAMES = ("vol", "exx", "eyy", "ezz", "exy", "exz", "eyz", "eq")
+STRAIN_GROUPS = {"vol": 1, "e": 2, "eq": 4}
+_STRAIN_GROUP_OF = (1, 2, 2, 2, 2, 2, 2, 4)
+
+
+def _strain_mask(fields):
+    """F3D_STRAIN_* bits of an iterable of group names ("vol", "e", "eq") or of a comma-separated string of them"""
+    if isinstance(fields, str):
+        fields = fields.split(",")
+    mask = 0
+    for f in fields:
+        if f not in STRAIN_GROUPS:
+            raise ValueError(f"unknown strain group {f!r} (one of {', '.join(STRAIN_GROUPS)})")
+        mask |= STRAIN_GROUPS[f]
+    if not mask:
+        raise ValueError("no strain group selected")
+    return mask
+
+
+def _strain_entry():
+    """f3d_flow_strain of the device library, declared on first use like f3d_compose_flow (_compose_entry)"""
+    L = hip()
+    try:
+        fn = L.f3d_flow_strain
+    except AttributeError:
+        raise F3dError(f"{os.path.join(_LIBDIR, 'libf3d_hip.so')} has no f3d_flow_strain: this device library cannot compute "
+                       "strain fields") from None
+    fn.argtypes = [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(StrainStats)]
+    fn.restype = C.c_int
+    return fn
+
+
+def flow_strain(u, v, w, fields=("vol", "e", "eq")):
+    """Strain fields of a displacement on the device (include/f3d.h, f3d_flow_strain) for volumes from anywhere: u, v, w numpy
+    [z, y, x] float32 in voxel units (a pair's flow, a cumulative displacement, the out-of-core or z-slab drivers' results when they
+    fit on one device).  fields: groups "vol" (J - 1), "e" (Green-Lagrange exx .. eyz), "eq" (equivalent strain).  Returns a dict
+    name -> array for the selected outputs and "stats" -> dict (defined, folded, vol_min, vol_max, eq_max, vol_sum)."""
+    fn = _strain_entry()
+    mask = _strain_mask(fields)
+    d3 = [np.ascontiguousarray(a, dtype=np.float32) for a in (u, v, w)]
+    if any(a.ndim != 3 or a.shape != d3[0].shape for a in d3):
+        raise ValueError("u, v and w must be three [z, y, x] volumes of one shape")
+    d, h, wd = d3[0].shape
+    box = Containers(wd, h, d)
+    previous = Size4()
+    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
+    try:
+        pin = [box.new(a) for a in d3]
+        outs = [box.alloc() if mask & g else 0 for g in _STRAIN_GROUP_OF]
+        box.set_current()
+        stats = StrainStats()
+        check(fn(*pin, (_dp * 8)(*outs), mask, wd, h, d, C.byref(stats)), "f3d_flow_strain")
+        res = {n: box.download(p, (wd, h, d)) for n, p in zip(STRAIN_NAMES, outs) if p}
+    finally:
+        if previous.pitch:   # the geometry of whoever set one before (a driver on this lane)
+            hip().f3d_set_container(C.byref(previous))
+        box.free()
+    res["stats"] = stats.as_dict()
+    return res
 
 
 def _f32(a):
@@ -834,6 +906,28 @@ class OpticalFlow:
 
     def trajectory_end(self):
         _host_check(host().f3d_flow_trajectory_end(self._h), "f3d_flow_trajectory_end")
+
+    # ---- strain fields (include/f3d_host.h, f3d_flow_strain_*) ----
+    def strain(self, source="flow", fields=("vol", "e", "eq")):
+        """Strain fields of the flow the driver holds (source="flow", after compute_resident) or of the trajectory
+        (source="trajectory", after trajectory_begin); same result shape as flow_strain().  Works between the yields of
+        compute_sequence, where the driver holds both."""
+        src = {"flow": 0, "trajectory": 1}.get(source)
+        if src is None:
+            raise ValueError(f"source must be 'flow' or 'trajectory', not {source!r}")
+        mask = _strain_mask(fields)
+        w, h, d = self.dims
+        arrays = [np.empty((d, h, w), np.float32) if mask & g else None for g in _STRAIN_GROUP_OF]
+        ptrs = (_fp * 8)(*[a.ctypes.data_as(_fp) if a is not None else None for a in arrays])
+        stats = StrainStats()
+        _host_check(host().f3d_flow_strain_compute(self._h, src, mask, ptrs, C.byref(stats)), "f3d_flow_strain_compute")
+        res = {n: a for n, a in zip(STRAIN_NAMES, arrays) if a is not None}
+        res["stats"] = stats.as_dict()
+        return res
+
+    def strain_end(self):
+        """free the strain containers (destroy() does too)"""
+        _host_check(host().f3d_flow_strain_end(self._h), "f3d_flow_strain_end")
 
     def compute_sequence(self, frames, cumulative=False, silent=True, **kw):
         """Generator over the consecutive pairs of `frames` (an iterable of [z, y, x] volumes): yields (k, (u, v, w), disp) for

@@ -1,5 +1,6 @@
 // C ABI of the host side (include/f3d_host.h): thin, exception-free wrappers over the C++ classes.
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -229,6 +230,37 @@ int f3d_flow_trajectory_end(f3d_flow flow)
   if (!flow) return HostFail("f3d_flow_trajectory_end: null driver");
   flow->driver.ReleaseTrajectory();
   flow->trajectory_started = false;
+  return 0;
+}
+
+int f3d_flow_strain_compute(f3d_flow flow, int source, unsigned fields, float* const out[8], f3d_strain_stats* stats)
+{
+  g_host_error.clear();
+  if (!flow || !out) return HostFail("f3d_flow_strain_compute: null argument");
+  if (source != F3D_STRAIN_OF_FLOW && source != F3D_STRAIN_OF_TRAJECTORY)
+    return HostFail("f3d_flow_strain_compute: source must be F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY");
+  if (source == F3D_STRAIN_OF_TRAJECTORY && !flow->trajectory_started)
+    return HostFail("f3d_flow_strain_compute: no trajectory is active (f3d_flow_trajectory_begin first)");
+  OpticalFlowE& d = flow->driver;
+  const bool ok = source == F3D_STRAIN_OF_FLOW ? d.ComputeStrain(fields, stats) : d.ComputeStrainOfTrajectory(fields, stats);
+  if (!ok) return HostFail(d.StrainError().c_str());
+  const DataSize4& c = d.ContainerSize();
+  std::unique_ptr<Data3D> views[8];
+  Data3D* dst[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 8; ++i)
+    if (out[i]) {
+      views[i].reset(new Data3D(out[i], c.width, c.height, c.depth));
+      dst[i] = views[i].get();
+    }
+  if (!d.DownloadStrain(dst, fields)) return HostFail(d.StrainError().c_str());
+  return 0;
+}
+
+int f3d_flow_strain_end(f3d_flow flow)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_strain_end: null driver");
+  flow->driver.ReleaseStrain();
   return 0;
 }
 

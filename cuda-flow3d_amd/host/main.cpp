@@ -5,6 +5,7 @@
 // flags:  flow3d --dims W H D --frames f0.raw f1.raw [f2.raw ...] [--f32] [--out prefix] [--levels N] [--scale s]
 //                [--outer N] [--inner N] [--alpha a] [--eps-smooth e] [--eps-data e] [--median r] [--sigma s]
 //                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
+//                [--strain vol,e,eq]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -17,6 +18,10 @@
 // --cumulative (resident driver, pairs in order) also composes every pair's flow into the displacement of each voxel of frame 0 on
 // the device (f3d_compose_flow) and writes <prefix>_<k>_disp-{u,v,w}-W-H-D.raw: frame 0 -> frame k+1 on frame 0's grid, NaN where
 // the point has left the volume.
+// --strain LIST (resident driver, pairs in order; LIST a comma-separated subset of vol,e,eq) also differentiates every pair's flow --
+// with --cumulative the displacement frame 0 -> frame k+1 instead -- on the device (f3d_flow_strain) and writes the selected fields
+// as <tag>_strain-{vol | exx,eyy,ezz,exy,exz,eyz | eq}-W-H-D.raw with the flow's (or the displacement's) tag, and one line of
+// statistics per pair.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -39,7 +44,7 @@ static void Usage()
   std::printf("usage: flow3d --dims W H D (--frames f0.raw f1.raw [f2.raw ...] [--f32] | --synthetic) [--out prefix]\n"
               "              [--levels N] [--scale s] [--outer N] [--inner N] [--alpha a] [--eps-smooth e]\n"
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
-              "              [--concurrent N] [--cumulative]\n");
+              "              [--concurrent N] [--cumulative] [--strain vol,e,eq]\n");
 }
 
 int main(int argc, char** argv)
@@ -50,6 +55,7 @@ int main(int argc, char** argv)
   bool f32_input = false, synthetic = false, write_vtk = false, silent_mode = false, print_stats = false;
   bool use_partial_gpu = false, partial_full = false, cumulative = false;
   size_t concurrent = 1;
+  unsigned strain_fields = 0;  // --strain: F3D_STRAIN_* groups
 
   // defaults of src/main.cpp:77-85
   size_t warp_levels_count = 40;
@@ -95,6 +101,21 @@ int main(int argc, char** argv)
     else if (a == "--budget-mb") { need(1); setenv("F3D_P_BUDGET_MB", argv[++i], 1); }
     else if (a == "--concurrent") { need(1); concurrent = std::strtoull(argv[++i], nullptr, 10); }
     else if (a == "--cumulative") cumulative = true;
+    else if (a == "--strain") {
+      need(1);
+      const std::string list = argv[++i];
+      size_t at = 0;
+      while (true) {
+        const size_t end = list.find(',', at);
+        const std::string item = list.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        if (item == "vol") strain_fields |= F3D_STRAIN_VOL;
+        else if (item == "e") strain_fields |= F3D_STRAIN_E;
+        else if (item == "eq") strain_fields |= F3D_STRAIN_EQ;
+        else { Usage(); return 64; }
+        if (end == std::string::npos) break;
+        at = end + 1;
+      }
+    }
     else { Usage(); return 64; }
   }
   if (width == 0 || height == 0 || depth == 0 || (!synthetic && files.size() < 2)) {
@@ -103,6 +124,11 @@ int main(int argc, char** argv)
   }
   if (cumulative && (use_partial_gpu || concurrent > 1)) {
     std::printf("--cumulative needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    return 64;
+  }
+  if (strain_fields && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--strain needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
                 use_partial_gpu ? "--partial" : "--concurrent N > 1");
     return 64;
   }
@@ -279,6 +305,30 @@ int main(int argc, char** argv)
     for (size_t i = 0; i < n; ++i) lost += std::isnan(u[i]) ? 1 : 0;
     std::printf("displacement frame 0 -> frame %zu: %zu of %zu voxels have left the volume\n", k + 1, lost, n);
   };
+  // --strain: the selected fields of pair k (of its flow, or with --cumulative of the displacement frame 0 -> frame k+1) and the
+  // statistics the device computed with them
+  static const char* const strain_names[8] = {"vol", "exx", "eyy", "ezz", "exy", "exz", "eyz", "eq"};
+  auto strain_selected = [&](int i) {
+    return (strain_fields & (i == 0 ? F3D_STRAIN_VOL : (i == 7 ? F3D_STRAIN_EQ : F3D_STRAIN_E))) != 0;
+  };
+  Data3D strain_host[8];
+  Data3D* strain_out[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 8; ++i)
+    if (strain_selected(i)) {
+      if (!strain_host[i].Allocate(width, height, depth)) return 2;
+      strain_out[i] = &strain_host[i];
+    }
+  f3d_strain_stats strain_stats = {};
+  auto write_strain = [&](size_t k) {
+    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
+    for (int i = 0; i < 8; ++i)
+      if (strain_out[i]) strain_host[i].WriteRAWToFileF32((tag + "_strain-" + strain_names[i] + suffix).c_str());
+    const f3d_strain_stats& st = strain_stats;
+    const double mean = st.defined ? st.vol_sum / static_cast<double>(st.defined) : std::nan("");
+    std::printf("strain frame %zu -> frame %zu: vol min/mean/max %.6g/%.6g/%.6g, eq max %.6g, %llu folded, %llu undefined of %zu "
+                "voxels\n", cumulative ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max, st.eq_max, st.folded,
+                static_cast<unsigned long long>(width * height * depth) - st.defined, width * height * depth);
+  };
 
   if (pairs == 1) {
     if (!synthetic && !load(frame_1, files[1])) return 2;
@@ -292,6 +342,12 @@ int main(int argc, char** argv)
           !optical_flow_e.DownloadTrajectory(disp[0], disp[1], disp[2], nullptr))
         return 3;
       write_disp(0);
+    }
+    if (strain_fields) {
+      const bool ok = cumulative ? optical_flow_e.ComputeStrainOfTrajectory(strain_fields, &strain_stats)
+                                 : optical_flow_e.ComputeStrain(strain_fields, &strain_stats);
+      if (!ok || !optical_flow_e.DownloadStrain(strain_out, strain_fields)) return 3;
+      write_strain(0);
     }
   } else {
     // Sequence: pair k solves on the device while the host reads frame k+2 and uploads it on one copy queue, and downloads and
@@ -318,6 +374,8 @@ int main(int argc, char** argv)
       for (Data3D& f : set) pin(f);
     if (cumulative)
       for (Data3D& d : disp) pin(d);
+    for (Data3D* d : strain_out)
+      if (d) pin(*d);
     f3d_queue up = nullptr, down = nullptr;
     f3d_event uploaded[3] = {nullptr, nullptr, nullptr};
     if (CheckDeviceError(f3d_queue_create(&up)) || CheckDeviceError(f3d_queue_create(&down))) return 3;
@@ -340,6 +398,12 @@ int main(int argc, char** argv)
       if (CheckDeviceError(f3d_event_create(&composed)) || CheckDeviceError(f3d_event_create(&disp_down))) return 3;
       if (!optical_flow_e.ResetTrajectory()) return 3;
     }
+    // --strain: the same pattern for the strain containers.  Strain k runs on the library stream right after compose k (or after
+    // TakeResult); its statistics wait for that kernel only.  The fields go down on `down` beside solve k+1 once strain k is done
+    // (`strained`), and strain k+1, which rewrites the same containers, waits for that download (`strain_down`).
+    f3d_event strained = nullptr, strain_down = nullptr;
+    if (strain_fields)
+      if (CheckDeviceError(f3d_event_create(&strained)) || CheckDeviceError(f3d_event_create(&strain_down))) return 3;
     DevicePtr taken[3] = {0, 0, 0};
     bool pending_output = false;
     const bool serial_sequence = std::getenv("F3D_SEQ_SERIAL") && std::atoi(std::getenv("F3D_SEQ_SERIAL")) != 0;
@@ -357,6 +421,7 @@ int main(int argc, char** argv)
         optical_flow_e.GiveResultBack(taken);
         write_pair(k - 1, host_flow[(k - 1) & 1][0], host_flow[(k - 1) & 1][1], host_flow[(k - 1) & 1][2]);
         if (cumulative) write_disp(k - 1);
+        if (strain_fields) write_strain(k - 1);
         pending_output = false;
       }
       optical_flow_e.EndComputeFlowResident();
@@ -376,6 +441,19 @@ int main(int argc, char** argv)
                                                   optical_flow_e.TrajectoryContainer(i), c.pitch, c.height, 0));
         CheckDeviceError(f3d_event_record_on(disp_down, down));
       }
+      if (strain_fields) {
+        if (k > 0) CheckDeviceError(f3d_queue_wait_event(nullptr, strain_down));
+        const bool ok = cumulative ? optical_flow_e.ComputeStrainOfTrajectory(strain_fields, &strain_stats)
+                                   : optical_flow_e.ComputeStrain(taken, strain_fields, &strain_stats);
+        if (!ok) return 3;
+        CheckDeviceError(f3d_event_record(strained));
+        CheckDeviceError(f3d_queue_wait_event(down, strained));
+        for (int i = 0; i < 8; ++i)
+          if (strain_out[i])
+            CheckDeviceError(f3d_copy_planes_d2h_on(down, strain_host[i].DataPtr(), width, height, width, height, depth,
+                                                    optical_flow_e.StrainContainer(i), c.pitch, c.height, 0));
+        CheckDeviceError(f3d_event_record_on(strain_down, down));
+      }
       pending_output = true;
     }
     CheckDeviceError(f3d_queue_sync(down));
@@ -385,6 +463,11 @@ int main(int argc, char** argv)
       write_disp(pairs - 1);
       f3d_event_destroy(composed);
       f3d_event_destroy(disp_down);
+    }
+    if (strain_fields) {
+      write_strain(pairs - 1);
+      f3d_event_destroy(strained);
+      f3d_event_destroy(strain_down);
     }
     CheckDeviceError(f3d_queue_sync(up));
     for (f3d_event e : uploaded) f3d_event_destroy(e);

@@ -17,6 +17,8 @@
 extern "C" int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr acc_w, f3d_devptr inc_u, f3d_devptr inc_v,
                                 f3d_devptr inc_w, size_t width, size_t height, size_t depth, unsigned long long* lost)
     __attribute__((weak));
+extern "C" int f3d_flow_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[8], unsigned fields, size_t width,
+                               size_t height, size_t depth, f3d_strain_stats* stats) __attribute__((weak));
 
 // ---- base --------------------------------------------------------------------------------------------------
 
@@ -471,6 +473,96 @@ void OpticalFlowE::ReleaseTrajectory()
   }
 }
 
+// ---- strain fields of a displacement ------------------------------------------------------------------------------------------
+
+namespace {
+
+// the F3D_STRAIN_* group of output i (vol, exx .. eyz, eq)
+unsigned StrainGroup(int i) { return i == 0 ? F3D_STRAIN_VOL : (i == 7 ? F3D_STRAIN_EQ : F3D_STRAIN_E); }
+
+}  // namespace
+
+bool OpticalFlowE::StrainFail(const char* what)
+{
+  strain_error_ = std::string("'") + GetName() + "': " + what;
+  std::printf("Error: %s\n", strain_error_.c_str());
+  return false;
+}
+
+bool OpticalFlowE::AllocateStrain(unsigned fields)
+{
+  const size_t rows = dev_container_size_.height * dev_container_size_.depth;
+  for (int i = 0; i < 8; ++i) {
+    if (!(fields & StrainGroup(i)) || strain_[i]) continue;
+    size_t pitch = 0;
+    if (f3d_alloc_pitched(&strain_[i], &pitch, dev_container_size_.width * sizeof(float), rows) != 0) strain_[i] = 0;
+    if (!strain_[i] || pitch != dev_container_size_.pitch) {
+      ReleaseStrain();
+      return StrainFail("the strain containers do not fit beside the driver's on the device");
+    }
+  }
+  return true;
+}
+
+bool OpticalFlowE::ComputeStrain(const DevicePtr (&disp)[3], unsigned fields, f3d_strain_stats* stats)
+{
+  strain_error_.clear();
+  if (!f3d_flow_strain) return StrainFail("the device library has no f3d_flow_strain (strain fields)");
+  if (!initialized_) return StrainFail("the driver was not initialized");
+  if (!disp[0] || !disp[1] || !disp[2]) return StrainFail("no displacement to differentiate");
+  if (fields == 0 || (fields & ~(F3D_STRAIN_VOL | F3D_STRAIN_E | F3D_STRAIN_EQ)))
+    return StrainFail("fields must be a non-empty combination of F3D_STRAIN_VOL, F3D_STRAIN_E, F3D_STRAIN_EQ");
+  if (!AllocateStrain(fields)) return false;
+  const f3d_size4 c = {dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, dev_container_size_.pitch};
+  if (CheckDeviceError(f3d_set_container(&c)) ||
+      CheckDeviceError(f3d_flow_strain(disp[0], disp[1], disp[2], strain_, fields, dev_container_size_.width,
+                                       dev_container_size_.height, dev_container_size_.depth, stats)))
+    return StrainFail(f3d_last_error());
+  return true;
+}
+
+bool OpticalFlowE::ComputeStrain(unsigned fields, f3d_strain_stats* stats)
+{
+  if (!result_flow_[0]) {
+    strain_error_.clear();
+    return StrainFail("no flow is held on the device (ComputeFlowResident first)");
+  }
+  const DevicePtr flow[3] = {result_flow_[0], result_flow_[1], result_flow_[2]};
+  return ComputeStrain(flow, fields, stats);
+}
+
+bool OpticalFlowE::ComputeStrainOfTrajectory(unsigned fields, f3d_strain_stats* stats)
+{
+  if (!trajectory_[0]) {
+    strain_error_.clear();
+    return StrainFail("the trajectory was not started (ResetTrajectory first)");
+  }
+  const DevicePtr disp[3] = {trajectory_[0], trajectory_[1], trajectory_[2]};
+  return ComputeStrain(disp, fields, stats);
+}
+
+bool OpticalFlowE::DownloadStrain(Data3D* const (&out)[8], unsigned fields)
+{
+  strain_error_.clear();
+  for (int i = 0; i < 8; ++i) {
+    if (!(fields & StrainGroup(i))) continue;
+    if (!strain_[i]) return StrainFail("a requested strain field has not been computed");
+    if (!out[i]) return StrainFail("no host volume for a requested strain field");
+    if (CheckDeviceError(f3d_copy3d_d2h(out[i]->DataPtr(), out[i]->Width(), out[i]->Height(), out[i]->Depth(), strain_[i],
+                                        dev_container_size_.pitch, dev_container_size_.height, 0)))
+      return StrainFail(f3d_last_error());
+  }
+  return true;
+}
+
+void OpticalFlowE::ReleaseStrain()
+{
+  for (DevicePtr& p : strain_) {
+    if (p) CheckDeviceError(f3d_free(p));
+    p = 0;
+  }
+}
+
 // The coarse-to-fine solve on two frames that are already on the device (optical_flow_e.cpp:208-533 is the sequence of operator
 // calls this reproduces: pre-blur; per level frames from the originals, flow from the level before, registration, solve, update,
 // median).  Containers are named by what they hold:
@@ -636,6 +728,7 @@ void OpticalFlowE::Destroy()
   for (CudaOperationBase* cuop : cuda_operations_) cuop->Destroy();
   ReleaseResult();
   ReleaseTrajectory();
+  ReleaseStrain();
   size_t freed = 0;
   while (!free_containers_.empty()) {
     CheckDeviceError(f3d_free(free_containers_.back()));

@@ -115,6 +115,19 @@ class OpticalFlowE : public OpticalFlowBase {
   void ReleaseTrajectory();
   const std::string& TrajectoryError() const { return trajectory_error_; }
 
+  // Strain fields of a displacement (f3d_flow_strain: vol = J - 1, Green-Lagrange E, equivalent strain; include/f3d.h has the
+  // definition).  Eight outputs in the order vol, exx, eyy, ezz, exy, exz, eyz, eq, selected in groups by F3D_STRAIN_* bits; each
+  // selected output gets a container of its own, allocated on first use and freed by ReleaseStrain() and Destroy().  Compute enqueues
+  // on the library stream and waits only when stats is given.  Every call returns false with StrainError() set when it cannot run --
+  // among other reasons when the device library lacks f3d_flow_strain.
+  bool ComputeStrain(const DevicePtr (&disp)[3], unsigned fields, f3d_strain_stats* stats);  // three given containers (TakeResult's)
+  bool ComputeStrain(unsigned fields, f3d_strain_stats* stats);                // of the flow ComputeFlowResident() left on the device
+  bool ComputeStrainOfTrajectory(unsigned fields, f3d_strain_stats* stats);    // of the trajectory (ResetTrajectory first)
+  DevicePtr StrainContainer(int field) const { return strain_[field]; }        // 0 until a computation has selected the field
+  bool DownloadStrain(Data3D* const (&out)[8], unsigned fields);               // the selected fields (entries of others ignored)
+  void ReleaseStrain();
+  const std::string& StrainError() const { return strain_error_; }
+
  private:
   static constexpr size_t kContainers = 15;  // optical_flow_e.h:40
 
@@ -136,6 +149,10 @@ class OpticalFlowE : public OpticalFlowBase {
   DevicePtr trajectory_[3] = {0, 0, 0};
   std::string trajectory_error_;
   bool TrajectoryFail(const char* what);
+  DevicePtr strain_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::string strain_error_;
+  bool StrainFail(const char* what);
+  bool AllocateStrain(unsigned fields);
   std::vector<LevelStatistics> level_stats_;
   bool ResidualOf(DevicePtr frame_0, DevicePtr warped, const DataSize4& size, Residual& out);
 

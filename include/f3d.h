@@ -436,6 +436,46 @@ int f3d_residual_stats(f3d_devptr frame_0, f3d_devptr frame_1_warped, size_t wid
 int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr acc_w, f3d_devptr inc_u, f3d_devptr inc_v,
                      f3d_devptr inc_w, size_t width, size_t height, size_t depth, unsigned long long* lost);
 
+/* Strain fields of a displacement (no reference counterpart: the deformation analysis a motion study does with the flows of
+ * src/main.cpp:132-185).  d = (u, v, w) is a pair's flow or a cumulative displacement, voxel units.  G[r][c] = d d_r / d x_c
+ * (row r = component 0 u, 1 v, 2 w; column c = axis 0 x, 1 y, 2 z), F = I + G.
+ * Missing samples: a grid point is missing when it lies outside the volume or any of its three components is NaN.  For voxel p:
+ *   p missing                          -> every output of p is NaN
+ *   per axis a of size n:  n == 1      -> column a of G is 0
+ *     else, m = p - e_a, q = p + e_a:  both present  G[:,a] = (d(q) - d(m)) * 0.5f
+ *                                      only q        G[:,a] = d(q) - d(p)
+ *                                      only m        G[:,a] = d(p) - d(m)
+ *                                      neither       every output of p is NaN
+ * Outputs, in this order (out[0..7]), selected by group:
+ *   F3D_STRAIN_VOL  out[0] vol = J - 1 (J = det F)
+ *   F3D_STRAIN_E    out[1..6] exx eyy ezz exy exz eyz: Green-Lagrange E = 1/2 (F^T F - I) (tensor components, not 2 exy)
+ *   F3D_STRAIN_EQ   out[7] eq: equivalent (von Mises) strain of E
+ * Every operation float32, rounded on its own, in exactly this order (G itself, not F, so small strains do not cancel against 1):
+ *   I1  = (G00 + G11) + G22
+ *   I2  = ((G00*G11 - G01*G10) + (G11*G22 - G12*G21)) + (G00*G22 - G02*G20)
+ *   I3  = (G00*(G11*G22 - G12*G21) - G01*(G10*G22 - G12*G20)) + G02*(G10*G21 - G11*G20)
+ *   vol = (I1 + I2) + I3
+ *   E_rc = 0.5f * ((G_rc + G_cr) + ((G_0r*G_0c + G_1r*G_1c) + G_2r*G_2c))        (r, c in {0,1,2} = x,y,z)
+ *   m = ((Exx + Eyy) + Ezz) / 3.f ;  a = Exx - m ;  b = Eyy - m ;  c = Ezz - m
+ *   s = ((a*a + b*b) + c*c) + 2.f * ((Exy*Exy + Exz*Exz) + Eyz*Eyz)
+ *   eq = sqrtf(s / 1.5f)
+ * Geometry from the current container (f3d_set_container), whole volume, library stream.  Entries of out for groups not selected
+ * are ignored and never written.  Refused: a null input; a null selected output; fields 0 or with unknown bits; a selected output
+ * that is also an input; two selected outputs that are the same container.
+ * stats (nullable; asking waits for the stream): defined = voxels whose vol is not NaN, folded = voxels with vol <= -1 (J <= 0),
+ * vol_min / vol_max / eq_max over the defined voxels (exact; NaN when none is defined), vol_sum accumulated in double (0 when none).
+ * vol and eq are computed for the statistics whether or not they are stored. */
+#define F3D_STRAIN_VOL 1u
+#define F3D_STRAIN_E 2u
+#define F3D_STRAIN_EQ 4u
+typedef struct f3d_strain_stats {
+  unsigned long long defined, folded;
+  float vol_min, vol_max, eq_max;
+  double vol_sum;
+} f3d_strain_stats;
+int f3d_flow_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[8], unsigned fields, size_t width,
+                    size_t height, size_t depth, f3d_strain_stats* stats /* nullable; non-null waits */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,16 @@ int f3d_flow_trajectory_begin(f3d_flow flow);
 int f3d_flow_trajectory_append(f3d_flow flow);
 int f3d_flow_trajectory_download(f3d_flow flow, float* u, float* v, float* w, unsigned long long* lost);
 int f3d_flow_trajectory_end(f3d_flow flow);
+/* Strain fields (f3d_flow_strain of include/f3d.h has the definition): of the flow the driver holds (source F3D_STRAIN_OF_FLOW, after
+ * f3d_flow_compute_resident) or of the trajectory (F3D_STRAIN_OF_TRAJECTORY, after f3d_flow_trajectory_begin).  fields selects groups
+ * of the eight outputs vol, exx, eyy, ezz, exy, exz, eyz, eq (F3D_STRAIN_VOL / _E / _EQ); out[i] of a selected output receives
+ * width*height*depth floats, the others are ignored; stats (nullable) the statistics.  Blocks until the fields are on the host.
+ * The driver keeps a container per selected field until f3d_flow_strain_end (or f3d_flow_destroy).  A device library without
+ * f3d_flow_strain still loads; then the call fails.  Failures are described by f3d_host_last_error(). */
+#define F3D_STRAIN_OF_FLOW 0
+#define F3D_STRAIN_OF_TRAJECTORY 1
+int f3d_flow_strain_compute(f3d_flow flow, int source, unsigned fields, float* const out[8], f3d_strain_stats* stats);
+int f3d_flow_strain_end(f3d_flow flow);
 /* message of this thread's last call that failed in the host library itself; f3d_last_error() when there is none */
 const char* f3d_host_last_error(void);
 int f3d_flow_destroy(f3d_flow flow);

@@ -4,7 +4,9 @@ pipelined (default: the next frame uploads and the previous flow downloads and i
 F3D_SEQ_SERIAL=1 (the same work one step after the other), and with --concurrent 2 / 3 (that many pairs solved at once on lanes of
 their own: what sequences of SMALL volumes want).   python tools/sequence_bench.py [--size 384] [--frames 6] [--concurrent 2 3]
 --cumulative [--rounds R]: instead, what --cumulative (the displacement from frame 0 composed on the device and written beside the
-flows) costs: pipelined runs without and with it, alternated R times, with the flow files of both compared."""
+flows) costs: pipelined runs without and with it, alternated R times, with the flow files of both compared.
+--strain LIST [--rounds R]: the same for `--strain LIST` (e.g. vol,eq: the strain of each pair's flow computed on the device and
+written beside it; add --cumulative for the strain of the displacement from frame 0, measured against --cumulative alone)."""
 import argparse
 import importlib
 import os
@@ -23,6 +25,7 @@ ap.add_argument("--size", type=int, default=384)
 ap.add_argument("--frames", type=int, default=6)
 ap.add_argument("--concurrent", type=int, nargs="*", default=[2])
 ap.add_argument("--cumulative", action="store_true")
+ap.add_argument("--strain", default=None)
 ap.add_argument("--rounds", type=int, default=3)
 a = ap.parse_args()
 pkg = importlib.import_module("cuda-flow3d_amd")
@@ -36,23 +39,28 @@ with tempfile.TemporaryDirectory(dir="/dev/shm" if os.path.isdir("/dev/shm") els
         p = os.path.join(tmp, f"f{k}.raw")
         ((1 - t) * f0 + t * f1).astype(np.float32).tofile(p)
         paths.append(p)
-    if a.cumulative:
-        walls = {"plain": [], "cumulative": []}
+    if a.cumulative or a.strain:
+        # A = the runs without the option measured, B = with it (--strain: both with --cumulative when it is given)
+        base = ["--cumulative"] if a.cumulative and a.strain else []
+        b_tag = "strain" if a.strain else "cumulative"
+        extra = {"plain": base, b_tag: base + (["--strain", a.strain] if a.strain else ["--cumulative"])}
+        walls = {"plain": [], b_tag: []}
         for r in range(a.rounds):
-            for tag in ("plain", "cumulative"):
+            for tag in ("plain", b_tag):
                 t0 = time.time()
                 run = subprocess.run([exe, "--dims", str(S), str(S), str(S), "--f32", "--frames", *paths, "--out", os.path.join(tmp, tag),
-                                      "--silent"] + (["--cumulative"] if tag == "cumulative" else []), capture_output=True, text=True)
+                                      "--silent"] + extra[tag], capture_output=True, text=True)
                 wall = time.time() - t0
                 walls[tag].append(wall / (N - 1))
                 lost = re.findall(r"(\d+) of \d+ voxels have left the volume", run.stdout)
+                folded = re.findall(r"(\d+) folded", run.stdout)
                 print(f"round {r} {tag:10s} {S}^3 x {N} frames: wall {wall:.2f} s ({wall / (N - 1):.3f} s per pair), rc {run.returncode}"
-                      + (f", lost per pair {lost}" if lost else ""), flush=True)
-        same = all(open(os.path.join(tmp, f"cumulative_{k}_flow-{c}-{S}-{S}-{S}.raw"), "rb").read() ==
+                      + (f", lost per pair {lost}" if lost else "") + (f", folded per pair {folded}" if folded else ""), flush=True)
+        same = all(open(os.path.join(tmp, f"{b_tag}_{k}_flow-{c}-{S}-{S}-{S}.raw"), "rb").read() ==
                    open(os.path.join(tmp, f"plain_{k}_flow-{c}-{S}-{S}-{S}.raw"), "rb").read() for k in range(N - 1) for c in "uvw")
         med = {k: sorted(v)[len(v) // 2] for k, v in walls.items()}
-        print(f"median per pair: plain {med['plain']:.4f} s, cumulative {med['cumulative']:.4f} s "
-              f"({100 * (med['cumulative'] / med['plain'] - 1):+.2f} %); flows identical: {same}", flush=True)
+        print(f"median per pair: plain {med['plain']:.4f} s, {b_tag} {med[b_tag]:.4f} s "
+              f"({100 * (med[b_tag] / med['plain'] - 1):+.2f} %); flows identical: {same}", flush=True)
         sys.exit(0)
     for tag, env in (("pipelined", {}), ("serial", {"F3D_SEQ_SERIAL": "1"})):
         t0 = time.time()
