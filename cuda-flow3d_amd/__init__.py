@@ -50,6 +50,13 @@ class StrainStats(C.Structure):  # f3d_strain_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PrincipalStats(C.Structure):  # f3d_principal_stats
+    _fields_ = [("defined", C.c_ulonglong), ("e1_max", C.c_float), ("e3_min", C.c_float), ("shear_max", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class FlowParams(C.Structure):  # f3d_flow_params
     _fields_ = [
         ("warp_levels_count", C.c_size_t), ("warp_scale_factor", C.c_float),
@@ -218,6 +225,8 @@ def host():
         "f3d_flow_trajectory_end": [C.c_void_p],
         "f3d_flow_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(StrainStats)],
         "f3d_flow_strain_end": [C.c_void_p],
+        "f3d_flow_principal_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(PrincipalStats)],
+        "f3d_flow_principal_end": [C.c_void_p],
         "f3d_op_create": [C.POINTER(C.c_void_p), C.c_char_p], "f3d_op_initialize": [C.c_void_p, C.POINTER(Size4)],
         "f3d_op_execute": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), _sz],
         "f3d_op_execute_batch": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(_sz), _sz],
@@ -410,6 +419,68 @@ def flow_strain(u, v, w, fields=("vol", "e", "eq")):
         stats = StrainStats()
         check(fn(*pin, (_dp * 8)(*outs), mask, wd, h, d, C.byref(stats)), "f3d_flow_strain")
         res = {n: box.download(p, (wd, h, d)) for n, p in zip(STRAIN_NAMES, outs) if p}
+    finally:
+        if previous.pitch:   # the geometry of whoever set one before (a driver on this lane)
+            hip().f3d_set_container(C.byref(previous))
+        box.free()
+    res["stats"] = stats.as_dict()
+    return res
+
+
+# the ten outputs of f3d_principal_strain in ABI order, and the F3D_PRINCIPAL_* group of each
+PRINCIPAL_NAMES = ("e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z")
+PRINCIPAL_GROUPS = {"val": 1, "shear": 2, "dir1": 4, "dir3": 8}
+_PRINCIPAL_GROUP_OF = (1, 1, 1, 2, 4, 4, 4, 8, 8, 8)
+
+
+def _principal_mask(fields):
+    """F3D_PRINCIPAL_* bits of an iterable of group names ("val", "shear", "dir1", "dir3") or of a comma-separated string of them"""
+    if isinstance(fields, str):
+        fields = fields.split(",")
+    mask = 0
+    for f in fields:
+        if f not in PRINCIPAL_GROUPS:
+            raise ValueError(f"unknown principal strain group {f!r} (one of {', '.join(PRINCIPAL_GROUPS)})")
+        mask |= PRINCIPAL_GROUPS[f]
+    if not mask:
+        raise ValueError("no principal strain group selected")
+    return mask
+
+
+def _principal_entry():
+    """f3d_principal_strain of the device library, declared on first use like f3d_flow_strain (_strain_entry)"""
+    L = hip()
+    try:
+        fn = L.f3d_principal_strain
+    except AttributeError:
+        raise F3dError(f"{os.path.join(_LIBDIR, 'libf3d_hip.so')} has no f3d_principal_strain: this device library cannot compute "
+                       "principal strains") from None
+    fn.argtypes = [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(PrincipalStats)]
+    fn.restype = C.c_int
+    return fn
+
+
+def principal_strain(u, v, w, fields=("val", "shear")):
+    """Principal strains of a displacement on the device (include/f3d.h, f3d_principal_strain) for volumes from anywhere: u, v, w
+    numpy [z, y, x] float32 in voxel units.  fields: groups "val" (e1 >= e2 >= e3 of the Green-Lagrange tensor), "shear"
+    (gmax = (e1 - e3) / 2), "dir1" / "dir3" (unit directions of e1 / e3 as d1x d1y d1z / d3x d3y d3z).  Returns a dict name -> array
+    for the selected outputs and "stats" -> dict (defined, e1_max, e3_min, shear_max)."""
+    fn = _principal_entry()
+    mask = _principal_mask(fields)
+    d3 = [np.ascontiguousarray(a, dtype=np.float32) for a in (u, v, w)]
+    if any(a.ndim != 3 or a.shape != d3[0].shape for a in d3):
+        raise ValueError("u, v and w must be three [z, y, x] volumes of one shape")
+    d, h, wd = d3[0].shape
+    box = Containers(wd, h, d)
+    previous = Size4()
+    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
+    try:
+        pin = [box.new(a) for a in d3]
+        outs = [box.alloc() if mask & g else 0 for g in _PRINCIPAL_GROUP_OF]
+        box.set_current()
+        stats = PrincipalStats()
+        check(fn(*pin, (_dp * 10)(*outs), mask, wd, h, d, C.byref(stats)), "f3d_principal_strain")
+        res = {n: box.download(p, (wd, h, d)) for n, p in zip(PRINCIPAL_NAMES, outs) if p}
     finally:
         if previous.pitch:   # the geometry of whoever set one before (a driver on this lane)
             hip().f3d_set_container(C.byref(previous))
@@ -928,6 +999,28 @@ class OpticalFlow:
     def strain_end(self):
         """free the strain containers (destroy() does too)"""
         _host_check(host().f3d_flow_strain_end(self._h), "f3d_flow_strain_end")
+
+    # ---- principal strains (include/f3d_host.h, f3d_flow_principal_*) ----
+    def principal(self, source="flow", fields=("val", "shear")):
+        """Principal strains of the flow the driver holds (source="flow", after compute_resident) or of the trajectory
+        (source="trajectory", after trajectory_begin); same result shape as principal_strain().  Works between the yields of
+        compute_sequence, where the driver holds both."""
+        src = {"flow": 0, "trajectory": 1}.get(source)
+        if src is None:
+            raise ValueError(f"source must be 'flow' or 'trajectory', not {source!r}")
+        mask = _principal_mask(fields)
+        w, h, d = self.dims
+        arrays = [np.empty((d, h, w), np.float32) if mask & g else None for g in _PRINCIPAL_GROUP_OF]
+        ptrs = (_fp * 10)(*[a.ctypes.data_as(_fp) if a is not None else None for a in arrays])
+        stats = PrincipalStats()
+        _host_check(host().f3d_flow_principal_compute(self._h, src, mask, ptrs, C.byref(stats)), "f3d_flow_principal_compute")
+        res = {n: a for n, a in zip(PRINCIPAL_NAMES, arrays) if a is not None}
+        res["stats"] = stats.as_dict()
+        return res
+
+    def principal_end(self):
+        """free the principal strain containers (destroy() does too)"""
+        _host_check(host().f3d_flow_principal_end(self._h), "f3d_flow_principal_end")
 
     def compute_sequence(self, frames, cumulative=False, silent=True, **kw):
         """Generator over the consecutive pairs of `frames` (an iterable of [z, y, x] volumes): yields (k, (u, v, w), disp) for

@@ -12,9 +12,11 @@
 //
 // Statistics (optional): each workgroup reduces its voxels into one partial (counts, min / max, double sum) in a buffer of its own;
 // a one-workgroup kernel then folds the partials in a fixed order, so the result does not depend on scheduling.
-#include "f3d_internal.h"
+#include "f3d_strain_grad.h"
 
 namespace {
+
+using namespace f3d_strain;
 
 constexpr int kBX = 64;
 constexpr int kBY = 4;
@@ -30,72 +32,6 @@ struct StrainPartial {
 struct StrainOut {
   float* f[8];  // vol, exx, eyy, ezz, exy, exz, eyz, eq (null = not stored)
 };
-
-struct Sample {
-  float u, v, w;
-};
-
-__device__ __forceinline__ bool present(const Sample& s) { return !(isnan(s.u) || isnan(s.v) || isnan(s.w)); }
-
-__device__ __forceinline__ Sample load(const float* __restrict__ u, const float* __restrict__ v, const float* __restrict__ w,
-                                       size_t i, bool in)
-{
-  const float nan = __builtin_nanf("");
-  Sample s = {nan, nan, nan};
-  if (in) {
-    s.u = u[i];
-    s.v = v[i];
-    s.w = w[i];
-  }
-  return s;
-}
-
-// column a of G from the samples at p - e_a (m), p (c) and p + e_a (q); n1: the axis has size 1; false when neither neighbour exists
-__device__ __forceinline__ bool column(const Sample& m, const Sample& c, const Sample& q, bool n1, float& g0, float& g1, float& g2)
-{
-  if (n1) {
-    g0 = g1 = g2 = 0.f;
-    return true;
-  }
-  const bool hm = present(m), hq = present(q);
-  if (hm && hq) {
-    g0 = (q.u - m.u) * 0.5f;
-    g1 = (q.v - m.v) * 0.5f;
-    g2 = (q.w - m.w) * 0.5f;
-  } else if (hq) {
-    g0 = q.u - c.u;
-    g1 = q.v - c.v;
-    g2 = q.w - c.w;
-  } else if (hm) {
-    g0 = c.u - m.u;
-    g1 = c.v - m.v;
-    g2 = c.w - m.w;
-  } else {
-    return false;
-  }
-  return true;
-}
-
-__device__ __forceinline__ float wave_min(float x)
-{
-  for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_xor(x, o));
-  return x;
-}
-__device__ __forceinline__ float wave_max(float x)
-{
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
-__device__ __forceinline__ double wave_sum(double x)
-{
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x)
-{
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
 
 template <bool STATS>
 __global__ __launch_bounds__(kBX* kBY) void k_flow_strain(const float* __restrict__ du, const float* __restrict__ dv,
@@ -148,12 +84,8 @@ __global__ __launch_bounds__(kBX* kBY) void k_flow_strain(const float* __restric
     const float I2 = ((G00 * G11 - G01 * G10) + (G11 * G22 - G12 * G21)) + (G00 * G22 - G02 * G20);
     const float I3 = (G00 * (G11 * G22 - G12 * G21) - G01 * (G10 * G22 - G12 * G20)) + G02 * (G10 * G21 - G11 * G20);
     float vol = (I1 + I2) + I3;
-    float exx = 0.5f * ((G00 + G00) + ((G00 * G00 + G10 * G10) + G20 * G20));
-    float eyy = 0.5f * ((G11 + G11) + ((G01 * G01 + G11 * G11) + G21 * G21));
-    float ezz = 0.5f * ((G22 + G22) + ((G02 * G02 + G12 * G12) + G22 * G22));
-    float exy = 0.5f * ((G01 + G10) + ((G00 * G01 + G10 * G11) + G20 * G21));
-    float exz = 0.5f * ((G02 + G20) + ((G00 * G02 + G10 * G12) + G20 * G22));
-    float eyz = 0.5f * ((G12 + G21) + ((G01 * G02 + G11 * G12) + G21 * G22));
+    float exx, eyy, ezz, exy, exz, eyz;
+    green_lagrange(G00, G01, G02, G10, G11, G12, G20, G21, G22, exx, eyy, ezz, exy, exz, eyz);
     const float mean = ((exx + eyy) + ezz) / 3.f;
     const float a = exx - mean, b = eyy - mean, c = ezz - mean;
     const float s = ((a * a + b * b) + c * c) + 2.f * ((exy * exy + exz * exz) + eyz * eyz);

@@ -264,6 +264,37 @@ int f3d_flow_strain_end(f3d_flow flow)
   return 0;
 }
 
+int f3d_flow_principal_compute(f3d_flow flow, int source, unsigned fields, float* const out[10], f3d_principal_stats* stats)
+{
+  g_host_error.clear();
+  if (!flow || !out) return HostFail("f3d_flow_principal_compute: null argument");
+  if (source != F3D_STRAIN_OF_FLOW && source != F3D_STRAIN_OF_TRAJECTORY)
+    return HostFail("f3d_flow_principal_compute: source must be F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY");
+  if (source == F3D_STRAIN_OF_TRAJECTORY && !flow->trajectory_started)
+    return HostFail("f3d_flow_principal_compute: no trajectory is active (f3d_flow_trajectory_begin first)");
+  OpticalFlowE& d = flow->driver;
+  const bool ok = source == F3D_STRAIN_OF_FLOW ? d.ComputePrincipal(fields, stats) : d.ComputePrincipalOfTrajectory(fields, stats);
+  if (!ok) return HostFail(d.PrincipalError().c_str());
+  const DataSize4& c = d.ContainerSize();
+  std::unique_ptr<Data3D> views[10];
+  Data3D* dst[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 10; ++i)
+    if (out[i]) {
+      views[i].reset(new Data3D(out[i], c.width, c.height, c.depth));
+      dst[i] = views[i].get();
+    }
+  if (!d.DownloadPrincipal(dst, fields)) return HostFail(d.PrincipalError().c_str());
+  return 0;
+}
+
+int f3d_flow_principal_end(f3d_flow flow)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_principal_end: null driver");
+  flow->driver.ReleasePrincipal();
+  return 0;
+}
+
 const char* f3d_host_last_error(void) { return g_host_error.empty() ? f3d_last_error() : g_host_error.c_str(); }
 
 int f3d_flow_destroy(f3d_flow flow)

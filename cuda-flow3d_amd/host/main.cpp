@@ -5,7 +5,7 @@
 // flags:  flow3d --dims W H D --frames f0.raw f1.raw [f2.raw ...] [--f32] [--out prefix] [--levels N] [--scale s]
 //                [--outer N] [--inner N] [--alpha a] [--eps-smooth e] [--eps-data e] [--median r] [--sigma s]
 //                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
-//                [--strain vol,e,eq]
+//                [--strain vol,e,eq] [--principal val,shear,dir1,dir3]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -22,6 +22,10 @@
 // with --cumulative the displacement frame 0 -> frame k+1 instead -- on the device (f3d_flow_strain) and writes the selected fields
 // as <tag>_strain-{vol | exx,eyy,ezz,exy,exz,eyz | eq}-W-H-D.raw with the flow's (or the displacement's) tag, and one line of
 // statistics per pair.
+// --principal LIST (same conditions and the same source as --strain, with which it may be combined; LIST a comma-separated subset of
+// val,shear,dir1,dir3) diagonalises the Green-Lagrange tensor of that displacement on the device (f3d_principal_strain) and writes
+// the selected fields as <tag>_principal-{e1,e2,e3 | gmax | d1x,d1y,d1z | d3x,d3y,d3z}-W-H-D.raw, and one line of statistics per
+// pair.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -44,7 +48,7 @@ static void Usage()
   std::printf("usage: flow3d --dims W H D (--frames f0.raw f1.raw [f2.raw ...] [--f32] | --synthetic) [--out prefix]\n"
               "              [--levels N] [--scale s] [--outer N] [--inner N] [--alpha a] [--eps-smooth e]\n"
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
-              "              [--concurrent N] [--cumulative] [--strain vol,e,eq]\n");
+              "              [--concurrent N] [--cumulative] [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n");
 }
 
 int main(int argc, char** argv)
@@ -55,7 +59,8 @@ int main(int argc, char** argv)
   bool f32_input = false, synthetic = false, write_vtk = false, silent_mode = false, print_stats = false;
   bool use_partial_gpu = false, partial_full = false, cumulative = false;
   size_t concurrent = 1;
-  unsigned strain_fields = 0;  // --strain: F3D_STRAIN_* groups
+  unsigned strain_fields = 0;     // --strain: F3D_STRAIN_* groups
+  unsigned principal_fields = 0;  // --principal: F3D_PRINCIPAL_* groups
 
   // defaults of src/main.cpp:77-85
   size_t warp_levels_count = 40;
@@ -116,6 +121,22 @@ int main(int argc, char** argv)
         at = end + 1;
       }
     }
+    else if (a == "--principal") {
+      need(1);
+      const std::string list = argv[++i];
+      size_t at = 0;
+      while (true) {
+        const size_t end = list.find(',', at);
+        const std::string item = list.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        if (item == "val") principal_fields |= F3D_PRINCIPAL_VALUES;
+        else if (item == "shear") principal_fields |= F3D_PRINCIPAL_SHEAR;
+        else if (item == "dir1") principal_fields |= F3D_PRINCIPAL_DIR1;
+        else if (item == "dir3") principal_fields |= F3D_PRINCIPAL_DIR3;
+        else { Usage(); return 64; }
+        if (end == std::string::npos) break;
+        at = end + 1;
+      }
+    }
     else { Usage(); return 64; }
   }
   if (width == 0 || height == 0 || depth == 0 || (!synthetic && files.size() < 2)) {
@@ -130,6 +151,12 @@ int main(int argc, char** argv)
   if (strain_fields && (use_partial_gpu || concurrent > 1)) {
     std::printf("--strain needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
                 use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    return 64;
+  }
+  if (principal_fields && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--principal needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
     return 64;
   }
 
@@ -329,6 +356,30 @@ int main(int argc, char** argv)
                 "voxels\n", cumulative ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max, st.eq_max, st.folded,
                 static_cast<unsigned long long>(width * height * depth) - st.defined, width * height * depth);
   };
+  // --principal: the same for the principal strains of that displacement
+  static const char* const principal_names[10] = {"e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z"};
+  auto principal_selected = [&](int i) {
+    const unsigned group =
+        i < 3 ? F3D_PRINCIPAL_VALUES : (i == 3 ? F3D_PRINCIPAL_SHEAR : (i < 7 ? F3D_PRINCIPAL_DIR1 : F3D_PRINCIPAL_DIR3));
+    return (principal_fields & group) != 0;
+  };
+  Data3D principal_host[10];
+  Data3D* principal_out[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 10; ++i)
+    if (principal_selected(i)) {
+      if (!principal_host[i].Allocate(width, height, depth)) return 2;
+      principal_out[i] = &principal_host[i];
+    }
+  f3d_principal_stats principal_stats = {};
+  auto write_principal = [&](size_t k) {
+    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
+    for (int i = 0; i < 10; ++i)
+      if (principal_out[i]) principal_host[i].WriteRAWToFileF32((tag + "_principal-" + principal_names[i] + suffix).c_str());
+    const f3d_principal_stats& st = principal_stats;
+    std::printf("principal frame %zu -> frame %zu: e1 max %.6g, e3 min %.6g, shear max %.6g, %llu undefined of %zu voxels\n",
+                cumulative ? size_t(0) : k, k + 1, st.e1_max, st.e3_min, st.shear_max,
+                static_cast<unsigned long long>(width * height * depth) - st.defined, width * height * depth);
+  };
 
   if (pairs == 1) {
     if (!synthetic && !load(frame_1, files[1])) return 2;
@@ -348,6 +399,12 @@ int main(int argc, char** argv)
                                  : optical_flow_e.ComputeStrain(strain_fields, &strain_stats);
       if (!ok || !optical_flow_e.DownloadStrain(strain_out, strain_fields)) return 3;
       write_strain(0);
+    }
+    if (principal_fields) {
+      const bool ok = cumulative ? optical_flow_e.ComputePrincipalOfTrajectory(principal_fields, &principal_stats)
+                                 : optical_flow_e.ComputePrincipal(principal_fields, &principal_stats);
+      if (!ok || !optical_flow_e.DownloadPrincipal(principal_out, principal_fields)) return 3;
+      write_principal(0);
     }
   } else {
     // Sequence: pair k solves on the device while the host reads frame k+2 and uploads it on one copy queue, and downloads and
@@ -375,6 +432,8 @@ int main(int argc, char** argv)
     if (cumulative)
       for (Data3D& d : disp) pin(d);
     for (Data3D* d : strain_out)
+      if (d) pin(*d);
+    for (Data3D* d : principal_out)
       if (d) pin(*d);
     f3d_queue up = nullptr, down = nullptr;
     f3d_event uploaded[3] = {nullptr, nullptr, nullptr};
@@ -404,6 +463,10 @@ int main(int argc, char** argv)
     f3d_event strained = nullptr, strain_down = nullptr;
     if (strain_fields)
       if (CheckDeviceError(f3d_event_create(&strained)) || CheckDeviceError(f3d_event_create(&strain_down))) return 3;
+    // --principal: once more the same, with containers and events of its own (`principal_done`, `principal_down`)
+    f3d_event principal_done = nullptr, principal_down = nullptr;
+    if (principal_fields)
+      if (CheckDeviceError(f3d_event_create(&principal_done)) || CheckDeviceError(f3d_event_create(&principal_down))) return 3;
     DevicePtr taken[3] = {0, 0, 0};
     bool pending_output = false;
     const bool serial_sequence = std::getenv("F3D_SEQ_SERIAL") && std::atoi(std::getenv("F3D_SEQ_SERIAL")) != 0;
@@ -422,6 +485,7 @@ int main(int argc, char** argv)
         write_pair(k - 1, host_flow[(k - 1) & 1][0], host_flow[(k - 1) & 1][1], host_flow[(k - 1) & 1][2]);
         if (cumulative) write_disp(k - 1);
         if (strain_fields) write_strain(k - 1);
+        if (principal_fields) write_principal(k - 1);
         pending_output = false;
       }
       optical_flow_e.EndComputeFlowResident();
@@ -454,6 +518,19 @@ int main(int argc, char** argv)
                                                     optical_flow_e.StrainContainer(i), c.pitch, c.height, 0));
         CheckDeviceError(f3d_event_record_on(strain_down, down));
       }
+      if (principal_fields) {
+        if (k > 0) CheckDeviceError(f3d_queue_wait_event(nullptr, principal_down));
+        const bool ok = cumulative ? optical_flow_e.ComputePrincipalOfTrajectory(principal_fields, &principal_stats)
+                                   : optical_flow_e.ComputePrincipal(taken, principal_fields, &principal_stats);
+        if (!ok) return 3;
+        CheckDeviceError(f3d_event_record(principal_done));
+        CheckDeviceError(f3d_queue_wait_event(down, principal_done));
+        for (int i = 0; i < 10; ++i)
+          if (principal_out[i])
+            CheckDeviceError(f3d_copy_planes_d2h_on(down, principal_host[i].DataPtr(), width, height, width, height, depth,
+                                                    optical_flow_e.PrincipalContainer(i), c.pitch, c.height, 0));
+        CheckDeviceError(f3d_event_record_on(principal_down, down));
+      }
       pending_output = true;
     }
     CheckDeviceError(f3d_queue_sync(down));
@@ -468,6 +545,11 @@ int main(int argc, char** argv)
       write_strain(pairs - 1);
       f3d_event_destroy(strained);
       f3d_event_destroy(strain_down);
+    }
+    if (principal_fields) {
+      write_principal(pairs - 1);
+      f3d_event_destroy(principal_done);
+      f3d_event_destroy(principal_down);
     }
     CheckDeviceError(f3d_queue_sync(up));
     for (f3d_event e : uploaded) f3d_event_destroy(e);

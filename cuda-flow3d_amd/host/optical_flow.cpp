@@ -19,6 +19,8 @@ extern "C" int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr a
     __attribute__((weak));
 extern "C" int f3d_flow_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[8], unsigned fields, size_t width,
                                size_t height, size_t depth, f3d_strain_stats* stats) __attribute__((weak));
+extern "C" int f3d_principal_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[10], unsigned fields,
+                                    size_t width, size_t height, size_t depth, f3d_principal_stats* stats) __attribute__((weak));
 
 // ---- base --------------------------------------------------------------------------------------------------
 
@@ -563,6 +565,102 @@ void OpticalFlowE::ReleaseStrain()
   }
 }
 
+// ---- principal strains of a displacement --------------------------------------------------------------------------------------
+
+namespace {
+
+const unsigned kPrincipalAll = F3D_PRINCIPAL_VALUES | F3D_PRINCIPAL_SHEAR | F3D_PRINCIPAL_DIR1 | F3D_PRINCIPAL_DIR3;
+
+// the F3D_PRINCIPAL_* group of output i (e1 e2 e3, gmax, d1x d1y d1z, d3x d3y d3z)
+unsigned PrincipalGroup(int i)
+{
+  return i < 3 ? F3D_PRINCIPAL_VALUES : (i == 3 ? F3D_PRINCIPAL_SHEAR : (i < 7 ? F3D_PRINCIPAL_DIR1 : F3D_PRINCIPAL_DIR3));
+}
+
+}  // namespace
+
+bool OpticalFlowE::PrincipalFail(const char* what)
+{
+  principal_error_ = std::string("'") + GetName() + "': " + what;
+  std::printf("Error: %s\n", principal_error_.c_str());
+  return false;
+}
+
+bool OpticalFlowE::AllocatePrincipal(unsigned fields)
+{
+  const size_t rows = dev_container_size_.height * dev_container_size_.depth;
+  for (int i = 0; i < 10; ++i) {
+    if (!(fields & PrincipalGroup(i)) || principal_[i]) continue;
+    size_t pitch = 0;
+    if (f3d_alloc_pitched(&principal_[i], &pitch, dev_container_size_.width * sizeof(float), rows) != 0) principal_[i] = 0;
+    if (!principal_[i] || pitch != dev_container_size_.pitch) {
+      ReleasePrincipal();
+      return PrincipalFail("the principal strain containers do not fit beside the driver's on the device");
+    }
+  }
+  return true;
+}
+
+bool OpticalFlowE::ComputePrincipal(const DevicePtr (&disp)[3], unsigned fields, f3d_principal_stats* stats)
+{
+  principal_error_.clear();
+  if (!f3d_principal_strain) return PrincipalFail("the device library has no f3d_principal_strain (principal strains)");
+  if (!initialized_) return PrincipalFail("the driver was not initialized");
+  if (!disp[0] || !disp[1] || !disp[2]) return PrincipalFail("no displacement to differentiate");
+  if (fields == 0 || (fields & ~kPrincipalAll))
+    return PrincipalFail("fields must be a non-empty combination of F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_SHEAR, F3D_PRINCIPAL_DIR1, "
+                         "F3D_PRINCIPAL_DIR3");
+  if (!AllocatePrincipal(fields)) return false;
+  const f3d_size4 c = {dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, dev_container_size_.pitch};
+  if (CheckDeviceError(f3d_set_container(&c)) ||
+      CheckDeviceError(f3d_principal_strain(disp[0], disp[1], disp[2], principal_, fields, dev_container_size_.width,
+                                            dev_container_size_.height, dev_container_size_.depth, stats)))
+    return PrincipalFail(f3d_last_error());
+  return true;
+}
+
+bool OpticalFlowE::ComputePrincipal(unsigned fields, f3d_principal_stats* stats)
+{
+  if (!result_flow_[0]) {
+    principal_error_.clear();
+    return PrincipalFail("no flow is held on the device (ComputeFlowResident first)");
+  }
+  const DevicePtr flow[3] = {result_flow_[0], result_flow_[1], result_flow_[2]};
+  return ComputePrincipal(flow, fields, stats);
+}
+
+bool OpticalFlowE::ComputePrincipalOfTrajectory(unsigned fields, f3d_principal_stats* stats)
+{
+  if (!trajectory_[0]) {
+    principal_error_.clear();
+    return PrincipalFail("the trajectory was not started (ResetTrajectory first)");
+  }
+  const DevicePtr disp[3] = {trajectory_[0], trajectory_[1], trajectory_[2]};
+  return ComputePrincipal(disp, fields, stats);
+}
+
+bool OpticalFlowE::DownloadPrincipal(Data3D* const (&out)[10], unsigned fields)
+{
+  principal_error_.clear();
+  for (int i = 0; i < 10; ++i) {
+    if (!(fields & PrincipalGroup(i))) continue;
+    if (!principal_[i]) return PrincipalFail("a requested principal strain field has not been computed");
+    if (!out[i]) return PrincipalFail("no host volume for a requested principal strain field");
+    if (CheckDeviceError(f3d_copy3d_d2h(out[i]->DataPtr(), out[i]->Width(), out[i]->Height(), out[i]->Depth(), principal_[i],
+                                        dev_container_size_.pitch, dev_container_size_.height, 0)))
+      return PrincipalFail(f3d_last_error());
+  }
+  return true;
+}
+
+void OpticalFlowE::ReleasePrincipal()
+{
+  for (DevicePtr& p : principal_) {
+    if (p) CheckDeviceError(f3d_free(p));
+    p = 0;
+  }
+}
+
 // The coarse-to-fine solve on two frames that are already on the device (optical_flow_e.cpp:208-533 is the sequence of operator
 // calls this reproduces: pre-blur; per level frames from the originals, flow from the level before, registration, solve, update,
 // median).  Containers are named by what they hold:
@@ -729,6 +827,7 @@ void OpticalFlowE::Destroy()
   ReleaseResult();
   ReleaseTrajectory();
   ReleaseStrain();
+  ReleasePrincipal();
   size_t freed = 0;
   while (!free_containers_.empty()) {
     CheckDeviceError(f3d_free(free_containers_.back()));

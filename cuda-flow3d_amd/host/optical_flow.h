@@ -128,6 +128,19 @@ class OpticalFlowE : public OpticalFlowBase {
   void ReleaseStrain();
   const std::string& StrainError() const { return strain_error_; }
 
+  // Principal strains of a displacement (f3d_principal_strain: e1 >= e2 >= e3 of the Green-Lagrange tensor, maximum shear, the
+  // directions of e1 and e3; include/f3d.h has the definition), in the forms and with the conventions of the strain fields above:
+  // fields is a combination of F3D_PRINCIPAL_VALUES / _SHEAR / _DIR1 / _DIR3, a container per selected output is allocated on first
+  // use and freed by ReleasePrincipal() and Destroy(), and a call that cannot run -- among other reasons when the device library
+  // lacks f3d_principal_strain -- returns false with PrincipalError() set.
+  bool ComputePrincipal(const DevicePtr (&disp)[3], unsigned fields, f3d_principal_stats* stats);
+  bool ComputePrincipal(unsigned fields, f3d_principal_stats* stats);
+  bool ComputePrincipalOfTrajectory(unsigned fields, f3d_principal_stats* stats);
+  DevicePtr PrincipalContainer(int field) const { return principal_[field]; }
+  bool DownloadPrincipal(Data3D* const (&out)[10], unsigned fields);
+  void ReleasePrincipal();
+  const std::string& PrincipalError() const { return principal_error_; }
+
  private:
   static constexpr size_t kContainers = 15;  // optical_flow_e.h:40
 
@@ -153,6 +166,10 @@ class OpticalFlowE : public OpticalFlowBase {
   std::string strain_error_;
   bool StrainFail(const char* what);
   bool AllocateStrain(unsigned fields);
+  DevicePtr principal_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  std::string principal_error_;
+  bool PrincipalFail(const char* what);
+  bool AllocatePrincipal(unsigned fields);
   std::vector<LevelStatistics> level_stats_;
   bool ResidualOf(DevicePtr frame_0, DevicePtr warped, const DataSize4& size, Residual& out);
 

@@ -476,6 +476,49 @@ typedef struct f3d_strain_stats {
 int f3d_flow_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[8], unsigned fields, size_t width,
                     size_t height, size_t depth, f3d_strain_stats* stats /* nullable; non-null waits */);
 
+/* Principal strains of a displacement: the eigenvalues e1 >= e2 >= e3 of the Green-Lagrange tensor E of f3d_flow_strain (largest
+ * extension, largest compaction, independent of how the sample sits in the grid), the maximum shear and the directions of e1 and
+ * e3, in one stencil pass from d = (u, v, w); E itself is not stored.  Per voxel:
+ * 1. G, the missing-sample rules and the set of undefined voxels are exactly f3d_flow_strain's, and E (Exx Eyy Ezz Exy Exz Eyz) is
+ *    formed from G by exactly its expressions, so the tensor diagonalised here is the one f3d_flow_strain stores.  An undefined
+ *    voxel is NaN in every output.
+ * 2. Cyclic Jacobi: A = E (a00 a11 a22 a01 a02 a12, symmetric), V = I.  Five sweeps; in each sweep the pairs
+ *    (p, q) = (0,1), (0,2), (1,2) in this order, r the third index.  For a pair, every operation float32, rounded on its own, in
+ *    exactly this order (only + - * / and sqrt: float32 numpy agrees bit for bit, which the closed trigonometric form would not):
+ *      if a_pq == 0: nothing happens               (so a sweep that finds all three off-diagonals zero is the identity)
+ *      theta = (a_qq - a_pp) / (2.f * a_pq)
+ *      t = 1.f / (fabsf(theta) + sqrtf(theta * theta + 1.f)) ;  if theta < 0: t = -t
+ *      c = 1.f / sqrtf(t * t + 1.f) ;  s = t * c ;  h = t * a_pq
+ *      a_pp = a_pp - h ;  a_qq = a_qq + h ;  a_pq = 0.f
+ *      (a_rp, a_rq) = (c * a_rp - s * a_rq,  s * a_rp + c * a_rq)              (old values on the right)
+ *      for k in 0..2:  (V_kp, V_kq) = (c * V_kp - s * V_kq,  s * V_kp + c * V_kq)
+ *    Five sweeps leave no off-diagonal on any tensor tried; the count is fixed and part of the definition.
+ * 3. lambda_i = a_ii, direction i = column i of V.  Ordered by three compare-exchanges (0,1), (0,2), (1,2): value and column are
+ *    exchanged together when lambda_i < lambda_j (strictly, so equal values keep their order).  e1, e2, e3 = the three values;
+ *    gmax = 0.5f * (e1 - e3).
+ * 4. Sign of a stored direction d: k = the first of x, y, z with the largest fabsf(d_k); if d_k < 0 all three components are
+ *    negated.  The middle direction is d3 x d1 and is not stored.
+ * Outputs, in this order (out[0..9]), selected by group:
+ *   F3D_PRINCIPAL_VALUES  out[0..2] e1 e2 e3
+ *   F3D_PRINCIPAL_SHEAR   out[3]    gmax
+ *   F3D_PRINCIPAL_DIR1    out[4..6] x, y, z components of the unit direction of e1
+ *   F3D_PRINCIPAL_DIR3    out[7..9] x, y, z components of the unit direction of e3
+ * Geometry from the current container (f3d_set_container), whole volume, library stream.  Entries of out for groups not selected
+ * are ignored and never written.  Refused: a null input; a null selected output; fields 0 or with unknown bits; a selected output
+ * that is also an input; two selected outputs that are the same container.
+ * stats (nullable; asking waits for the stream): over the voxels whose e1 is not NaN, defined = their number, e1_max, e3_min and
+ * shear_max = the exact max of e1, min of e3 and max of gmax (NaN when there is none), whether or not those fields are stored. */
+#define F3D_PRINCIPAL_VALUES 1u
+#define F3D_PRINCIPAL_SHEAR 2u
+#define F3D_PRINCIPAL_DIR1 4u
+#define F3D_PRINCIPAL_DIR3 8u
+typedef struct f3d_principal_stats {
+  unsigned long long defined;
+  float e1_max, e3_min, shear_max;
+} f3d_principal_stats;
+int f3d_principal_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[10], unsigned fields, size_t width,
+                         size_t height, size_t depth, f3d_principal_stats* stats /* nullable; non-null waits */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,14 @@ int f3d_flow_trajectory_end(f3d_flow flow);
 #define F3D_STRAIN_OF_TRAJECTORY 1
 int f3d_flow_strain_compute(f3d_flow flow, int source, unsigned fields, float* const out[8], f3d_strain_stats* stats);
 int f3d_flow_strain_end(f3d_flow flow);
+
+/* Principal strains (f3d_principal_strain of include/f3d.h has the definition) of the same two sources, F3D_STRAIN_OF_FLOW or
+ * F3D_STRAIN_OF_TRAJECTORY.  fields selects groups of the ten outputs e1, e2, e3, gmax, d1x, d1y, d1z, d3x, d3y, d3z
+ * (F3D_PRINCIPAL_VALUES / _SHEAR / _DIR1 / _DIR3); out[i] of a selected output receives width * height * depth floats, entries of
+ * other outputs are ignored; stats is nullable.  The driver keeps a container per selected field until f3d_flow_principal_end (or
+ * f3d_flow_destroy).  A device library without f3d_principal_strain still loads; then the call fails with a message naming it. */
+int f3d_flow_principal_compute(f3d_flow flow, int source, unsigned fields, float* const out[10], f3d_principal_stats* stats);
+int f3d_flow_principal_end(f3d_flow flow);
 /* message of this thread's last call that failed in the host library itself; f3d_last_error() when there is none */
 const char* f3d_host_last_error(void);
 int f3d_flow_destroy(f3d_flow flow);

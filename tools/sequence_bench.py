@@ -6,7 +6,8 @@ their own: what sequences of SMALL volumes want).   python tools/sequence_bench.
 --cumulative [--rounds R]: instead, what --cumulative (the displacement from frame 0 composed on the device and written beside the
 flows) costs: pipelined runs without and with it, alternated R times, with the flow files of both compared.
 --strain LIST [--rounds R]: the same for `--strain LIST` (e.g. vol,eq: the strain of each pair's flow computed on the device and
-written beside it; add --cumulative for the strain of the displacement from frame 0, measured against --cumulative alone)."""
+written beside it; add --cumulative for the strain of the displacement from frame 0, measured against --cumulative alone).
+--principal LIST [--rounds R]: the same for `--principal LIST` (e.g. val,shear: the principal strains of each pair's flow)."""
 import argparse
 import importlib
 import os
@@ -26,6 +27,7 @@ ap.add_argument("--frames", type=int, default=6)
 ap.add_argument("--concurrent", type=int, nargs="*", default=[2])
 ap.add_argument("--cumulative", action="store_true")
 ap.add_argument("--strain", default=None)
+ap.add_argument("--principal", default=None)
 ap.add_argument("--rounds", type=int, default=3)
 a = ap.parse_args()
 pkg = importlib.import_module("cuda-flow3d_amd")
@@ -39,11 +41,12 @@ with tempfile.TemporaryDirectory(dir="/dev/shm" if os.path.isdir("/dev/shm") els
         p = os.path.join(tmp, f"f{k}.raw")
         ((1 - t) * f0 + t * f1).astype(np.float32).tofile(p)
         paths.append(p)
-    if a.cumulative or a.strain:
-        # A = the runs without the option measured, B = with it (--strain: both with --cumulative when it is given)
-        base = ["--cumulative"] if a.cumulative and a.strain else []
-        b_tag = "strain" if a.strain else "cumulative"
-        extra = {"plain": base, b_tag: base + (["--strain", a.strain] if a.strain else ["--cumulative"])}
+    if a.cumulative or a.strain or a.principal:
+        # A = the runs without the option measured, B = with it (--strain, --principal: both with --cumulative when it is given)
+        field_option = ["--principal", a.principal] if a.principal else (["--strain", a.strain] if a.strain else None)
+        base = ["--cumulative"] if a.cumulative and field_option else []
+        b_tag = "principal" if a.principal else ("strain" if a.strain else "cumulative")
+        extra = {"plain": base, b_tag: base + (field_option or ["--cumulative"])}
         walls = {"plain": [], b_tag: []}
         for r in range(a.rounds):
             for tag in ("plain", b_tag):
