@@ -9,7 +9,12 @@
 //   r = 7    : 343 values do not fit the register file; exact rank selection by bisection on the
 //              order-preserving integer image of the floats (32 counting passes over the window).
 // The only observable difference to a stable sort is the sign of a zero result when the window holds both
-// -0 and +0 (they compare equal); values are otherwise identical.
+// -0 and +0 (they compare equal); values are otherwise identical.  Between the kernels of this file the same holds:
+// v_min_f32 / v_max_f32 of gfx950 order -0 below +0 (the ISA's pseudo-code handles the pair explicitly), so any two
+// correct networks of them alone return the same bits, but the file is built with NaN-free min/max and the compiler
+// then turns some max(min(a, b), min(max(a, b), c)) into v_med3_f32, which picks by comparing for equality.
+// k_median_share can therefore differ from k_median_keep in the sign of a zero result of such a window, and nowhere
+// else (tests/test_gpu_median_share.py counts it: none of 14 479 zero results on its mixed-zero volume).
 #include "f3d_internal.h"
 
 #include <cstdlib>
@@ -289,6 +294,166 @@ __global__ __launch_bounds__(kBX* kBY) void k_median_keep(MedVols mv, F3dGeo g, 
   }
 }
 
+#include "f3d_median_nets_share.h"
+
+typedef __attribute__((address_space(3))) float LdsFloat;
+// one dword per lane from memory into LDS without a register in between: lane L's value lands at lds_dst + L (the s_nop is the
+// wait state the M0 write in front of the instruction needs)
+__device__ __forceinline__ void dma4_lane(const float* lane_addr, float* lds_dst)
+{
+  const unsigned m0v = static_cast<unsigned>(reinterpret_cast<unsigned long>((LdsFloat*)lds_dst));
+  asm volatile("s_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(lane_addr), "{m0}"(m0v) : "memory");
+}
+
+// 5^3 with the sorted planes kept AND shared.  Against k_median_keep:
+//   * merge25 of two neighbouring plane lists is formed once.  The pair (z+1, z+2) that a step merges is the pair the next
+//     step needs first, so its sorted 50 go through LDS (keep[50][256], lane-major: a lane only ever reads what it wrote, and
+//     the lanes of a wave hit consecutive banks) and only THREE plane lists are carried in registers: with (la, lb, lc) =
+//     planes (z-2, z, z+1), a step makes q4 = z+2 and q5 = z+3 and hands (lb, q4, q5) on.  lc dies in the merge and q5 takes
+//     la's registers behind med_a, so four register arrays rotate with period four and the march is unrolled four deep.
+//   * a plane list is not sorted from the raw 25: every lane sorts ONE y-column (x, y-2 .. y+2) of a freshly fetched plane
+//     (18 min/max; the 68 x 4 tile has 272 columns, so the first 16 lanes sort a second one), publishes it, and every lane
+//     merges the five columns x-2 .. x+2 (202) -- 220 per list instead of 280.
+// A step: 2 x 18 + 2 x 202 + 238 (merge25) + 244 (candidates) + 2 x 50 (selection) = 1 022 min/max for two outputs, two
+// barriers, 66 432 B of LDS (two workgroups per CU).  Lanes and rows outside the volume take part in the exchange: their
+// columns are read at mirrored, clamped indices like everything else.
+// The file is compiled with NaN-free min/max semantics (Makefile): the window holds in-box voxels only, and without the
+// promise the compiler puts a canonicalising v_max_f32 v, v, v in front of every fminf / fmaxf of a value it read from LDS.
+__global__ __launch_bounds__(kBX* kBY) void k_median_share(MedVols mv, F3dGeo g, int zchunk)
+{
+  int zb;
+  const int vol = med_volume(mv, zb);
+  const float* __restrict__ in = mv.in[vol];
+  float* __restrict__ out = mv.out[vol];
+  constexpr int HALF = 2;
+  constexpr int TW = kBX + 2 * HALF, TH = kBY + 2 * HALF;
+  constexpr int NT = kBX * kBY, NCOL = TW * kBY;
+  __shared__ float keep[50][NT];
+  __shared__ float ring[2][TH][TW];
+  __shared__ float cols[2][5][NCOL];
+  const int tid = threadIdx.y * kBX + threadIdx.x;
+  const int x0 = blockIdx.x * kBX, y0 = blockIdx.y * kBY;
+  const int x = x0 + threadIdx.x;
+  const int y = y0 + threadIdx.y;
+  const int z0 = g.z_lo + zb * zchunk;
+  const int z1 = min(z0 + zchunk, g.z_hi);
+  const bool owner = x < g.W && y < g.H;
+  const int zz_max = z1 - 1 + HALF;
+  const int own = threadIdx.y * TW + threadIdx.x;  // the column x-2 of this lane's window
+
+  // A plane goes from memory straight into the ring (global_load_lds_dword: lane L's value lands at M0 + 4 L, and a 64-lane
+  // row of the workgroup is a wave, so element tid + 256 k of the flat footprint is lane L of the piece at 64 wave + 256 k).
+  // No register holds a value in flight, so the planes of the NEXT step are requested as soon as the ring is free and arrive
+  // behind this step's networks.  The in-plane offsets of the (at most three) elements a lane fetches do not change along
+  // the march: the mirror and clamp arithmetic is done once, a request is a scalar plane base plus these.
+  static_assert(kBX == 64, "one row of the workgroup must be one wave");
+  constexpr int NF = (TW * TH + NT - 1) / NT;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.y));
+  int off[NF];
+#pragma unroll
+  for (int k = 0; k < NF; ++k) {
+    const int i = min(tid + k * NT, TW * TH - 1);
+    const int ty = i / TW, tx = i - ty * TW;
+    const int xs = f3d_clampi(f3d_mir(x0 + tx - HALF, g.W), 0, g.W - 1);
+    const int ys = f3d_clampi(f3d_mir(y0 + ty - HALF, g.H), 0, g.H - 1);
+    off[k] = ys * g.pitch + xs;
+  }
+  auto request = [&](int zz, int slot) __attribute__((always_inline)) {
+    const int zm = f3d_clampi(f3d_mir(min(zz, zz_max), g.D), 0, g.D - 1);
+    const float* plane = in + f3d_row(g, 0, zm);
+    float* dst = &ring[slot][0][0] + wave * 64;
+#pragma unroll
+    for (int k = 0; k < NF; ++k)
+      if (tid + k * NT < TW * TH) dma4_lane(plane + off[k], dst + k * NT);
+  };
+  auto sort_column = [&](int slot, int c) __attribute__((always_inline)) {
+    // column c = (row c / TW, tile column c % TW): ring rows have the pitch of the column tile, so it starts at element c
+    const float* top = &ring[slot][0][0] + c;
+    float raw[5], s[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) raw[k] = top[k * TW];
+    sort5(raw, s);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) cols[slot][k][c] = s[k];
+  };
+  // the two requested planes -> sorted columns in cols[0] and cols[1]; leaves behind a barrier, after which the ring is free
+  // for the next request and cols is read until the next call's first barrier
+  auto columns = [&]() __attribute__((always_inline)) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces have landed ...
+    __syncthreads();                                  // ... and so have everybody's
+#pragma unroll
+    for (int slot = 0; slot < 2; ++slot) {
+      sort_column(slot, tid);
+      if (tid < NCOL - NT) sort_column(slot, NT + tid);
+    }
+    __syncthreads();
+  };
+  auto plane_list = [&](int slot, float (&q)[25]) __attribute__((always_inline)) {
+    float v[25];
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+#pragma unroll
+      for (int k = 0; k < 5; ++k) v[j * 5 + k] = cols[slot][k][own + j];
+    merge5x5(v, q);
+  };
+  // one pair of outputs: la = z-2, lb = z, lc = z+1 come in sorted, keep holds merge25(z-1, z); q4 = z+2 is made here, and
+  // z+3 lands in la
+  auto step = [&](float (&la)[25], const float (&lb)[25], const float (&lc)[25], float (&q4)[25], int z) __attribute__((always_inline)) {
+    columns();
+    if (z + 2 < z1) {  // the planes of the next step
+      request(z + HALF + 2, 0);
+      request(z + HALF + 3, 1);
+    }
+    plane_list(0, q4);
+    float c[26];
+    {
+      float ab[50], cd[50];
+      merge25(lc, q4, cd);
+#pragma unroll
+      for (int i = 0; i < 50; ++i) ab[i] = keep[i][tid];
+      candidates(ab, cd, c);
+#pragma unroll
+      for (int i = 0; i < 50; ++i) keep[i][tid] = cd[i];
+    }
+    const float med_a = rank_nb_of_two_sorted<25>(c, la);
+    plane_list(1, la);
+    const float med_b = rank_nb_of_two_sorted<25>(c, la);
+    if (owner) {
+      out[f3d_row(g, y, z) + x] = med_a;
+      if (z + 1 < z1) out[f3d_row(g, y, z + 1) + x] = med_b;
+    }
+    (void)lb;
+  };
+  float A[25], B[25], C[25], E[25];
+  request(z0 - 2, 0);
+  request(z0 - 1, 1);
+  columns();
+  request(z0, 0);
+  request(z0 + 1, 1);
+  plane_list(0, A);
+  plane_list(1, E);
+  columns();
+  request(z0 + 2, 0);
+  request(z0 + 3, 1);
+  plane_list(0, B);
+  plane_list(1, C);
+  {
+    float ab[50];
+    merge25(E, B, ab);
+#pragma unroll
+    for (int i = 0; i < 50; ++i) keep[i][tid] = ab[i];
+  }
+  for (int z = z0; z < z1; z += 8) {
+    step(A, B, C, E, z);
+    if (z + 2 >= z1) break;
+    step(B, E, A, C, z + 2);
+    if (z + 4 >= z1) break;
+    step(E, C, B, A, z + 4);
+    if (z + 6 >= z1) break;
+    step(C, A, E, B, z + 6);
+  }
+}
+
 __device__ __forceinline__ unsigned order_key(float f)
 {
   const unsigned b = __float_as_uint(f);
@@ -378,8 +543,9 @@ static int median_launch(const f3d_devptr* inputs, size_t count, size_t width, s
     const int planes = g.z_hi - g.z_lo;
     // workgroups of ONE z-chunk layer of the launch: the volumes of a batch fill the rounds together
     const long tiles = static_cast<long>((g.W + kBX - 1) / kBX) * ((g.H + kBY - 1) / kBY) * static_cast<long>(count);
-    // F3D_MEDIAN_PAIR: 0 = the one-output-per-step network, 1 = k_median_pair, 2 = k_median_keep (timing comparisons);
-    // unset = whichever the model below prefers.  Read per call (a launch costs far more) so that tests can switch it.
+    // F3D_MEDIAN_PAIR: 0 = the one-output-per-step network, 1 = k_median_pair, 2 = k_median_keep, 3 = k_median_share (timing
+    // comparisons); unset = k_median_pair or k_median_share, whichever the model below prefers.  Read per call (a launch costs
+    // far more) so that tests can switch it.
     const char* forced_env = std::getenv("F3D_MEDIAN_PAIR");
     const int forced = forced_env ? std::atoi(forced_env) : -1;
     if (forced == 0) {
@@ -398,9 +564,14 @@ static int median_launch(const f3d_devptr* inputs, size_t count, size_t width, s
       // workgroup puts one wave on each SIMD of its CU, so 256 workgroups make a round whatever the occupancy, and below
       // two waves per SIMD nothing hides the LDS latency (x 1.3, measured).  Even chunks, so that only the last chunk of
       // an odd range computes a plane for nothing.  (512^3: keep 3.6 ms, pair 5.1-5.5 ms, single-output network 9.0 ms.)
+      // k_median_share takes k_median_keep's place in the same model with its own counts.
+      const bool share = radius == 5 && forced != 1 && forced != 2;  // unset or 3: k_median_share instead of k_median_keep
       const bool can_keep = radius == 5 && forced != 1;
-      const bool can_pair = !(radius == 5 && forced == 2);
+      const bool can_pair = !(radius == 5 && (forced == 2 || forced == 3));
       const long pair_ops = radius == 5 ? 2600 : 330;
+      // k_median_share, counted in its assembly: 1 010 min/max per pair of planes, and a chunk starts with four plane lists
+      // from shared columns and one merge25 (1 190)
+      const long keep_ops = share ? 1010 : 1430, keep_start = share ? 1190 : 1200;
       int zchunk = 2;
       bool keep = false;
       long best = -1;
@@ -408,7 +579,7 @@ static int median_launch(const f3d_devptr* inputs, size_t count, size_t width, s
         const long wgs = tiles * ((planes + zc - 1) / zc);
         const long rounds = (wgs + 255) / 256, thin = wgs < 512 ? 13 : 10;
         const long cost_pair = rounds * thin * (300 + (zc / 2) * pair_ops);
-        const long cost_keep = rounds * thin * (300 + 1200 + (zc / 2) * 1430);
+        const long cost_keep = rounds * thin * (300 + keep_start + (zc / 2) * keep_ops);
         if (can_pair && (best < 0 || cost_pair < best)) {
           best = cost_pair;
           zchunk = zc;
@@ -423,7 +594,8 @@ static int median_launch(const f3d_devptr* inputs, size_t count, size_t width, s
       mv.zblocks = (planes + zchunk - 1) / zchunk;
       const dim3 grid((g.W + kBX - 1) / kBX, (g.H + kBY - 1) / kBY, mv.zblocks * nvol);
       if (radius == 3) hipLaunchKernelGGL(k_median_pair<3>, grid, block, 0, f3d::stream(), mv, g, zchunk);
-      if (radius == 5 && keep) hipLaunchKernelGGL(k_median_keep, grid, block, 0, f3d::stream(), mv, g, zchunk);
+      if (radius == 5 && keep && share) hipLaunchKernelGGL(k_median_share, grid, block, 0, f3d::stream(), mv, g, zchunk);
+      if (radius == 5 && keep && !share) hipLaunchKernelGGL(k_median_keep, grid, block, 0, f3d::stream(), mv, g, zchunk);
       if (radius == 5 && !keep) hipLaunchKernelGGL(k_median_pair<5>, grid, block, 0, f3d::stream(), mv, g, zchunk);
     }
   }
