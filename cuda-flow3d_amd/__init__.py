@@ -9,6 +9,7 @@ native handles raises -- build them with `python -c "import __graft_entry__ as g
 `make -C cuda-flow3d_amd`.
 """
 import atexit
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -332,18 +333,82 @@ def _host_check(status, what):
         raise F3dError(f"{what} failed: {msg.decode() if msg else 'status %d' % status}")
 
 
-def _compose_entry():
-    """f3d_compose_flow of the device library, declared on first use: it is not in hip()'s table, so that a library without it
+def _entry(name, argtypes, what):
+    """An entry point of the device library that is declared on first use: it is not in hip()'s table, so that a library without it
     (an older build, the host-memory stand-in of the tests) still loads; using it there raises."""
-    L = hip()
     try:
-        fn = L.f3d_compose_flow
+        fn = getattr(hip(), name)
     except AttributeError:
-        raise F3dError(f"{os.path.join(_LIBDIR, 'libf3d_hip.so')} has no f3d_compose_flow: this device library cannot compose "
-                       "flows into a trajectory") from None
-    fn.argtypes = [_dp] * 6 + [_sz] * 3 + [C.POINTER(C.c_ulonglong)]
+        raise F3dError(f"{os.path.join(_LIBDIR, 'libf3d_hip.so')} has no {name}: this device library cannot {what}") from None
+    fn.argtypes = argtypes
     fn.restype = C.c_int
     return fn
+
+
+def _compose_entry():
+    return _entry("f3d_compose_flow", [_dp] * 6 + [_sz] * 3 + [C.POINTER(C.c_ulonglong)], "compose flows into a trajectory")
+
+
+def _strain_entry():
+    return _entry("f3d_flow_strain", [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(StrainStats)], "compute strain fields")
+
+
+def _principal_entry():
+    return _entry("f3d_principal_strain", [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(PrincipalStats)],
+                  "compute principal strains")
+
+
+def _inverse_entry():
+    return _entry("f3d_invert_displacement", [_dp] * 7 + [_sz] * 3 + [C.c_uint, C.c_float, C.POINTER(InverseStats)],
+                  "invert displacements")
+
+
+def _carry_entry():
+    return _entry("f3d_carry_field", [_dp] * 5 + [_sz] * 3 + [C.c_uint, C.POINTER(C.c_ulonglong)],
+                  "carry fields through a displacement")
+
+
+def _mask(fields, groups, what):
+    """the F3D_* bits of an iterable of group names (the keys of `groups`) or of a comma-separated string of them"""
+    if isinstance(fields, str):
+        fields = fields.split(",")
+    mask = 0
+    for f in fields:
+        if f not in groups:
+            raise ValueError(f"unknown {what} group {f!r} (one of {', '.join(groups)})")
+        mask |= groups[f]
+    if not mask:
+        raise ValueError(f"no {what} group selected")
+    return mask
+
+
+def _source(source):
+    """F3D_STRAIN_OF_FLOW / F3D_STRAIN_OF_TRAJECTORY of the `source` argument of OpticalFlow.strain, .principal and .inverse"""
+    src = {"flow": 0, "trajectory": 1}.get(source)
+    if src is None:
+        raise ValueError(f"source must be 'flow' or 'trajectory', not {source!r}")
+    return src
+
+
+@contextlib.contextmanager
+def _on_device(volumes, mismatch):
+    """Volumes from anywhere in device containers of their own: yields (box, pointers, (w, h, d)) with `volumes` (numpy [z, y, x], made
+    contiguous float32; ValueError(mismatch) unless all are 3-D of one shape) uploaded into a fresh Containers of their size.  The
+    caller allocates its outputs, calls box.set_current() and the entry point, and downloads; on the way out the container
+    geometry of whoever set one before (a driver on this lane) is put back and everything is freed."""
+    vols = [np.ascontiguousarray(a, dtype=np.float32) for a in volumes]
+    if any(a.ndim != 3 or a.shape != vols[0].shape for a in vols):
+        raise ValueError(mismatch)
+    d, h, w = vols[0].shape
+    box = Containers(w, h, d)
+    previous = Size4()
+    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
+    try:
+        yield box, [box.new(a) for a in vols], (w, h, d)
+    finally:
+        if previous.pitch:
+            hip().f3d_set_container(C.byref(previous))
+        box.free()
 
 
 def compose_flow(acc, inc):
@@ -352,59 +417,54 @@ def compose_flow(acc, inc):
     (u, v, w, lost): acc + inc sampled trilinearly at x + acc, NaN where the point has left the volume, and the number of voxels
     whose u is NaN.  The inputs are not modified."""
     fn = _compose_entry()
-    acc = [np.ascontiguousarray(a, dtype=np.float32) for a in acc]
-    inc = [np.ascontiguousarray(a, dtype=np.float32) for a in inc]
-    if len(acc) != 3 or len(inc) != 3 or any(a.ndim != 3 or a.shape != acc[0].shape for a in acc + inc):
-        raise ValueError("acc and inc must be three [z, y, x] volumes of one shape each")
-    d, h, w = acc[0].shape
-    box = Containers(w, h, d)
-    previous = Size4()
-    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
-    try:
-        pa = [box.new(a) for a in acc]
-        pi = [box.new(a) for a in inc]
+    acc, inc = list(acc), list(inc)
+    mismatch = "acc and inc must be three [z, y, x] volumes of one shape each"
+    if len(acc) != 3 or len(inc) != 3:
+        raise ValueError(mismatch)
+    with _on_device(acc + inc, mismatch) as (box, p, dims):
         box.set_current()
         lost = C.c_ulonglong()
-        check(fn(*pa, *pi, w, h, d, C.byref(lost)), "f3d_compose_flow")
-        out = tuple(box.download(p, (w, h, d)) for p in pa)
-    finally:
-        if previous.pitch:   # the geometry of whoever set one before (a driver on this lane)
-            hip().f3d_set_container(C.byref(previous))
-        box.free()
-    return out + (int(lost.value),)
+        check(fn(*p, *dims, C.byref(lost)), "f3d_compose_flow")
+        return tuple(box.download(a, dims) for a in p[:3]) + (int(lost.value),)
 
 
 # the eight outputs of f3d_flow_strain in ABI order, and the F3D_STRAIN_* group of each
 STRAIN_NAMES = ("vol", "exx", "eyy", "ezz", "exy", "exz", "eyz", "eq")
 STRAIN_GROUPS = {"vol": 1, "e": 2, "eq": 4}
 _STRAIN_GROUP_OF = (1, 2, 2, 2, 2, 2, 2, 4)
+# the ten outputs of f3d_principal_strain in ABI order, and the F3D_PRINCIPAL_* group of each
+PRINCIPAL_NAMES = ("e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z")
+PRINCIPAL_GROUPS = {"val": 1, "shear": 2, "dir1": 4, "dir3": 8}
+_PRINCIPAL_GROUP_OF = (1, 1, 1, 2, 4, 4, 4, 8, 8, 8)
+# the four outputs of f3d_invert_displacement in ABI order, and the modes of f3d_carry_field
+INVERSE_NAMES = ("gu", "gv", "gw", "err")
+CARRY_MODES = {"linear": 1, "nearest": 2}
 
 
 def _strain_mask(fields):
-    """F3D_STRAIN_* bits of an iterable of group names ("vol", "e", "eq") or of a comma-separated string of them"""
-    if isinstance(fields, str):
-        fields = fields.split(",")
-    mask = 0
-    for f in fields:
-        if f not in STRAIN_GROUPS:
-            raise ValueError(f"unknown strain group {f!r} (one of {', '.join(STRAIN_GROUPS)})")
-        mask |= STRAIN_GROUPS[f]
-    if not mask:
-        raise ValueError("no strain group selected")
-    return mask
+    return _mask(fields, STRAIN_GROUPS, "strain")
 
 
-def _strain_entry():
-    """f3d_flow_strain of the device library, declared on first use like f3d_compose_flow (_compose_entry)"""
-    L = hip()
-    try:
-        fn = L.f3d_flow_strain
-    except AttributeError:
-        raise F3dError(f"{os.path.join(_LIBDIR, 'libf3d_hip.so')} has no f3d_flow_strain: this device library cannot compute "
-                       "strain fields") from None
-    fn.argtypes = [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(StrainStats)]
-    fn.restype = C.c_int
-    return fn
+def _principal_mask(fields):
+    return _mask(fields, PRINCIPAL_GROUPS, "principal strain")
+
+
+def _carry_mode(mode):
+    if mode not in CARRY_MODES:
+        raise ValueError(f"unknown carry mode {mode!r} (one of {', '.join(CARRY_MODES)})")
+    return CARRY_MODES[mode]
+
+
+def _grouped_fields(fn, what, u, v, w, mask, names, group_of, stats):
+    """f3d_flow_strain / f3d_principal_strain of (u, v, w) from anywhere: a dict name -> array of the outputs `mask` selects,
+    plus "stats" -> dict"""
+    with _on_device((u, v, w), "u, v and w must be three [z, y, x] volumes of one shape") as (box, p, dims):
+        outs = [box.alloc() if mask & g else 0 for g in group_of]
+        box.set_current()
+        check(fn(*p, (_dp * len(outs))(*outs), mask, *dims, C.byref(stats)), what)
+        res = {n: box.download(o, dims) for n, o in zip(names, outs) if o}
+    res["stats"] = stats.as_dict()
+    return res
 
 
 def flow_strain(u, v, w, fields=("vol", "e", "eq")):
@@ -413,60 +473,7 @@ def flow_strain(u, v, w, fields=("vol", "e", "eq")):
     fit on one device).  fields: groups "vol" (J - 1), "e" (Green-Lagrange exx .. eyz), "eq" (equivalent strain).  Returns a dict
     name -> array for the selected outputs and "stats" -> dict (defined, folded, vol_min, vol_max, eq_max, vol_sum)."""
     fn = _strain_entry()
-    mask = _strain_mask(fields)
-    d3 = [np.ascontiguousarray(a, dtype=np.float32) for a in (u, v, w)]
-    if any(a.ndim != 3 or a.shape != d3[0].shape for a in d3):
-        raise ValueError("u, v and w must be three [z, y, x] volumes of one shape")
-    d, h, wd = d3[0].shape
-    box = Containers(wd, h, d)
-    previous = Size4()
-    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
-    try:
-        pin = [box.new(a) for a in d3]
-        outs = [box.alloc() if mask & g else 0 for g in _STRAIN_GROUP_OF]
-        box.set_current()
-        stats = StrainStats()
-        check(fn(*pin, (_dp * 8)(*outs), mask, wd, h, d, C.byref(stats)), "f3d_flow_strain")
-        res = {n: box.download(p, (wd, h, d)) for n, p in zip(STRAIN_NAMES, outs) if p}
-    finally:
-        if previous.pitch:   # the geometry of whoever set one before (a driver on this lane)
-            hip().f3d_set_container(C.byref(previous))
-        box.free()
-    res["stats"] = stats.as_dict()
-    return res
-
-
-# the ten outputs of f3d_principal_strain in ABI order, and the F3D_PRINCIPAL_* group of each
-PRINCIPAL_NAMES = ("e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z")
-PRINCIPAL_GROUPS = {"val": 1, "shear": 2, "dir1": 4, "dir3": 8}
-_PRINCIPAL_GROUP_OF = (1, 1, 1, 2, 4, 4, 4, 8, 8, 8)
-
-
-def _principal_mask(fields):
-    """F3D_PRINCIPAL_* bits of an iterable of group names ("val", "shear", "dir1", "dir3") or of a comma-separated string of them"""
-    if isinstance(fields, str):
-        fields = fields.split(",")
-    mask = 0
-    for f in fields:
-        if f not in PRINCIPAL_GROUPS:
-            raise ValueError(f"unknown principal strain group {f!r} (one of {', '.join(PRINCIPAL_GROUPS)})")
-        mask |= PRINCIPAL_GROUPS[f]
-    if not mask:
-        raise ValueError("no principal strain group selected")
-    return mask
-
-
-def _principal_entry():
-    """f3d_principal_strain of the device library, declared on first use like f3d_flow_strain (_strain_entry)"""
-    L = hip()
-    try:
-        fn = L.f3d_principal_strain
-    except AttributeError:
-        raise F3dError(f"{os.path.join(_LIBDIR, 'libf3d_hip.so')} has no f3d_principal_strain: this device library cannot compute "
-                       "principal strains") from None
-    fn.argtypes = [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(PrincipalStats)]
-    fn.restype = C.c_int
-    return fn
+    return _grouped_fields(fn, "f3d_flow_strain", u, v, w, _strain_mask(fields), STRAIN_NAMES, _STRAIN_GROUP_OF, StrainStats())
 
 
 def principal_strain(u, v, w, fields=("val", "shear")):
@@ -475,64 +482,8 @@ def principal_strain(u, v, w, fields=("val", "shear")):
     (gmax = (e1 - e3) / 2), "dir1" / "dir3" (unit directions of e1 / e3 as d1x d1y d1z / d3x d3y d3z).  Returns a dict name -> array
     for the selected outputs and "stats" -> dict (defined, e1_max, e3_min, shear_max)."""
     fn = _principal_entry()
-    mask = _principal_mask(fields)
-    d3 = [np.ascontiguousarray(a, dtype=np.float32) for a in (u, v, w)]
-    if any(a.ndim != 3 or a.shape != d3[0].shape for a in d3):
-        raise ValueError("u, v and w must be three [z, y, x] volumes of one shape")
-    d, h, wd = d3[0].shape
-    box = Containers(wd, h, d)
-    previous = Size4()
-    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
-    try:
-        pin = [box.new(a) for a in d3]
-        outs = [box.alloc() if mask & g else 0 for g in _PRINCIPAL_GROUP_OF]
-        box.set_current()
-        stats = PrincipalStats()
-        check(fn(*pin, (_dp * 10)(*outs), mask, wd, h, d, C.byref(stats)), "f3d_principal_strain")
-        res = {n: box.download(p, (wd, h, d)) for n, p in zip(PRINCIPAL_NAMES, outs) if p}
-    finally:
-        if previous.pitch:   # the geometry of whoever set one before (a driver on this lane)
-            hip().f3d_set_container(C.byref(previous))
-        box.free()
-    res["stats"] = stats.as_dict()
-    return res
-
-
-# the four outputs of f3d_invert_displacement in ABI order, and the modes of f3d_carry_field
-INVERSE_NAMES = ("gu", "gv", "gw", "err")
-CARRY_MODES = {"linear": 1, "nearest": 2}
-
-
-def _inverse_entry():
-    """f3d_invert_displacement of the device library, declared on first use like f3d_compose_flow (_compose_entry)"""
-    L = hip()
-    try:
-        fn = L.f3d_invert_displacement
-    except AttributeError:
-        raise F3dError(f"{os.path.join(_LIBDIR, 'libf3d_hip.so')} has no f3d_invert_displacement: this device library cannot invert "
-                       "displacements") from None
-    fn.argtypes = [_dp] * 7 + [_sz] * 3 + [C.c_uint, C.c_float, C.POINTER(InverseStats)]
-    fn.restype = C.c_int
-    return fn
-
-
-def _carry_entry():
-    """f3d_carry_field of the device library, declared on first use like f3d_compose_flow (_compose_entry)"""
-    L = hip()
-    try:
-        fn = L.f3d_carry_field
-    except AttributeError:
-        raise F3dError(f"{os.path.join(_LIBDIR, 'libf3d_hip.so')} has no f3d_carry_field: this device library cannot carry fields "
-                       "through a displacement") from None
-    fn.argtypes = [_dp] * 5 + [_sz] * 3 + [C.c_uint, C.POINTER(C.c_ulonglong)]
-    fn.restype = C.c_int
-    return fn
-
-
-def _carry_mode(mode):
-    if mode not in CARRY_MODES:
-        raise ValueError(f"unknown carry mode {mode!r} (one of {', '.join(CARRY_MODES)})")
-    return CARRY_MODES[mode]
+    return _grouped_fields(fn, "f3d_principal_strain", u, v, w, _principal_mask(fields), PRINCIPAL_NAMES, _PRINCIPAL_GROUP_OF,
+                           PrincipalStats())
 
 
 def invert_displacement(u, v, w, iterations=32, tolerance=1e-3):
@@ -542,25 +493,12 @@ def invert_displacement(u, v, w, iterations=32, tolerance=1e-3):
     steps per voxel, stopped where the round-trip residual is at most `tolerance`; err that residual of the stored g; NaN where the
     point leaves the volume; stats a dict (defined, unconverged, steps_sum, err_max)."""
     fn = _inverse_entry()
-    d3 = [np.ascontiguousarray(a, dtype=np.float32) for a in (u, v, w)]
-    if any(a.ndim != 3 or a.shape != d3[0].shape for a in d3):
-        raise ValueError("u, v and w must be three [z, y, x] volumes of one shape")
-    d, h, wd = d3[0].shape
-    box = Containers(wd, h, d)
-    previous = Size4()
-    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
-    try:
-        pin = [box.new(a) for a in d3]
+    with _on_device((u, v, w), "u, v and w must be three [z, y, x] volumes of one shape") as (box, p, dims):
         outs = [box.alloc() for _ in INVERSE_NAMES]
         box.set_current()
         stats = InverseStats()
-        check(fn(*pin, *outs, wd, h, d, iterations, tolerance, C.byref(stats)), "f3d_invert_displacement")
-        res = tuple(box.download(p, (wd, h, d)) for p in outs)
-    finally:
-        if previous.pitch:   # the geometry of whoever set one before (a driver on this lane)
-            hip().f3d_set_container(C.byref(previous))
-        box.free()
-    return res + (stats.as_dict(),)
+        check(fn(*p, *outs, *dims, iterations, tolerance, C.byref(stats)), "f3d_invert_displacement")
+        return tuple(box.download(o, dims) for o in outs) + (stats.as_dict(),)
 
 
 def carry_field(field, u, v, w, mode="linear"):
@@ -570,25 +508,12 @@ def carry_field(field, u, v, w, mode="linear"):
     for bit: labels).  Returns (out, lost): NaN where the point is outside the volume, and the number of NaN outputs."""
     fn = _carry_entry()
     m = _carry_mode(mode)
-    vols = [np.ascontiguousarray(a, dtype=np.float32) for a in (field, u, v, w)]
-    if any(a.ndim != 3 or a.shape != vols[0].shape for a in vols):
-        raise ValueError("field, u, v and w must be four [z, y, x] volumes of one shape")
-    d, h, wd = vols[0].shape
-    box = Containers(wd, h, d)
-    previous = Size4()
-    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
-    try:
-        pin = [box.new(a) for a in vols]
+    with _on_device((field, u, v, w), "field, u, v and w must be four [z, y, x] volumes of one shape") as (box, p, dims):
         out = box.alloc()
         box.set_current()
         lost = C.c_ulonglong()
-        check(fn(*pin, out, wd, h, d, m, C.byref(lost)), "f3d_carry_field")
-        res = box.download(out, (wd, h, d))
-    finally:
-        if previous.pitch:   # the geometry of whoever set one before (a driver on this lane)
-            hip().f3d_set_container(C.byref(previous))
-        box.free()
-    return res, int(lost.value)
+        check(fn(*p, out, *dims, m, C.byref(lost)), "f3d_carry_field")
+        return box.download(out, dims), int(lost.value)
 
 
 def _f32(a):
@@ -1080,20 +1005,21 @@ class OpticalFlow:
     def trajectory_end(self):
         _host_check(host().f3d_flow_trajectory_end(self._h), "f3d_flow_trajectory_end")
 
-    # ---- strain fields (include/f3d_host.h, f3d_flow_strain_*) ----
+    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_strain_* / _principal_* / _inverse_*) ----
+    def _derived(self, compute, src, selected, stats, *args):
+        """one f3d_flow_*_compute into fresh host arrays: a list with an array per selected output and None for the others"""
+        w, h, d = self.dims
+        arrays = [np.empty((d, h, w), np.float32) if s else None for s in selected]
+        ptrs = (_fp * len(arrays))(*[a.ctypes.data_as(_fp) if a is not None else None for a in arrays])
+        _host_check(getattr(host(), compute)(self._h, src, *args, ptrs, C.byref(stats)), compute)
+        return arrays
+
     def strain(self, source="flow", fields=("vol", "e", "eq")):
         """Strain fields of the flow the driver holds (source="flow", after compute_resident) or of the trajectory
         (source="trajectory", after trajectory_begin); same result shape as flow_strain().  Works between the yields of
         compute_sequence, where the driver holds both."""
-        src = {"flow": 0, "trajectory": 1}.get(source)
-        if src is None:
-            raise ValueError(f"source must be 'flow' or 'trajectory', not {source!r}")
-        mask = _strain_mask(fields)
-        w, h, d = self.dims
-        arrays = [np.empty((d, h, w), np.float32) if mask & g else None for g in _STRAIN_GROUP_OF]
-        ptrs = (_fp * 8)(*[a.ctypes.data_as(_fp) if a is not None else None for a in arrays])
-        stats = StrainStats()
-        _host_check(host().f3d_flow_strain_compute(self._h, src, mask, ptrs, C.byref(stats)), "f3d_flow_strain_compute")
+        src, mask, stats = _source(source), _strain_mask(fields), StrainStats()
+        arrays = self._derived("f3d_flow_strain_compute", src, [mask & g for g in _STRAIN_GROUP_OF], stats, mask)
         res = {n: a for n, a in zip(STRAIN_NAMES, arrays) if a is not None}
         res["stats"] = stats.as_dict()
         return res
@@ -1102,20 +1028,12 @@ class OpticalFlow:
         """free the strain containers (destroy() does too)"""
         _host_check(host().f3d_flow_strain_end(self._h), "f3d_flow_strain_end")
 
-    # ---- principal strains (include/f3d_host.h, f3d_flow_principal_*) ----
     def principal(self, source="flow", fields=("val", "shear")):
         """Principal strains of the flow the driver holds (source="flow", after compute_resident) or of the trajectory
         (source="trajectory", after trajectory_begin); same result shape as principal_strain().  Works between the yields of
         compute_sequence, where the driver holds both."""
-        src = {"flow": 0, "trajectory": 1}.get(source)
-        if src is None:
-            raise ValueError(f"source must be 'flow' or 'trajectory', not {source!r}")
-        mask = _principal_mask(fields)
-        w, h, d = self.dims
-        arrays = [np.empty((d, h, w), np.float32) if mask & g else None for g in _PRINCIPAL_GROUP_OF]
-        ptrs = (_fp * 10)(*[a.ctypes.data_as(_fp) if a is not None else None for a in arrays])
-        stats = PrincipalStats()
-        _host_check(host().f3d_flow_principal_compute(self._h, src, mask, ptrs, C.byref(stats)), "f3d_flow_principal_compute")
+        src, mask, stats = _source(source), _principal_mask(fields), PrincipalStats()
+        arrays = self._derived("f3d_flow_principal_compute", src, [mask & g for g in _PRINCIPAL_GROUP_OF], stats, mask)
         res = {n: a for n, a in zip(PRINCIPAL_NAMES, arrays) if a is not None}
         res["stats"] = stats.as_dict()
         return res
@@ -1124,20 +1042,12 @@ class OpticalFlow:
         """free the principal strain containers (destroy() does too)"""
         _host_check(host().f3d_flow_principal_end(self._h), "f3d_flow_principal_end")
 
-    # ---- inverse displacement (include/f3d_host.h, f3d_flow_inverse_*) ----
     def inverse(self, source="flow", iterations=32, tolerance=1e-3):
         """The inverse displacement of the flow the driver holds (source="flow", after compute_resident) or of the trajectory
         (source="trajectory", after trajectory_begin); same result shape as invert_displacement().  Works between the yields of
         compute_sequence, where the driver holds both."""
-        src = {"flow": 0, "trajectory": 1}.get(source)
-        if src is None:
-            raise ValueError(f"source must be 'flow' or 'trajectory', not {source!r}")
-        w, h, d = self.dims
-        arrays = [np.empty((d, h, w), np.float32) for _ in INVERSE_NAMES]
-        ptrs = (_fp * 4)(*[a.ctypes.data_as(_fp) for a in arrays])
         stats = InverseStats()
-        _host_check(host().f3d_flow_inverse_compute(self._h, src, iterations, tolerance, ptrs, C.byref(stats)),
-                    "f3d_flow_inverse_compute")
+        arrays = self._derived("f3d_flow_inverse_compute", _source(source), [True] * 4, stats, iterations, tolerance)
         return tuple(arrays) + (stats.as_dict(),)
 
     def inverse_end(self):

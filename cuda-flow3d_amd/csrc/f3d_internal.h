@@ -25,6 +25,11 @@ hipStream_t stream();                    // library stream (valid after f3d_init
 bool ready();
 const f3d_size4& container();
 bool make_geo(F3dGeo* g, size_t w, size_t h, size_t d, const f3d_slab* slab, const char* who);
+// The outputs a derived-field entry point `who` stores: ptr[f] = out[f] for each of the `count` outputs whose group is in `fields`
+// (groups null: every output that is not null, named without its index), null for the others.  Fails when a selected output is
+// null, is one of the inputs u, v, w (`reads` says why that cannot be), or is the container of an earlier one.
+bool select_outputs(const char* who, const char* reads, float** ptr, const f3d_devptr* out, int count, const char* const* names,
+                    const unsigned* groups, unsigned fields, f3d_devptr u, f3d_devptr v, f3d_devptr w);
 // conv taps live in host memory and are passed to the kernels by value
 struct ConvTaps { float k[51]; int count; };
 const ConvTaps& conv_taps();

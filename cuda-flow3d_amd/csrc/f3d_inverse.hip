@@ -4,81 +4,35 @@
 // volume.  The definitions, the lost rules and the evaluation order are those of include/f3d.h (f3d_invert_displacement,
 // f3d_carry_field); tests/inverse_ref.py restates them in float32 numpy and matches the kernels bit for bit.
 //
-// Shape as k_compose_flow (f3d_trajectory.hip): one voxel per lane, a wave64 on 64 consecutive x of one row, a workgroup 4 rows.  The
+// Shape as k_compose_flow (f3d_gather.h): one voxel per lane, a wave64 on 64 consecutive x of one row, a workgroup 4 rows.  The
 // iterate of a voxel needs only itself and d, never a neighbour's iterate, so the whole iteration is one launch: every step is one
 // compose-like gather (24 loads: 8 corners x 3 components, on the same and the neighbouring rows while displacements are small, served
 // by L1/L2), and a voxel stops on its own residual.  A wave leaves the loop when a ballot finds no lane still iterating; lanes outside
 // the volume and lost lanes count as stopped.  Stores of g and err are full rows (256 B per wave).
 //
 // Statistics (optional): each workgroup reduces its voxels into one partial in a buffer of its own; a one-workgroup kernel then folds
-// the partials in a fixed order as k_flow_strain_stats does, so the result does not depend on scheduling (no float atomics).
-#include "f3d_internal.h"
+// the partials in a fixed order (f3d_partials.h), so the result does not depend on scheduling (no float atomics).
+#include "f3d_gather.h"
+#include "f3d_partials.h"
 
 namespace {
 
-constexpr int kBX = 64;
-constexpr int kBY = 4;
-constexpr int kReduceThreads = 256;
+using namespace f3d_gather;
+using namespace f3d_partials;
 
 struct InversePartial {
   unsigned long long defined, unconverged, steps_sum;
   float err_max, pad;
+
+  static __device__ __forceinline__ InversePartial identity() { return {0ull, 0ull, 0ull, -INFINITY, 0.f}; }
+  __device__ __forceinline__ void merge(const InversePartial& q)
+  {
+    defined += q.defined;
+    unconverged += q.unconverged;
+    steps_sum += q.steps_sum;
+    err_max = fmaxf(err_max, q.err_max);
+  }
 };
-
-// p inside [0, W-1] x [0, H-1] x [0, D-1] and not NaN (f3d_compose_flow's test)
-__device__ __forceinline__ bool inside(const F3dGeo& g, float x_f, float y_f, float z_f)
-{
-  return !(isnan(x_f) || isnan(y_f) || isnan(z_f) || (x_f < 0.f) || (x_f > static_cast<float>(g.W - 1)) || (y_f < 0.f) ||
-           (y_f > static_cast<float>(g.H - 1)) || (z_f < 0.f) || (z_f > static_cast<float>(g.D - 1)));
-}
-
-// the corners and fractions of an inside position: f3d_compose_flow's (floor, fractions, min(n - 1, i + 1))
-struct Cell {
-  size_t r00, r10, r01, r11;
-  int xi, x1;
-  float dx, dy, dz;
-};
-
-__device__ __forceinline__ Cell cell_of(const F3dGeo& g, float x_f, float y_f, float z_f)
-{
-  Cell c;
-  c.xi = static_cast<int>(floorf(x_f));
-  const int yi = static_cast<int>(floorf(y_f));
-  const int zi = static_cast<int>(floorf(z_f));
-  c.dx = x_f - static_cast<float>(c.xi);
-  c.dy = y_f - static_cast<float>(yi);
-  c.dz = z_f - static_cast<float>(zi);
-  c.x1 = min(g.W - 1, c.xi + 1);
-  const int y1 = min(g.H - 1, yi + 1);
-  const int z1 = min(g.D - 1, zi + 1);
-  c.r00 = f3d_row(g, yi, zi);
-  c.r10 = f3d_row(g, y1, zi);
-  c.r01 = f3d_row(g, yi, z1);
-  c.r11 = f3d_row(g, y1, z1);
-  return c;
-}
-
-// k_compose_flow's trilinear expression tree (the products and sums in that order; contraction is off in this build)
-__device__ __forceinline__ float trilinear(const float* __restrict__ f, const Cell& c)
-{
-  const float dx = c.dx, dy = c.dy, dz = c.dz;
-  const float v0 = (1.f - dx) * (1.f - dy) * f[c.r00 + c.xi] + (dx) * (1.f - dy) * f[c.r00 + c.x1] +
-                   (1.f - dx) * (dy)*f[c.r10 + c.xi] + (dx) * (dy)*f[c.r10 + c.x1];
-  const float v1 = (1.f - dx) * (1.f - dy) * f[c.r01 + c.xi] + (dx) * (1.f - dy) * f[c.r01 + c.x1] +
-                   (1.f - dx) * (dy)*f[c.r11 + c.xi] + (dx) * (dy)*f[c.r11 + c.x1];
-  return (1.f - dz) * v0 + dz * v1;
-}
-
-__device__ __forceinline__ float wave_max(float x)
-{
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x)
-{
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
 
 // include/f3d.h, f3d_invert_displacement.  err is nullable; partials only with STATS.
 template <bool STATS>
@@ -136,54 +90,13 @@ __global__ __launch_bounds__(kBX* kBY) void k_invert_displacement(const float* _
   }
 
   if (STATS) {
-    // wave reduction, then the kBY waves through LDS, one partial per workgroup
-    __shared__ InversePartial wave_part[kBY];
     const bool def = in && !lost;
     const unsigned long long n_defined = __popcll(__ballot(def));
     const unsigned long long n_unconverged = __popcll(__ballot(def && e > tolerance));
     const unsigned long long steps = wave_sum(static_cast<unsigned long long>(def ? n : 0u));
     const float emax = wave_max(def ? e : -INFINITY);
-    if (threadIdx.x == 0) wave_part[threadIdx.y] = {n_defined, n_unconverged, steps, emax, 0.f};
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-      InversePartial p = wave_part[0];
-      for (int i = 1; i < kBY; ++i) {
-        p.defined += wave_part[i].defined;
-        p.unconverged += wave_part[i].unconverged;
-        p.steps_sum += wave_part[i].steps_sum;
-        p.err_max = fmaxf(p.err_max, wave_part[i].err_max);
-      }
-      partials[(static_cast<size_t>(blockIdx.z) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = p;
-    }
+    block_partial<InversePartial, kBY>({n_defined, n_unconverged, steps, emax, 0.f}, partials);
   }
-}
-
-// the n partials folded into partials[n] by one workgroup: strided per thread, then a tree in LDS (a fixed order)
-__global__ __launch_bounds__(kReduceThreads) void k_invert_displacement_stats(InversePartial* __restrict__ partials, size_t n)
-{
-  __shared__ InversePartial part[kReduceThreads];
-  InversePartial p = {0ull, 0ull, 0ull, -INFINITY, 0.f};
-  for (size_t i = threadIdx.x; i < n; i += kReduceThreads) {
-    const InversePartial q = partials[i];
-    p.defined += q.defined;
-    p.unconverged += q.unconverged;
-    p.steps_sum += q.steps_sum;
-    p.err_max = fmaxf(p.err_max, q.err_max);
-  }
-  part[threadIdx.x] = p;
-  __syncthreads();
-  for (int s = kReduceThreads / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) {
-      InversePartial& a = part[threadIdx.x];
-      const InversePartial& b = part[threadIdx.x + s];
-      a.defined += b.defined;
-      a.unconverged += b.unconverged;
-      a.steps_sum += b.steps_sum;
-      a.err_max = fmaxf(a.err_max, b.err_max);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partials[n] = part[0];
 }
 
 // include/f3d.h, f3d_carry_field: out(x) = field(x + m(x)); the field travels as its bits, so the nearest mode copies exactly
@@ -215,11 +128,7 @@ __global__ __launch_bounds__(kBX* kBY) void k_carry_field(const float* __restric
     is_lost = isnan(r);
     out[i] = r;
   }
-  if (lost) {
-    // every lane of the wave takes part (no early return above): a ballot, and one atomic per wave that has anything to add
-    const unsigned long long n = __popcll(__ballot(is_lost));
-    if (threadIdx.x == 0 && n) atomicAdd(lost, n);
-  }
+  count_lost(lost, is_lost);
 }
 
 }  // namespace
@@ -235,14 +144,10 @@ int f3d_invert_displacement(f3d_devptr d_u, f3d_devptr d_v, f3d_devptr d_w, f3d_
   if (!g_u || !g_v || !g_w) return f3d::fail("f3d_invert_displacement: null output (g_u, g_v and g_w are all required)");
   static const char* const names[4] = {"g_u", "g_v", "g_w", "err"};
   const f3d_devptr outs[4] = {g_u, g_v, g_w, err};
-  for (int f = 0; f < 4; ++f) {
-    if (!outs[f]) continue;
-    if (outs[f] == d_u || outs[f] == d_v || outs[f] == d_w)
-      return f3d::fail("f3d_invert_displacement: output %s is also an input (every step gathers from the inputs)", names[f]);
-    for (int e = 0; e < f; ++e)
-      if (outs[e] == outs[f])
-        return f3d::fail("f3d_invert_displacement: outputs %s and %s are the same container", names[e], names[f]);
-  }
+  float* q[4];
+  if (!f3d::select_outputs("f3d_invert_displacement", "every step gathers from the inputs", q, outs, 4, names, nullptr, 0, d_u, d_v,
+                           d_w))
+    return 1;
   if (iterations < 1 || iterations > 64)
     return f3d::fail("f3d_invert_displacement: iterations must be 1 .. 64 (got %u)", iterations);
   if (!(tolerance >= 0.f)) return f3d::fail("f3d_invert_displacement: tolerance must be a number >= 0 (got %g)", tolerance);
@@ -250,36 +155,20 @@ int f3d_invert_displacement(f3d_devptr d_u, f3d_devptr d_v, f3d_devptr d_w, f3d_
   if (!f3d::make_geo(&g, width, height, depth, nullptr, "f3d_invert_displacement")) return 1;
   const dim3 grid((g.W + kBX - 1) / kBX, (g.H + kBY - 1) / kBY, g.z_hi - g.z_lo);
   const float *pu = f3d_ptr<const float>(d_u), *pv = f3d_ptr<const float>(d_v), *pw = f3d_ptr<const float>(d_w);
-  float *qu = f3d_ptr<float>(g_u), *qv = f3d_ptr<float>(g_v), *qw = f3d_ptr<float>(g_w), *qe = f3d_ptr<float>(err);
   if (!stats) {
     if (g.z_hi > g.z_lo) {
-      hipLaunchKernelGGL(k_invert_displacement<false>, grid, dim3(kBX, kBY, 1), 0, f3d::stream(), pu, pv, pw, qu, qv, qw, qe, g,
+      hipLaunchKernelGGL(k_invert_displacement<false>, grid, dim3(kBX, kBY, 1), 0, f3d::stream(), pu, pv, pw, q[0], q[1], q[2], q[3], g,
                          iterations, tolerance, nullptr);
       F3D_HIP(hipGetLastError());
     }
     return 0;
   }
-  // one partial per workgroup and one for the result; per thread: two lanes may ask at once
-  static thread_local InversePartial* d_part = nullptr;
-  static thread_local size_t d_part_count = 0;
-  const size_t n = static_cast<size_t>(grid.x) * grid.y * grid.z;
-  if (d_part_count < n + 1) {
-    if (d_part) F3D_HIP(hipFree(d_part));
-    d_part = nullptr;
-    d_part_count = 0;
-    F3D_HIP(hipMalloc(reinterpret_cast<void**>(&d_part), (n + 1) * sizeof(InversePartial)));
-    d_part_count = n + 1;
-  }
-  if (n) {
-    hipLaunchKernelGGL(k_invert_displacement<true>, grid, dim3(kBX, kBY, 1), 0, f3d::stream(), pu, pv, pw, qu, qv, qw, qe, g,
-                       iterations, tolerance, d_part);
-    F3D_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_invert_displacement_stats, dim3(1), dim3(kReduceThreads), 0, f3d::stream(), d_part, n);
-  F3D_HIP(hipGetLastError());
   InversePartial r;
-  F3D_HIP(hipMemcpyAsync(&r, d_part + n, sizeof(r), hipMemcpyDeviceToHost, f3d::stream()));
-  F3D_HIP(hipStreamSynchronize(f3d::stream()));
+  if (reduce_partials(static_cast<size_t>(grid.x) * grid.y * grid.z, &r, [&](InversePartial* d_part) {
+        hipLaunchKernelGGL(k_invert_displacement<true>, grid, dim3(kBX, kBY, 1), 0, f3d::stream(), pu, pv, pw, q[0], q[1], q[2], q[3],
+                           g, iterations, tolerance, d_part);
+      }))
+    return 1;
   stats->defined = r.defined;
   stats->unconverged = r.unconverged;
   stats->steps_sum = r.steps_sum;
@@ -298,30 +187,21 @@ int f3d_carry_field(f3d_devptr field, f3d_devptr m_u, f3d_devptr m_v, f3d_devptr
     return f3d::fail("f3d_carry_field: out is also an input (the gather reads other voxels)");
   F3dGeo g;
   if (!f3d::make_geo(&g, width, height, depth, nullptr, "f3d_carry_field")) return 1;
-  static thread_local unsigned long long* d_lost = nullptr;   // per thread: two lanes may ask at once
-  if (lost) {
-    if (!d_lost) F3D_HIP(hipMalloc(reinterpret_cast<void**>(&d_lost), sizeof(unsigned long long)));
-    F3D_HIP(hipMemsetAsync(d_lost, 0, sizeof(unsigned long long), f3d::stream()));
-  }
+  unsigned long long* d_lost;
+  if (lost_zero(lost, &d_lost)) return 1;
   if (g.z_hi > g.z_lo) {
     const dim3 grid((g.W + kBX - 1) / kBX, (g.H + kBY - 1) / kBY, g.z_hi - g.z_lo);
     const float *pf = f3d_ptr<const float>(field), *pu = f3d_ptr<const float>(m_u), *pv = f3d_ptr<const float>(m_v),
                 *pw = f3d_ptr<const float>(m_w);
     if (mode == F3D_CARRY_NEAREST)
       hipLaunchKernelGGL(k_carry_field<true>, grid, dim3(kBX, kBY, 1), 0, f3d::stream(), pf, pu, pv, pw, f3d_ptr<float>(out), g,
-                         lost ? d_lost : nullptr);
+                         d_lost);
     else
       hipLaunchKernelGGL(k_carry_field<false>, grid, dim3(kBX, kBY, 1), 0, f3d::stream(), pf, pu, pv, pw, f3d_ptr<float>(out), g,
-                         lost ? d_lost : nullptr);
+                         d_lost);
     F3D_HIP(hipGetLastError());
   }
-  if (lost) {
-    unsigned long long n = 0;
-    F3D_HIP(hipMemcpyAsync(&n, d_lost, sizeof(n), hipMemcpyDeviceToHost, f3d::stream()));
-    F3D_HIP(hipStreamSynchronize(f3d::stream()));
-    *lost = n;
-  }
-  return 0;
+  return lost_read(lost, d_lost);
 }
 
 }  // extern "C"

@@ -127,6 +127,28 @@ bool make_geo(F3dGeo* g, size_t w, size_t h, size_t d, const f3d_slab* slab, con
   return true;
 }
 
+bool select_outputs(const char* who, const char* reads, float** ptr, const f3d_devptr* out, int count, const char* const* names,
+                    const unsigned* groups, unsigned fields, f3d_devptr u, f3d_devptr v, f3d_devptr w)
+{
+  char a[32], b[32];
+  auto label = [&](char* text, int f) {
+    if (groups) std::snprintf(text, sizeof(a), "%d (%s)", f, names[f]);
+    else std::snprintf(text, sizeof(a), "%s", names[f]);
+    return text;
+  };
+  for (int f = 0; f < count; ++f) {
+    ptr[f] = nullptr;
+    if (groups ? !(fields & groups[f]) : !out[f]) continue;
+    if (!out[f]) return !fail("%s: output %s is selected but null", who, label(a, f));
+    if (out[f] == u || out[f] == v || out[f] == w) return !fail("%s: output %s is also an input (%s)", who, label(a, f), reads);
+    for (int e = 0; e < f; ++e)
+      if (ptr[e] && out[e] == out[f])
+        return !fail("%s: outputs %s and %s are the same container", who, label(a, e), label(b, f));
+    ptr[f] = f3d_ptr<float>(out[f]);
+  }
+  return true;
+}
+
 void prof_begin(int kernel, size_t voxels)
 {
   if (t_lane) return;   // the event bracket belongs to the default lane (bench.py, tools/kbench.py)

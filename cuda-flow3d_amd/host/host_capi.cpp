@@ -233,96 +233,75 @@ int f3d_flow_trajectory_end(f3d_flow flow)
   return 0;
 }
 
-int f3d_flow_strain_compute(f3d_flow flow, int source, unsigned fields, float* const out[8], f3d_strain_stats* stats)
+namespace {
+
+// the checks every f3d_flow_*_compute makes of its driver, its source and the trajectory; `who` is the entry point's name
+bool DerivedSource(f3d_flow flow, int source, bool have_out, const char* who, OpticalFlowE::Displacement* of)
 {
   g_host_error.clear();
-  if (!flow || !out) return HostFail("f3d_flow_strain_compute: null argument");
+  const std::string name(who);
+  if (!flow || !have_out) return !HostFail((name + ": null argument").c_str());
   if (source != F3D_STRAIN_OF_FLOW && source != F3D_STRAIN_OF_TRAJECTORY)
-    return HostFail("f3d_flow_strain_compute: source must be F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY");
+    return !HostFail((name + ": source must be F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY").c_str());
   if (source == F3D_STRAIN_OF_TRAJECTORY && !flow->trajectory_started)
-    return HostFail("f3d_flow_strain_compute: no trajectory is active (f3d_flow_trajectory_begin first)");
-  OpticalFlowE& d = flow->driver;
-  const bool ok = source == F3D_STRAIN_OF_FLOW ? d.ComputeStrain(fields, stats) : d.ComputeStrainOfTrajectory(fields, stats);
-  if (!ok) return HostFail(d.StrainError().c_str());
-  const DataSize4& c = d.ContainerSize();
-  std::unique_ptr<Data3D> views[8];
-  Data3D* dst[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 8; ++i)
-    if (out[i]) {
-      views[i].reset(new Data3D(out[i], c.width, c.height, c.depth));
-      dst[i] = views[i].get();
-    }
-  if (!d.DownloadStrain(dst, fields)) return HostFail(d.StrainError().c_str());
-  return 0;
+    return !HostFail((name + ": no trajectory is active (f3d_flow_trajectory_begin first)").c_str());
+  *of = source == F3D_STRAIN_OF_FLOW ? OpticalFlowE::HeldFlow() : OpticalFlowE::Trajectory();
+  return true;
 }
 
-int f3d_flow_strain_end(f3d_flow flow)
+// the result of a Compute, then out[0 .. count) viewed as volumes of the container's size and the selected fields downloaded
+int DerivedDownload(f3d_flow flow, OpticalFlowE::Derived which, bool computed, float* const* out, unsigned fields)
 {
-  g_host_error.clear();
-  if (!flow) return HostFail("f3d_flow_strain_end: null driver");
-  flow->driver.ReleaseStrain();
-  return 0;
-}
-
-int f3d_flow_principal_compute(f3d_flow flow, int source, unsigned fields, float* const out[10], f3d_principal_stats* stats)
-{
-  g_host_error.clear();
-  if (!flow || !out) return HostFail("f3d_flow_principal_compute: null argument");
-  if (source != F3D_STRAIN_OF_FLOW && source != F3D_STRAIN_OF_TRAJECTORY)
-    return HostFail("f3d_flow_principal_compute: source must be F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY");
-  if (source == F3D_STRAIN_OF_TRAJECTORY && !flow->trajectory_started)
-    return HostFail("f3d_flow_principal_compute: no trajectory is active (f3d_flow_trajectory_begin first)");
   OpticalFlowE& d = flow->driver;
-  const bool ok = source == F3D_STRAIN_OF_FLOW ? d.ComputePrincipal(fields, stats) : d.ComputePrincipalOfTrajectory(fields, stats);
-  if (!ok) return HostFail(d.PrincipalError().c_str());
+  if (!computed) return HostFail(d.DerivedError(which).c_str());
   const DataSize4& c = d.ContainerSize();
   std::unique_ptr<Data3D> views[10];
   Data3D* dst[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 10; ++i)
+  for (int i = 0; i < OpticalFlowE::DerivedFieldCount(which); ++i)
     if (out[i]) {
       views[i].reset(new Data3D(out[i], c.width, c.height, c.depth));
       dst[i] = views[i].get();
     }
-  if (!d.DownloadPrincipal(dst, fields)) return HostFail(d.PrincipalError().c_str());
+  return d.DownloadDerived(which, dst, fields) ? 0 : HostFail(d.DerivedError(which).c_str());
+}
+
+int DerivedEnd(f3d_flow flow, OpticalFlowE::Derived which, const char* null_driver)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail(null_driver);
+  flow->driver.ReleaseDerived(which);
   return 0;
 }
 
-int f3d_flow_principal_end(f3d_flow flow)
+}  // namespace
+
+int f3d_flow_strain_compute(f3d_flow flow, int source, unsigned fields, float* const out[8], f3d_strain_stats* stats)
 {
-  g_host_error.clear();
-  if (!flow) return HostFail("f3d_flow_principal_end: null driver");
-  flow->driver.ReleasePrincipal();
-  return 0;
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out != nullptr, "f3d_flow_strain_compute", &of)) return 1;
+  return DerivedDownload(flow, OpticalFlowE::kStrain, flow->driver.ComputeStrain(of, fields, stats), out, fields);
 }
+
+int f3d_flow_strain_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kStrain, "f3d_flow_strain_end: null driver"); }
+
+int f3d_flow_principal_compute(f3d_flow flow, int source, unsigned fields, float* const out[10], f3d_principal_stats* stats)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out != nullptr, "f3d_flow_principal_compute", &of)) return 1;
+  return DerivedDownload(flow, OpticalFlowE::kPrincipal, flow->driver.ComputePrincipal(of, fields, stats), out, fields);
+}
+
+int f3d_flow_principal_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kPrincipal, "f3d_flow_principal_end: null driver"); }
 
 int f3d_flow_inverse_compute(f3d_flow flow, int source, unsigned iterations, float tolerance, float* const out[4],
                              f3d_inverse_stats* stats)
 {
-  g_host_error.clear();
-  if (!flow || !out || !out[0] || !out[1] || !out[2] || !out[3]) return HostFail("f3d_flow_inverse_compute: null argument");
-  if (source != F3D_STRAIN_OF_FLOW && source != F3D_STRAIN_OF_TRAJECTORY)
-    return HostFail("f3d_flow_inverse_compute: source must be F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY");
-  if (source == F3D_STRAIN_OF_TRAJECTORY && !flow->trajectory_started)
-    return HostFail("f3d_flow_inverse_compute: no trajectory is active (f3d_flow_trajectory_begin first)");
-  OpticalFlowE& d = flow->driver;
-  const bool ok = source == F3D_STRAIN_OF_FLOW ? d.ComputeInverse(iterations, tolerance, stats)
-                                               : d.ComputeInverseOfTrajectory(iterations, tolerance, stats);
-  if (!ok) return HostFail(d.InverseError().c_str());
-  const DataSize4& c = d.ContainerSize();
-  Data3D gu(out[0], c.width, c.height, c.depth), gv(out[1], c.width, c.height, c.depth), gw(out[2], c.width, c.height, c.depth),
-      err(out[3], c.width, c.height, c.depth);
-  Data3D* const dst[4] = {&gu, &gv, &gw, &err};
-  if (!d.DownloadInverse(dst)) return HostFail(d.InverseError().c_str());
-  return 0;
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out && out[0] && out[1] && out[2] && out[3], "f3d_flow_inverse_compute", &of)) return 1;
+  return DerivedDownload(flow, OpticalFlowE::kInverse, flow->driver.ComputeInverse(of, iterations, tolerance, stats), out, 1);
 }
 
-int f3d_flow_inverse_end(f3d_flow flow)
-{
-  g_host_error.clear();
-  if (!flow) return HostFail("f3d_flow_inverse_end: null driver");
-  flow->driver.ReleaseInverse();
-  return 0;
-}
+int f3d_flow_inverse_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kInverse, "f3d_flow_inverse_end: null driver"); }
 
 const char* f3d_host_last_error(void) { return g_host_error.empty() ? f3d_last_error() : g_host_error.c_str(); }
 

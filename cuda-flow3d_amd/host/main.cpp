@@ -36,6 +36,7 @@
 #include <cstring>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -347,72 +348,68 @@ int main(int argc, char** argv)
     for (size_t i = 0; i < n; ++i) lost += std::isnan(u[i]) ? 1 : 0;
     std::printf("displacement frame 0 -> frame %zu: %zu of %zu voxels have left the volume\n", k + 1, lost, n);
   };
-  // --strain: the selected fields of pair k (of its flow, or with --cumulative of the displacement frame 0 -> frame k+1) and the
-  // statistics the device computed with them
+  // --strain, --principal, --inverse: the derived fields of pair k (of its flow, or with --cumulative of the displacement frame 0 ->
+  // frame k+1) and the statistics the device computed with them.  One descriptor per feature, in the order in which they run on the
+  // library stream and go down on the `down` queue.
+  struct DerivedField {
+    const char* option;  // without the dashes; the files are <tag>_<option>-<name><suffix>
+    OpticalFlowE::Derived which;
+    unsigned fields;     // the selection; 0 when the option was not given
+    const char* const* names;
+    std::function<bool(const OpticalFlowE::Displacement&)> compute;
+    std::function<void(size_t)> print;  // the statistics line of pair k
+    Data3D host[10];
+    Data3D* out[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // sequence mode: the kernel of pair k has run (`done`); its fields have gone down, so pair k+1 may rewrite them (`down`)
+    f3d_event done = nullptr, down = nullptr;
+  };
   static const char* const strain_names[8] = {"vol", "exx", "eyy", "ezz", "exy", "exz", "eyz", "eq"};
-  auto strain_selected = [&](int i) {
-    return (strain_fields & (i == 0 ? F3D_STRAIN_VOL : (i == 7 ? F3D_STRAIN_EQ : F3D_STRAIN_E))) != 0;
-  };
-  Data3D strain_host[8];
-  Data3D* strain_out[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 8; ++i)
-    if (strain_selected(i)) {
-      if (!strain_host[i].Allocate(width, height, depth)) return 2;
-      strain_out[i] = &strain_host[i];
-    }
-  f3d_strain_stats strain_stats = {};
-  auto write_strain = [&](size_t k) {
-    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
-    for (int i = 0; i < 8; ++i)
-      if (strain_out[i]) strain_host[i].WriteRAWToFileF32((tag + "_strain-" + strain_names[i] + suffix).c_str());
-    const f3d_strain_stats& st = strain_stats;
-    const double mean = st.defined ? st.vol_sum / static_cast<double>(st.defined) : std::nan("");
-    std::printf("strain frame %zu -> frame %zu: vol min/mean/max %.6g/%.6g/%.6g, eq max %.6g, %llu folded, %llu undefined of %zu "
-                "voxels\n", cumulative ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max, st.eq_max, st.folded,
-                static_cast<unsigned long long>(width * height * depth) - st.defined, width * height * depth);
-  };
-  // --principal: the same for the principal strains of that displacement
   static const char* const principal_names[10] = {"e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z"};
-  auto principal_selected = [&](int i) {
-    const unsigned group =
-        i < 3 ? F3D_PRINCIPAL_VALUES : (i == 3 ? F3D_PRINCIPAL_SHEAR : (i < 7 ? F3D_PRINCIPAL_DIR1 : F3D_PRINCIPAL_DIR3));
-    return (principal_fields & group) != 0;
-  };
-  Data3D principal_host[10];
-  Data3D* principal_out[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 10; ++i)
-    if (principal_selected(i)) {
-      if (!principal_host[i].Allocate(width, height, depth)) return 2;
-      principal_out[i] = &principal_host[i];
-    }
-  f3d_principal_stats principal_stats = {};
-  auto write_principal = [&](size_t k) {
-    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
-    for (int i = 0; i < 10; ++i)
-      if (principal_out[i]) principal_host[i].WriteRAWToFileF32((tag + "_principal-" + principal_names[i] + suffix).c_str());
-    const f3d_principal_stats& st = principal_stats;
-    std::printf("principal frame %zu -> frame %zu: e1 max %.6g, e3 min %.6g, shear max %.6g, %llu undefined of %zu voxels\n",
-                cumulative ? size_t(0) : k, k + 1, st.e1_max, st.e3_min, st.shear_max,
-                static_cast<unsigned long long>(width * height * depth) - st.defined, width * height * depth);
-  };
-  // --inverse: the inverse of that displacement (g_u, g_v, g_w and the round-trip residual) and its statistics
   static const char* const inverse_names[4] = {"u", "v", "w", "err"};
-  Data3D inverse_host[4];
-  Data3D* inverse_out[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (inverse)
-    for (int i = 0; i < 4; ++i) {
-      if (!inverse_host[i].Allocate(width, height, depth)) return 2;
-      inverse_out[i] = &inverse_host[i];
-    }
+  const size_t voxels = width * height * depth;
+  f3d_strain_stats strain_stats = {};
+  f3d_principal_stats principal_stats = {};
   f3d_inverse_stats inverse_stats = {};
-  auto write_inverse = [&](size_t k) {
+  DerivedField derived[3] = {
+      {"strain", OpticalFlowE::kStrain, strain_fields, strain_names,
+       [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputeStrain(of, strain_fields, &strain_stats); },
+       [&](size_t k) {
+         const f3d_strain_stats& st = strain_stats;
+         const double mean = st.defined ? st.vol_sum / static_cast<double>(st.defined) : std::nan("");
+         std::printf("strain frame %zu -> frame %zu: vol min/mean/max %.6g/%.6g/%.6g, eq max %.6g, %llu folded, %llu undefined of %zu "
+                     "voxels\n", cumulative ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max, st.eq_max, st.folded,
+                     static_cast<unsigned long long>(voxels) - st.defined, voxels);
+       }},
+      {"principal", OpticalFlowE::kPrincipal, principal_fields, principal_names,
+       [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputePrincipal(of, principal_fields, &principal_stats); },
+       [&](size_t k) {
+         const f3d_principal_stats& st = principal_stats;
+         std::printf("principal frame %zu -> frame %zu: e1 max %.6g, e3 min %.6g, shear max %.6g, %llu undefined of %zu voxels\n",
+                     cumulative ? size_t(0) : k, k + 1, st.e1_max, st.e3_min, st.shear_max,
+                     static_cast<unsigned long long>(voxels) - st.defined, voxels);
+       }},
+      {"inverse", OpticalFlowE::kInverse, inverse ? 1u : 0u, inverse_names,
+       [&](const OpticalFlowE::Displacement& of) {
+         return optical_flow_e.ComputeInverse(of, inverse_iterations, inverse_tolerance, &inverse_stats);
+       },
+       [&](size_t k) {
+         const f3d_inverse_stats& st = inverse_stats;
+         const double mean = st.defined ? static_cast<double>(st.steps_sum) / static_cast<double>(st.defined) : std::nan("");
+         std::printf("inverse frame %zu -> frame %zu: err max %.6g, mean steps %.6g, %llu unconverged, %llu lost of %zu voxels\n", k + 1,
+                     cumulative ? size_t(0) : k, st.err_max, mean, st.unconverged, static_cast<unsigned long long>(voxels) - st.defined,
+                     voxels);
+       }}};
+  for (DerivedField& f : derived)
+    for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)
+      if (OpticalFlowE::DerivedSelected(f.which, i, f.fields)) {
+        if (!f.host[i].Allocate(width, height, depth)) return 2;
+        f.out[i] = &f.host[i];
+      }
+  auto write_derived = [&](DerivedField& f, size_t k) {
     const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
-    for (int i = 0; i < 4; ++i) inverse_host[i].WriteRAWToFileF32((tag + "_inverse-" + inverse_names[i] + suffix).c_str());
-    const f3d_inverse_stats& st = inverse_stats;
-    const double mean = st.defined ? static_cast<double>(st.steps_sum) / static_cast<double>(st.defined) : std::nan("");
-    std::printf("inverse frame %zu -> frame %zu: err max %.6g, mean steps %.6g, %llu unconverged, %llu lost of %zu voxels\n", k + 1,
-                cumulative ? size_t(0) : k, st.err_max, mean, st.unconverged,
-                static_cast<unsigned long long>(width * height * depth) - st.defined, width * height * depth);
+    for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)
+      if (f.out[i]) f.host[i].WriteRAWToFileF32((tag + "_" + f.option + "-" + f.names[i] + suffix).c_str());
+    f.print(k);
   };
 
   if (pairs == 1) {
@@ -428,23 +425,12 @@ int main(int argc, char** argv)
         return 3;
       write_disp(0);
     }
-    if (strain_fields) {
-      const bool ok = cumulative ? optical_flow_e.ComputeStrainOfTrajectory(strain_fields, &strain_stats)
-                                 : optical_flow_e.ComputeStrain(strain_fields, &strain_stats);
-      if (!ok || !optical_flow_e.DownloadStrain(strain_out, strain_fields)) return 3;
-      write_strain(0);
-    }
-    if (principal_fields) {
-      const bool ok = cumulative ? optical_flow_e.ComputePrincipalOfTrajectory(principal_fields, &principal_stats)
-                                 : optical_flow_e.ComputePrincipal(principal_fields, &principal_stats);
-      if (!ok || !optical_flow_e.DownloadPrincipal(principal_out, principal_fields)) return 3;
-      write_principal(0);
-    }
-    if (inverse) {
-      const bool ok = cumulative ? optical_flow_e.ComputeInverseOfTrajectory(inverse_iterations, inverse_tolerance, &inverse_stats)
-                                 : optical_flow_e.ComputeInverse(inverse_iterations, inverse_tolerance, &inverse_stats);
-      if (!ok || !optical_flow_e.DownloadInverse(inverse_out)) return 3;
-      write_inverse(0);
+    for (DerivedField& f : derived) {
+      if (!f.fields) continue;
+      if (!f.compute(cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::HeldFlow()) ||
+          !optical_flow_e.DownloadDerived(f.which, f.out, f.fields))
+        return 3;
+      write_derived(f, 0);
     }
   } else {
     // Sequence: pair k solves on the device while the host reads frame k+2 and uploads it on one copy queue, and downloads and
@@ -471,12 +457,9 @@ int main(int argc, char** argv)
       for (Data3D& f : set) pin(f);
     if (cumulative)
       for (Data3D& d : disp) pin(d);
-    for (Data3D* d : strain_out)
-      if (d) pin(*d);
-    for (Data3D* d : principal_out)
-      if (d) pin(*d);
-    for (Data3D* d : inverse_out)
-      if (d) pin(*d);
+    for (DerivedField& f : derived)
+      for (Data3D* d : f.out)
+        if (d) pin(*d);
     f3d_queue up = nullptr, down = nullptr;
     f3d_event uploaded[3] = {nullptr, nullptr, nullptr};
     if (CheckDeviceError(f3d_queue_create(&up)) || CheckDeviceError(f3d_queue_create(&down))) return 3;
@@ -499,20 +482,13 @@ int main(int argc, char** argv)
       if (CheckDeviceError(f3d_event_create(&composed)) || CheckDeviceError(f3d_event_create(&disp_down))) return 3;
       if (!optical_flow_e.ResetTrajectory()) return 3;
     }
-    // --strain: the same pattern for the strain containers.  Strain k runs on the library stream right after compose k (or after
-    // TakeResult); its statistics wait for that kernel only.  The fields go down on `down` beside solve k+1 once strain k is done
-    // (`strained`), and strain k+1, which rewrites the same containers, waits for that download (`strain_down`).
-    f3d_event strained = nullptr, strain_down = nullptr;
-    if (strain_fields)
-      if (CheckDeviceError(f3d_event_create(&strained)) || CheckDeviceError(f3d_event_create(&strain_down))) return 3;
-    // --principal: once more the same, with containers and events of its own (`principal_done`, `principal_down`)
-    f3d_event principal_done = nullptr, principal_down = nullptr;
-    if (principal_fields)
-      if (CheckDeviceError(f3d_event_create(&principal_done)) || CheckDeviceError(f3d_event_create(&principal_down))) return 3;
-    // --inverse: and again (`inverse_done`, `inverse_down`)
-    f3d_event inverse_done = nullptr, inverse_down = nullptr;
-    if (inverse)
-      if (CheckDeviceError(f3d_event_create(&inverse_done)) || CheckDeviceError(f3d_event_create(&inverse_down))) return 3;
+    // --strain, --principal, --inverse: the same pattern for each one's containers.  The kernel of pair k runs on the library stream
+    // right after compose k (or after TakeResult); its statistics wait for that kernel only.  The fields go down on `down` beside
+    // solve k+1 once the kernel is done (`done`), and the kernel of pair k+1, which rewrites the same containers, waits for that
+    // download (`down`).
+    for (DerivedField& f : derived)
+      if (f.fields)
+        if (CheckDeviceError(f3d_event_create(&f.done)) || CheckDeviceError(f3d_event_create(&f.down))) return 3;
     DevicePtr taken[3] = {0, 0, 0};
     bool pending_output = false;
     const bool serial_sequence = std::getenv("F3D_SEQ_SERIAL") && std::atoi(std::getenv("F3D_SEQ_SERIAL")) != 0;
@@ -530,9 +506,8 @@ int main(int argc, char** argv)
         optical_flow_e.GiveResultBack(taken);
         write_pair(k - 1, host_flow[(k - 1) & 1][0], host_flow[(k - 1) & 1][1], host_flow[(k - 1) & 1][2]);
         if (cumulative) write_disp(k - 1);
-        if (strain_fields) write_strain(k - 1);
-        if (principal_fields) write_principal(k - 1);
-        if (inverse) write_inverse(k - 1);
+        for (DerivedField& f : derived)
+          if (f.fields) write_derived(f, k - 1);
         pending_output = false;
       }
       optical_flow_e.EndComputeFlowResident();
@@ -552,44 +527,17 @@ int main(int argc, char** argv)
                                                   optical_flow_e.TrajectoryContainer(i), c.pitch, c.height, 0));
         CheckDeviceError(f3d_event_record_on(disp_down, down));
       }
-      if (strain_fields) {
-        if (k > 0) CheckDeviceError(f3d_queue_wait_event(nullptr, strain_down));
-        const bool ok = cumulative ? optical_flow_e.ComputeStrainOfTrajectory(strain_fields, &strain_stats)
-                                   : optical_flow_e.ComputeStrain(taken, strain_fields, &strain_stats);
-        if (!ok) return 3;
-        CheckDeviceError(f3d_event_record(strained));
-        CheckDeviceError(f3d_queue_wait_event(down, strained));
-        for (int i = 0; i < 8; ++i)
-          if (strain_out[i])
-            CheckDeviceError(f3d_copy_planes_d2h_on(down, strain_host[i].DataPtr(), width, height, width, height, depth,
-                                                    optical_flow_e.StrainContainer(i), c.pitch, c.height, 0));
-        CheckDeviceError(f3d_event_record_on(strain_down, down));
-      }
-      if (principal_fields) {
-        if (k > 0) CheckDeviceError(f3d_queue_wait_event(nullptr, principal_down));
-        const bool ok = cumulative ? optical_flow_e.ComputePrincipalOfTrajectory(principal_fields, &principal_stats)
-                                   : optical_flow_e.ComputePrincipal(taken, principal_fields, &principal_stats);
-        if (!ok) return 3;
-        CheckDeviceError(f3d_event_record(principal_done));
-        CheckDeviceError(f3d_queue_wait_event(down, principal_done));
-        for (int i = 0; i < 10; ++i)
-          if (principal_out[i])
-            CheckDeviceError(f3d_copy_planes_d2h_on(down, principal_host[i].DataPtr(), width, height, width, height, depth,
-                                                    optical_flow_e.PrincipalContainer(i), c.pitch, c.height, 0));
-        CheckDeviceError(f3d_event_record_on(principal_down, down));
-      }
-      if (inverse) {
-        if (k > 0) CheckDeviceError(f3d_queue_wait_event(nullptr, inverse_down));
-        const bool ok = cumulative
-                            ? optical_flow_e.ComputeInverseOfTrajectory(inverse_iterations, inverse_tolerance, &inverse_stats)
-                            : optical_flow_e.ComputeInverse(taken, inverse_iterations, inverse_tolerance, &inverse_stats);
-        if (!ok) return 3;
-        CheckDeviceError(f3d_event_record(inverse_done));
-        CheckDeviceError(f3d_queue_wait_event(down, inverse_done));
-        for (int i = 0; i < 4; ++i)
-          CheckDeviceError(f3d_copy_planes_d2h_on(down, inverse_host[i].DataPtr(), width, height, width, height, depth,
-                                                  optical_flow_e.InverseContainer(i), c.pitch, c.height, 0));
-        CheckDeviceError(f3d_event_record_on(inverse_down, down));
+      for (DerivedField& f : derived) {
+        if (!f.fields) continue;
+        if (k > 0) CheckDeviceError(f3d_queue_wait_event(nullptr, f.down));
+        if (!f.compute(cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return 3;
+        CheckDeviceError(f3d_event_record(f.done));
+        CheckDeviceError(f3d_queue_wait_event(down, f.done));
+        for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)
+          if (f.out[i])
+            CheckDeviceError(f3d_copy_planes_d2h_on(down, f.host[i].DataPtr(), width, height, width, height, depth,
+                                                    optical_flow_e.DerivedContainer(f.which, i), c.pitch, c.height, 0));
+        CheckDeviceError(f3d_event_record_on(f.down, down));
       }
       pending_output = true;
     }
@@ -601,20 +549,11 @@ int main(int argc, char** argv)
       f3d_event_destroy(composed);
       f3d_event_destroy(disp_down);
     }
-    if (strain_fields) {
-      write_strain(pairs - 1);
-      f3d_event_destroy(strained);
-      f3d_event_destroy(strain_down);
-    }
-    if (principal_fields) {
-      write_principal(pairs - 1);
-      f3d_event_destroy(principal_done);
-      f3d_event_destroy(principal_down);
-    }
-    if (inverse) {
-      write_inverse(pairs - 1);
-      f3d_event_destroy(inverse_done);
-      f3d_event_destroy(inverse_down);
+    for (DerivedField& f : derived) {
+      if (!f.fields) continue;
+      write_derived(f, pairs - 1);
+      f3d_event_destroy(f.done);
+      f3d_event_destroy(f.down);
     }
     CheckDeviceError(f3d_queue_sync(up));
     for (f3d_event e : uploaded) f3d_event_destroy(e);

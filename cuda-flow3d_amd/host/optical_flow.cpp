@@ -76,7 +76,35 @@ OpticalFlowBase::~OpticalFlowBase() {}
 
 // ---- single-GPU driver ---------------------------------------------------------------------------------------
 
-OpticalFlowE::OpticalFlowE() : OpticalFlowBase("Optical Flow Single GPU")
+// the F3D_* bit that selects each output of f3d_flow_strain and f3d_principal_strain (the inverse has no selection)
+namespace {
+
+const unsigned kStrainGroups[8] = {F3D_STRAIN_VOL, F3D_STRAIN_E, F3D_STRAIN_E, F3D_STRAIN_E,
+                                   F3D_STRAIN_E,   F3D_STRAIN_E, F3D_STRAIN_E, F3D_STRAIN_EQ};
+const unsigned kPrincipalGroups[10] = {F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_SHEAR,
+                                       F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR3,
+                                       F3D_PRINCIPAL_DIR3,   F3D_PRINCIPAL_DIR3};
+const unsigned kPrincipalAll = F3D_PRINCIPAL_VALUES | F3D_PRINCIPAL_SHEAR | F3D_PRINCIPAL_DIR1 | F3D_PRINCIPAL_DIR3;
+const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4};
+const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr};
+const char* const kTrajectoryNotStarted = "the trajectory was not started (ResetTrajectory first)";
+
+}  // namespace
+
+OpticalFlowE::OpticalFlowE()
+    : OpticalFlowBase("Optical Flow Single GPU"),
+      trajectory_{this, 3, nullptr, "the three trajectory containers do not fit beside the driver's on the device",
+                  kTrajectoryNotStarted, "no host volume for a trajectory component",
+                  "the device library has no f3d_compose_flow (trajectory composition)", "no flow to compose"},
+      derived_{{this, kDerivedFields[kStrain], kStrainGroups, "the strain containers do not fit beside the driver's on the device",
+                "a requested strain field has not been computed", "no host volume for a requested strain field",
+                "the device library has no f3d_flow_strain (strain fields)", "no displacement to differentiate"},
+               {this, kDerivedFields[kPrincipal], kPrincipalGroups, "the principal strain containers do not fit beside the driver's on the device",
+                "a requested principal strain field has not been computed", "no host volume for a requested principal strain field",
+                "the device library has no f3d_principal_strain (principal strains)", "no displacement to differentiate"},
+               {this, kDerivedFields[kInverse], nullptr, "the inverse displacement containers do not fit beside the driver's on the device",
+                "the inverse displacement has not been computed", "no host volume for an inverse displacement field",
+                "the device library has no f3d_invert_displacement (inverse displacement)", "no displacement to invert"}}
 {
   // same initialisation order as the reference's forward_list built with push_front (optical_flow_e.cpp:34-39)
   cuda_operations_ = {&cuop_solve_, &cuop_resample_, &cuop_register_, &cuop_median_, &cuop_convolution_, &cuop_add_};
@@ -390,48 +418,91 @@ bool OpticalFlowE::FinalResidual(Residual& registered, Residual& unregistered)
   return ok;
 }
 
-// ---- trajectory of a frame sequence ------------------------------------------------------------------------------------------
+// ---- containers of the trajectory and of the derived fields ------------------------------------------------------------------
 
-bool OpticalFlowE::TrajectoryFail(const char* what)
+int OpticalFlowE::DerivedFieldCount(Derived which) { return kDerivedFields[which]; }
+
+bool OpticalFlowE::DerivedSelected(Derived which, int field, unsigned fields)
 {
-  trajectory_error_ = std::string("'") + GetName() + "': " + what;
-  std::printf("Error: %s\n", trajectory_error_.c_str());
+  return kDerivedGroups[which] ? (fields & kDerivedGroups[which][field]) != 0 : fields != 0;
+}
+
+bool OpticalFlowE::FieldSet::Fail(const char* what)
+{
+  error = std::string("'") + driver->GetName() + "': " + what;
+  std::printf("Error: %s\n", error.c_str());
   return false;
 }
 
-bool OpticalFlowE::AllocateTrajectory()
+bool OpticalFlowE::FieldSet::Allocate(unsigned mask)
 {
-  trajectory_error_.clear();
-  if (!f3d_compose_flow) return TrajectoryFail("the device library has no f3d_compose_flow (trajectory composition)");
-  if (!initialized_) return TrajectoryFail("the driver was not initialized");
-  if (trajectory_[0]) return true;
-  const size_t rows = dev_container_size_.height * dev_container_size_.depth;
-  for (DevicePtr& p : trajectory_) {
+  const DataSize4& c = driver->dev_container_size_;
+  for (int i = 0; i < count; ++i) {
+    if (!Selected(i, mask) || ptr[i]) continue;
     size_t pitch = 0;
-    if (f3d_alloc_pitched(&p, &pitch, dev_container_size_.width * sizeof(float), rows) != 0) p = 0;
-    if (!p || pitch != dev_container_size_.pitch) {
-      ReleaseTrajectory();
-      return TrajectoryFail("the three trajectory containers do not fit beside the driver's on the device");
+    if (f3d_alloc_pitched(&ptr[i], &pitch, c.width * sizeof(float), c.height * c.depth) != 0) ptr[i] = 0;
+    if (!ptr[i] || pitch != c.pitch) {
+      Release();
+      return Fail(fit);
     }
   }
   return true;
+}
+
+bool OpticalFlowE::FieldSet::Download(Data3D* const* out, unsigned mask)
+{
+  error.clear();
+  const DataSize4& c = driver->dev_container_size_;
+  for (int i = 0; i < count; ++i) {
+    if (!Selected(i, mask)) continue;
+    if (!ptr[i]) return Fail(not_computed);
+    if (!out[i]) return Fail(no_volume);
+    if (!Check(CheckDeviceError(f3d_copy3d_d2h(out[i]->DataPtr(), out[i]->Width(), out[i]->Height(), out[i]->Depth(), ptr[i], c.pitch,
+                                               c.height, 0))))
+      return false;
+  }
+  return true;
+}
+
+void OpticalFlowE::FieldSet::Release()
+{
+  for (DevicePtr& p : ptr) {
+    if (p) CheckDeviceError(f3d_free(p));
+    p = 0;
+  }
+}
+
+f3d_size4 OpticalFlowE::Container() const
+{
+  return {dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, dev_container_size_.pitch};
+}
+
+// ---- trajectory of a frame sequence ------------------------------------------------------------------------------------------
+
+bool OpticalFlowE::AllocateTrajectory()
+{
+  trajectory_.error.clear();
+  if (!f3d_compose_flow) return trajectory_.Fail(trajectory_.no_entry);
+  if (!initialized_) return trajectory_.Fail("the driver was not initialized");
+  return trajectory_.Allocate(0);
 }
 
 bool OpticalFlowE::ResetTrajectory()
 {
   if (!AllocateTrajectory()) return false;
   const size_t rows = dev_container_size_.height * dev_container_size_.depth;
-  for (DevicePtr p : trajectory_)
-    if (CheckDeviceError(f3d_memset2d(p, dev_container_size_.pitch, 0, dev_container_size_.width * sizeof(float), rows)))
-      return TrajectoryFail(f3d_last_error());
+  for (int i = 0; i < 3; ++i)
+    if (!trajectory_.Check(CheckDeviceError(f3d_memset2d(trajectory_.ptr[i], dev_container_size_.pitch, 0,
+                                                         dev_container_size_.width * sizeof(float), rows))))
+      return false;
   return true;
 }
 
 bool OpticalFlowE::ComposeTrajectory()
 {
   if (!result_flow_[0]) {
-    trajectory_error_.clear();
-    return TrajectoryFail("no flow is held on the device (ComputeFlowResident first)");
+    trajectory_.error.clear();
+    return trajectory_.Fail("no flow is held on the device (ComputeFlowResident first)");
   }
   const DevicePtr flow[3] = {result_flow_[0], result_flow_[1], result_flow_[2]};
   return ComposeTrajectory(flow);
@@ -439,27 +510,20 @@ bool OpticalFlowE::ComposeTrajectory()
 
 bool OpticalFlowE::ComposeTrajectory(const DevicePtr (&flow)[3])
 {
-  trajectory_error_.clear();
-  if (!f3d_compose_flow) return TrajectoryFail("the device library has no f3d_compose_flow (trajectory composition)");
-  if (!trajectory_[0]) return TrajectoryFail("the trajectory was not started (ResetTrajectory first)");
-  if (!flow[0] || !flow[1] || !flow[2]) return TrajectoryFail("no flow to compose");
-  const f3d_size4 c = {dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, dev_container_size_.pitch};
-  if (CheckDeviceError(f3d_set_container(&c)) ||
-      CheckDeviceError(f3d_compose_flow(trajectory_[0], trajectory_[1], trajectory_[2], flow[0], flow[1], flow[2],
-                                        dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, nullptr)))
-    return TrajectoryFail(f3d_last_error());
-  return true;
+  trajectory_.error.clear();
+  if (!f3d_compose_flow) return trajectory_.Fail(trajectory_.no_entry);
+  if (!trajectory_.ptr[0]) return trajectory_.Fail(kTrajectoryNotStarted);
+  if (!flow[0] || !flow[1] || !flow[2]) return trajectory_.Fail(trajectory_.no_displacement);
+  const f3d_size4 c = Container();
+  return trajectory_.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         trajectory_.Check(CheckDeviceError(f3d_compose_flow(trajectory_.ptr[0], trajectory_.ptr[1], trajectory_.ptr[2], flow[0],
+                                                             flow[1], flow[2], c.width, c.height, c.depth, nullptr)));
 }
 
 bool OpticalFlowE::DownloadTrajectory(Data3D& u, Data3D& v, Data3D& w, unsigned long long* lost)
 {
-  trajectory_error_.clear();
-  if (!trajectory_[0]) return TrajectoryFail("the trajectory was not started (ResetTrajectory first)");
-  Data3D* out[3] = {&u, &v, &w};
-  for (int c = 0; c < 3; ++c)
-    if (CheckDeviceError(f3d_copy3d_d2h(out[c]->DataPtr(), out[c]->Width(), out[c]->Height(), out[c]->Depth(), trajectory_[c],
-                                        dev_container_size_.pitch, dev_container_size_.height, 0)))
-      return TrajectoryFail(f3d_last_error());
+  Data3D* const out[3] = {&u, &v, &w};
+  if (!trajectory_.Download(out, 0)) return false;
   if (lost) {
     const float* p = u.DataPtr();
     const size_t n = u.Width() * u.Height() * u.Depth();
@@ -470,279 +534,63 @@ bool OpticalFlowE::DownloadTrajectory(Data3D& u, Data3D& v, Data3D& w, unsigned 
   return true;
 }
 
-void OpticalFlowE::ReleaseTrajectory()
+// ---- derived fields of a displacement: strain, principal strain, inverse ----------------------------------------------------------
+
+bool OpticalFlowE::ResolveDisplacement(FieldSet& set, const Displacement& of, bool have_entry, DevicePtr (&disp)[3])
 {
-  for (DevicePtr& p : trajectory_) {
-    if (p) CheckDeviceError(f3d_free(p));
-    p = 0;
+  set.error.clear();
+  const DevicePtr* from = of.containers;
+  if (of.kind == Displacement::kHeldFlow) {
+    if (!result_flow_[0]) return set.Fail("no flow is held on the device (ComputeFlowResident first)");
+    from = result_flow_;
+  } else if (of.kind == Displacement::kTrajectory) {
+    if (!trajectory_.ptr[0]) return set.Fail(kTrajectoryNotStarted);
+    from = trajectory_.ptr;
   }
-}
-
-// ---- strain fields of a displacement ------------------------------------------------------------------------------------------
-
-namespace {
-
-// the F3D_STRAIN_* group of output i (vol, exx .. eyz, eq)
-unsigned StrainGroup(int i) { return i == 0 ? F3D_STRAIN_VOL : (i == 7 ? F3D_STRAIN_EQ : F3D_STRAIN_E); }
-
-}  // namespace
-
-bool OpticalFlowE::StrainFail(const char* what)
-{
-  strain_error_ = std::string("'") + GetName() + "': " + what;
-  std::printf("Error: %s\n", strain_error_.c_str());
-  return false;
-}
-
-bool OpticalFlowE::AllocateStrain(unsigned fields)
-{
-  const size_t rows = dev_container_size_.height * dev_container_size_.depth;
-  for (int i = 0; i < 8; ++i) {
-    if (!(fields & StrainGroup(i)) || strain_[i]) continue;
-    size_t pitch = 0;
-    if (f3d_alloc_pitched(&strain_[i], &pitch, dev_container_size_.width * sizeof(float), rows) != 0) strain_[i] = 0;
-    if (!strain_[i] || pitch != dev_container_size_.pitch) {
-      ReleaseStrain();
-      return StrainFail("the strain containers do not fit beside the driver's on the device");
-    }
-  }
+  if (!have_entry) return set.Fail(set.no_entry);
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!from[0] || !from[1] || !from[2]) return set.Fail(set.no_displacement);
+  for (int i = 0; i < 3; ++i) disp[i] = from[i];
   return true;
 }
 
-bool OpticalFlowE::ComputeStrain(const DevicePtr (&disp)[3], unsigned fields, f3d_strain_stats* stats)
+bool OpticalFlowE::ComputeStrain(const Displacement& of, unsigned fields, f3d_strain_stats* stats)
 {
-  strain_error_.clear();
-  if (!f3d_flow_strain) return StrainFail("the device library has no f3d_flow_strain (strain fields)");
-  if (!initialized_) return StrainFail("the driver was not initialized");
-  if (!disp[0] || !disp[1] || !disp[2]) return StrainFail("no displacement to differentiate");
+  FieldSet& set = derived_[kStrain];
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, f3d_flow_strain != nullptr, d)) return false;
   if (fields == 0 || (fields & ~(F3D_STRAIN_VOL | F3D_STRAIN_E | F3D_STRAIN_EQ)))
-    return StrainFail("fields must be a non-empty combination of F3D_STRAIN_VOL, F3D_STRAIN_E, F3D_STRAIN_EQ");
-  if (!AllocateStrain(fields)) return false;
-  const f3d_size4 c = {dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, dev_container_size_.pitch};
-  if (CheckDeviceError(f3d_set_container(&c)) ||
-      CheckDeviceError(f3d_flow_strain(disp[0], disp[1], disp[2], strain_, fields, dev_container_size_.width,
-                                       dev_container_size_.height, dev_container_size_.depth, stats)))
-    return StrainFail(f3d_last_error());
-  return true;
+    return set.Fail("fields must be a non-empty combination of F3D_STRAIN_VOL, F3D_STRAIN_E, F3D_STRAIN_EQ");
+  if (!set.Allocate(fields)) return false;
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         set.Check(CheckDeviceError(f3d_flow_strain(d[0], d[1], d[2], set.ptr, fields, c.width, c.height, c.depth, stats)));
 }
 
-bool OpticalFlowE::ComputeStrain(unsigned fields, f3d_strain_stats* stats)
+bool OpticalFlowE::ComputePrincipal(const Displacement& of, unsigned fields, f3d_principal_stats* stats)
 {
-  if (!result_flow_[0]) {
-    strain_error_.clear();
-    return StrainFail("no flow is held on the device (ComputeFlowResident first)");
-  }
-  const DevicePtr flow[3] = {result_flow_[0], result_flow_[1], result_flow_[2]};
-  return ComputeStrain(flow, fields, stats);
-}
-
-bool OpticalFlowE::ComputeStrainOfTrajectory(unsigned fields, f3d_strain_stats* stats)
-{
-  if (!trajectory_[0]) {
-    strain_error_.clear();
-    return StrainFail("the trajectory was not started (ResetTrajectory first)");
-  }
-  const DevicePtr disp[3] = {trajectory_[0], trajectory_[1], trajectory_[2]};
-  return ComputeStrain(disp, fields, stats);
-}
-
-bool OpticalFlowE::DownloadStrain(Data3D* const (&out)[8], unsigned fields)
-{
-  strain_error_.clear();
-  for (int i = 0; i < 8; ++i) {
-    if (!(fields & StrainGroup(i))) continue;
-    if (!strain_[i]) return StrainFail("a requested strain field has not been computed");
-    if (!out[i]) return StrainFail("no host volume for a requested strain field");
-    if (CheckDeviceError(f3d_copy3d_d2h(out[i]->DataPtr(), out[i]->Width(), out[i]->Height(), out[i]->Depth(), strain_[i],
-                                        dev_container_size_.pitch, dev_container_size_.height, 0)))
-      return StrainFail(f3d_last_error());
-  }
-  return true;
-}
-
-void OpticalFlowE::ReleaseStrain()
-{
-  for (DevicePtr& p : strain_) {
-    if (p) CheckDeviceError(f3d_free(p));
-    p = 0;
-  }
-}
-
-// ---- principal strains of a displacement --------------------------------------------------------------------------------------
-
-namespace {
-
-const unsigned kPrincipalAll = F3D_PRINCIPAL_VALUES | F3D_PRINCIPAL_SHEAR | F3D_PRINCIPAL_DIR1 | F3D_PRINCIPAL_DIR3;
-
-// the F3D_PRINCIPAL_* group of output i (e1 e2 e3, gmax, d1x d1y d1z, d3x d3y d3z)
-unsigned PrincipalGroup(int i)
-{
-  return i < 3 ? F3D_PRINCIPAL_VALUES : (i == 3 ? F3D_PRINCIPAL_SHEAR : (i < 7 ? F3D_PRINCIPAL_DIR1 : F3D_PRINCIPAL_DIR3));
-}
-
-}  // namespace
-
-bool OpticalFlowE::PrincipalFail(const char* what)
-{
-  principal_error_ = std::string("'") + GetName() + "': " + what;
-  std::printf("Error: %s\n", principal_error_.c_str());
-  return false;
-}
-
-bool OpticalFlowE::AllocatePrincipal(unsigned fields)
-{
-  const size_t rows = dev_container_size_.height * dev_container_size_.depth;
-  for (int i = 0; i < 10; ++i) {
-    if (!(fields & PrincipalGroup(i)) || principal_[i]) continue;
-    size_t pitch = 0;
-    if (f3d_alloc_pitched(&principal_[i], &pitch, dev_container_size_.width * sizeof(float), rows) != 0) principal_[i] = 0;
-    if (!principal_[i] || pitch != dev_container_size_.pitch) {
-      ReleasePrincipal();
-      return PrincipalFail("the principal strain containers do not fit beside the driver's on the device");
-    }
-  }
-  return true;
-}
-
-bool OpticalFlowE::ComputePrincipal(const DevicePtr (&disp)[3], unsigned fields, f3d_principal_stats* stats)
-{
-  principal_error_.clear();
-  if (!f3d_principal_strain) return PrincipalFail("the device library has no f3d_principal_strain (principal strains)");
-  if (!initialized_) return PrincipalFail("the driver was not initialized");
-  if (!disp[0] || !disp[1] || !disp[2]) return PrincipalFail("no displacement to differentiate");
+  FieldSet& set = derived_[kPrincipal];
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, f3d_principal_strain != nullptr, d)) return false;
   if (fields == 0 || (fields & ~kPrincipalAll))
-    return PrincipalFail("fields must be a non-empty combination of F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_SHEAR, F3D_PRINCIPAL_DIR1, "
-                         "F3D_PRINCIPAL_DIR3");
-  if (!AllocatePrincipal(fields)) return false;
-  const f3d_size4 c = {dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, dev_container_size_.pitch};
-  if (CheckDeviceError(f3d_set_container(&c)) ||
-      CheckDeviceError(f3d_principal_strain(disp[0], disp[1], disp[2], principal_, fields, dev_container_size_.width,
-                                            dev_container_size_.height, dev_container_size_.depth, stats)))
-    return PrincipalFail(f3d_last_error());
-  return true;
+    return set.Fail("fields must be a non-empty combination of F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_SHEAR, F3D_PRINCIPAL_DIR1, "
+                    "F3D_PRINCIPAL_DIR3");
+  if (!set.Allocate(fields)) return false;
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         set.Check(CheckDeviceError(f3d_principal_strain(d[0], d[1], d[2], set.ptr, fields, c.width, c.height, c.depth, stats)));
 }
 
-bool OpticalFlowE::ComputePrincipal(unsigned fields, f3d_principal_stats* stats)
+bool OpticalFlowE::ComputeInverse(const Displacement& of, unsigned iterations, float tolerance, f3d_inverse_stats* stats)
 {
-  if (!result_flow_[0]) {
-    principal_error_.clear();
-    return PrincipalFail("no flow is held on the device (ComputeFlowResident first)");
-  }
-  const DevicePtr flow[3] = {result_flow_[0], result_flow_[1], result_flow_[2]};
-  return ComputePrincipal(flow, fields, stats);
-}
-
-bool OpticalFlowE::ComputePrincipalOfTrajectory(unsigned fields, f3d_principal_stats* stats)
-{
-  if (!trajectory_[0]) {
-    principal_error_.clear();
-    return PrincipalFail("the trajectory was not started (ResetTrajectory first)");
-  }
-  const DevicePtr disp[3] = {trajectory_[0], trajectory_[1], trajectory_[2]};
-  return ComputePrincipal(disp, fields, stats);
-}
-
-bool OpticalFlowE::DownloadPrincipal(Data3D* const (&out)[10], unsigned fields)
-{
-  principal_error_.clear();
-  for (int i = 0; i < 10; ++i) {
-    if (!(fields & PrincipalGroup(i))) continue;
-    if (!principal_[i]) return PrincipalFail("a requested principal strain field has not been computed");
-    if (!out[i]) return PrincipalFail("no host volume for a requested principal strain field");
-    if (CheckDeviceError(f3d_copy3d_d2h(out[i]->DataPtr(), out[i]->Width(), out[i]->Height(), out[i]->Depth(), principal_[i],
-                                        dev_container_size_.pitch, dev_container_size_.height, 0)))
-      return PrincipalFail(f3d_last_error());
-  }
-  return true;
-}
-
-void OpticalFlowE::ReleasePrincipal()
-{
-  for (DevicePtr& p : principal_) {
-    if (p) CheckDeviceError(f3d_free(p));
-    p = 0;
-  }
-}
-
-// ---- inverse of a displacement ------------------------------------------------------------------------------------------------
-
-bool OpticalFlowE::InverseFail(const char* what)
-{
-  inverse_error_ = std::string("'") + GetName() + "': " + what;
-  std::printf("Error: %s\n", inverse_error_.c_str());
-  return false;
-}
-
-bool OpticalFlowE::AllocateInverse()
-{
-  const size_t rows = dev_container_size_.height * dev_container_size_.depth;
-  for (DevicePtr& p : inverse_) {
-    if (p) continue;
-    size_t pitch = 0;
-    if (f3d_alloc_pitched(&p, &pitch, dev_container_size_.width * sizeof(float), rows) != 0) p = 0;
-    if (!p || pitch != dev_container_size_.pitch) {
-      ReleaseInverse();
-      return InverseFail("the inverse displacement containers do not fit beside the driver's on the device");
-    }
-  }
-  return true;
-}
-
-bool OpticalFlowE::ComputeInverse(const DevicePtr (&disp)[3], unsigned iterations, float tolerance, f3d_inverse_stats* stats)
-{
-  inverse_error_.clear();
-  if (!f3d_invert_displacement) return InverseFail("the device library has no f3d_invert_displacement (inverse displacement)");
-  if (!initialized_) return InverseFail("the driver was not initialized");
-  if (!disp[0] || !disp[1] || !disp[2]) return InverseFail("no displacement to invert");
-  if (!AllocateInverse()) return false;
-  const f3d_size4 c = {dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth, dev_container_size_.pitch};
-  if (CheckDeviceError(f3d_set_container(&c)) ||
-      CheckDeviceError(f3d_invert_displacement(disp[0], disp[1], disp[2], inverse_[0], inverse_[1], inverse_[2], inverse_[3],
-                                               dev_container_size_.width, dev_container_size_.height, dev_container_size_.depth,
-                                               iterations, tolerance, stats)))
-    return InverseFail(f3d_last_error());
-  return true;
-}
-
-bool OpticalFlowE::ComputeInverse(unsigned iterations, float tolerance, f3d_inverse_stats* stats)
-{
-  if (!result_flow_[0]) {
-    inverse_error_.clear();
-    return InverseFail("no flow is held on the device (ComputeFlowResident first)");
-  }
-  const DevicePtr flow[3] = {result_flow_[0], result_flow_[1], result_flow_[2]};
-  return ComputeInverse(flow, iterations, tolerance, stats);
-}
-
-bool OpticalFlowE::ComputeInverseOfTrajectory(unsigned iterations, float tolerance, f3d_inverse_stats* stats)
-{
-  if (!trajectory_[0]) {
-    inverse_error_.clear();
-    return InverseFail("the trajectory was not started (ResetTrajectory first)");
-  }
-  const DevicePtr disp[3] = {trajectory_[0], trajectory_[1], trajectory_[2]};
-  return ComputeInverse(disp, iterations, tolerance, stats);
-}
-
-bool OpticalFlowE::DownloadInverse(Data3D* const (&out)[4])
-{
-  inverse_error_.clear();
-  for (int i = 0; i < 4; ++i) {
-    if (!inverse_[i]) return InverseFail("the inverse displacement has not been computed");
-    if (!out[i]) return InverseFail("no host volume for an inverse displacement field");
-    if (CheckDeviceError(f3d_copy3d_d2h(out[i]->DataPtr(), out[i]->Width(), out[i]->Height(), out[i]->Depth(), inverse_[i],
-                                        dev_container_size_.pitch, dev_container_size_.height, 0)))
-      return InverseFail(f3d_last_error());
-  }
-  return true;
-}
-
-void OpticalFlowE::ReleaseInverse()
-{
-  for (DevicePtr& p : inverse_) {
-    if (p) CheckDeviceError(f3d_free(p));
-    p = 0;
-  }
+  FieldSet& set = derived_[kInverse];
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, f3d_invert_displacement != nullptr, d)) return false;
+  if (!set.Allocate(0)) return false;
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         set.Check(CheckDeviceError(f3d_invert_displacement(d[0], d[1], d[2], set.ptr[0], set.ptr[1], set.ptr[2], set.ptr[3], c.width,
+                                                            c.height, c.depth, iterations, tolerance, stats)));
 }
 
 // The coarse-to-fine solve on two frames that are already on the device (optical_flow_e.cpp:208-533 is the sequence of operator
@@ -909,10 +757,8 @@ void OpticalFlowE::Destroy()
 {
   for (CudaOperationBase* cuop : cuda_operations_) cuop->Destroy();
   ReleaseResult();
-  ReleaseTrajectory();
-  ReleaseStrain();
-  ReleasePrincipal();
-  ReleaseInverse();
+  trajectory_.Release();
+  for (FieldSet& set : derived_) set.Release();
   size_t freed = 0;
   while (!free_containers_.empty()) {
     CheckDeviceError(f3d_free(free_containers_.back()));

@@ -111,48 +111,38 @@ class OpticalFlowE : public OpticalFlowBase {
   bool ComposeTrajectory();                                         // with the flow ComputeFlowResident() left on the device
   bool ComposeTrajectory(const DevicePtr (&flow)[3]);               // with three given containers (TakeResult's)
   bool DownloadTrajectory(Data3D& u, Data3D& v, Data3D& w, unsigned long long* lost);  // lost: voxels whose u is NaN
-  DevicePtr TrajectoryContainer(int component) const { return trajectory_[component]; }
-  void ReleaseTrajectory();
-  const std::string& TrajectoryError() const { return trajectory_error_; }
+  DevicePtr TrajectoryContainer(int component) const { return trajectory_.ptr[component]; }
+  void ReleaseTrajectory() { trajectory_.Release(); }
+  const std::string& TrajectoryError() const { return trajectory_.error; }
 
-  // Strain fields of a displacement (f3d_flow_strain: vol = J - 1, Green-Lagrange E, equivalent strain; include/f3d.h has the
-  // definition).  Eight outputs in the order vol, exx, eyy, ezz, exy, exz, eyz, eq, selected in groups by F3D_STRAIN_* bits; each
-  // selected output gets a container of its own, allocated on first use and freed by ReleaseStrain() and Destroy().  Compute enqueues
-  // on the library stream and waits only when stats is given.  Every call returns false with StrainError() set when it cannot run --
-  // among other reasons when the device library lacks f3d_flow_strain.
-  bool ComputeStrain(const DevicePtr (&disp)[3], unsigned fields, f3d_strain_stats* stats);  // three given containers (TakeResult's)
-  bool ComputeStrain(unsigned fields, f3d_strain_stats* stats);                // of the flow ComputeFlowResident() left on the device
-  bool ComputeStrainOfTrajectory(unsigned fields, f3d_strain_stats* stats);    // of the trajectory (ResetTrajectory first)
-  DevicePtr StrainContainer(int field) const { return strain_[field]; }        // 0 until a computation has selected the field
-  bool DownloadStrain(Data3D* const (&out)[8], unsigned fields);               // the selected fields (entries of others ignored)
-  void ReleaseStrain();
-  const std::string& StrainError() const { return strain_error_; }
-
-  // Principal strains of a displacement (f3d_principal_strain: e1 >= e2 >= e3 of the Green-Lagrange tensor, maximum shear, the
-  // directions of e1 and e3; include/f3d.h has the definition), in the forms and with the conventions of the strain fields above:
-  // fields is a combination of F3D_PRINCIPAL_VALUES / _SHEAR / _DIR1 / _DIR3, a container per selected output is allocated on first
-  // use and freed by ReleasePrincipal() and Destroy(), and a call that cannot run -- among other reasons when the device library
-  // lacks f3d_principal_strain -- returns false with PrincipalError() set.
-  bool ComputePrincipal(const DevicePtr (&disp)[3], unsigned fields, f3d_principal_stats* stats);
-  bool ComputePrincipal(unsigned fields, f3d_principal_stats* stats);
-  bool ComputePrincipalOfTrajectory(unsigned fields, f3d_principal_stats* stats);
-  DevicePtr PrincipalContainer(int field) const { return principal_[field]; }
-  bool DownloadPrincipal(Data3D* const (&out)[10], unsigned fields);
-  void ReleasePrincipal();
-  const std::string& PrincipalError() const { return principal_error_; }
-
-  // Inverse of a displacement (f3d_invert_displacement: g on the deformed frame's grid with g(y) = -d(y + g(y)), and the round-trip
-  // residual err of the stored g; include/f3d.h has the definition), in the forms and with the conventions of the strain fields
-  // above: four containers (g_u, g_v, g_w, err) allocated on first use and freed by ReleaseInverse() and Destroy(); Compute enqueues
-  // on the library stream and waits only when stats is given; a call that cannot run -- among other reasons when the device library
-  // lacks f3d_invert_displacement -- returns false with InverseError() set.
-  bool ComputeInverse(const DevicePtr (&disp)[3], unsigned iterations, float tolerance, f3d_inverse_stats* stats);
-  bool ComputeInverse(unsigned iterations, float tolerance, f3d_inverse_stats* stats);
-  bool ComputeInverseOfTrajectory(unsigned iterations, float tolerance, f3d_inverse_stats* stats);
-  DevicePtr InverseContainer(int field) const { return inverse_[field]; }       // 0 until a computation has run
-  bool DownloadInverse(Data3D* const (&out)[4]);
-  void ReleaseInverse();
-  const std::string& InverseError() const { return inverse_error_; }
+  // Derived fields of a displacement (include/f3d.h has the definitions):
+  //   kStrain     f3d_flow_strain: vol = J - 1, Green-Lagrange E, equivalent strain.  Eight outputs in the order vol, exx, eyy, ezz,
+  //               exy, exz, eyz, eq, selected in groups by F3D_STRAIN_* bits.
+  //   kPrincipal  f3d_principal_strain: e1 >= e2 >= e3 of E, maximum shear, the directions of e1 and e3.  Ten outputs in the order
+  //               e1, e2, e3, gmax, d1x, d1y, d1z, d3x, d3y, d3z, selected by F3D_PRINCIPAL_VALUES / _SHEAR / _DIR1 / _DIR3.
+  //   kInverse    f3d_invert_displacement: g on the deformed frame's grid with g(y) = -d(y + g(y)), and the round-trip residual
+  //               of the stored g.  Four outputs g_u, g_v, g_w, err, always all of them (fields is ignored).
+  // Each selected output gets a container of its own, allocated on first use and freed by ReleaseDerived() and Destroy().  Compute
+  // enqueues on the library stream and waits only when stats is given.  Every call returns false with DerivedError() set when it
+  // cannot run -- among other reasons when the device library lacks the entry point.
+  enum Derived { kStrain = 0, kPrincipal, kInverse, kDerivedCount };
+  // the displacement a derived field is computed of
+  struct Displacement {
+    enum Kind { kHeldFlow, kTrajectory, kContainers } kind;
+    DevicePtr containers[3];
+  };
+  static Displacement HeldFlow() { return {Displacement::kHeldFlow, {0, 0, 0}}; }      // what ComputeFlowResident() left on the device
+  static Displacement Trajectory() { return {Displacement::kTrajectory, {0, 0, 0}}; }  // ResetTrajectory first
+  static Displacement Containers(const DevicePtr (&d)[3]) { return {Displacement::kContainers, {d[0], d[1], d[2]}}; }  // TakeResult's
+  bool ComputeStrain(const Displacement& of, unsigned fields, f3d_strain_stats* stats);
+  bool ComputePrincipal(const Displacement& of, unsigned fields, f3d_principal_stats* stats);
+  bool ComputeInverse(const Displacement& of, unsigned iterations, float tolerance, f3d_inverse_stats* stats);
+  static int DerivedFieldCount(Derived which);
+  static bool DerivedSelected(Derived which, int field, unsigned fields);
+  DevicePtr DerivedContainer(Derived which, int field) const { return derived_[which].ptr[field]; }  // 0 until computed
+  bool DownloadDerived(Derived which, Data3D* const* out, unsigned fields) { return derived_[which].Download(out, fields); }
+  void ReleaseDerived(Derived which) { derived_[which].Release(); }
+  const std::string& DerivedError(Derived which) const { return derived_[which].error; }
 
  private:
   static constexpr size_t kContainers = 15;  // optical_flow_e.h:40
@@ -172,21 +162,31 @@ class OpticalFlowE : public OpticalFlowBase {
   f3d_event ev_begin_ = nullptr, ev_end_ = nullptr;
   DevicePtr result_flow_[3] = {0, 0, 0};
   float last_device_seconds_ = 0.f;
-  DevicePtr trajectory_[3] = {0, 0, 0};
-  std::string trajectory_error_;
-  bool TrajectoryFail(const char* what);
-  DevicePtr strain_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  std::string strain_error_;
-  bool StrainFail(const char* what);
-  bool AllocateStrain(unsigned fields);
-  DevicePtr principal_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  std::string principal_error_;
-  bool PrincipalFail(const char* what);
-  bool AllocatePrincipal(unsigned fields);
-  DevicePtr inverse_[4] = {0, 0, 0, 0};
-  std::string inverse_error_;
-  bool InverseFail(const char* what);
-  bool AllocateInverse();
+  // A set of device containers one feature owns: the trajectory's three, the outputs of a derived field.
+  struct FieldSet {
+    OpticalFlowE* driver;
+    int count;
+    const unsigned* groups;    // the F3D_* bit that selects each field; null: every field, whatever the mask
+    const char* fit;           // what Allocate says when the device has no room
+    const char* not_computed;  // what Download says of a field without a container, and of one without a host volume
+    const char* no_volume;
+    const char* no_entry;      // what Compute says when the device library lacks the entry point, and when there is no displacement
+    const char* no_displacement;
+    DevicePtr ptr[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::string error;
+
+    bool Selected(int field, unsigned mask) const { return !groups || (mask & groups[field]) != 0; }
+    bool Fail(const char* what);
+    bool Check(bool device_error) { return device_error ? Fail(f3d_last_error()) : true; }  // of a CheckDeviceError(call)
+    bool Allocate(unsigned mask);                      // a container for each selected field that has none
+    bool Download(Data3D* const* out, unsigned mask);  // the selected fields (entries of others ignored)
+    void Release();
+  };
+  FieldSet trajectory_;
+  FieldSet derived_[kDerivedCount];
+  // clears set's error and gives the three containers of `of`, or fails with the text that says what is missing
+  bool ResolveDisplacement(FieldSet& set, const Displacement& of, bool have_entry, DevicePtr (&disp)[3]);
+  f3d_size4 Container() const;
   std::vector<LevelStatistics> level_stats_;
   bool ResidualOf(DevicePtr frame_0, DevicePtr warped, const DataSize4& size, Residual& out);
 
