@@ -65,6 +65,14 @@ class InverseStats(C.Structure):  # f3d_inverse_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class CorrelationStats(C.Structure):  # f3d_correlation_stats
+    _fields_ = [("defined", C.c_ulonglong), ("lost", C.c_ulonglong), ("below", C.c_ulonglong), ("zncc_min", C.c_float),
+                ("rmsd_max", C.c_float), ("zncc_sum", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class FlowParams(C.Structure):  # f3d_flow_params
     _fields_ = [
         ("warp_levels_count", C.c_size_t), ("warp_scale_factor", C.c_float),
@@ -237,6 +245,8 @@ def host():
         "f3d_flow_principal_end": [C.c_void_p],
         "f3d_flow_inverse_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_float, C.POINTER(_fp), C.POINTER(InverseStats)],
         "f3d_flow_inverse_end": [C.c_void_p],
+        "f3d_flow_match_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_float, C.POINTER(_fp), C.POINTER(CorrelationStats)],
+        "f3d_flow_match_end": [C.c_void_p],
         "f3d_op_create": [C.POINTER(C.c_void_p), C.c_char_p], "f3d_op_initialize": [C.c_void_p, C.POINTER(Size4)],
         "f3d_op_execute": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), _sz],
         "f3d_op_execute_batch": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(_sz), _sz],
@@ -368,6 +378,11 @@ def _carry_entry():
                   "carry fields through a displacement")
 
 
+def _correlation_entry():
+    return _entry("f3d_local_correlation", [_dp] * 2 + [_dpp, C.c_uint, C.c_uint, C.c_float] + [_sz] * 3 + [C.POINTER(CorrelationStats)],
+                  "compute the local correlation of two volumes")
+
+
 def _mask(fields, groups, what):
     """the F3D_* bits of an iterable of group names (the keys of `groups`) or of a comma-separated string of them"""
     if isinstance(fields, str):
@@ -439,6 +454,13 @@ _PRINCIPAL_GROUP_OF = (1, 1, 1, 2, 4, 4, 4, 8, 8, 8)
 # the four outputs of f3d_invert_displacement in ABI order, and the modes of f3d_carry_field
 INVERSE_NAMES = ("gu", "gv", "gw", "err")
 CARRY_MODES = {"linear": 1, "nearest": 2}
+
+
+# the outputs of OpticalFlow.match in the order of f3d_flow_match_compute, and the F3D_MATCH_* bit of each; f3d_local_correlation
+# stores the last two (F3D_CORRELATION_ZNCC, F3D_CORRELATION_RMSD)
+MATCH_NAMES = ("warped", "zncc", "rmsd")
+MATCH_GROUPS = {"warped": 1, "zncc": 2, "rmsd": 4}
+CORRELATION_GROUPS = {"zncc": 1, "rmsd": 2}
 
 
 def _strain_mask(fields):
@@ -514,6 +536,25 @@ def carry_field(field, u, v, w, mode="linear"):
         lost = C.c_ulonglong()
         check(fn(*p, out, *dims, m, C.byref(lost)), "f3d_carry_field")
         return box.download(out, dims), int(lost.value)
+
+
+def local_correlation(a, b, radius=3, threshold=0.8, fields=("zncc", "rmsd")):
+    """Per-voxel match quality of two volumes on one grid on the device (include/f3d.h, f3d_local_correlation): a, b numpy [z, y, x]
+    float32, in practice frame 0 and frame 1 carried onto frame 0's grid (carry_field; NaN where the point left the volume).  Over the
+    (2 radius + 1)^3 window of every voxel, of the voxels present in both: "zncc" the zero-normalised cross-correlation (NaN where the
+    window is flat), "rmsd" the RMS difference; both NaN where the voxel itself is absent.  radius 1 .. 4.  Returns a dict name -> array
+    for the selected fields and "stats" -> dict (defined, lost, below = defined voxels with zncc < threshold, zncc_min, rmsd_max,
+    zncc_sum)."""
+    fn = _correlation_entry()
+    mask = _mask(fields, CORRELATION_GROUPS, "correlation")
+    with _on_device((a, b), "a and b must be two [z, y, x] volumes of one shape") as (box, p, dims):
+        outs = [box.alloc() if mask & g else 0 for g in CORRELATION_GROUPS.values()]
+        box.set_current()
+        stats = CorrelationStats()
+        check(fn(*p, (_dp * 2)(*outs), mask, radius, threshold, *dims, C.byref(stats)), "f3d_local_correlation")
+        res = {n: box.download(o, dims) for n, o in zip(CORRELATION_GROUPS, outs) if o}
+    res["stats"] = stats.as_dict()
+    return res
 
 
 def _f32(a):
@@ -1005,7 +1046,7 @@ class OpticalFlow:
     def trajectory_end(self):
         _host_check(host().f3d_flow_trajectory_end(self._h), "f3d_flow_trajectory_end")
 
-    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_strain_* / _principal_* / _inverse_*) ----
+    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_{strain,principal,inverse,match}_*) ----
     def _derived(self, compute, src, selected, stats, *args):
         """one f3d_flow_*_compute into fresh host arrays: a list with an array per selected output and None for the others"""
         w, h, d = self.dims
@@ -1053,6 +1094,22 @@ class OpticalFlow:
     def inverse_end(self):
         """free the inverse displacement containers (destroy() does too)"""
         _host_check(host().f3d_flow_inverse_end(self._h), "f3d_flow_inverse_end")
+
+    def match(self, fields=("zncc", "rmsd"), radius=3, threshold=0.8):
+        """Match quality of the flow the driver holds against the frames it holds (after upload + compute_resident): frame 1 carried
+        onto frame 0's grid through the flow ("warped", NaN where the point leaves the volume) and its local correlation with frame 0
+        ("zncc", "rmsd"; local_correlation() has the definition).  Returns a dict name -> array for the selected fields and
+        "stats" -> dict.  Works between the yields of compute_sequence for the pair just solved; the cumulative displacement has no
+        match quality (frame 0 is not kept)."""
+        mask, stats = _mask(fields, MATCH_GROUPS, "match"), CorrelationStats()
+        arrays = self._derived("f3d_flow_match_compute", 0, [mask & g for g in MATCH_GROUPS.values()], stats, mask, radius, threshold)
+        res = {n: a for n, a in zip(MATCH_NAMES, arrays) if a is not None}
+        res["stats"] = stats.as_dict()
+        return res
+
+    def match_end(self):
+        """free the match quality containers (destroy() does too)"""
+        _host_check(host().f3d_flow_match_end(self._h), "f3d_flow_match_end")
 
     def compute_sequence(self, frames, cumulative=False, silent=True, **kw):
         """Generator over the consecutive pairs of `frames` (an iterable of [z, y, x] volumes): yields (k, (u, v, w), disp) for

@@ -303,6 +303,19 @@ int f3d_flow_inverse_compute(f3d_flow flow, int source, unsigned iterations, flo
 
 int f3d_flow_inverse_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kInverse, "f3d_flow_inverse_end: null driver"); }
 
+static_assert(F3D_MATCH_WARPED == OpticalFlowE::kMatchWarped && F3D_MATCH_ZNCC == OpticalFlowE::kMatchZncc &&
+                  F3D_MATCH_RMSD == OpticalFlowE::kMatchRmsd, "f3d_host.h and optical_flow.h name the match fields alike");
+
+int f3d_flow_match_compute(f3d_flow flow, int source, unsigned fields, unsigned radius, float threshold, float* const out[3],
+                           f3d_correlation_stats* stats)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out != nullptr, "f3d_flow_match_compute", &of)) return 1;
+  return DerivedDownload(flow, OpticalFlowE::kMatch, flow->driver.ComputeMatch(of, 0, 0, fields, radius, threshold, stats), out, fields);
+}
+
+int f3d_flow_match_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kMatch, "f3d_flow_match_end: null driver"); }
+
 const char* f3d_host_last_error(void) { return g_host_error.empty() ? f3d_last_error() : g_host_error.c_str(); }
 
 int f3d_flow_destroy(f3d_flow flow)

@@ -5,7 +5,7 @@
 // flags:  flow3d --dims W H D --frames f0.raw f1.raw [f2.raw ...] [--f32] [--out prefix] [--levels N] [--scale s]
 //                [--outer N] [--inner N] [--alpha a] [--eps-smooth e] [--eps-data e] [--median r] [--sigma s]
 //                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
-//                [--strain vol,e,eq] [--principal val,shear,dir1,dir3] [--inverse]
+//                [--strain vol,e,eq] [--principal val,shear,dir1,dir3] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -30,6 +30,10 @@
 // steps, tolerance 1e-3): <tag>_inverse-{u,v,w,err}-W-H-D.raw is the displacement on the LATER frame's grid that leads back to the
 // earlier one (NaN where the point comes from outside the volume) and the round-trip residual of it, and one line of statistics per
 // pair.
+// --match LIST (resident driver, pairs in order; LIST a comma-separated subset of warped,zncc,rmsd) says where the flow is to be
+// believed: frame k+1 is carried onto frame k's grid through the PAIR's flow (f3d_carry_field; also under --cumulative, since frame 0
+// is not kept) and compared with frame k over (2R+1)^3 windows on the device (f3d_local_correlation; --match-radius R, 1 .. 4,
+// default 3).  <tag>_match-{warped,zncc,rmsd}-W-H-D.raw with the flow's tag, and one line of statistics per pair.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -54,7 +58,7 @@ static void Usage()
               "              [--levels N] [--scale s] [--outer N] [--inner N] [--alpha a] [--eps-smooth e]\n"
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
               "              [--concurrent N] [--cumulative] [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
-              "              [--inverse]\n");
+              "              [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n");
 }
 
 int main(int argc, char** argv)
@@ -68,6 +72,10 @@ int main(int argc, char** argv)
   unsigned strain_fields = 0;     // --strain: F3D_STRAIN_* groups
   unsigned principal_fields = 0;  // --principal: F3D_PRINCIPAL_* groups
   bool inverse = false;           // --inverse
+  unsigned match_fields = 0;      // --match: OpticalFlowE::kMatch* bits
+  unsigned match_radius = 3;      // --match-radius
+  bool match_radius_given = false;
+  const float match_threshold = 0.8f;
   const unsigned inverse_iterations = 32;
   const float inverse_tolerance = 1e-3f;
 
@@ -147,6 +155,29 @@ int main(int argc, char** argv)
         at = end + 1;
       }
     }
+    else if (a == "--match") {
+      need(1);
+      const std::string list = argv[++i];
+      size_t at = 0;
+      while (true) {
+        const size_t end = list.find(',', at);
+        const std::string item = list.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        if (item == "warped") match_fields |= OpticalFlowE::kMatchWarped;
+        else if (item == "zncc") match_fields |= OpticalFlowE::kMatchZncc;
+        else if (item == "rmsd") match_fields |= OpticalFlowE::kMatchRmsd;
+        else { Usage(); return 64; }
+        if (end == std::string::npos) break;
+        at = end + 1;
+      }
+    }
+    else if (a == "--match-radius") {
+      need(1);
+      char* rest = nullptr;
+      const unsigned long r = std::strtoul(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest || r < 1 || r > 4) { Usage(); return 64; }
+      match_radius = static_cast<unsigned>(r);
+      match_radius_given = true;
+    }
     else { Usage(); return 64; }
   }
   if (width == 0 || height == 0 || depth == 0 || (!synthetic && files.size() < 2)) {
@@ -171,6 +202,17 @@ int main(int argc, char** argv)
   }
   if (inverse && (use_partial_gpu || concurrent > 1)) {
     std::printf("--inverse needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if (match_radius_given && !match_fields) {
+    std::printf("--match-radius needs --match\n");
+    Usage();
+    return 64;
+  }
+  if (match_fields && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--match needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
                 use_partial_gpu ? "--partial" : "--concurrent N > 1");
     Usage();
     return 64;
@@ -349,13 +391,14 @@ int main(int argc, char** argv)
     std::printf("displacement frame 0 -> frame %zu: %zu of %zu voxels have left the volume\n", k + 1, lost, n);
   };
   // --strain, --principal, --inverse: the derived fields of pair k (of its flow, or with --cumulative of the displacement frame 0 ->
-  // frame k+1) and the statistics the device computed with them.  One descriptor per feature, in the order in which they run on the
-  // library stream and go down on the `down` queue.
+  // frame k+1) and the statistics the device computed with them; --match: always of the pair's flow and the pair's frames.  One
+  // descriptor per feature, in the order in which they run on the library stream and go down on the `down` queue.
   struct DerivedField {
     const char* option;  // without the dashes; the files are <tag>_<option>-<name><suffix>
     OpticalFlowE::Derived which;
     unsigned fields;     // the selection; 0 when the option was not given
     const char* const* names;
+    bool of_pair;        // computed of the pair's flow also under --cumulative
     std::function<bool(const OpticalFlowE::Displacement&)> compute;
     std::function<void(size_t)> print;  // the statistics line of pair k
     Data3D host[10];
@@ -366,12 +409,14 @@ int main(int argc, char** argv)
   static const char* const strain_names[8] = {"vol", "exx", "eyy", "ezz", "exy", "exz", "eyz", "eq"};
   static const char* const principal_names[10] = {"e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z"};
   static const char* const inverse_names[4] = {"u", "v", "w", "err"};
+  static const char* const match_names[3] = {"warped", "zncc", "rmsd"};
   const size_t voxels = width * height * depth;
   f3d_strain_stats strain_stats = {};
   f3d_principal_stats principal_stats = {};
   f3d_inverse_stats inverse_stats = {};
-  DerivedField derived[3] = {
-      {"strain", OpticalFlowE::kStrain, strain_fields, strain_names,
+  f3d_correlation_stats match_stats = {};
+  DerivedField derived[4] = {
+      {"strain", OpticalFlowE::kStrain, strain_fields, strain_names, false,
        [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputeStrain(of, strain_fields, &strain_stats); },
        [&](size_t k) {
          const f3d_strain_stats& st = strain_stats;
@@ -380,7 +425,7 @@ int main(int argc, char** argv)
                      "voxels\n", cumulative ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max, st.eq_max, st.folded,
                      static_cast<unsigned long long>(voxels) - st.defined, voxels);
        }},
-      {"principal", OpticalFlowE::kPrincipal, principal_fields, principal_names,
+      {"principal", OpticalFlowE::kPrincipal, principal_fields, principal_names, false,
        [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputePrincipal(of, principal_fields, &principal_stats); },
        [&](size_t k) {
          const f3d_principal_stats& st = principal_stats;
@@ -388,7 +433,7 @@ int main(int argc, char** argv)
                      cumulative ? size_t(0) : k, k + 1, st.e1_max, st.e3_min, st.shear_max,
                      static_cast<unsigned long long>(voxels) - st.defined, voxels);
        }},
-      {"inverse", OpticalFlowE::kInverse, inverse ? 1u : 0u, inverse_names,
+      {"inverse", OpticalFlowE::kInverse, inverse ? 1u : 0u, inverse_names, false,
        [&](const OpticalFlowE::Displacement& of) {
          return optical_flow_e.ComputeInverse(of, inverse_iterations, inverse_tolerance, &inverse_stats);
        },
@@ -398,6 +443,18 @@ int main(int argc, char** argv)
          std::printf("inverse frame %zu -> frame %zu: err max %.6g, mean steps %.6g, %llu unconverged, %llu lost of %zu voxels\n", k + 1,
                      cumulative ? size_t(0) : k, st.err_max, mean, st.unconverged, static_cast<unsigned long long>(voxels) - st.defined,
                      voxels);
+       }},
+      // the frames of the pair are the resident pair: in a sequence SelectResidentPair(k, k+1) holds until the next solve begins
+      {"match", OpticalFlowE::kMatch, match_fields, match_names, true,
+       [&](const OpticalFlowE::Displacement& of) {
+         return optical_flow_e.ComputeMatch(of, 0, 0, match_fields, match_radius, match_threshold, &match_stats);
+       },
+       [&](size_t k) {
+         const f3d_correlation_stats& st = match_stats;
+         const double mean = st.defined ? st.zncc_sum / static_cast<double>(st.defined) : std::nan("");
+         std::printf("match frame %zu -> frame %zu: zncc min/mean %.6g/%.6g, %llu below %.6g, rmsd max %.6g, %llu flat, %llu lost of %zu "
+                     "voxels\n", k, k + 1, st.zncc_min, mean, st.below, match_threshold, st.rmsd_max,
+                     static_cast<unsigned long long>(voxels) - st.defined - st.lost, st.lost, voxels);
        }}};
   for (DerivedField& f : derived)
     for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)
@@ -427,7 +484,7 @@ int main(int argc, char** argv)
     }
     for (DerivedField& f : derived) {
       if (!f.fields) continue;
-      if (!f.compute(cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::HeldFlow()) ||
+      if (!f.compute(cumulative && !f.of_pair ? OpticalFlowE::Trajectory() : OpticalFlowE::HeldFlow()) ||
           !optical_flow_e.DownloadDerived(f.which, f.out, f.fields))
         return 3;
       write_derived(f, 0);
@@ -486,6 +543,11 @@ int main(int argc, char** argv)
     // right after compose k (or after TakeResult); its statistics wait for that kernel only.  The fields go down on `down` beside
     // solve k+1 once the kernel is done (`done`), and the kernel of pair k+1, which rewrites the same containers, waits for that
     // download (`down`).
+    // --match is the one reader of the frame containers after the solve: match k reads frames k and k+1, and the upload of frame k+3
+    // on `up`, issued right after solve k+1 is enqueued, overwrites frame k's slot.  The host wait of EndComputeFlowResident and of
+    // the statistics happens to order the two; the order is made explicit all the same: `up` waits for match k (`done`) before it
+    // reuses the slot.
+    DerivedField& match = derived[3];
     for (DerivedField& f : derived)
       if (f.fields)
         if (CheckDeviceError(f3d_event_create(&f.done)) || CheckDeviceError(f3d_event_create(&f.down))) return 3;
@@ -500,6 +562,7 @@ int main(int argc, char** argv)
       optical_flow_e.BeginComputeFlowResident(params);
       if (serial_sequence) optical_flow_e.EndComputeFlowResident();  // A/B timing: nothing runs beside the solve
       // beside it: frame k+2 into the container pair k-1 has released, and the previous pair's flow out to its files
+      if (match.fields && k > 0) CheckDeviceError(f3d_queue_wait_event(up, match.done));  // match k-1 read the slot of frame k+2
       if (k + 2 <= pairs && !upload(k + 2)) return 2;
       if (pending_output) {
         CheckDeviceError(f3d_queue_sync(down));
@@ -530,7 +593,7 @@ int main(int argc, char** argv)
       for (DerivedField& f : derived) {
         if (!f.fields) continue;
         if (k > 0) CheckDeviceError(f3d_queue_wait_event(nullptr, f.down));
-        if (!f.compute(cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return 3;
+        if (!f.compute(cumulative && !f.of_pair ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return 3;
         CheckDeviceError(f3d_event_record(f.done));
         CheckDeviceError(f3d_queue_wait_event(down, f.done));
         for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)

@@ -24,6 +24,11 @@ extern "C" int f3d_principal_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, co
 extern "C" int f3d_invert_displacement(f3d_devptr d_u, f3d_devptr d_v, f3d_devptr d_w, f3d_devptr g_u, f3d_devptr g_v,
                                        f3d_devptr g_w, f3d_devptr err, size_t width, size_t height, size_t depth,
                                        unsigned iterations, float tolerance, f3d_inverse_stats* stats) __attribute__((weak));
+extern "C" int f3d_carry_field(f3d_devptr field, f3d_devptr m_u, f3d_devptr m_v, f3d_devptr m_w, f3d_devptr out, size_t width,
+                               size_t height, size_t depth, unsigned mode, unsigned long long* lost) __attribute__((weak));
+extern "C" int f3d_local_correlation(f3d_devptr a, f3d_devptr b, const f3d_devptr out[2], unsigned fields, unsigned radius,
+                                     float threshold, size_t width, size_t height, size_t depth, f3d_correlation_stats* stats)
+    __attribute__((weak));
 
 // ---- base --------------------------------------------------------------------------------------------------
 
@@ -85,8 +90,10 @@ const unsigned kPrincipalGroups[10] = {F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_VALUE
                                        F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR3,
                                        F3D_PRINCIPAL_DIR3,   F3D_PRINCIPAL_DIR3};
 const unsigned kPrincipalAll = F3D_PRINCIPAL_VALUES | F3D_PRINCIPAL_SHEAR | F3D_PRINCIPAL_DIR1 | F3D_PRINCIPAL_DIR3;
-const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4};
-const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr};
+const unsigned kMatchGroups[3] = {OpticalFlowE::kMatchWarped, OpticalFlowE::kMatchZncc, OpticalFlowE::kMatchRmsd};
+const unsigned kMatchAll = OpticalFlowE::kMatchWarped | OpticalFlowE::kMatchZncc | OpticalFlowE::kMatchRmsd;
+const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3};
+const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr, kMatchGroups};
 const char* const kTrajectoryNotStarted = "the trajectory was not started (ResetTrajectory first)";
 
 }  // namespace
@@ -104,7 +111,10 @@ OpticalFlowE::OpticalFlowE()
                 "the device library has no f3d_principal_strain (principal strains)", "no displacement to differentiate"},
                {this, kDerivedFields[kInverse], nullptr, "the inverse displacement containers do not fit beside the driver's on the device",
                 "the inverse displacement has not been computed", "no host volume for an inverse displacement field",
-                "the device library has no f3d_invert_displacement (inverse displacement)", "no displacement to invert"}}
+                "the device library has no f3d_invert_displacement (inverse displacement)", "no displacement to invert"},
+               {this, kDerivedFields[kMatch], kMatchGroups, "the match quality containers do not fit beside the driver's on the device",
+                "a requested match quality field has not been computed", "no host volume for a requested match quality field",
+                "the device library has no f3d_local_correlation (match quality)", "no displacement to carry frame 1 through"}}
 {
   // same initialisation order as the reference's forward_list built with push_front (optical_flow_e.cpp:34-39)
   cuda_operations_ = {&cuop_solve_, &cuop_resample_, &cuop_register_, &cuop_median_, &cuop_convolution_, &cuop_add_};
@@ -534,7 +544,7 @@ bool OpticalFlowE::DownloadTrajectory(Data3D& u, Data3D& v, Data3D& w, unsigned 
   return true;
 }
 
-// ---- derived fields of a displacement: strain, principal strain, inverse ----------------------------------------------------------
+// ---- derived fields of a displacement: strain, principal strain, inverse, match quality -------------------------------------------
 
 bool OpticalFlowE::ResolveDisplacement(FieldSet& set, const Displacement& of, bool have_entry, DevicePtr (&disp)[3])
 {
@@ -591,6 +601,34 @@ bool OpticalFlowE::ComputeInverse(const Displacement& of, unsigned iterations, f
   return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
          set.Check(CheckDeviceError(f3d_invert_displacement(d[0], d[1], d[2], set.ptr[0], set.ptr[1], set.ptr[2], set.ptr[3], c.width,
                                                             c.height, c.depth, iterations, tolerance, stats)));
+}
+
+bool OpticalFlowE::ComputeMatch(const Displacement& of, DevicePtr frame_0, DevicePtr frame_1, unsigned fields, unsigned radius,
+                                float threshold, f3d_correlation_stats* stats)
+{
+  FieldSet& set = derived_[kMatch];
+  if (of.kind == Displacement::kTrajectory) {
+    set.error.clear();
+    return set.Fail("the match quality of a trajectory is not available: frame 0 of a sequence is not kept (use a pair's flow)");
+  }
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, f3d_local_correlation != nullptr, d)) return false;
+  if (!f3d_carry_field) return set.Fail("the device library has no f3d_carry_field (match quality carries frame 1 through the flow)");
+  if (fields == 0 || (fields & ~kMatchAll)) return set.Fail("fields must be a non-empty combination of kMatchWarped, kMatchZncc, kMatchRmsd");
+  if (!frame_0) frame_0 = resident_frame_[0];
+  if (!frame_1) frame_1 = resident_frame_[1];
+  if (!frame_0 || !frame_1) return set.Fail("no frames on the device (AllocateResidentFrames and UploadResidentFrames first)");
+  // the kernel stores at least one field: zncc when only the warped frame was asked for
+  const unsigned stored = fields & (kMatchZncc | kMatchRmsd) ? fields & (kMatchZncc | kMatchRmsd) : kMatchZncc;
+  if (!set.Allocate(kMatchWarped | stored)) return false;
+  const f3d_size4 c = Container();
+  const DevicePtr out[2] = {set.ptr[1], set.ptr[2]};
+  const unsigned device_fields = (stored & kMatchZncc ? F3D_CORRELATION_ZNCC : 0u) | (stored & kMatchRmsd ? F3D_CORRELATION_RMSD : 0u);
+  return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         set.Check(CheckDeviceError(f3d_carry_field(frame_1, d[0], d[1], d[2], set.ptr[0], c.width, c.height, c.depth, F3D_CARRY_LINEAR,
+                                                    nullptr))) &&
+         set.Check(CheckDeviceError(f3d_local_correlation(frame_0, set.ptr[0], out, device_fields, radius, threshold, c.width, c.height,
+                                                          c.depth, stats)));
 }
 
 // The coarse-to-fine solve on two frames that are already on the device (optical_flow_e.cpp:208-533 is the sequence of operator

@@ -122,10 +122,15 @@ class OpticalFlowE : public OpticalFlowBase {
   //               e1, e2, e3, gmax, d1x, d1y, d1z, d3x, d3y, d3z, selected by F3D_PRINCIPAL_VALUES / _SHEAR / _DIR1 / _DIR3.
   //   kInverse    f3d_invert_displacement: g on the deformed frame's grid with g(y) = -d(y + g(y)), and the round-trip residual
   //               of the stored g.  Four outputs g_u, g_v, g_w, err, always all of them (fields is ignored).
+  //   kMatch      f3d_local_correlation of frame 0 against frame 1 carried onto frame 0's grid through the displacement
+  //               (f3d_carry_field, linear; NaN where the point leaves the volume).  Three outputs warped, zncc, rmsd selected by
+  //               kMatchWarped / kMatchZncc / kMatchRmsd.  The warped container is the kernel's input and is always allocated; it
+  //               is downloaded only when selected.
   // Each selected output gets a container of its own, allocated on first use and freed by ReleaseDerived() and Destroy().  Compute
   // enqueues on the library stream and waits only when stats is given.  Every call returns false with DerivedError() set when it
   // cannot run -- among other reasons when the device library lacks the entry point.
-  enum Derived { kStrain = 0, kPrincipal, kInverse, kDerivedCount };
+  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kDerivedCount };
+  enum MatchField : unsigned { kMatchWarped = 1u, kMatchZncc = 2u, kMatchRmsd = 4u };
   // the displacement a derived field is computed of
   struct Displacement {
     enum Kind { kHeldFlow, kTrajectory, kContainers } kind;
@@ -137,6 +142,10 @@ class OpticalFlowE : public OpticalFlowBase {
   bool ComputeStrain(const Displacement& of, unsigned fields, f3d_strain_stats* stats);
   bool ComputePrincipal(const Displacement& of, unsigned fields, f3d_principal_stats* stats);
   bool ComputeInverse(const Displacement& of, unsigned iterations, float tolerance, f3d_inverse_stats* stats);
+  // frame_0 / frame_1: the containers of the two frames the displacement belongs to; 0 means the resident pair.  A trajectory is
+  // refused: frame 0 of a sequence is not kept.
+  bool ComputeMatch(const Displacement& of, DevicePtr frame_0, DevicePtr frame_1, unsigned fields, unsigned radius, float threshold,
+                    f3d_correlation_stats* stats);
   static int DerivedFieldCount(Derived which);
   static bool DerivedSelected(Derived which, int field, unsigned fields);
   DevicePtr DerivedContainer(Derived which, int field) const { return derived_[which].ptr[field]; }  // 0 until computed

@@ -567,6 +567,47 @@ int f3d_invert_displacement(f3d_devptr d_u, f3d_devptr d_v, f3d_devptr d_w, f3d_
 int f3d_carry_field(f3d_devptr field, f3d_devptr m_u, f3d_devptr m_v, f3d_devptr m_w, f3d_devptr out, size_t width, size_t height,
                     size_t depth, unsigned mode, unsigned long long* lost /* nullable; non-null waits */);
 
+/* Per-voxel match quality of two volumes on one grid (no reference counterpart: the correlation coefficient a volume-correlation
+ * workflow writes beside its displacement).  a and b are any two volumes; in practice a is frame 0 and b is frame 1 carried onto
+ * frame 0's grid by f3d_carry_field, NaN where the point left the volume.  For every voxel, over the (2r+1)^3 window round it, the
+ * zero-normalised cross-correlation (zncc) and the RMS difference (rmsd) of the voxels present in both.
+ * Presence: a voxel is present when it is inside the volume and neither a nor b is NaN there.
+ * Quantities per voxel, binary64:  m = 1 if present, else 0;  A = (double)a if present, else +0;  B likewise from b;
+ *   q1 = m   q2 = A   q3 = B   q4 = A*A   q5 = B*B   q6 = A*B   q7 = (A - B)*(A - B)        (the difference taken in binary64)
+ * Window sums, separably in the order x, then y, then z:
+ *   X_j(x,y,z) = (((t_-r + t_-r+1) + ...) + t_r)  with t_i = q_j(x+i, y, z);  terms outside the volume are +0 addends
+ *   Y_j = the same sum over X_j along y;  Z_j = the same sum over Y_j along z
+ * Every addition is rounded on its own in binary64, in ascending order of the coordinate; there are no running add / subtract sums,
+ * so a voxel's result does not depend on where a march started.  n, Sa, Sb, Saa, Sbb, Sab, Sdd = Z_1 .. Z_7.
+ * Outputs, float32:
+ *   the centre voxel absent:  both outputs NaN (the voxel counts as lost)
+ *   rmsd = sqrtf((float)Sdd / (float)n)
+ *   va = n*Saa - Sa*Sa ;  vb = n*Sbb - Sb*Sb ;  c = n*Sab - Sa*Sb        (binary64, every operation rounded on its own; no binary64
+ *                                                                          division or square root anywhere)
+ *   the window is flat when !(va > 0x1p-40 * (n*Saa)) or !(vb > 0x1p-40 * (n*Sbb))  (so a NaN counts as flat):  zncc = NaN
+ *     (the rounding noise of the sums is a few 1e-16 relative: constant volumes stay below 5e-16, 2^-40 is 9.1e-13, and a volume
+ *      of 1000 +- 0.01 is not flat)
+ *   else zncc = (float)c / (sqrtf((float)va) * sqrtf((float)vb))        (float32 operations rounded on their own, IEEE / and sqrt)
+ *   There is no clamp: a value may exceed 1 by an ulp.
+ * Outputs selected by bit: F3D_CORRELATION_ZNCC out[0], F3D_CORRELATION_RMSD out[1].  Geometry from the current container
+ * (f3d_set_container), whole volume, library stream.  Entries of out that are not selected are ignored and never written.  Refused:
+ * a null input; a null selected output; fields 0 or with unknown bits; radius outside 1 .. 4; a selected output that is also an
+ * input; two selected outputs that are the same container; a NaN threshold.  a and b may be the same container.
+ * stats (nullable; asking waits for the stream): defined = voxels whose zncc is not NaN, lost = voxels whose centre is absent,
+ * below = defined voxels with zncc < threshold, zncc_min = the exact min over the defined voxels (NaN when there is none), zncc_sum
+ * accumulated in double over them (0 when none), rmsd_max = the exact max of rmsd over the voxels that are not lost (NaN when all
+ * are).  The voxels that are neither defined nor lost are the flat ones.  Both outputs are computed for the statistics whether or
+ * not they are stored.  The same numbers every run: per-workgroup partials folded in a fixed order, no float atomics. */
+#define F3D_CORRELATION_ZNCC 1u
+#define F3D_CORRELATION_RMSD 2u
+typedef struct f3d_correlation_stats {
+  unsigned long long defined, lost, below;
+  float zncc_min, rmsd_max;
+  double zncc_sum;
+} f3d_correlation_stats;
+int f3d_local_correlation(f3d_devptr a, f3d_devptr b, const f3d_devptr out[2], unsigned fields, unsigned radius, float threshold,
+                          size_t width, size_t height, size_t depth, f3d_correlation_stats* stats /* nullable; non-null waits */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,22 @@ int f3d_flow_principal_end(f3d_flow flow);
 int f3d_flow_inverse_compute(f3d_flow flow, int source, unsigned iterations, float tolerance, float* const out[4],
                              f3d_inverse_stats* stats);
 int f3d_flow_inverse_end(f3d_flow flow);
+
+/* Match quality (f3d_local_correlation of include/f3d.h has the definition) of the flow the driver holds and the frames it holds
+ * (after f3d_flow_upload + f3d_flow_compute_resident): frame 1 is carried onto frame 0's grid through the flow (f3d_carry_field,
+ * linear; NaN where the point leaves the volume) and compared with frame 0 over (2 radius + 1)^3 windows.  fields selects the three
+ * outputs warped (the carried frame 1), zncc, rmsd (F3D_MATCH_WARPED / _ZNCC / _RMSD); out[i] of a selected output receives
+ * width * height * depth floats, entries of other outputs are ignored; radius 1 .. 4; stats is nullable (below counts zncc <
+ * threshold).  source must be F3D_STRAIN_OF_FLOW: frame 0 of a trajectory is not kept, so F3D_STRAIN_OF_TRAJECTORY is refused with a
+ * message.  Blocks until the fields are on the host.  The driver keeps the warped container and one per selected field until
+ * f3d_flow_match_end (or f3d_flow_destroy).  A device library without f3d_local_correlation still loads; then the call fails with a
+ * message naming it. */
+#define F3D_MATCH_WARPED 1u
+#define F3D_MATCH_ZNCC 2u
+#define F3D_MATCH_RMSD 4u
+int f3d_flow_match_compute(f3d_flow flow, int source, unsigned fields, unsigned radius, float threshold, float* const out[3],
+                           f3d_correlation_stats* stats);
+int f3d_flow_match_end(f3d_flow flow);
 /* message of this thread's last call that failed in the host library itself; f3d_last_error() when there is none */
 const char* f3d_host_last_error(void);
 int f3d_flow_destroy(f3d_flow flow);
