@@ -73,6 +73,36 @@ class CorrelationStats(C.Structure):  # f3d_correlation_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class MotionSums(C.Structure):  # struct f3d_motion_sums
+    _fields_ = [("n", C.c_ulonglong), ("Sx", C.c_double * 3), ("Sxx", C.c_double * 6), ("Sd", C.c_double * 3),
+                ("Sxd", C.c_double * 9), ("Sdd", C.c_double * 3)]
+
+    def as_dict(self):
+        return {name: (getattr(self, name) if name == "n" else list(getattr(self, name))) for name, _ in self._fields_}
+
+
+class MotionFit(C.Structure):  # f3d_motion_fit: d_fit(x) = t + M (x - centre)
+    _fields_ = [("centre", C.c_double * 3), ("t", C.c_double * 3), ("M", C.c_double * 9), ("n", C.c_ulonglong),
+                ("rms_before", C.c_double), ("cos_angle", C.c_double), ("axial", C.c_double * 3), ("model", C.c_int)]
+
+    @property
+    def matrix(self):
+        """M as a 3 x 3 array: row = component u, v, w; column = coordinate x, y, z"""
+        return np.array(list(self.M), np.float64).reshape(3, 3)
+
+    def as_dict(self):
+        return {"centre": list(self.centre), "t": list(self.t), "matrix": self.matrix.tolist(), "n": self.n,
+                "rms_before": self.rms_before, "cos_angle": self.cos_angle, "axial": list(self.axial),
+                "model": {v: k for k, v in MOTION_MODELS.items()}.get(self.model, self.model)}
+
+
+class MotionResidual(C.Structure):  # f3d_motion_residual
+    _fields_ = [("present", C.c_ulonglong), ("sum_sq", C.c_double), ("max_abs", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class FlowParams(C.Structure):  # f3d_flow_params
     _fields_ = [
         ("warp_levels_count", C.c_size_t), ("warp_scale_factor", C.c_float),
@@ -247,6 +277,10 @@ def host():
         "f3d_flow_inverse_end": [C.c_void_p],
         "f3d_flow_match_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_float, C.POINTER(_fp), C.POINTER(CorrelationStats)],
         "f3d_flow_match_end": [C.c_void_p],
+        "f3d_motion_solve": [C.POINTER(MotionSums), C.c_int, C.POINTER(MotionFit)],
+        "f3d_flow_motion_compute": [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(_fp), C.POINTER(MotionFit),
+                                    C.POINTER(MotionResidual)],
+        "f3d_flow_motion_end": [C.c_void_p],
         "f3d_op_create": [C.POINTER(C.c_void_p), C.c_char_p], "f3d_op_initialize": [C.c_void_p, C.POINTER(Size4)],
         "f3d_op_execute": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), _sz],
         "f3d_op_execute_batch": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(_sz), _sz],
@@ -383,6 +417,13 @@ def _correlation_entry():
                   "compute the local correlation of two volumes")
 
 
+def _motion_entry():
+    """(f3d_motion_sums, f3d_remove_motion)"""
+    what = "fit or remove the motion of a displacement"
+    return (_entry("f3d_motion_sums", [_dp] * 4 + [C.c_float] + [_sz] * 3 + [C.POINTER(MotionSums)], what),
+            _entry("f3d_remove_motion", [_dp] * 6 + [C.POINTER(MotionFit)] + [_sz] * 3 + [C.POINTER(MotionResidual)], what))
+
+
 def _mask(fields, groups, what):
     """the F3D_* bits of an iterable of group names (the keys of `groups`) or of a comma-separated string of them"""
     if isinstance(fields, str):
@@ -461,6 +502,16 @@ CARRY_MODES = {"linear": 1, "nearest": 2}
 MATCH_NAMES = ("warped", "zncc", "rmsd")
 MATCH_GROUPS = {"warped": 1, "zncc": 2, "rmsd": 4}
 CORRELATION_GROUPS = {"zncc": 1, "rmsd": 2}
+
+
+# the models of f3d_motion_solve (F3D_MOTION_*)
+MOTION_MODELS = {"translation": 0, "rigid": 1, "affine": 2}
+
+
+def _motion_model(model):
+    if model not in MOTION_MODELS:
+        raise ValueError(f"unknown motion model {model!r} (one of {', '.join(MOTION_MODELS)})")
+    return MOTION_MODELS[model]
 
 
 def _strain_mask(fields):
@@ -555,6 +606,49 @@ def local_correlation(a, b, radius=3, threshold=0.8, fields=("zncc", "rmsd")):
         res = {n: box.download(o, dims) for n, o in zip(CORRELATION_GROUPS, outs) if o}
     res["stats"] = stats.as_dict()
     return res
+
+
+def motion_sums(u, v, w, weight=None, weight_min=0.8):
+    """The moment sums of a displacement on the device (include/f3d.h, f3d_motion_sums): u, v, w numpy [z, y, x] float32; weight
+    (optional, same shape) masks the voxels with weight < weight_min or NaN out.  Returns a MotionSums (n, Sx, Sxx, Sd, Sxd, Sdd about
+    the centre of the volume)."""
+    fn, _ = _motion_entry()
+    vols = (u, v, w) if weight is None else (u, v, w, weight)
+    with _on_device(vols, "u, v, w and weight must be [z, y, x] volumes of one shape") as (box, p, dims):
+        box.set_current()
+        sums = MotionSums()
+        check(fn(p[0], p[1], p[2], p[3] if weight is not None else 0, weight_min, *dims, C.byref(sums)), "f3d_motion_sums")
+    return sums
+
+
+def solve_motion(sums, dims, model="rigid"):
+    """f3d_motion_solve (include/f3d_host.h; host code, no device): the MotionFit of `sums` taken over a (width, height, depth) volume"""
+    fit = MotionFit()
+    fit.centre[:] = [(n - 1) / 2 for n in dims]
+    _host_check(host().f3d_motion_solve(C.byref(sums), _motion_model(model), C.byref(fit)), "f3d_motion_solve")
+    return fit
+
+
+def fit_motion(u, v, w, model="rigid", weight=None, weight_min=0.8):
+    """The translation, rigid motion or affine map d ~ t + M (x - centre) that fits a displacement best (least squares over the voxels
+    where u, v, w are not NaN and, with `weight`, weight >= weight_min): the sums on the device, the solve on the host.  Returns a
+    MotionFit with .centre, .t, .matrix (3 x 3, rows = components), .n (voxels that took part), .rms_before and, for "rigid",
+    .cos_angle and .axial; .as_dict() gives the same as plain Python."""
+    _motion_model(model)
+    d, h, w_ = np.shape(u)
+    return solve_motion(motion_sums(u, v, w, weight, weight_min), (w_, h, d), model)
+
+
+def remove_motion(u, v, w, fit):
+    """A displacement with a fit taken out on the device (include/f3d.h, f3d_remove_motion): returns (ru, rv, rw, stats) with
+    r = d - (t + M (x - centre)) per voxel, NaN where d is, and stats a dict (present, sum_sq, max_abs) of the residual."""
+    _, fn = _motion_entry()
+    with _on_device((u, v, w), "u, v and w must be three [z, y, x] volumes of one shape") as (box, p, dims):
+        outs = [box.alloc() for _ in range(3)]
+        box.set_current()
+        stats = MotionResidual()
+        check(fn(*p, *outs, C.byref(fit), *dims, C.byref(stats)), "f3d_remove_motion")
+        return tuple(box.download(o, dims) for o in outs) + (stats.as_dict(),)
 
 
 def _f32(a):
@@ -1046,13 +1140,15 @@ class OpticalFlow:
     def trajectory_end(self):
         _host_check(host().f3d_flow_trajectory_end(self._h), "f3d_flow_trajectory_end")
 
-    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_{strain,principal,inverse,match}_*) ----
-    def _derived(self, compute, src, selected, stats, *args):
-        """one f3d_flow_*_compute into fresh host arrays: a list with an array per selected output and None for the others"""
+    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_{strain,principal,inverse,match,motion}_*) ----
+    def _derived(self, compute, src, selected, stats, *args, fit=None):
+        """one f3d_flow_*_compute into fresh host arrays: a list with an array per selected output and None for the others
+        (fit: the MotionFit f3d_flow_motion_compute takes between the arrays and the statistics)"""
         w, h, d = self.dims
         arrays = [np.empty((d, h, w), np.float32) if s else None for s in selected]
         ptrs = (_fp * len(arrays))(*[a.ctypes.data_as(_fp) if a is not None else None for a in arrays])
-        _host_check(getattr(host(), compute)(self._h, src, *args, ptrs, C.byref(stats)), compute)
+        tail = (C.byref(stats),) if fit is None else (C.byref(fit), C.byref(stats))
+        _host_check(getattr(host(), compute)(self._h, src, *args, ptrs, *tail), compute)
         return arrays
 
     def strain(self, source="flow", fields=("vol", "e", "eq")):
@@ -1110,6 +1206,21 @@ class OpticalFlow:
     def match_end(self):
         """free the match quality containers (destroy() does too)"""
         _host_check(host().f3d_flow_match_end(self._h), "f3d_flow_match_end")
+
+    def motion(self, source="flow", model="rigid", min_zncc=None):
+        """The motion of the flow the driver holds (source="flow") or of the trajectory (source="trajectory") fitted and taken out on
+        the device: a dict with the residual "u", "v", "w", "fit" -> MotionFit and "stats" -> dict (present, sum_sq, max_abs).
+        min_zncc: fit only where the zncc of the last match() of this pair is at least that (match() first; not for the trajectory)."""
+        fit, stats = MotionFit(), MotionResidual()
+        arrays = self._derived("f3d_flow_motion_compute", _source(source), [True] * 3, stats, _motion_model(model),
+                               float("nan") if min_zncc is None else min_zncc, fit=fit)
+        res = dict(zip("uvw", arrays))
+        res["fit"], res["stats"] = fit, stats.as_dict()
+        return res
+
+    def motion_end(self):
+        """free the motion residual containers (destroy() does too)"""
+        _host_check(host().f3d_flow_motion_end(self._h), "f3d_flow_motion_end")
 
     def compute_sequence(self, frames, cumulative=False, silent=True, **kw):
         """Generator over the consecutive pairs of `frames` (an iterable of [z, y, x] volumes): yields (k, (u, v, w), disp) for

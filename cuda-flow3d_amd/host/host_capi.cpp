@@ -7,6 +7,7 @@
 
 #include "f3d_host.h"
 #include "hip_utils.h"
+#include "motion_fit.h"
 #include "operations.h"
 #include "operations_p.h"
 #include "optical_flow.h"
@@ -18,6 +19,7 @@ struct f3d_flow_s {
   OpticalFlowE driver;
   bool device_ready = false;
   bool trajectory_started = false;
+  bool zncc_of_held_flow = false;  // the match container holds the zncc of the flow the driver holds (f3d_flow_motion_compute's mask)
 };
 
 struct f3d_slabflow_s {
@@ -117,6 +119,7 @@ int f3d_flow_compute(f3d_flow flow, const float* frame_0, const float* frame_1, 
 int f3d_flow_upload(f3d_flow flow, const float* frame_0, const float* frame_1)
 {
   if (!flow || !frame_0 || !frame_1) return 1;
+  flow->zncc_of_held_flow = false;
   const DataSize4& c = flow->driver.ContainerSize();
   Data3D f0(const_cast<float*>(frame_0), c.width, c.height, c.depth);
   Data3D f1(const_cast<float*>(frame_1), c.width, c.height, c.depth);
@@ -128,6 +131,7 @@ int f3d_flow_upload(f3d_flow flow, const float* frame_0, const float* frame_1)
 int f3d_flow_compute_resident(f3d_flow flow, const f3d_flow_params* params, int silent, float* device_seconds)
 {
   if (!flow || !params) return 1;
+  flow->zncc_of_held_flow = false;
   f3d_flow_params p = *params;
   OperationParameters bag;
   FillBag(bag, p);
@@ -311,10 +315,42 @@ int f3d_flow_match_compute(f3d_flow flow, int source, unsigned fields, unsigned 
 {
   OpticalFlowE::Displacement of;
   if (!DerivedSource(flow, source, out != nullptr, "f3d_flow_match_compute", &of)) return 1;
-  return DerivedDownload(flow, OpticalFlowE::kMatch, flow->driver.ComputeMatch(of, 0, 0, fields, radius, threshold, stats), out, fields);
+  const bool computed = flow->driver.ComputeMatch(of, 0, 0, fields, radius, threshold, stats);
+  // the kernel stores zncc unless rmsd alone was asked for
+  if (computed && ((fields & F3D_MATCH_ZNCC) || !(fields & F3D_MATCH_RMSD))) flow->zncc_of_held_flow = true;
+  return DerivedDownload(flow, OpticalFlowE::kMatch, computed, out, fields);
 }
 
-int f3d_flow_match_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kMatch, "f3d_flow_match_end: null driver"); }
+int f3d_flow_match_end(f3d_flow flow)
+{
+  if (flow) flow->zncc_of_held_flow = false;
+  return DerivedEnd(flow, OpticalFlowE::kMatch, "f3d_flow_match_end: null driver");
+}
+
+int f3d_motion_solve(const struct f3d_motion_sums* sums, int model, f3d_motion_fit* fit)
+{
+  g_host_error.clear();
+  if (!sums || !fit) return HostFail("f3d_motion_solve: null argument");
+  std::string why;
+  return SolveMotion(*sums, model, fit, &why) ? 0 : HostFail(why.c_str());
+}
+
+int f3d_flow_motion_compute(f3d_flow flow, int source, int model, float min_zncc, float* const out[3], f3d_motion_fit* fit,
+                            f3d_motion_residual* residual)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out && out[0] && out[1] && out[2] && fit, "f3d_flow_motion_compute", &of)) return 1;
+  DevicePtr weight = 0;
+  if (min_zncc == min_zncc) {
+    if (source == F3D_STRAIN_OF_TRAJECTORY)
+      return HostFail("f3d_flow_motion_compute: min_zncc cannot mask the trajectory: the zncc of a match lives on the pair's grid");
+    weight = flow->zncc_of_held_flow ? flow->driver.DerivedContainer(OpticalFlowE::kMatch, 1) : 0;
+    if (!weight) return HostFail("f3d_flow_motion_compute: min_zncc needs the zncc of a match of this pair (f3d_flow_match_compute first)");
+  }
+  return DerivedDownload(flow, OpticalFlowE::kMotion, flow->driver.ComputeMotion(of, model, weight, min_zncc, fit, residual), out, 1);
+}
+
+int f3d_flow_motion_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kMotion, "f3d_flow_motion_end: null driver"); }
 
 const char* f3d_host_last_error(void) { return g_host_error.empty() ? f3d_last_error() : g_host_error.c_str(); }
 

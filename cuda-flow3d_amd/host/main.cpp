@@ -6,6 +6,7 @@
 //                [--outer N] [--inner N] [--alpha a] [--eps-smooth e] [--eps-data e] [--median r] [--sigma s]
 //                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
 //                [--strain vol,e,eq] [--principal val,shear,dir1,dir3] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]
+//                [--detrend translation|rigid|affine [--detrend-min-zncc T]]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -34,6 +35,11 @@
 // believed: frame k+1 is carried onto frame k's grid through the PAIR's flow (f3d_carry_field; also under --cumulative, since frame 0
 // is not kept) and compared with frame k over (2R+1)^3 windows on the device (f3d_local_correlation; --match-radius R, 1 .. 4,
 // default 3).  <tag>_match-{warped,zncc,rmsd}-W-H-D.raw with the flow's tag, and one line of statistics per pair.
+// --detrend MODEL (same conditions and the same source as --strain) fits a translation, a rigid motion or an affine map to that
+// displacement on the device (f3d_motion_sums, f3d_motion_solve) and takes it out (f3d_remove_motion): the drift, settling and tilt
+// of the sample between the scans.  <tag>_detrended-{u,v,w}-W-H-D.raw is what remains, and one line per pair gives the motion.
+// --detrend-min-zncc T fits only where the zncc of --match (which must then select zncc) is at least T; not with --cumulative, whose
+// displacement lives on frame 0's grid and the zncc on the pair's.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -58,7 +64,8 @@ static void Usage()
               "              [--levels N] [--scale s] [--outer N] [--inner N] [--alpha a] [--eps-smooth e]\n"
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
               "              [--concurrent N] [--cumulative] [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
-              "              [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n");
+              "              [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
+              "              [--detrend translation|rigid|affine [--detrend-min-zncc T]]\n");
 }
 
 int main(int argc, char** argv)
@@ -76,6 +83,9 @@ int main(int argc, char** argv)
   unsigned match_radius = 3;      // --match-radius
   bool match_radius_given = false;
   const float match_threshold = 0.8f;
+  int detrend_model = -1;         // --detrend: F3D_MOTION_*
+  float detrend_min_zncc = std::nanf("");  // --detrend-min-zncc; NaN: no mask
+  bool detrend_min_given = false;
   const unsigned inverse_iterations = 32;
   const float inverse_tolerance = 1e-3f;
 
@@ -178,6 +188,21 @@ int main(int argc, char** argv)
       match_radius = static_cast<unsigned>(r);
       match_radius_given = true;
     }
+    else if (a == "--detrend") {
+      need(1);
+      const std::string model = argv[++i];
+      if (model == "translation") detrend_model = F3D_MOTION_TRANSLATION;
+      else if (model == "rigid") detrend_model = F3D_MOTION_RIGID;
+      else if (model == "affine") detrend_model = F3D_MOTION_AFFINE;
+      else { Usage(); return 64; }
+    }
+    else if (a == "--detrend-min-zncc") {
+      need(1);
+      char* rest = nullptr;
+      detrend_min_zncc = std::strtof(argv[++i], &rest);
+      if (rest == argv[i] || *rest || std::isnan(detrend_min_zncc)) { Usage(); return 64; }
+      detrend_min_given = true;
+    }
     else { Usage(); return 64; }
   }
   if (width == 0 || height == 0 || depth == 0 || (!synthetic && files.size() < 2)) {
@@ -214,6 +239,23 @@ int main(int argc, char** argv)
   if (match_fields && (use_partial_gpu || concurrent > 1)) {
     std::printf("--match needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
                 use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if (detrend_min_given && detrend_model < 0) {
+    std::printf("--detrend-min-zncc needs --detrend\n");
+    Usage();
+    return 64;
+  }
+  if (detrend_model >= 0 && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--detrend needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if (detrend_min_given && (cumulative || !(match_fields & OpticalFlowE::kMatchZncc))) {
+    std::printf(cumulative ? "--detrend-min-zncc cannot be combined with --cumulative: the zncc of --match lives on the pair's grid\n"
+                           : "--detrend-min-zncc needs --match with zncc in its list\n");
     Usage();
     return 64;
   }
@@ -410,12 +452,16 @@ int main(int argc, char** argv)
   static const char* const principal_names[10] = {"e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z"};
   static const char* const inverse_names[4] = {"u", "v", "w", "err"};
   static const char* const match_names[3] = {"warped", "zncc", "rmsd"};
+  static const char* const motion_names[3] = {"u", "v", "w"};
+  static const char* const motion_models[3] = {"translation", "rigid", "affine"};
   const size_t voxels = width * height * depth;
   f3d_strain_stats strain_stats = {};
   f3d_principal_stats principal_stats = {};
   f3d_inverse_stats inverse_stats = {};
   f3d_correlation_stats match_stats = {};
-  DerivedField derived[4] = {
+  f3d_motion_fit motion_fit = {};
+  f3d_motion_residual motion_residual = {};
+  DerivedField derived[5] = {
       {"strain", OpticalFlowE::kStrain, strain_fields, strain_names, false,
        [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputeStrain(of, strain_fields, &strain_stats); },
        [&](size_t k) {
@@ -455,6 +501,30 @@ int main(int argc, char** argv)
          std::printf("match frame %zu -> frame %zu: zncc min/mean %.6g/%.6g, %llu below %.6g, rmsd max %.6g, %llu flat, %llu lost of %zu "
                      "voxels\n", k, k + 1, st.zncc_min, mean, st.below, match_threshold, st.rmsd_max,
                      static_cast<unsigned long long>(voxels) - st.defined - st.lost, st.lost, voxels);
+       }},
+      // after the match: with --detrend-min-zncc the zncc container of this pair is the mask
+      {"detrended", OpticalFlowE::kMotion, detrend_model >= 0 ? 1u : 0u, motion_names, false,
+       [&](const OpticalFlowE::Displacement& of) {
+         const DevicePtr mask = detrend_min_given ? optical_flow_e.DerivedContainer(OpticalFlowE::kMatch, 1) : 0;
+         return optical_flow_e.ComputeMotion(of, detrend_model, mask, detrend_min_zncc, &motion_fit, &motion_residual);
+       },
+       [&](size_t k) {
+         const f3d_motion_fit& f = motion_fit;
+         const f3d_motion_residual& r = motion_residual;
+         std::printf("motion frame %zu -> frame %zu (%s): t (%.6g, %.6g, %.6g), ", cumulative ? size_t(0) : k, k + 1,
+                     motion_models[detrend_model], f.t[0], f.t[1], f.t[2]);
+         if (detrend_model == F3D_MOTION_RIGID) {
+           // degrees appear in this line only: the fit itself carries the cosine and the axial vector
+           const double sine = std::sqrt((f.axial[0] * f.axial[0] + f.axial[1] * f.axial[1]) + f.axial[2] * f.axial[2]);
+           const double unit = sine > 0 ? 1.0 / sine : 0.0;
+           std::printf("angle %.6g deg about (%.6g, %.6g, %.6g), ", std::atan2(sine, f.cos_angle) * (180.0 / 3.14159265358979323846),
+                       f.axial[0] * unit, f.axial[1] * unit, f.axial[2] * unit);
+         } else if (detrend_model == F3D_MOTION_AFFINE) {
+           std::printf("M (%.6g, %.6g, %.6g; %.6g, %.6g, %.6g; %.6g, %.6g, %.6g), ", f.M[0], f.M[1], f.M[2], f.M[3], f.M[4], f.M[5],
+                       f.M[6], f.M[7], f.M[8]);
+         }
+         const double after = r.present ? std::sqrt(r.sum_sq / static_cast<double>(r.present)) : std::nan("");
+         std::printf("rms %.6g -> %.6g, max |res| %.6g, %llu of %zu voxels\n", f.rms_before, after, r.max_abs, f.n, voxels);
        }}};
   for (DerivedField& f : derived)
     for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)

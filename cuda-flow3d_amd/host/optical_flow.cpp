@@ -11,6 +11,7 @@
 #include "common_utils.h"
 #include "operator_calls.h"
 #include "hip_utils.h"
+#include "motion_fit.h"
 
 // Declared weak: the host library keeps loading against a device library that lacks the entry (the address is then null and the
 // trajectory calls fail with a message instead of the whole library failing to load).
@@ -28,6 +29,11 @@ extern "C" int f3d_carry_field(f3d_devptr field, f3d_devptr m_u, f3d_devptr m_v,
                                size_t height, size_t depth, unsigned mode, unsigned long long* lost) __attribute__((weak));
 extern "C" int f3d_local_correlation(f3d_devptr a, f3d_devptr b, const f3d_devptr out[2], unsigned fields, unsigned radius,
                                      float threshold, size_t width, size_t height, size_t depth, f3d_correlation_stats* stats)
+    __attribute__((weak));
+extern "C" int f3d_motion_sums(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr weight, float weight_min, size_t width,
+                               size_t height, size_t depth, struct f3d_motion_sums* out) __attribute__((weak));
+extern "C" int f3d_remove_motion(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr out_u, f3d_devptr out_v, f3d_devptr out_w,
+                                 const f3d_motion_fit* fit, size_t width, size_t height, size_t depth, f3d_motion_residual* stats)
     __attribute__((weak));
 
 // ---- base --------------------------------------------------------------------------------------------------
@@ -92,8 +98,8 @@ const unsigned kPrincipalGroups[10] = {F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_VALUE
 const unsigned kPrincipalAll = F3D_PRINCIPAL_VALUES | F3D_PRINCIPAL_SHEAR | F3D_PRINCIPAL_DIR1 | F3D_PRINCIPAL_DIR3;
 const unsigned kMatchGroups[3] = {OpticalFlowE::kMatchWarped, OpticalFlowE::kMatchZncc, OpticalFlowE::kMatchRmsd};
 const unsigned kMatchAll = OpticalFlowE::kMatchWarped | OpticalFlowE::kMatchZncc | OpticalFlowE::kMatchRmsd;
-const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3};
-const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr, kMatchGroups};
+const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3};
+const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr, kMatchGroups, nullptr};
 const char* const kTrajectoryNotStarted = "the trajectory was not started (ResetTrajectory first)";
 
 }  // namespace
@@ -114,7 +120,10 @@ OpticalFlowE::OpticalFlowE()
                 "the device library has no f3d_invert_displacement (inverse displacement)", "no displacement to invert"},
                {this, kDerivedFields[kMatch], kMatchGroups, "the match quality containers do not fit beside the driver's on the device",
                 "a requested match quality field has not been computed", "no host volume for a requested match quality field",
-                "the device library has no f3d_local_correlation (match quality)", "no displacement to carry frame 1 through"}}
+                "the device library has no f3d_local_correlation (match quality)", "no displacement to carry frame 1 through"},
+               {this, kDerivedFields[kMotion], nullptr, "the motion residual containers do not fit beside the driver's on the device",
+                "the motion residual has not been computed", "no host volume for a motion residual field",
+                "the device library has no f3d_motion_sums (motion fit)", "no displacement to fit a motion to"}}
 {
   // same initialisation order as the reference's forward_list built with push_front (optical_flow_e.cpp:34-39)
   cuda_operations_ = {&cuop_solve_, &cuop_resample_, &cuop_register_, &cuop_median_, &cuop_convolution_, &cuop_add_};
@@ -629,6 +638,33 @@ bool OpticalFlowE::ComputeMatch(const Displacement& of, DevicePtr frame_0, Devic
                                                     nullptr))) &&
          set.Check(CheckDeviceError(f3d_local_correlation(frame_0, set.ptr[0], out, device_fields, radius, threshold, c.width, c.height,
                                                           c.depth, stats)));
+}
+
+bool OpticalFlowE::ComputeMotion(const Displacement& of, int model, DevicePtr weight, float weight_min, f3d_motion_fit* fit,
+                                 f3d_motion_residual* residual)
+{
+  FieldSet& set = derived_[kMotion];
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, f3d_motion_sums != nullptr, d)) return false;
+  if (!f3d_remove_motion) return set.Fail("the device library has no f3d_remove_motion (motion fit)");
+  if (!fit) return set.Fail("no fit to write to");
+  if (!set.Allocate(0)) return false;
+  const f3d_size4 c = Container();
+  struct f3d_motion_sums sums;
+  if (!set.Check(CheckDeviceError(f3d_set_container(&c))) ||
+      !set.Check(CheckDeviceError(f3d_motion_sums(d[0], d[1], d[2], weight, weight_min, c.width, c.height, c.depth, &sums))))
+    return false;
+  f3d_motion_fit solved = {};
+  solved.centre[0] = 0.5 * static_cast<double>(c.width - 1);
+  solved.centre[1] = 0.5 * static_cast<double>(c.height - 1);
+  solved.centre[2] = 0.5 * static_cast<double>(c.depth - 1);
+  std::string why;
+  if (!SolveMotion(sums, model, &solved, &why)) return set.Fail(why.c_str());
+  if (!set.Check(CheckDeviceError(f3d_remove_motion(d[0], d[1], d[2], set.ptr[0], set.ptr[1], set.ptr[2], &solved, c.width, c.height,
+                                                    c.depth, residual))))
+    return false;
+  *fit = solved;
+  return true;
 }
 
 // The coarse-to-fine solve on two frames that are already on the device (optical_flow_e.cpp:208-533 is the sequence of operator

@@ -126,10 +126,12 @@ class OpticalFlowE : public OpticalFlowBase {
   //               (f3d_carry_field, linear; NaN where the point leaves the volume).  Three outputs warped, zncc, rmsd selected by
   //               kMatchWarped / kMatchZncc / kMatchRmsd.  The warped container is the kernel's input and is always allocated; it
   //               is downloaded only when selected.
+  //   kMotion     f3d_motion_sums, the host solve (motion_fit.h) and f3d_remove_motion: the displacement with its best translation,
+  //               rigid motion or affine map taken out.  Three outputs, the residual u, v, w, always all of them.
   // Each selected output gets a container of its own, allocated on first use and freed by ReleaseDerived() and Destroy().  Compute
   // enqueues on the library stream and waits only when stats is given.  Every call returns false with DerivedError() set when it
   // cannot run -- among other reasons when the device library lacks the entry point.
-  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kDerivedCount };
+  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kDerivedCount };
   enum MatchField : unsigned { kMatchWarped = 1u, kMatchZncc = 2u, kMatchRmsd = 4u };
   // the displacement a derived field is computed of
   struct Displacement {
@@ -146,6 +148,11 @@ class OpticalFlowE : public OpticalFlowBase {
   // refused: frame 0 of a sequence is not kept.
   bool ComputeMatch(const Displacement& of, DevicePtr frame_0, DevicePtr frame_1, unsigned fields, unsigned radius, float threshold,
                     f3d_correlation_stats* stats);
+  // model: F3D_MOTION_*.  weight: a container whose voxels below weight_min (or NaN) take no part in the fit, 0 for none -- in
+  // practice DerivedContainer(kMatch, 1), the zncc of the same pair.  Enqueues the sums, waits for them, solves on the host, enqueues
+  // the subtraction and waits again only when residual is given.  fit (required) receives the fit with its centre.
+  bool ComputeMotion(const Displacement& of, int model, DevicePtr weight, float weight_min, f3d_motion_fit* fit,
+                     f3d_motion_residual* residual);
   static int DerivedFieldCount(Derived which);
   static bool DerivedSelected(Derived which, int field, unsigned fields);
   DevicePtr DerivedContainer(Derived which, int field) const { return derived_[which].ptr[field]; }  // 0 until computed

@@ -608,6 +608,73 @@ typedef struct f3d_correlation_stats {
 int f3d_local_correlation(f3d_devptr a, f3d_devptr b, const f3d_devptr out[2], unsigned fields, unsigned radius, float threshold,
                           size_t width, size_t height, size_t depth, f3d_correlation_stats* stats /* nullable; non-null waits */);
 
+/* Rigid-body or affine motion of a displacement (no reference counterpart: the drift, settling and tilt of a sample between two scans,
+ * which a volume-correlation workflow takes out of a displacement before it looks at it).  Two device passes with a host solve
+ * between them (f3d_motion_solve of include/f3d_host.h): the moment sums of d = (u, v, w), and the subtraction of a fit
+ * d_fit(x) = t + M (x - centre).
+ *
+ * f3d_motion_sums.  A voxel is present when it is inside the volume, none of u, v, w is NaN there and, when weight is not 0,
+ * weight[i] >= weight_min (a NaN weight fails the comparison and is absent; the mask is binary, there are no fractional weights).
+ * centre c = ((width-1)/2, (height-1)/2, (depth-1)/2); X = x - c is a half-integer per axis, exact in binary64.  Over the present
+ * voxels:
+ *   n                  their number
+ *   Sx[3]   = sum X                     Sxx[6] = sum X X^T in the order xx yy zz xy xz yz
+ *   Sd[3]   = sum d                     Sxd[9] = sum X_i d_j, row i = coordinate, column j = component (Sxd[3*i + j])
+ *   Sdd[3]  = sum d_j^2
+ * n, Sx and Sxx are integer sums of the doubled coordinates 2x - (width-1) in signed 64 bits, converted at the end (one multiplication
+ * by 0.5 or 0.25 of the integer rounded to binary64: exact whenever the sum is below 2^53).  The 64 bits hold for every volume of at
+ * most 32768 along an axis and 2^33 voxels; larger ones are refused.
+ * The d-sums are binary64 + and * only (no fma), d converted from float32, every operation rounded on its own:
+ *   a lane owns the run of at most 32 planes [32 k, 32 k + 32) of one column (x, y) and adds its present voxels in ascending z from +0:
+ *     s_j += d_j ;  sz_j += Z * d_j ;  q_j += d_j * d_j                       (j = u, v, w; the square of a float32 is exact)
+ *   the column's constant X and Y are factored out of the run:  Sd_j gets s_j, Sxd_xj gets X * s_j, Sxd_yj gets Y * s_j, Sxd_zj gets sz_j,
+ *   Sdd_j gets q_j  (so X * sum_z d, not sum_z X * d: one rounding of the product per run instead of one per voxel)
+ *   then the fixed order of the statistics of the other entries: the xor butterfly 32, 16, ..., 1 over the 64 consecutive x of a wave, the
+ *   4 rows of a workgroup in sequence, and the fold of the workgroup partials (x fastest, then y, then z): thread t takes t, t + 256, ...
+ *   in that order, then the halving tree 128 ... 1.  A sum that is zero is +0.
+ * The same input gives the same bytes every run (no float atomics).  Geometry from the current container (f3d_set_container), whole
+ * volume, library stream; the call waits for the stream.  Refused (status 1, a message): a null u, v, w or out; a NaN weight_min when
+ * weight is given; an empty or too large size.
+ * (The struct is declared without a typedef because the entry has its name: write `struct f3d_motion_sums`.) */
+struct f3d_motion_sums {
+  unsigned long long n;
+  double Sx[3], Sxx[6], Sd[3], Sxd[9], Sdd[3];
+};
+int f3d_motion_sums(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr weight /* 0: none */, float weight_min, size_t width,
+                    size_t height, size_t depth, struct f3d_motion_sums* out);
+
+/* f3d_remove_motion.  fit means d_fit(x) = t + M (x - centre), M row-major (M[3*r + c]: component r, coordinate c); only centre, t and
+ * M are read here, the rest is what f3d_motion_solve reports: model (F3D_MOTION_*), n and rms_before = sqrt((Sdd_u + Sdd_v + Sdd_w) / n)
+ * of the sums, and for the rigid model cos_angle = (tr R - 1) / 2 and the axial vector (R32 - R23, R13 - R31, R21 - R12) / 2 of
+ * R = I + M (its length is the sine of the angle, its direction the axis); both are 0 for the other models.
+ * Per voxel (x, y, z) and component r, with X = (double)x - centre[0], Y and Z likewise, in binary64, every operation rounded on its own,
+ * in exactly this order (part of the ABI):
+ *   res_r = (float)((double)d_r - (t_r + ((M_r0 * X + M_r1 * Y) + M_r2 * Z)))
+ * NaN in, NaN out (per component).  In place (out_u == u, out_v == v, out_w == w) is allowed; any other aliasing between the six
+ * volumes is refused, and so are a null volume or fit, a non-finite entry of centre, t or M, and an empty size; a refused call writes
+ * nothing.  Geometry from the current container, whole volume, library stream.
+ * stats (nullable; asking waits for the stream), from the stored float32 residuals: present = voxels none of whose three residuals is
+ * NaN, sum_sq = the binary64 sum over them of (double)res_r * (double)res_r, added u, v, w per voxel along the lane's run and then in the
+ * fixed order above, max_abs = the exact max of |res_r| over them (NaN when there is none). */
+#define F3D_MOTION_TRANSLATION 0
+#define F3D_MOTION_RIGID 1
+#define F3D_MOTION_AFFINE 2
+typedef struct f3d_motion_fit {
+  double centre[3], t[3], M[9];
+  unsigned long long n;
+  double rms_before;
+  double cos_angle, axial[3];
+  int model;
+} f3d_motion_fit;
+typedef struct f3d_motion_residual {
+  unsigned long long present;
+  double sum_sq;
+  float max_abs;
+} f3d_motion_residual;
+int f3d_remove_motion(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr out_u, f3d_devptr out_v, f3d_devptr out_w,
+                      const f3d_motion_fit* fit, size_t width, size_t height, size_t depth,
+                      f3d_motion_residual* stats /* nullable; non-null waits */);
+
 #ifdef __cplusplus
 }
 #endif

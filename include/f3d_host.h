@@ -131,6 +131,38 @@ int f3d_flow_inverse_end(f3d_flow flow);
 int f3d_flow_match_compute(f3d_flow flow, int source, unsigned fields, unsigned radius, float threshold, float* const out[3],
                            f3d_correlation_stats* stats);
 int f3d_flow_match_end(f3d_flow flow);
+
+/* The solve between f3d_motion_sums and f3d_remove_motion (include/f3d.h): the fit d ~ t + M X of a displacement from its moment sums,
+ * X the coordinates about the centre the sums were taken about.  Host code, plain binary64, no device needed.  fit->centre is not
+ * touched: the caller sets it to ((width-1)/2, (height-1)/2, (depth-1)/2).  t, M, n, rms_before, model, cos_angle and axial are
+ * written (f3d_remove_motion of include/f3d.h says what they mean); no transcendental function enters any of them.
+ *   F3D_MOTION_TRANSLATION  M = 0, t = Sd / n
+ *   F3D_MOTION_AFFINE       the least-squares t, M from the normal equations [[n, Sx^T], [Sx, Sxx]] with the three right-hand sides
+ *                           (Sd_j, Sxd_0j, Sxd_1j, Sxd_2j) by Cholesky.  An axis along which all present voxels have one coordinate
+ *                           (n Sxx_aa == Sx_a^2, decided in the exact integers of doubled coordinates) is left out and its column of M
+ *                           is 0; two such axes are refused (collinear).  A pivot that is not above 2^-40 of its diagonal entry is
+ *                           refused: the present voxels are coplanar.
+ *   F3D_MOTION_RIGID        Kabsch.  With xbar = Sx / n, dbar = Sd / n, Cxx = Sxx - n xbar xbar^T, Cxd = Sxd - n xbar dbar^T and
+ *                           H = Cxx + Cxd, R is the rotation (determinant +1) of the singular value decomposition of H^T: a Jacobi
+ *                           eigen-decomposition of H H^T carried out one-sidedly on the columns of H^T (rotations of column pairs
+ *                           until they are orthogonal, so no singular value is squared), the third singular vectors by cross
+ *                           products.  M = R - I, t = dbar - M xbar.  Refused with fewer than 3 voxels, and when the second singular
+ *                           value is not above 2^-40 of the first (collinear; the floor f3d_local_correlation uses for "flat").
+ * No present voxel (n == 0) is refused for every model, and so is an unknown model.  Returns non-zero with f3d_host_last_error() set
+ * and the fit untouched when refused. */
+int f3d_motion_solve(const struct f3d_motion_sums* sums, int model, f3d_motion_fit* fit);
+
+/* Motion of the flow the driver holds or of the trajectory (source F3D_STRAIN_OF_FLOW / F3D_STRAIN_OF_TRAJECTORY): f3d_motion_sums on
+ * the device, f3d_motion_solve, f3d_remove_motion into three containers the driver keeps until f3d_flow_motion_end (or
+ * f3d_flow_destroy).  out[0..2] receive the residual u, v, w (width * height * depth floats each; all three required); fit receives the
+ * fit with its centre (required); residual (nullable) the statistics of the residual.  min_zncc NaN: every voxel with a displacement
+ * takes part.  Otherwise only voxels with zncc >= min_zncc in the zncc container of the last f3d_flow_match_compute, which must have
+ * been computed of the same pair: the call fails with a message when there is none, and when source is the trajectory (that zncc
+ * lives on the pair's grid).  A device library without f3d_motion_sums or f3d_remove_motion still loads; then the call fails with a
+ * message naming the entry. */
+int f3d_flow_motion_compute(f3d_flow flow, int source, int model, float min_zncc, float* const out[3], f3d_motion_fit* fit,
+                            f3d_motion_residual* residual);
+int f3d_flow_motion_end(f3d_flow flow);
 /* message of this thread's last call that failed in the host library itself; f3d_last_error() when there is none */
 const char* f3d_host_last_error(void);
 int f3d_flow_destroy(f3d_flow flow);
