@@ -389,6 +389,12 @@ def _entry(name, argtypes, what):
     return fn
 
 
+def solve_sweep_add_entry():
+    """f3d_solve_sweep_add (include/f3d.h): the last sweep of a level that stores flow + increments; arguments of f3d_solve_sweep"""
+    return _entry("f3d_solve_sweep_add", [_dp] * 10 + [_sz] * 3 + [C.c_float] * 4 + [_dp] * 3 + [_slabp],
+                  "add the increments to the flow inside the last sweep")
+
+
 def _compose_entry():
     return _entry("f3d_compose_flow", [_dp] * 6 + [_sz] * 3 + [C.POINTER(C.c_ulonglong)], "compose flows into a trajectory")
 
@@ -994,6 +1000,8 @@ class Operation:
                 store[k] = _sz(v)
             elif k == "stat":
                 store[k] = v            # a Stat3 the operator fills in
+            elif k == "flow_update":
+                store[k] = C.c_bool(bool(v))   # solve: asks for flow += increments inside the solve; comes back True where it was done
             else:
                 raise TypeError(f"unknown parameter key {k!r}")
         n = len(store) + len(volumes)

@@ -143,6 +143,90 @@ __global__ __launch_bounds__(kBX* kBY) void k_resample_x_lds(Vols v, F3dGeo gi, 
   }
 }
 
+// The x pass for rows of up to 256 NLOAD floats resampled to up to 64 KOUT outputs (every level of a 512^3 or 1024^3 pyramid): a
+// wave walks `rows_per_wave` consecutive rows of one plane.  The window of an output x -- first source cell, cell count, the two end
+// fractions -- depends on x only, so a lane forms those of its KOUT outputs once and keeps them in registers (k_resample_x_lds forms
+// them again for every row: floorf, ceilf and three conversions per output).  The next row is requested into registers BEFORE the
+// current one is gathered out of LDS, so a wave has a row in flight while it computes; LDS holds two rows per wave, sized to the row
+// staged (dynamic shared memory: 16 KB per workgroup at 512 floats, where the 32 KB of k_resample_x_lds capped a CU at 20 waves).
+// Per output the float operations and their order are k_resample<0>'s: value = value + row[s] * frac for ascending j, then
+// * normalization, frac being 1 inside the window (the same multiplication as there).
+typedef float Float4 __attribute__((ext_vector_type(4)));  // (an array of HIP's float4 struct is left in scratch memory by the compiler)
+template <int KOUT, int NLOAD>
+__global__ __launch_bounds__(kBX* kBY) void k_resample_x_rows(Vols v, F3dGeo gi, F3dGeo g, int in_n, float delta, float normalization,
+                                                              int rows_per_wave, int row_floats)
+{
+  extern __shared__ __attribute__((aligned(16))) float rowbufs[];  // [kBY waves][2][row_floats], row_floats a multiple of 4
+  const float* __restrict__ in = v.in[blockIdx.x];
+  float* __restrict__ out = v.out[blockIdx.x];
+  const int lane = threadIdx.x;
+  const int z = g.z_lo + blockIdx.z;
+  const int y0 = (blockIdx.y * kBY + threadIdx.y) * rows_per_wave;
+  if (y0 >= g.H) return;  // (no workgroup barrier below: a wave shares nothing with the others)
+  const int y1 = min(y0 + rows_per_wave, g.H);
+  float* cur = rowbufs + threadIdx.y * 2 * row_floats;
+  float* nxt = cur + row_floats;
+
+  int left_i[KOUT], cnt[KOUT];
+  float frac_first[KOUT], frac_last[KOUT];
+#pragma unroll
+  for (int k = 0; k < KOUT; ++k) {
+    const int x = lane + k * kBX;
+    const float left_f = static_cast<float>(x) * delta;
+    const float right_f = static_cast<float>(x + 1) * delta;
+    left_i[k] = static_cast<int>(floorf(left_f));
+    const int right_i = static_cast<int>(fminf(static_cast<float>(in_n), ceilf(right_f)));
+    cnt[k] = x < g.W ? right_i - left_i[k] : 0;  // outputs beyond the row gather nothing
+    // frac of j == 0 (a window of one cell weighs delta), and of j == cnt - 1 where that is another cell
+    frac_first[k] = cnt[k] == 1 ? delta : static_cast<float>(left_i[k] + 1) - left_f;
+    frac_last[k] = right_f - static_cast<float>(left_i[k] + cnt[k] - 1);
+  }
+
+  // Lane pieces of 16 bytes; a piece beyond the row re-reads the row's last one instead of being skipped (a load inside a branch is
+  // waited for at the end of that branch, and then nothing is in flight during the gather) and is not staged.
+  int piece[NLOAD];
+#pragma unroll
+  for (int i = 0; i < NLOAD; ++i) piece[i] = min((i * kBX + lane) * 4, row_floats - 4);
+  Float4 q[NLOAD];
+  {
+    const float* src = in + f3d_row(gi, y0, z);
+#pragma unroll
+    for (int i = 0; i < NLOAD; ++i) q[i] = *reinterpret_cast<const Float4*>(src + piece[i]);
+#pragma unroll
+    for (int i = 0; i < NLOAD; ++i)
+      if ((i * kBX + lane) * 4 < in_n) *reinterpret_cast<Float4*>(cur + piece[i]) = q[i];
+  }
+  for (int y = y0; y < y1; ++y) {
+    // the wave reads what its own lanes wrote; LDS only: the stores of the row before stay in flight
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+    // the next row (the last iteration requests its own row again: no branch around the loads, see above)
+    const float* src = in + f3d_row(gi, min(y + 1, y1 - 1), z);
+#pragma unroll
+    for (int i = 0; i < NLOAD; ++i) q[i] = *reinterpret_cast<const Float4*>(src + piece[i]);
+    const size_t out_row = f3d_row(g, y, z);
+#pragma unroll
+    for (int k = 0; k < KOUT; ++k) {
+      const int x = lane + k * kBX;
+      float value = 0.f;
+      for (int j = 0; j < cnt[k]; ++j) {
+        float frac = 1.f;
+        if (j == cnt[k] - 1) frac = frac_last[k];
+        if (j == 0) frac = frac_first[k];
+        value = value + cur[left_i[k] + j] * frac;
+      }
+      if (x < g.W) out[out_row + x] = value * normalization;
+    }
+#pragma unroll
+    for (int i = 0; i < NLOAD; ++i)
+      if ((i * kBX + lane) * 4 < in_n) *reinterpret_cast<Float4*>(nxt + piece[i]) = q[i];
+    float* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+}
+
 // The y and z passes with four x per lane: the source window belongs to the row, x is contiguous, so a lane moves 16 bytes per
 // load.  Rows start on 256-byte boundaries (f3d_alloc_pitched) and the pitch is a multiple of four floats, so the last piece of
 // a row may read padding; only the columns inside the box are stored.
@@ -440,7 +524,21 @@ static int resample_launch(int axis, const f3d_devptr* inputs, const f3d_devptr*
   const float delta = static_cast<float>(n) / static_cast<float>(out_n);          // resample_3d.cu: the kernels' own divisions
   const float normalization = static_cast<float>(out_n) / static_cast<float>(n);
   const bool staged = x4 && n <= kResampleRowMax && (n + 3) / 4 * 4 <= gi.pitch;
-  if (axis == 0 && staged) hipLaunchKernelGGL(k_resample_x_lds, grid, block, 0, f3d::stream(), v, gi, g, n, delta, normalization);
+  // rows of up to 1024 floats to up to 1024 outputs: the kernel that walks several rows per wave (rows_per_wave: 8 where the launch
+  // still has workgroups for every CU several times over, fewer on small levels, which are bound by the launch anyway)
+  const bool rows = axis == 0 && staged && n <= 1024 && g.W <= 1024;
+  if (rows) {
+    const long waves = static_cast<long>(count) * g.H * (g.z_hi - g.z_lo);
+    const int rpw = waves >= 8 * 16384 ? 8 : (waves >= 4 * 16384 ? 4 : (waves >= 2 * 16384 ? 2 : 1));
+    const int row_floats = (n + 3) / 4 * 4;
+    const dim3 grid_rows(static_cast<unsigned>(count), (g.H + kBY * rpw - 1) / (kBY * rpw), g.z_hi - g.z_lo);
+    const size_t lds = static_cast<size_t>(kBY) * 2 * row_floats * sizeof(float);
+    if (n <= 512 && g.W <= 512)
+      hipLaunchKernelGGL((k_resample_x_rows<8, 2>), grid_rows, block, lds, f3d::stream(), v, gi, g, n, delta, normalization, rpw, row_floats);
+    else
+      hipLaunchKernelGGL((k_resample_x_rows<16, 4>), grid_rows, block, lds, f3d::stream(), v, gi, g, n, delta, normalization, rpw, row_floats);
+  }
+  if (axis == 0 && staged && !rows) hipLaunchKernelGGL(k_resample_x_lds, grid, block, 0, f3d::stream(), v, gi, g, n, delta, normalization);
   if (axis == 0 && !staged) hipLaunchKernelGGL(k_resample<0>, grid, block, 0, f3d::stream(), v, gi, g, n, delta, normalization);
   if (axis == 1 && x4) hipLaunchKernelGGL(k_resample_x4<1>, grid, block, 0, f3d::stream(), v, gi, g, n, delta, normalization);
   if (axis == 2 && x4) hipLaunchKernelGGL(k_resample_x4<2>, grid, block, 0, f3d::stream(), v, gi, g, n, delta, normalization);

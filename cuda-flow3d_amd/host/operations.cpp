@@ -13,6 +13,13 @@
 #include "common_utils.h"
 #include "hip_utils.h"
 
+// Declared weak: the host library keeps loading against a device library that lacks the entry (the address is then null, and the
+// solve operator leaves the flow update to its caller, as before the entry existed).
+extern "C" int f3d_solve_sweep_add(f3d_devptr frame_0, f3d_devptr frame_1, f3d_devptr flow_u, f3d_devptr flow_v, f3d_devptr flow_w,
+                                   f3d_devptr flow_du, f3d_devptr flow_dv, f3d_devptr flow_dw, f3d_devptr phi, f3d_devptr ksi,
+                                   size_t width, size_t height, size_t depth, float hx, float hy, float hz, float equation_alpha,
+                                   f3d_devptr sum_u, f3d_devptr sum_v, f3d_devptr sum_w, const f3d_slab* slab) __attribute__((weak));
+
 // ---- base ------------------------------------------------------------------------------------------------
 
 bool CudaOperationBase::IsInitialized() const
@@ -468,6 +475,11 @@ void CudaOperationSolve::Execute(OperationParameters& params)
   GET_PARAM_OR_RETURN(params, float, hz, "hz");
   GET_PARAM_OR_RETURN(params, DataSize4, data_size, "data_size");
   NoteSolveWeights(equation_alpha, hx, hy, hz);
+  // Optional "flow_update" (bool*): its presence asks for flow += increments inside the solve.  Granted when the level ends with a launch
+  // of ONE sweep and the device library has the entry (f3d_solve_sweep_add then writes the sums where that sweep would have written the increments); *flow_update tells the
+  // caller whether dev_flow_d* (after the swaps) hold the sums -- true -- or the increments as always -- false, the caller adds.
+  bool* flow_update = static_cast<bool*>(params.GetValuePtr("flow_update"));
+  if (flow_update) *flow_update = false;
 
   // increments start from zero at every level: the level's box, one launch for the three (the reference clears every row of every
   // plane of the container, :183-188; nothing reads outside the box -- rows and planes mirror by address inside it)
@@ -586,7 +598,11 @@ void CudaOperationSolve::Execute(OperationParameters& params)
         status = f3d_solve_sweep_phi_ksi(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr,
                                          phi_cur, ksi_cur, w, h, d, hx, hy, hz, equation_alpha, equation_smoothness, equation_data,
                                          *tdu_ptr, *tdv_ptr, *tdw_ptr, phi_nxt, ksi_nxt, slab_);
-      else
+      else if (flow_update && f3d_solve_sweep_add && !more && j + 1 == inner_iterations_count) {  // the last launch of the level, and it is one sweep
+        status = f3d_solve_sweep_add(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_cur,
+                                     ksi_cur, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
+        *flow_update = status == 0;
+      } else
         status = f3d_solve_sweep(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_cur,
                                  ksi_cur, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
       if (CheckDeviceError(status)) return;

@@ -58,6 +58,17 @@ inline OperationParameters& Solve(OperationParameters& bag, DevicePtr* frame_0, 
                        {"equation_data", s.data}, {"data_size", size}, {"hx", h.hx}, {"hy", h.hy}, {"hz", h.hz}});
 }
 
+// Solve that is also asked for the flow update (key "flow_update"): *flow_updated comes back true when the increments' containers
+// hold flow + increments, false when they hold the increments and the caller still has to add
+inline OperationParameters& SolveAndUpdate(OperationParameters& bag, DevicePtr* frame_0, DevicePtr* frame_1_registered, const Flow& flow,
+                                           const Flow& increment, const Flow& partner, DevicePtr* phi, DevicePtr* ksi,
+                                           const SolverSettings& s, DataSize4* size, const Spacing& h, bool* flow_updated)
+{
+  Solve(bag, frame_0, frame_1_registered, flow, increment, partner, phi, ksi, s, size, h);
+  bag.PushValuePtr("flow_update", flow_updated);
+  return bag;
+}
+
 inline OperationParameters& Add(OperationParameters& bag, DevicePtr* accumulator, DevicePtr* addend, DataSize4* size)
 {
   return FillBag(bag, {{"operand_0", accumulator}, {"operand_1", addend}, {"data_size", size}});

@@ -782,27 +782,35 @@ bool OpticalFlowE::RunPyramid(OperationParameters& params, DevicePtr raw_0, Devi
       level_stats_.push_back(st);
     }
 
-    // 4. the increments of this level: weights + sweeps; five containers on loan for the duration
+    // 4. the increments of this level: weights + sweeps; five containers on loan for the duration.  The solve is asked to add the
+    //    increments to the flow in its last launch (the sweep has both in registers); it says whether it did.
+    bool flow_updated = false;
     {
       DevicePtr phi = Borrow(), ksi = Borrow();
       DevicePtr partner[3] = {Borrow(), Borrow(), Borrow()};
       const calls::Flow partner_roles = {&partner[0], &partner[1], &partner[2]};
       cuop_solve_.silent = silent;
-      cuop_solve_.Execute(calls::Solve(bag, &level_frame[0], &level_frame[1], flow_roles, step_roles, partner_roles, &phi, &ksi, settings,
-                                       &box, spacing));
+      cuop_solve_.Execute(calls::SolveAndUpdate(bag, &level_frame[0], &level_frame[1], flow_roles, step_roles, partner_roles, &phi, &ksi,
+                                                settings, &box, spacing, &flow_updated));
       for (DevicePtr p : {phi, ksi, partner[0], partner[1], partner[2]}) GiveBack(p);
     }
 
     // 5. flow += increments, then the median of every component.  The components are independent through both, so the three go out
     //    in one launch each; the increments are consumed by "+=", so their containers receive the filtered flow and the roles swap
-    //    (the reference filters through one scratch container, a component at a time)
+    //    (the reference filters through one scratch container, a component at a time).  Where the solve has left the sums in the
+    //    increments' containers there is nothing to add: the median reads them there and writes the flow's containers, no swap.
     {
       OperationParameters bags[3];
-      for (int c = 0; c < 3; ++c) calls::Add(bags[c], &flow[c], &step[c], &box);
-      cuop_add_.ExecuteBatch(bags, 3);
-      for (int c = 0; c < 3; ++c) calls::Median(bags[c], &flow[c], &step[c], &box, &median_radius);
-      cuop_median_.ExecuteBatch(bags, 3);
-      for (int c = 0; c < 3; ++c) std::swap(flow[c], step[c]);
+      if (flow_updated) {
+        for (int c = 0; c < 3; ++c) calls::Median(bags[c], &step[c], &flow[c], &box, &median_radius);
+        cuop_median_.ExecuteBatch(bags, 3);
+      } else {
+        for (int c = 0; c < 3; ++c) calls::Add(bags[c], &flow[c], &step[c], &box);
+        cuop_add_.ExecuteBatch(bags, 3);
+        for (int c = 0; c < 3; ++c) calls::Median(bags[c], &flow[c], &step[c], &box, &median_radius);
+        cuop_median_.ExecuteBatch(bags, 3);
+        for (int c = 0; c < 3; ++c) std::swap(flow[c], step[c]);
+      }
     }
 
     if (collect_level_statistics) {

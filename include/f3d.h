@@ -172,6 +172,16 @@ int f3d_solve_sweep(f3d_devptr frame_0, f3d_devptr frame_1, f3d_devptr flow_u, f
                     size_t width, size_t height, size_t depth, float hx, float hy, float hz, float equation_alpha,
                     f3d_devptr temp_du, f3d_devptr temp_dv, f3d_devptr temp_dw, const f3d_slab* slab);
 
+/* The LAST sweep of a level with the flow update in it: f3d_solve_sweep whose three outputs receive flow_u + du', flow_v + dv',
+ * flow_w + dw' (du', dv', dw' being what f3d_solve_sweep would have written; one binary32 add each) -- bit for bit what
+ * f3d_solve_sweep followed by f3d_add(flow_*, temp_d*) leaves in flow_*, without the nine array passes of the add: the sweep has
+ * both operands in registers.  Same arguments, slab window and refusals as f3d_solve_sweep; in addition an output that is also one of
+ * the ten inputs is refused.  flow_* and flow_d* are not written. */
+int f3d_solve_sweep_add(f3d_devptr frame_0, f3d_devptr frame_1, f3d_devptr flow_u, f3d_devptr flow_v, f3d_devptr flow_w,
+                        f3d_devptr flow_du, f3d_devptr flow_dv, f3d_devptr flow_dw, f3d_devptr phi, f3d_devptr ksi,
+                        size_t width, size_t height, size_t depth, float hx, float hy, float hz, float equation_alpha,
+                        f3d_devptr sum_u, f3d_devptr sum_v, f3d_devptr sum_w, const f3d_slab* slab);
+
 /* TWO consecutive solve_3d sweeps in one launch: temp_d* receive what two f3d_solve_sweep calls with a buffer swap in
  * between would leave in flow_d* (bit for bit); the intermediate field never goes to HBM, so the pair moves the bytes of
  * one sweep.  Replaces two iterations of the inner loop of cuda_operation_solve.cpp:222-255; the caller swaps ONCE.
@@ -266,7 +276,11 @@ int f3d_warp(f3d_devptr frame_0, f3d_devptr frame_1, f3d_devptr flow_u, f3d_devp
              const f3d_slab* slab);
 
 /* resample_{x,y,z}_3d, 6 args: cuda_operation_resample.cpp:115-120,138-143,161-166; src/kernels/resample_3d.cu.
- * slab_in describes the input container (z pass only reads through it), slab the output planes. */
+ * slab_in describes the input container (z pass only reads through it), slab the output planes.
+ * The x pass takes one of three kernels with the same bits: rows of up to 1024 floats resampled to up to 1024 outputs are walked
+ * several per wave with the output windows held in registers (k_resample_x_rows), longer rows of up to 2048 floats are staged one
+ * per wave (k_resample_x_lds), and anything else -- longer rows, rows that do not start 16-byte aligned -- reads global memory
+ * directly (k_resample<0>). */
 int f3d_resample_x(f3d_devptr input, f3d_devptr output, size_t out_width, size_t out_height, size_t out_depth,
                    size_t in_width, const f3d_slab* slab);
 int f3d_resample_y(f3d_devptr input, f3d_devptr output, size_t out_width, size_t out_height, size_t out_depth,

@@ -51,7 +51,7 @@ SRC = os.path.join(ROOT, "cuda-flow3d_amd", "csrc", "f3d_solve.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-I" + os.path.join(ROOT, "include"),
          "-I" + os.path.join(ROOT, "cuda-flow3d_amd", "csrc"), "-S", "--cuda-device-only"]
-KERNELS = ("k_sweep6", "k_phiksi6", "k_sweep7")
+KERNELS = ("k_sweep6", "k_last_sweep_flow", "k_phiksi6", "k_sweep7")
 
 
 def compile_to_asm():
