@@ -270,7 +270,9 @@ int f3d_solve_sweep_phi_ksi_edges_fd(f3d_devptr fx, f3d_devptr fy, f3d_devptr fz
                                      f3d_devptr temp_dv, f3d_devptr temp_dw, f3d_devptr phi_next, f3d_devptr ksi_next,
                                      const f3d_slab* slab, int keep_below, int keep_above);
 
-/* registration_3d, 12 args: cuda_operation_registration.cpp:110-122; kernel src/kernels/registration_3d.cu:28-82 */
+/* registration_3d, 12 args: cuda_operation_registration.cpp:110-122; kernel src/kernels/registration_3d.cu:28-82.
+ * output must not be frame_1 (every voxel gathers from other voxels of it; refused, as cuda_operation_registration.cpp:100-103 does).
+ * output may be frame_0: a voxel reads only its own voxel of frame_0, before it writes, and the reference's operator allows it. */
 int f3d_warp(f3d_devptr frame_0, f3d_devptr frame_1, f3d_devptr flow_u, f3d_devptr flow_v, f3d_devptr flow_w,
              size_t width, size_t height, size_t depth, float hx, float hy, float hz, f3d_devptr output,
              const f3d_slab* slab);

@@ -428,7 +428,7 @@ int f3d_warp(f3d_devptr f0, f3d_devptr f1, f3d_devptr u, f3d_devptr v, f3d_devpt
 {
   Geo o;
   if (!make_geo(&o, width, height, depth, slab, "f3d_warp")) return 1;
-  if (output == f1 || output == f0) return fail("f3d_warp: input buffer cannot serve as output buffer");
+  if (output == f1) return fail("f3d_warp: input buffer cannot serve as output buffer");  // frame_0 may be the output (include/f3d.h)
   orc_warp(P<float>(f0), P<float>(f1), P<float>(u), P<float>(v), P<float>(w), o.W, o.H, o.D, hx, hy, hz, P<float>(output), &o.g);
   return 0;
 }

@@ -984,9 +984,10 @@ def _dev_array(ptrs):
 @pytest.mark.parametrize("dims,cdims,window", [((37, 21, 9), (64, 32, 16), None), ((70, 9, 5), (70, 9, 5), None),
                                                ((20, 12, 17), (24, 12, 17), (3, 11)), ((129, 7, 6), (132, 8, 6), None)])
 def test_batched_entries_equal_the_single_volume_ones(f3d, oracle, dims, cdims, window, count, monkeypatch):
-    """f3d_add_n, f3d_median_n (3, 5 -- every 5^3 kernel -- and 7), f3d_resample_{x,y,z}_n and f3d_clear_box_n on one, two and
-    three volumes of a box: what the single-volume entries (pinned to the oracle above) leave, volume by volume, also on a slab
-    window; nothing outside the box or the window is written."""
+    """f3d_add_n, f3d_median_n (3, 5 -- every 5^3 kernel -- and 7) and f3d_clear_box_n on one, two and three volumes of a box: what
+    the single-volume entries (pinned to the oracle above) leave, volume by volume, also on a slab window; add and clear write
+    nothing outside the box or the window.  (f3d_resample_x_n: tests/test_gpu_resample_paths.py; f3d_resample_y_n and
+    f3d_resample_z_n: tests/test_gpu_stream_routes.py.)"""
     hip = f3d.hip()
     rng = np.random.default_rng(hash((dims, count)) % 2**32)
     W, H, D = dims
