@@ -29,7 +29,8 @@
 // Both keep the reference's expression trees operation for operation; what is shared between
 // the stages are values the reference computes twice from the same operands (fx, fy, fz, ft, the J products, U[x+1] - U[x-1]).
 //
-// Tile: TY core rows x 64 columns, marching along z.  Waves: TY + 2 row waves (rows y0-1 .. y0+TY), one column wave
+// Tile: TY core rows x 64 columns, marching along z (in the last tile column of a level whose width leaves 1 .. 32 columns there: two
+// bands of TY rows x 32 columns, FOLD below).  Waves: TY + 2 row waves (rows y0-1 .. y0+TY), one column wave
 // (stage 1 of the 2 x TY voxels left and right of the tile), one loader wave.  TY = 12 -> 16 waves, four per SIMD, 117 / 125
 // VGPRs (SS / SP); TY = 8 -> 12 waves; TY = 4 -> 8 waves for levels so small that a workgroup has its CU to itself.  The
 // launcher prices the three shapes per level (pair8_rows in f3d_solve.hip).  Nothing that is the same for every lane of a wave
@@ -274,6 +275,22 @@ __device__ __forceinline__ void phi_ksi_stage2(const CarryP& k, const S3& xm, co
   }
 }
 
+// Tiles of a chunk, numbered x first.  With a folded last column (`fold`) a pair of tile rows (ty, ty + 1), ty even, is numbered: the
+// ntx - 1 regular tiles of row ty, the folded tile, the regular tiles of row ty + 1 -- so the folded tile marches in step with its y
+// neighbours; with nty odd the last row is alone with its folded tile (whose band B is empty).
+__host__ __device__ inline int pair8_tiles_per_chunk(int ntx, int nty, bool fold)
+{
+  return fold ? (ntx - 1) * nty + (nty + 1) / 2 : ntx * nty;
+}
+// F3D_PAIR8_FOLD=0 keeps one band per tile everywhere (A/B timing and the tests; read per call like F3D_PAIR8_TY): the same results
+inline bool pair8_folds(int width, int rows, int ty)
+{
+  const char* e = std::getenv("F3D_PAIR8_FOLD");
+  if (e && e[0] == '0') return false;
+  const int rem = width % kLanes;
+  return rem >= 1 && rem <= kLanes / 2 && width > kLanes && rows > ty;   // ntx >= 2, nty >= 2
+}
+
 // ABL (timing experiments only, wrong results): bit 0 = the loader issues nothing after the prologue, bit 1 = no stage
 // arithmetic (LDS traffic, barriers and stores stay), bit 2 = the compute waves only keep the barriers, bit 3 = arithmetic only behind the
 // prologue (no LDS reads, no step barriers), bit 5 (with bit 3: F3D_ABLATE8=40) = the prologue fetches one plane instead of three
@@ -283,9 +300,20 @@ __device__ __forceinline__ void phi_ksi_stage2(const CarryP& k, const S3& xm, co
 // FD: the kernel reads the frame derivatives fx, fy, fz, ft (k_frame_derivatives, once per level) instead of the frames: they
 // are centre values, so the frame entries of every neighbour -- their LDS reads, lane shifts, differences and the three
 // divisions by 4h -- drop out of stage 1 (a seventh of its arithmetic), for two more arrays to stream.
-template <int MODE, int TY, int ABL, bool FD, bool YM, bool TIGHT>
+//
+// FOLD (z-marching builds, last tile column of a level with 1 <= W mod 64 <= 32): the tile holds TWO row bands side by side in the
+// lanes -- lanes 0-31 are columns x0 .. x0+31 of band A (rows from y0), lanes 32-63 the same columns of band B (rows from y0 + TY) --
+// so that one workgroup does the work of two tiles that would each be at least half padding.  The tile's right side is the x face
+// of the volume, where the mirror rule substitutes the neighbour and the right halo pieces were fetched for nothing: the [side]
+// index of the halo area, of the column wave and of hc1 means "band" here, and both sides are LEFT halos.  Row wave r serves row
+// y0-1+r of band A and row y0+TY-1+r of band B; each band keeps its own halo rows (the two that are the other band's edge rows are
+// computed twice).  Piece counts, LDS layout and the counted wait are those of the regular tile: only per-lane offsets differ.
+// FOLDS: a build for the levels that fold (both tile kinds, one branch per workgroup).  The levels that do not fold keep the build
+// without it: with both bodies in every kernel a solve was 0.5 % slower where nothing folds (profiles/r13_pair8_fold_ab.txt).
+template <int MODE, int TY, int ABL, bool FD, bool YM, bool TIGHT, bool FOLDS = false>
 __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, int zchunk, int ntx, int nty, int n_tiles, int xcd_remap)
 {
+  static_assert(!FOLDS || (!YM && !TIGHT && ABL == 0), "two row bands per tile: z-marching product builds only");
   static_assert(!(YM && FD), "the frame-derivative launchers march along z only");
   static_assert(!TIGHT || (YM && ABL == 0), "a tile without halo rows holds every row of the volume: thin volumes marched along y");
   constexpr int RH = TIGHT ? 0 : 1;   // halo rows on either side of the tile's rows that get a row wave (and twice that many ring rows)
@@ -311,10 +339,24 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
     tile = (tile % 8) * per_xcd + tile / 8;
   }
   if (tile >= n_tiles) return;
-  const int tx = tile % ntx;
-  const int ty = (tile / ntx) % nty;
-  const int tz = tile / (ntx * nty);
+  // the tile's place (FOLDS: the numbering described at pair8_tiles_per_chunk)
+  int tx = tile % ntx;
+  int ty = (tile / ntx) % nty;
+  int tz = tile / (ntx * nty);
+  bool folded = false;
+  if constexpr (FOLDS) {
+    const int per_chunk = pair8_tiles_per_chunk(ntx, nty, true);
+    tz = tile / per_chunk;
+    const int i = tile % per_chunk;
+    const int pair = i / (2 * ntx - 1), k = i % (2 * ntx - 1);
+    folded = k == ntx - 1;
+    tx = k < ntx ? k : k - ntx;
+    ty = k < ntx ? 2 * pair : 2 * pair + 1;
+  }
 
+  // ONE branch on the tile kind per workgroup: everything below exists twice in a build that folds, over the same LDS
+  auto tile_body = [&](auto fold_c) __attribute__((always_inline)) {
+  constexpr bool FOLD = decltype(fold_c)::value;
   int lane = threadIdx.x;  // re-made at the top of every step where registers are short (see fresh_lane)
   const int r = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.y));
   const bool colw = r == NR;
@@ -350,15 +392,17 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
     const float* base[NA];
 #pragma unroll
     for (int i = 0; i < NA; ++i) base[i] = uniform_ptr(a.in[i] + base_off);
-    // row pieces: lane -> (row 4k + lane/16, floats 4 (lane%16) ..)
+    // row pieces: lane -> (row 4k + lane/16, floats 4 (lane%16) ..); FOLD: the upper eight lanes of a row fetch band B's row
+    const bool bandb = FOLD && (lane & 15) >= 8;
+    const int seg = bandb ? (lane & 15) - 8 : (lane & 15);
     unsigned rowb[NK];
     bool rowv[NK];
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
       const int j = 4 * k + (lane >> 4);
       rowv[k] = j < NJ;
-      const int yrow = f3d_clampi(f3d_mir(y0 - 2 * RH + (rowv[k] ? j : 0), RDIM), 0, RDIM - 1);
-      rowb[k] = static_cast<unsigned>(yrow) * row_b + static_cast<unsigned>(x0 + 4 * (lane & 15)) * 4u;
+      const int yrow = f3d_clampi(f3d_mir(y0 + (bandb ? TY : 0) - 2 * RH + (rowv[k] ? j : 0), RDIM), 0, RDIM - 1);
+      rowb[k] = static_cast<unsigned>(yrow) * row_b + static_cast<unsigned>(x0 + 4 * seg) * 4u;
     }
     // halo pieces: lane' = 64 h + lane -> [array][side][row]; four floats left of the tile (x0-4 ..) or right of it (x0+64 ..)
     const float* hptr[NH];
@@ -375,9 +419,10 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
 #pragma unroll
       for (int i = SB + 1; i < SB + L::NS; ++i)
         if (arr == i) b = base[i];
-      const int yrow = f3d_clampi(f3d_mir(y0 - 2 * RH + j, RDIM), 0, RDIM - 1);
+      const int yrow = f3d_clampi(f3d_mir(y0 + (FOLD && s ? TY : 0) - 2 * RH + j, RDIM), 0, RDIM - 1);
       // tiles at an x face fetch a piece from inside the row instead (never used: the mirror rule substitutes there)
-      const int xc = s == 0 ? (left_face ? 0 : x0 - 4) : (right_face ? x0 + kLanes - 4 : x0 + kLanes);
+      // FOLD: side 1 is band B's LEFT halo
+      const int xc = FOLD ? x0 - 4 : s == 0 ? (left_face ? 0 : x0 - 4) : (right_face ? x0 + kLanes - 4 : x0 + kLanes);
       hptr[h] = b + static_cast<size_t>(yrow) * static_cast<size_t>(row_b >> 2) + xc;
     }
     auto issue = [&](int p) {  // plane p (mirrored for the address) into slot (p - (qs-1)) mod 3
@@ -410,8 +455,8 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
       for (int k = 0; k < NKC; ++k) {
         const int j = 4 * k + (lane >> 4);
         crowv[k] = j < L::NRC;
-        const int yrow = f3d_clampi(f3d_mir(y0 - 1 + (crowv[k] ? j : 0), RDIM), 0, RDIM - 1);
-        crowb[k] = static_cast<unsigned>(yrow) * row_b + static_cast<unsigned>(x0 + 4 * (lane & 15)) * 4u;
+        const int yrow = f3d_clampi(f3d_mir(y0 + (bandb ? TY : 0) - 1 + (crowv[k] ? j : 0), RDIM), 0, RDIM - 1);
+        crowb[k] = static_cast<unsigned>(yrow) * row_b + static_cast<unsigned>(x0 + 4 * seg) * 4u;
       }
 #pragma unroll
       for (int h = 0; h < NHC; ++h) {
@@ -425,8 +470,8 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
 #pragma unroll
         for (int i = 1; i < 5; ++i)
           if (arr == i) b = base[kCIn[i]];
-        const int yrow = f3d_clampi(f3d_mir(y0 + j, RDIM), 0, RDIM - 1);
-        const int xc = s == 0 ? (left_face ? 0 : x0 - 4) : (right_face ? x0 + kLanes - 4 : x0 + kLanes);
+        const int yrow = f3d_clampi(f3d_mir(y0 + (FOLD && s ? TY : 0) + j, RDIM), 0, RDIM - 1);
+        const int xc = FOLD ? x0 - 4 : s == 0 ? (left_face ? 0 : x0 - 4) : (right_face ? x0 + kLanes - 4 : x0 + kLanes);
         chptr[h] = b + static_cast<size_t>(yrow) * static_cast<size_t>(row_b >> 2) + xc;
       }
     }
@@ -488,13 +533,13 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
     sdivs.ok = a.sdivs_ok != 0;
   }
 
-  // row waves
+  // row waves (FOLD: y, yy, r_ym, r_yp are band A's; band B's row is y + TY, its image rows r_ymb, r_ypb)
   const int y = y0 - RH + r;
   const int yy = f3d_clampi(f3d_mir(y, RDIM), 0, RDIM - 1);
-  const int x = x0 + lane;
-  const bool core = r >= RH && r < RH + TY;
-  const bool owner = core && x < g.W && y < RDIM;
   const int side = lane < 32 ? 0 : 1;
+  const int x = FOLD ? x0 + (lane & 31) : x0 + lane;
+  const bool core = r >= RH && r < RH + TY;
+  const bool owner = core && x < g.W && (FOLD && side ? y + TY : y) < RDIM;
   const int jr = r + RH;  // ring row of this wave's row
   // ring rows of its two row neighbours: the rows beside it -- or, in a tile without halo rows, the mirror image at a face of the volume
   const int jr_m = (TIGHT && y == 0) ? jr + 1 : jr - 1;
@@ -504,17 +549,27 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
   // instead of six vector selects per step.
   const int r_ym = y == 0 ? r + 1 : r - 1;
   const int r_yp = y == RDIM - 1 ? r - 1 : r + 1;
-  const unsigned xb = static_cast<unsigned>(x) * 4u;
+  const int r_ymb = r - 1;   // (band B never holds row 0)
+  const int r_ypb = y + TY == RDIM - 1 ? r - 1 : r + 1;
+  // FOLD: band B stores TY rows below band A
+  const unsigned xb = static_cast<unsigned>(x) * 4u + (FOLD && side ? static_cast<unsigned>(TY) * row_b : 0u);
   // column wave: lane = side * 32 + core row (lanes beyond TY rows repeat the last row and publish nothing)
   const bool cactive = (lane & 31) < TY;
   const int crow = cactive ? (lane & 31) : TY - 1;
-  const int cy = y0 + crow;
-  const int cx = side == 0 ? x0 - 1 : x0 + kLanes;
+  const int cy = y0 + crow + (FOLD && side ? TY : 0);
+  const int cx = FOLD || side == 0 ? x0 - 1 : x0 + kLanes;   // FOLD: the left halo column of either band
   const int jc = crow + 2 * RH;  // ring row of the column wave's voxel
   const int jc_m = (TIGHT && cy == 0) ? jc + 1 : jc - 1;
   const int jc_p = (TIGHT && cy == RDIM - 1) ? jc - 1 : jc + 1;
-  const int e_near = side == 0 ? 3 : 0;  // element of the 4-float halo piece next to the tile, and the one beyond it
-  const int e_far = side == 0 ? 2 : 1;
+  const int e_near = FOLD || side == 0 ? 3 : 0;  // element of the 4-float halo piece next to the tile, and the one beyond it
+  const int e_far = FOLD || side == 0 ? 2 : 1;
+  // FOLD: a shift to the right hands lane 32 (band B's first column) band A's last one: it takes its own left halo value instead,
+  // as lane 0 does.  (Shifts to the left need nothing: lane 31 sits at x >= W-1, where the mirror rule substitutes or nothing counts.)
+  auto left_or = [&](float v, float edge) __attribute__((always_inline)) {
+    const float s = lane_left_or(v, edge);
+    if constexpr (FOLD) return lane == 32 ? edge : s;
+    else return s;
+  };
 
   float* obase[5];
 #pragma unroll
@@ -593,7 +648,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
     PlaneRegs T0, T1, T2;
     if constexpr (CW) {
       PlaneRegs T;
-      const float* d = S + jc * kLanes + (side ? kLanes - 1 : 0);
+      const float* d = S + jc * kLanes + (side ? (FOLD ? 32 : kLanes - 1) : 0);   // FOLD: band B's first column
       constexpr int st = NJP * kLanes;
       if (ABL & 8) {
         fake_raw(T);
@@ -641,6 +696,9 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
     constexpr bool CW = decltype(colw_c)::value;  // the column wave runs a loop of its own: no value merges with the row waves
     constexpr int SLOT = decltype(slot_c)::value;
     if constexpr (TY > 8 || TIGHT) lane = fresh_lane();
+    // FOLD: the band of a row wave's lane, from the lane number of THIS step where that is re-made: what is selected by it (the y-face
+    // weights, the image rows) is then made per step from scalars instead of being carried through the march in vector registers
+    const int band = FOLD ? lane >> 5 : 0;
     if (!(ABL & 8)) __syncthreads();  // B_q: plane q+1 is in the ring, img1 / hc1 of plane q-1 are complete
     if (ABL & 4) return;
     const float* Sp = &ring[SLOT][0];
@@ -665,11 +723,11 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
         const Face6 inner = nIn;
 #pragma unroll
         for (int i = 0; i < kNL; ++i) {
-          xm.v[i] = side ? inner.v[i] : outer.v[i];
-          xp.v[i] = side ? outer.v[i] : inner.v[i];
+          xm.v[i] = !FOLD && side ? inner.v[i] : outer.v[i];
+          xp.v[i] = !FOLD && side ? outer.v[i] : inner.v[i];
         }
-        rxm = side ? rinner : router;
-        rxp = side ? router : rinner;
+        rxm = !FOLD && side ? rinner : router;
+        rxp = !FOLD && side ? router : rinner;
         vx = cx;
         vy = cy;
         // A halo column can be the LAST column of the volume (W = 64 k + 1): its right neighbour lies beyond the row, where
@@ -686,15 +744,15 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
         const Face6 cf = plane_face(C);
 #pragma unroll
         for (int i = 0; i < kNL; ++i) {
-          xm.v[i] = lane_left_or(cf.v[i], xf.v[i]);
+          xm.v[i] = left_or(cf.v[i], xf.v[i]);
           xp.v[i] = lane_right_or(cf.v[i], xf.v[i]);
         }
         if (MODE == PAIR_SP) {
-          rxm = {lane_left_or(C.u, rx.u), lane_left_or(C.v, rx.v), lane_left_or(C.w, rx.w)};
+          rxm = {left_or(C.u, rx.u), left_or(C.v, rx.v), left_or(C.w, rx.w)};
           rxp = {lane_right_or(C.u, rx.u), lane_right_or(C.v, rx.v), lane_right_or(C.w, rx.w)};
         }
         vx = x;
-        vy = y;
+        vy = band ? y + TY : y;
         // mirror rule at the x faces of the volume (index -1 -> 1, W -> W-2): the missing neighbour is the opposite one
         if (tile_at_x_face) {
           if (x == 0) {
@@ -772,11 +830,12 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
         yp.u = opaque(seedv); yp.v = opaque(seedv); yp.w = opaque(seedv);
         eu = opaque(seedv); ev = opaque(seedv); ew = opaque(seedv);
       } else {
-        ym.u = img1[pb][0][r_ym][lane]; ym.v = img1[pb][1][r_ym][lane]; ym.w = img1[pb][2][r_ym][lane];
-        yp.u = img1[pb][0][r_yp][lane]; yp.v = img1[pb][1][r_yp][lane]; yp.w = img1[pb][2][r_yp][lane];
+        const int im = band ? r_ymb : r_ym, ip = band ? r_ypb : r_yp;
+        ym.u = img1[pb][0][im][lane]; ym.v = img1[pb][1][im][lane]; ym.w = img1[pb][2][im][lane];
+        yp.u = img1[pb][0][ip][lane]; yp.v = img1[pb][1][ip][lane]; yp.w = img1[pb][2][ip][lane];
         eu = hc1[pb][0][side][r - RH]; ev = hc1[pb][1][side][r - RH]; ew = hc1[pb][2][side][r - RH];
       }
-      xm.u = lane_left_or(hC.u, eu); xm.v = lane_left_or(hC.v, ev); xm.w = lane_left_or(hC.w, ew);
+      xm.u = left_or(hC.u, eu); xm.v = left_or(hC.v, ev); xm.w = left_or(hC.w, ew);
       xp.u = lane_right_or(hC.u, eu); xp.v = lane_right_or(hC.v, ev); xp.w = lane_right_or(hC.w, ew);
       zm = hM;
       zp = sN;
@@ -869,14 +928,19 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
   if (colw) march(std::true_type{});
   else march(std::false_type{});
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores issued by hand
+  };
+  if constexpr (FOLDS) {
+    if (__builtin_amdgcn_readfirstlane(static_cast<int>(folded))) return tile_body(std::true_type{});
+  }
+  tile_body(std::false_type{});
 }
 
 // the kernels: one body, two sets of launch attributes
-template <int MODE, int TY, int ABL = 0, bool FD = false, bool YM = false>
+template <int MODE, int TY, int ABL = 0, bool FD = false, bool YM = false, bool FOLDS = false>
 __global__ __launch_bounds__(kLanes*(TY + 4)) void k_pair8(PairArgs a, F3dGeo g, int zchunk, int ntx, int nty, int n_tiles,
                                                            int xcd_remap)
 {
-  pair8_body<MODE, TY, ABL, FD, YM, false>(a, g, zchunk, ntx, nty, n_tiles, xcd_remap);
+  pair8_body<MODE, TY, ABL, FD, YM, false, FOLDS>(a, g, zchunk, ntx, nty, n_tiles, xcd_remap);
 }
 // ... a tile without halo rows (thin volumes marched along y, all planes in the tile): TY + 2 waves and ~50 KB of LDS per workgroup, held to
 // 128 registers so that TWO workgroups share a CU (four waves per SIMD) -- a level of BASELINE config 3 is then spread over twice as
@@ -899,9 +963,10 @@ struct Pair8Plan {
   long wgs = 0;
 };
 // `rows` / `planes`: extent along the tile rows and along the march (H and the z window; D and H for a y march)
-inline Pair8Plan pair8_plan_dims(int width, int rows, int planes, int ty, int zc_limit, long per_round = 256)
+// `fold`: the last tile column holds two row bands per tile (pair8_folds; never for a y march)
+inline Pair8Plan pair8_plan_dims(int width, int rows, int planes, int ty, int zc_limit, long per_round = 256, bool fold = false)
 {
-  const long tiles = static_cast<long>((width + kLanes - 1) / kLanes) * ((rows + ty - 1) / ty);
+  const long tiles = pair8_tiles_per_chunk((width + kLanes - 1) / kLanes, (rows + ty - 1) / ty, fold);
   const int max_chunks = planes > 0 ? planes : 1;  // down to one plane per chunk: three steps instead of four where one round covers it
   // what a chunk costs beside its planes, in plane steps (F3D_PAIR8_CHUNK_STEPS: launch-geometry experiments)
   static const int extra = std::getenv("F3D_PAIR8_CHUNK_STEPS") ? std::atoi(std::getenv("F3D_PAIR8_CHUNK_STEPS")) : 7;
@@ -925,7 +990,7 @@ inline Pair8Plan pair8_plan_dims(int width, int rows, int planes, int ty, int zc
 }
 inline Pair8Plan pair8_plan(const F3dGeo& g, int ty, long per_round = 256)
 {
-  return pair8_plan_dims(g.W, g.H, g.z_hi - g.z_lo, ty, max_planes_per_chunk(g), per_round);
+  return pair8_plan_dims(g.W, g.H, g.z_hi - g.z_lo, ty, max_planes_per_chunk(g), per_round, pair8_folds(g.W, g.H, ty));
 }
 
 // Thin volumes march along y (YM, see the top of this file): the whole level in one launch, no slab window, every byte offset
@@ -963,23 +1028,31 @@ void launch_pair8(const PairArgs& args, const F3dGeo& g, int force_zchunk, int x
   const int ntx = (g.W + kLanes - 1) / kLanes;
   const int nty = (rows + TY - 1) / TY;
   const int zc_limit = YM ? planes : max_planes_per_chunk(g);
+#ifdef F3D_LAB
+  static const int abl = std::getenv("F3D_ABLATE8") ? std::atoi(std::getenv("F3D_ABLATE8")) : 0;
+#else
+  constexpr int abl = 0;
+#endif
+  const int fold = !YM && abl == 0 && pair8_folds(g.W, rows, TY) ? 1 : 0;   // (the timing builds of the lab keep one band per tile)
   // (two workgroups of a tile without halo rows share a CU: 512 per round)
-  int zchunk = pair8_plan_dims(g.W, rows, planes, TY, zc_limit, TIGHT ? 512 : 256).zchunk;
+  int zchunk = pair8_plan_dims(g.W, rows, planes, TY, zc_limit, TIGHT ? 512 : 256, fold != 0).zchunk;
   if (force_zchunk > 0) zchunk = force_zchunk;
   zchunk = std::min(zchunk, zc_limit);
   const int nz = (planes + zchunk - 1) / zchunk;
-  const int n_tiles = ntx * nty * nz;
+  const int n_tiles = pair8_tiles_per_chunk(ntx, nty, fold != 0) * nz;
   const int per_xcd = (n_tiles + 7) / 8;
   const int blocks = xcd_remap ? per_xcd * 8 : n_tiles;
   const dim3 grid(blocks, 1, 1), block(kLanes, TY + (TIGHT ? 2 : 4), 1);
   auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, f3d::stream(), a, g, zchunk, ntx, nty, n_tiles, xcd_remap); };
+  if constexpr (!YM) {
+    if (fold) return go(k_pair8<MODE, TY, 0, FD, false, true>);
+  }
   if constexpr (YM && TIGHT) return go(k_pair8t<MODE, TY>);
   else if constexpr (YM) return go(k_pair8<MODE, TY, 0, false, true>);
   else if constexpr (FD) return go(k_pair8<MODE, TY, 0, true>);
   else {
 #ifdef F3D_LAB  // timing builds that skip parts of the work (WRONG results): only in lib/lab/libf3d_hip.so (make lab, tools/kbench.py
                 // --ablate); the shipped library has no switch that changes a result and no ABL != 0 instantiation
-    static const int abl = std::getenv("F3D_ABLATE8") ? std::atoi(std::getenv("F3D_ABLATE8")) : 0;
     if constexpr (TY == 12) {
       if (abl == 16) return go(k_pair8<MODE, TY, 16>);
     }
