@@ -103,6 +103,14 @@ class MotionResidual(C.Structure):  # f3d_motion_residual
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class ValidateStats(C.Structure):  # f3d_validate_stats
+    _fields_ = [("present", C.c_ulonglong), ("tested", C.c_ulonglong), ("outliers", C.c_ulonglong), ("replaced", C.c_ulonglong),
+                ("undefined", C.c_ulonglong), ("r_max", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class FlowParams(C.Structure):  # f3d_flow_params
     _fields_ = [
         ("warp_levels_count", C.c_size_t), ("warp_scale_factor", C.c_float),
@@ -281,6 +289,9 @@ def host():
         "f3d_flow_motion_compute": [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(_fp), C.POINTER(MotionFit),
                                     C.POINTER(MotionResidual)],
         "f3d_flow_motion_end": [C.c_void_p],
+        "f3d_flow_validate_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_float, C.c_uint, C.c_uint, C.c_uint, C.c_float,
+                                      C.POINTER(_fp), C.POINTER(ValidateStats)],
+        "f3d_flow_validate_end": [C.c_void_p],
         "f3d_op_create": [C.POINTER(C.c_void_p), C.c_char_p], "f3d_op_initialize": [C.c_void_p, C.POINTER(Size4)],
         "f3d_op_execute": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), _sz],
         "f3d_op_execute_batch": [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(_sz), _sz],
@@ -430,6 +441,11 @@ def _motion_entry():
             _entry("f3d_remove_motion", [_dp] * 6 + [C.POINTER(MotionFit)] + [_sz] * 3 + [C.POINTER(MotionResidual)], what))
 
 
+def _validate_entry():
+    return _entry("f3d_validate_displacement", [_dp] * 4 + [C.c_float, C.c_uint, C.c_float, C.c_float, C.c_uint, C.c_uint, _dpp, C.c_uint] +
+                  [_sz] * 3 + [C.POINTER(ValidateStats)], "validate a displacement")
+
+
 def _mask(fields, groups, what):
     """the F3D_* bits of an iterable of group names (the keys of `groups`) or of a comma-separated string of them"""
     if isinstance(fields, str):
@@ -518,6 +534,19 @@ def _motion_model(model):
     if model not in MOTION_MODELS:
         raise ValueError(f"unknown motion model {model!r} (one of {', '.join(MOTION_MODELS)})")
     return MOTION_MODELS[model]
+
+
+# the outputs of f3d_validate_displacement in ABI order, the F3D_VALIDATE_* group of each, and its modes
+VALIDATE_NAMES = ("r", "u", "v", "w")
+VALIDATE_GROUPS = {"r": 1, "d": 2}
+_VALIDATE_GROUP_OF = (1, 2, 2, 2)
+VALIDATE_MODES = {"mark": 1, "replace": 2}
+
+
+def _validate_mode(mode):
+    if mode not in VALIDATE_MODES:
+        raise ValueError(f"unknown validation mode {mode!r} (one of {', '.join(VALIDATE_MODES)})")
+    return VALIDATE_MODES[mode]
 
 
 def _strain_mask(fields):
@@ -655,6 +684,47 @@ def remove_motion(u, v, w, fit):
         stats = MotionResidual()
         check(fn(*p, *outs, C.byref(fit), *dims, C.byref(stats)), "f3d_remove_motion")
         return tuple(box.download(o, dims) for o in outs) + (stats.as_dict(),)
+
+
+def validate_displacement(u, v, w, weight=None, weight_min=0.8, step=1, eps=0.1, threshold=2.0, min_neighbours=9, mode="replace",
+                          fill_passes=0, fields=("r", "d")):
+    """The normalised median test of a displacement on the device (include/f3d.h, f3d_validate_displacement): u, v, w numpy [z, y, x]
+    float32; every vector is compared with the median of its up to 26 neighbours `step` voxels away, in units of the median residual
+    of those neighbours plus eps.  A voxel is absent where u, v or w is NaN or, with `weight` (same shape, e.g. the zncc of a match),
+    where weight < weight_min or NaN.  Vectors with r > threshold (tested with at least min_neighbours neighbours) and absent voxels
+    are rejected: NaN under mode "mark", the neighbour median under "replace" (NaN with fewer than min_neighbours neighbours).
+    fill_passes (needs "d"): up to that many further passes over the result with threshold inf and no weight, each of which gives
+    undefined voxels with enough defined neighbours their median; they stop when nothing is undefined or the count stops falling.
+    fields: "r" (the normalised residual, NaN where untested), "d" (the validated u, v, w).  Returns a dict name -> array for the
+    selected outputs and "stats" -> dict (present, tested, outliers, replaced, undefined, r_max) of the first pass with replaced and
+    undefined brought to the final state."""
+    fn = _validate_entry()
+    mask, m = _mask(fields, VALIDATE_GROUPS, "validation"), _validate_mode(mode)
+    if fill_passes and not mask & VALIDATE_GROUPS["d"]:
+        raise ValueError("fill_passes needs the validated displacement (\"d\" in fields)")
+    vols = (u, v, w) if weight is None else (u, v, w, weight)
+    with _on_device(vols, "u, v, w and weight must be [z, y, x] volumes of one shape") as (box, p, dims):
+        outs = [box.alloc() if mask & g else 0 for g in _VALIDATE_GROUP_OF]
+        box.set_current()
+        stats = ValidateStats()
+        check(fn(p[0], p[1], p[2], p[3] if weight is not None else 0, weight_min, step, eps, threshold, min_neighbours, m,
+                 (_dp * 4)(*outs), mask, *dims, C.byref(stats)), "f3d_validate_displacement")
+        spare = [0] + [box.alloc() for _ in range(3)] if fill_passes and stats.undefined else None
+        for _ in range(fill_passes):
+            if not stats.undefined:
+                break
+            filled = ValidateStats()
+            check(fn(outs[1], outs[2], outs[3], 0, 0.0, step, eps, float("inf"), min_neighbours, VALIDATE_MODES["replace"],
+                     (_dp * 4)(*spare), VALIDATE_GROUPS["d"], *dims, C.byref(filled)), "f3d_validate_displacement")
+            outs[1:], spare[1:] = spare[1:], outs[1:]
+            fell = filled.undefined < stats.undefined
+            stats.replaced += filled.replaced
+            stats.undefined = filled.undefined
+            if not fell:
+                break
+        res = {n: box.download(o, dims) for n, o in zip(VALIDATE_NAMES, outs) if o}
+    res["stats"] = stats.as_dict()
+    return res
 
 
 def _f32(a):
@@ -1148,7 +1218,7 @@ class OpticalFlow:
     def trajectory_end(self):
         _host_check(host().f3d_flow_trajectory_end(self._h), "f3d_flow_trajectory_end")
 
-    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_{strain,principal,inverse,match,motion}_*) ----
+    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_{strain,principal,inverse,match,motion,validate}_*) ----
     def _derived(self, compute, src, selected, stats, *args, fit=None):
         """one f3d_flow_*_compute into fresh host arrays: a list with an array per selected output and None for the others
         (fit: the MotionFit f3d_flow_motion_compute takes between the arrays and the statistics)"""
@@ -1229,6 +1299,25 @@ class OpticalFlow:
     def motion_end(self):
         """free the motion residual containers (destroy() does too)"""
         _host_check(host().f3d_flow_motion_end(self._h), "f3d_flow_motion_end")
+
+    def validate(self, source="flow", step=1, eps=0.1, threshold=2.0, min_neighbours=9, mode="replace", fill_passes=0,
+                 fields=("r", "d"), min_zncc=None):
+        """The flow the driver holds (source="flow") or the trajectory (source="trajectory") validated on the device by the normalised
+        median test (validate_displacement has the parameters): a dict name -> array for "r" and / or "u", "v", "w" as `fields` selects,
+        and "stats" -> dict.  min_zncc: voxels whose zncc of the last match() of this pair is below that are rejected as well and are
+        no neighbour of anyone (match() first; not for the trajectory)."""
+        mask = _mask(fields, VALIDATE_GROUPS, "validation")
+        stats = ValidateStats()
+        arrays = self._derived("f3d_flow_validate_compute", _source(source), [bool(mask & g) for g in _VALIDATE_GROUP_OF], stats, step,
+                               eps, threshold, min_neighbours, _validate_mode(mode), fill_passes,
+                               float("nan") if min_zncc is None else min_zncc)
+        res = {n: a for n, a in zip(VALIDATE_NAMES, arrays) if a is not None}
+        res["stats"] = stats.as_dict()
+        return res
+
+    def validate_end(self):
+        """free the containers of the validated displacement (destroy() does too)"""
+        _host_check(host().f3d_flow_validate_end(self._h), "f3d_flow_validate_end")
 
     def compute_sequence(self, frames, cumulative=False, silent=True, **kw):
         """Generator over the consecutive pairs of `frames` (an iterable of [z, y, x] volumes): yields (k, (u, v, w), disp) for

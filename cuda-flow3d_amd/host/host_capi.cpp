@@ -352,6 +352,31 @@ int f3d_flow_motion_compute(f3d_flow flow, int source, int model, float min_zncc
 
 int f3d_flow_motion_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kMotion, "f3d_flow_motion_end: null driver"); }
 
+int f3d_flow_validate_compute(f3d_flow flow, int source, unsigned step, float eps, float threshold, unsigned min_neighbours,
+                              unsigned mode, unsigned fill_passes, float min_zncc, float* const out[4], f3d_validate_stats* stats)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out != nullptr, "f3d_flow_validate_compute", &of)) return 1;
+  const int d_given = (out[1] ? 1 : 0) + (out[2] ? 1 : 0) + (out[3] ? 1 : 0);
+  if (d_given != 0 && d_given != 3) return HostFail("f3d_flow_validate_compute: out[1], out[2] and out[3] go together");
+  const unsigned fields = (out[0] ? F3D_VALIDATE_R : 0u) | (d_given ? F3D_VALIDATE_D : 0u);
+  if (!fields) return HostFail("f3d_flow_validate_compute: no output is asked for");
+  DevicePtr weight = 0;
+  if (min_zncc == min_zncc) {
+    if (source == F3D_STRAIN_OF_TRAJECTORY)
+      return HostFail("f3d_flow_validate_compute: min_zncc cannot mask the trajectory: the zncc of a match lives on the pair's grid");
+    weight = flow->zncc_of_held_flow ? flow->driver.DerivedContainer(OpticalFlowE::kMatch, 1) : 0;
+    if (!weight)
+      return HostFail("f3d_flow_validate_compute: min_zncc needs the zncc of a match of this pair (f3d_flow_match_compute first)");
+  }
+  return DerivedDownload(flow, OpticalFlowE::kValidated,
+                         flow->driver.ComputeValidated(of, weight, min_zncc, step, eps, threshold, min_neighbours, mode, fill_passes,
+                                                       fields, stats),
+                         out, fields);
+}
+
+int f3d_flow_validate_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kValidated, "f3d_flow_validate_end: null driver"); }
+
 const char* f3d_host_last_error(void) { return g_host_error.empty() ? f3d_last_error() : g_host_error.c_str(); }
 
 int f3d_flow_destroy(f3d_flow flow)

@@ -7,6 +7,8 @@
 //                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
 //                [--strain vol,e,eq] [--principal val,shear,dir1,dir3] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]
 //                [--detrend translation|rigid|affine [--detrend-min-zncc T]]
+//                [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]
+//                 [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -40,6 +42,14 @@
 // of the sample between the scans.  <tag>_detrended-{u,v,w}-W-H-D.raw is what remains, and one line per pair gives the motion.
 // --detrend-min-zncc T fits only where the zncc of --match (which must then select zncc) is at least T; not with --cumulative, whose
 // displacement lives on frame 0's grid and the zncc on the pair's.
+// --validate MODE (same conditions and the same source as --strain) runs the normalised median test on that displacement on the device
+// (f3d_validate_displacement: every vector against the median of its up to 26 neighbours --validate-step voxels away, default 1, in
+// units of their median residual plus --validate-eps, default 0.1) and sets what exceeds --validate-threshold (default 2; tested with
+// at least --validate-min-neighbours neighbours, default 9) to NaN (mark) or to the neighbour median (replace).  --validate-min-zncc Z
+// also rejects the voxels whose zncc of --match is below Z (conditions of --detrend-min-zncc); --validate-fill N runs up to N further
+// passes that give undefined voxels the median of their defined neighbours.  <tag>_validated-{r,u,v,w}-W-H-D.raw and one line per pair.
+// --use-validated makes --strain, --principal and --detrend take the validated displacement in place of the raw one; the validated
+// field is then computed before them, and after the match.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -65,7 +75,9 @@ static void Usage()
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
               "              [--concurrent N] [--cumulative] [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
               "              [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
-              "              [--detrend translation|rigid|affine [--detrend-min-zncc T]]\n");
+              "              [--detrend translation|rigid|affine [--detrend-min-zncc T]]\n"
+              "              [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]\n"
+              "               [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]\n");
 }
 
 int main(int argc, char** argv)
@@ -86,6 +98,11 @@ int main(int argc, char** argv)
   int detrend_model = -1;         // --detrend: F3D_MOTION_*
   float detrend_min_zncc = std::nanf("");  // --detrend-min-zncc; NaN: no mask
   bool detrend_min_given = false;
+  unsigned validate_mode = 0;     // --validate: F3D_VALIDATE_MARK / F3D_VALIDATE_REPLACE
+  unsigned validate_step = 1, validate_min_neighbours = 9, validate_fill = 0;
+  float validate_threshold = 2.0f, validate_eps = 0.1f;
+  float validate_min_zncc = std::nanf("");  // --validate-min-zncc; NaN: no mask
+  bool validate_min_given = false, validate_sub_given = false, use_validated = false;
   const unsigned inverse_iterations = 32;
   const float inverse_tolerance = 1e-3f;
 
@@ -203,6 +220,48 @@ int main(int argc, char** argv)
       if (rest == argv[i] || *rest || std::isnan(detrend_min_zncc)) { Usage(); return 64; }
       detrend_min_given = true;
     }
+    else if (a == "--validate") {
+      need(1);
+      const std::string mode = argv[++i];
+      if (mode == "mark") validate_mode = F3D_VALIDATE_MARK;
+      else if (mode == "replace") validate_mode = F3D_VALIDATE_REPLACE;
+      else { Usage(); return 64; }
+    }
+    else if (a == "--validate-step" || a == "--validate-min-neighbours" || a == "--validate-fill") {
+      need(1);
+      char* rest = nullptr;
+      const unsigned long n = std::strtoul(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest || argv[i][0] == '-') { Usage(); return 64; }
+      if (a == "--validate-step") {
+        if (n < 1 || n > 16) { Usage(); return 64; }
+        validate_step = static_cast<unsigned>(n);
+      } else if (a == "--validate-min-neighbours") {
+        if (n < 1 || n > 26) { Usage(); return 64; }
+        validate_min_neighbours = static_cast<unsigned>(n);
+      } else {
+        if (n > 1000) { Usage(); return 64; }
+        validate_fill = static_cast<unsigned>(n);
+      }
+      validate_sub_given = true;
+    }
+    else if (a == "--validate-threshold" || a == "--validate-eps" || a == "--validate-min-zncc") {
+      need(1);
+      char* rest = nullptr;
+      const float x = std::strtof(argv[++i], &rest);
+      if (rest == argv[i] || *rest || std::isnan(x)) { Usage(); return 64; }
+      if (a == "--validate-threshold") {
+        if (x < 0.f) { Usage(); return 64; }
+        validate_threshold = x;
+      } else if (a == "--validate-eps") {
+        if (!(x > 0.f) || std::isinf(x)) { Usage(); return 64; }
+        validate_eps = x;
+      } else {
+        validate_min_zncc = x;
+        validate_min_given = true;
+      }
+      validate_sub_given = true;
+    }
+    else if (a == "--use-validated") use_validated = true;
     else { Usage(); return 64; }
   }
   if (width == 0 || height == 0 || depth == 0 || (!synthetic && files.size() < 2)) {
@@ -256,6 +315,24 @@ int main(int argc, char** argv)
   if (detrend_min_given && (cumulative || !(match_fields & OpticalFlowE::kMatchZncc))) {
     std::printf(cumulative ? "--detrend-min-zncc cannot be combined with --cumulative: the zncc of --match lives on the pair's grid\n"
                            : "--detrend-min-zncc needs --match with zncc in its list\n");
+    Usage();
+    return 64;
+  }
+  if ((validate_sub_given || use_validated) && !validate_mode) {
+    std::printf(use_validated ? "--use-validated needs --validate\n" : "--validate-step, -threshold, -eps, -min-neighbours, -fill and "
+                                                                       "-min-zncc need --validate\n");
+    Usage();
+    return 64;
+  }
+  if (validate_mode && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--validate needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if (validate_min_given && (cumulative || !(match_fields & OpticalFlowE::kMatchZncc))) {
+    std::printf(cumulative ? "--validate-min-zncc cannot be combined with --cumulative: the zncc of --match lives on the pair's grid\n"
+                           : "--validate-min-zncc needs --match with zncc in its list\n");
     Usage();
     return 64;
   }
@@ -454,6 +531,7 @@ int main(int argc, char** argv)
   static const char* const match_names[3] = {"warped", "zncc", "rmsd"};
   static const char* const motion_names[3] = {"u", "v", "w"};
   static const char* const motion_models[3] = {"translation", "rigid", "affine"};
+  static const char* const validated_names[4] = {"r", "u", "v", "w"};
   const size_t voxels = width * height * depth;
   f3d_strain_stats strain_stats = {};
   f3d_principal_stats principal_stats = {};
@@ -461,9 +539,18 @@ int main(int argc, char** argv)
   f3d_correlation_stats match_stats = {};
   f3d_motion_fit motion_fit = {};
   f3d_motion_residual motion_residual = {};
-  DerivedField derived[5] = {
+  f3d_validate_stats validate_stats = {};
+  // --use-validated: what --strain, --principal and --detrend are computed of
+  auto validated_or = [&](const OpticalFlowE::Displacement& of) {
+    if (!use_validated) return of;
+    const DevicePtr d[3] = {optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 1),
+                            optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 2),
+                            optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 3)};
+    return OpticalFlowE::Containers(d);
+  };
+  DerivedField derived[6] = {
       {"strain", OpticalFlowE::kStrain, strain_fields, strain_names, false,
-       [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputeStrain(of, strain_fields, &strain_stats); },
+       [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputeStrain(validated_or(of), strain_fields, &strain_stats); },
        [&](size_t k) {
          const f3d_strain_stats& st = strain_stats;
          const double mean = st.defined ? st.vol_sum / static_cast<double>(st.defined) : std::nan("");
@@ -472,7 +559,7 @@ int main(int argc, char** argv)
                      static_cast<unsigned long long>(voxels) - st.defined, voxels);
        }},
       {"principal", OpticalFlowE::kPrincipal, principal_fields, principal_names, false,
-       [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputePrincipal(of, principal_fields, &principal_stats); },
+       [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputePrincipal(validated_or(of), principal_fields, &principal_stats); },
        [&](size_t k) {
          const f3d_principal_stats& st = principal_stats;
          std::printf("principal frame %zu -> frame %zu: e1 max %.6g, e3 min %.6g, shear max %.6g, %llu undefined of %zu voxels\n",
@@ -506,7 +593,7 @@ int main(int argc, char** argv)
       {"detrended", OpticalFlowE::kMotion, detrend_model >= 0 ? 1u : 0u, motion_names, false,
        [&](const OpticalFlowE::Displacement& of) {
          const DevicePtr mask = detrend_min_given ? optical_flow_e.DerivedContainer(OpticalFlowE::kMatch, 1) : 0;
-         return optical_flow_e.ComputeMotion(of, detrend_model, mask, detrend_min_zncc, &motion_fit, &motion_residual);
+         return optical_flow_e.ComputeMotion(validated_or(of), detrend_model, mask, detrend_min_zncc, &motion_fit, &motion_residual);
        },
        [&](size_t k) {
          const f3d_motion_fit& f = motion_fit;
@@ -525,7 +612,28 @@ int main(int argc, char** argv)
          }
          const double after = r.present ? std::sqrt(r.sum_sq / static_cast<double>(r.present)) : std::nan("");
          std::printf("rms %.6g -> %.6g, max |res| %.6g, %llu of %zu voxels\n", f.rms_before, after, r.max_abs, f.n, voxels);
+       }},
+      // after the match for the same reason; with --use-validated before the fields that are computed of it (`order` below)
+      {"validated", OpticalFlowE::kValidated, validate_mode ? F3D_VALIDATE_R | F3D_VALIDATE_D : 0u, validated_names, false,
+       [&](const OpticalFlowE::Displacement& of) {
+         const DevicePtr mask = validate_min_given ? optical_flow_e.DerivedContainer(OpticalFlowE::kMatch, 1) : 0;
+         return optical_flow_e.ComputeValidated(of, mask, validate_min_zncc, validate_step, validate_eps, validate_threshold,
+                                                validate_min_neighbours, validate_mode, validate_fill,
+                                                F3D_VALIDATE_R | F3D_VALIDATE_D, &validate_stats);
+       },
+       [&](size_t k) {
+         const f3d_validate_stats& st = validate_stats;
+         std::printf("validate frame %zu -> frame %zu (%s, step %u): %llu tested, %llu outliers, %llu replaced, %llu undefined, r max %.6g "
+                     "of %zu voxels\n", cumulative ? size_t(0) : k, k + 1, validate_mode == F3D_VALIDATE_MARK ? "mark" : "replace",
+                     validate_step, st.tested, st.outliers, st.replaced, st.undefined, st.r_max, voxels);
        }}};
+  // the order in which the features run and their files and lines come out: as listed, or with --use-validated the match (whose zncc
+  // may be the mask) and the validated field first
+  DerivedField* order[6] = {&derived[0], &derived[1], &derived[2], &derived[3], &derived[4], &derived[5]};
+  if (use_validated) {
+    DerivedField* const first[6] = {&derived[3], &derived[5], &derived[0], &derived[1], &derived[2], &derived[4]};
+    for (int i = 0; i < 6; ++i) order[i] = first[i];
+  }
   for (DerivedField& f : derived)
     for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)
       if (OpticalFlowE::DerivedSelected(f.which, i, f.fields)) {
@@ -552,7 +660,8 @@ int main(int argc, char** argv)
         return 3;
       write_disp(0);
     }
-    for (DerivedField& f : derived) {
+    for (DerivedField* fp : order) {
+      DerivedField& f = *fp;
       if (!f.fields) continue;
       if (!f.compute(cumulative && !f.of_pair ? OpticalFlowE::Trajectory() : OpticalFlowE::HeldFlow()) ||
           !optical_flow_e.DownloadDerived(f.which, f.out, f.fields))
@@ -639,8 +748,8 @@ int main(int argc, char** argv)
         optical_flow_e.GiveResultBack(taken);
         write_pair(k - 1, host_flow[(k - 1) & 1][0], host_flow[(k - 1) & 1][1], host_flow[(k - 1) & 1][2]);
         if (cumulative) write_disp(k - 1);
-        for (DerivedField& f : derived)
-          if (f.fields) write_derived(f, k - 1);
+        for (DerivedField* f : order)
+          if (f->fields) write_derived(*f, k - 1);
         pending_output = false;
       }
       optical_flow_e.EndComputeFlowResident();
@@ -660,7 +769,8 @@ int main(int argc, char** argv)
                                                   optical_flow_e.TrajectoryContainer(i), c.pitch, c.height, 0));
         CheckDeviceError(f3d_event_record_on(disp_down, down));
       }
-      for (DerivedField& f : derived) {
+      for (DerivedField* fp : order) {
+        DerivedField& f = *fp;
         if (!f.fields) continue;
         if (k > 0) CheckDeviceError(f3d_queue_wait_event(nullptr, f.down));
         if (!f.compute(cumulative && !f.of_pair ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return 3;
@@ -682,7 +792,8 @@ int main(int argc, char** argv)
       f3d_event_destroy(composed);
       f3d_event_destroy(disp_down);
     }
-    for (DerivedField& f : derived) {
+    for (DerivedField* fp : order) {
+      DerivedField& f = *fp;
       if (!f.fields) continue;
       write_derived(f, pairs - 1);
       f3d_event_destroy(f.done);

@@ -35,6 +35,10 @@ extern "C" int f3d_motion_sums(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_dev
 extern "C" int f3d_remove_motion(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr out_u, f3d_devptr out_v, f3d_devptr out_w,
                                  const f3d_motion_fit* fit, size_t width, size_t height, size_t depth, f3d_motion_residual* stats)
     __attribute__((weak));
+extern "C" int f3d_validate_displacement(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr weight, float weight_min, unsigned step,
+                                         float eps, float threshold, unsigned min_neighbours, unsigned mode, const f3d_devptr out[4],
+                                         unsigned fields, size_t width, size_t height, size_t depth, f3d_validate_stats* stats)
+    __attribute__((weak));
 
 // ---- base --------------------------------------------------------------------------------------------------
 
@@ -98,8 +102,14 @@ const unsigned kPrincipalGroups[10] = {F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_VALUE
 const unsigned kPrincipalAll = F3D_PRINCIPAL_VALUES | F3D_PRINCIPAL_SHEAR | F3D_PRINCIPAL_DIR1 | F3D_PRINCIPAL_DIR3;
 const unsigned kMatchGroups[3] = {OpticalFlowE::kMatchWarped, OpticalFlowE::kMatchZncc, OpticalFlowE::kMatchRmsd};
 const unsigned kMatchAll = OpticalFlowE::kMatchWarped | OpticalFlowE::kMatchZncc | OpticalFlowE::kMatchRmsd;
-const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3};
-const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr, kMatchGroups, nullptr};
+// r, u, v, w, and the second u, v, w the fill passes alternate with (a bit of its own, never downloaded)
+const unsigned kValidatedSpare = 4u;
+const int kValidatedContainers = 7;
+const unsigned kValidatedGroups[kValidatedContainers] = {F3D_VALIDATE_R, F3D_VALIDATE_D, F3D_VALIDATE_D, F3D_VALIDATE_D,
+                                                         kValidatedSpare,  kValidatedSpare,  kValidatedSpare};
+const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3, 4};
+const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr,
+                                                                     kMatchGroups,  nullptr,          kValidatedGroups};
 const char* const kTrajectoryNotStarted = "the trajectory was not started (ResetTrajectory first)";
 
 }  // namespace
@@ -123,7 +133,12 @@ OpticalFlowE::OpticalFlowE()
                 "the device library has no f3d_local_correlation (match quality)", "no displacement to carry frame 1 through"},
                {this, kDerivedFields[kMotion], nullptr, "the motion residual containers do not fit beside the driver's on the device",
                 "the motion residual has not been computed", "no host volume for a motion residual field",
-                "the device library has no f3d_motion_sums (motion fit)", "no displacement to fit a motion to"}}
+                "the device library has no f3d_motion_sums (motion fit)", "no displacement to fit a motion to"},
+               {this, kValidatedContainers, kValidatedGroups,
+                "the validated displacement's containers do not fit beside the driver's on the device",
+                "a requested field of the validated displacement has not been computed",
+                "no host volume for a requested field of the validated displacement",
+                "the device library has no f3d_validate_displacement (displacement validation)", "no displacement to validate"}}
 {
   // same initialisation order as the reference's forward_list built with push_front (optical_flow_e.cpp:34-39)
   cuda_operations_ = {&cuop_solve_, &cuop_resample_, &cuop_register_, &cuop_median_, &cuop_convolution_, &cuop_add_};
@@ -664,6 +679,42 @@ bool OpticalFlowE::ComputeMotion(const Displacement& of, int model, DevicePtr we
                                                     c.depth, residual))))
     return false;
   *fit = solved;
+  return true;
+}
+
+bool OpticalFlowE::ComputeValidated(const Displacement& of, DevicePtr weight, float weight_min, unsigned step, float eps,
+                                    float threshold, unsigned min_neighbours, unsigned mode, unsigned fill_passes, unsigned fields,
+                                    f3d_validate_stats* stats)
+{
+  FieldSet& set = derived_[kValidated];
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, f3d_validate_displacement != nullptr, d)) return false;
+  if (fields == 0 || (fields & ~(F3D_VALIDATE_R | F3D_VALIDATE_D)))
+    return set.Fail("fields must be a non-empty combination of F3D_VALIDATE_R, F3D_VALIDATE_D");
+  if (fill_passes && !(fields & F3D_VALIDATE_D)) return set.Fail("fill passes need the validated displacement (F3D_VALIDATE_D)");
+  if (!set.Allocate(fields | (fill_passes ? kValidatedSpare : 0u))) return false;
+  const f3d_size4 c = Container();
+  f3d_validate_stats first = {};
+  if (!set.Check(CheckDeviceError(f3d_set_container(&c))) ||
+      !set.Check(CheckDeviceError(f3d_validate_displacement(d[0], d[1], d[2], weight, weight_min, step, eps, threshold, min_neighbours,
+                                                            mode, set.ptr, fields, c.width, c.height, c.depth,
+                                                            stats || fill_passes ? &first : nullptr))))
+    return false;
+  // the fill: no weight, nothing is an outlier, absent voxels with enough present neighbours receive their median
+  for (unsigned pass = 0; pass < fill_passes && first.undefined; ++pass) {
+    const DevicePtr out[4] = {0, set.ptr[4], set.ptr[5], set.ptr[6]};
+    f3d_validate_stats filled = {};
+    if (!set.Check(CheckDeviceError(f3d_validate_displacement(set.ptr[1], set.ptr[2], set.ptr[3], 0, 0.f, step, eps, INFINITY,
+                                                              min_neighbours, F3D_VALIDATE_REPLACE, out, F3D_VALIDATE_D, c.width,
+                                                              c.height, c.depth, &filled))))
+      return false;
+    for (int i = 1; i <= 3; ++i) std::swap(set.ptr[i], set.ptr[i + 3]);
+    const bool fell = filled.undefined < first.undefined;
+    first.replaced += filled.replaced;
+    first.undefined = filled.undefined;
+    if (!fell) break;
+  }
+  if (stats) *stats = first;
   return true;
 }
 

@@ -128,10 +128,12 @@ class OpticalFlowE : public OpticalFlowBase {
   //               is downloaded only when selected.
   //   kMotion     f3d_motion_sums, the host solve (motion_fit.h) and f3d_remove_motion: the displacement with its best translation,
   //               rigid motion or affine map taken out.  Three outputs, the residual u, v, w, always all of them.
+  //   kValidated  f3d_validate_displacement: the normalised median test and the repair of what it rejects.  Four outputs r, u, v, w
+  //               selected by F3D_VALIDATE_R (r) and F3D_VALIDATE_D (u, v, w); the fill passes keep a second u, v, w beside them.
   // Each selected output gets a container of its own, allocated on first use and freed by ReleaseDerived() and Destroy().  Compute
   // enqueues on the library stream and waits only when stats is given.  Every call returns false with DerivedError() set when it
   // cannot run -- among other reasons when the device library lacks the entry point.
-  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kDerivedCount };
+  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kValidated, kDerivedCount };
   enum MatchField : unsigned { kMatchWarped = 1u, kMatchZncc = 2u, kMatchRmsd = 4u };
   // the displacement a derived field is computed of
   struct Displacement {
@@ -153,6 +155,15 @@ class OpticalFlowE : public OpticalFlowBase {
   // the subtraction and waits again only when residual is given.  fit (required) receives the fit with its centre.
   bool ComputeMotion(const Displacement& of, int model, DevicePtr weight, float weight_min, f3d_motion_fit* fit,
                      f3d_motion_residual* residual);
+  // weight / weight_min as in ComputeMotion; step, eps, threshold, min_neighbours, mode (F3D_VALIDATE_MARK / _REPLACE) and fields
+  // (F3D_VALIDATE_R | F3D_VALIDATE_D) as in include/f3d.h.  fill_passes (needs F3D_VALIDATE_D): after the first call up to that many
+  // further calls on its own output with threshold +inf, no weight and F3D_VALIDATE_REPLACE, between two container sets: each gives
+  // the absent voxels with enough present neighbours their median; they stop when no voxel is undefined or the count stops falling,
+  // and they wait for the stream.  stats (nullable) are those of the first call with replaced and undefined brought to the final
+  // state; r is that of the first call.  DerivedContainer(kValidated, 1 .. 3) is the validated displacement afterwards, which
+  // Containers() hands to the strain, principal strain and motion calls.
+  bool ComputeValidated(const Displacement& of, DevicePtr weight, float weight_min, unsigned step, float eps, float threshold,
+                        unsigned min_neighbours, unsigned mode, unsigned fill_passes, unsigned fields, f3d_validate_stats* stats);
   static int DerivedFieldCount(Derived which);
   static bool DerivedSelected(Derived which, int field, unsigned fields);
   DevicePtr DerivedContainer(Derived which, int field) const { return derived_[which].ptr[field]; }  // 0 until computed

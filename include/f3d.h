@@ -691,6 +691,52 @@ int f3d_remove_motion(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr out_u
                       const f3d_motion_fit* fit, size_t width, size_t height, size_t depth,
                       f3d_motion_residual* stats /* nullable; non-null waits */);
 
+/* Validation of a displacement (no reference counterpart: the normalised median test of PIV and volume-correlation post-processing,
+ * Westerweel & Scarano 2005, which a workflow applies between the displacement and the strain).  A vector is compared with the median
+ * of its neighbours, scaled by the median residual of those neighbours; a rejected vector becomes NaN (which f3d_flow_strain and
+ * f3d_principal_strain treat as a missing sample) or the neighbour median.  Nothing is smoothed: a voxel is kept bit for bit, set to
+ * NaN, or replaced by a median of input values.  Every operation is float32 and rounded on its own.
+ *
+ * Presence is f3d_motion_sums': a voxel is present when it is inside the volume, none of u, v, w is NaN there and, when weight is
+ * not 0, weight[i] >= weight_min (a NaN weight fails the comparison).
+ * Neighbours of voxel p are the up to 26 points p + step * (i, j, k), (i, j, k) in {-1, 0, 1}^3 without (0, 0, 0), that lie inside
+ * the volume and are present; there is no mirroring.  k is their number.  (The dense flow is smooth at the scale of a voxel and its
+ * errors are blobs, so the neighbours are taken step voxels away; step = 1 is the classic test.)
+ * The median of k >= 1 values s_0 <= ... <= s_{k-1} is s_{(k-1)/2} for odd k and 0.5f * (s_{k/2-1} + s_{k/2}) for even k.
+ * Per component c of d = (u, v, w):
+ *   med_c = the median of the neighbours' d_c;  rm_c = the median of fabsf(n_c - med_c) over the same neighbours;
+ *   r_c = fabsf(d_c - med_c) / (rm_c + eps), IEEE division;   r = fmaxf(fmaxf(r_u, r_v), r_w).
+ * Classes: tested = present and k >= min_neighbours; outlier = tested and r > threshold; kept = present and not an outlier (a present
+ * voxel with too few neighbours is kept, untested); every other voxel is rejected: the outliers and the absent voxels, those absent
+ * only by the weight included (this is how a zncc mask is applied).  threshold = +inf is accepted: nothing is an outlier, and the call
+ * only fills absent voxels.
+ *   out[0]     (F3D_VALIDATE_R)  r where tested, NaN elsewhere
+ *   out[1..3]  (F3D_VALIDATE_D)  a kept voxel bit for bit; a rejected voxel NaN in all three under F3D_VALIDATE_MARK; under
+ *              F3D_VALIDATE_REPLACE (med_u + 0.f, med_v + 0.f, med_w + 0.f) when k >= min_neighbours and NaN in all three otherwise.
+ *              The + 0.f stores a zero median as +0: which of several zeros of mixed sign is the middle one is not defined, and
+ *              nothing else depends on that sign.  One Jacobi pass: the medians are of the input, an outlier neighbour still votes.
+ * stats (nullable; asking waits for the stream): present, tested, outliers count the classes; replaced counts rejected voxels that
+ * received a median (0 under MARK); undefined counts voxels whose validated u is NaN (whether or not D is stored); r_max is the exact
+ * maximum of r over the tested voxels, NaN when there are none.  They are combined in the fixed order of the other statistics (the
+ * xor butterfly over the 64 x of a wave, the 4 rows of a workgroup, the fold of the workgroup partials), no float atomics: the same
+ * input gives the same bytes.  Infinite inputs are outside the definition.
+ * Geometry from the current container (f3d_set_container), whole volume, library stream.  Refused (status 1, a message, nothing
+ * written): a null u, v or w; a null selected output; fields 0 or with unknown bits; an unknown mode; step outside 1 .. 16;
+ * min_neighbours outside 1 .. 26; eps NaN, infinite or not above 0; threshold NaN or negative; a NaN weight_min when a weight is
+ * given; a selected output that is also an input (the weight included) or the container of another selected output; an empty size. */
+#define F3D_VALIDATE_R 1u       /* out[0]      r, the normalised residual            */
+#define F3D_VALIDATE_D 2u       /* out[1..3]   the validated u, v, w                 */
+#define F3D_VALIDATE_MARK 1u    /* rejected voxels become NaN                        */
+#define F3D_VALIDATE_REPLACE 2u /* rejected voxels become the neighbour median       */
+typedef struct f3d_validate_stats {
+  unsigned long long present, tested, outliers, replaced, undefined;
+  float r_max;
+} f3d_validate_stats;
+int f3d_validate_displacement(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr weight /* 0: none */, float weight_min,
+                              unsigned step, float eps, float threshold, unsigned min_neighbours, unsigned mode,
+                              const f3d_devptr out[4], unsigned fields, size_t width, size_t height, size_t depth,
+                              f3d_validate_stats* stats /* nullable; non-null waits */);
+
 #ifdef __cplusplus
 }
 #endif

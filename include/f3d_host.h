@@ -163,6 +163,21 @@ int f3d_motion_solve(const struct f3d_motion_sums* sums, int model, f3d_motion_f
 int f3d_flow_motion_compute(f3d_flow flow, int source, int model, float min_zncc, float* const out[3], f3d_motion_fit* fit,
                             f3d_motion_residual* residual);
 int f3d_flow_motion_end(f3d_flow flow);
+
+/* Validation of the flow the driver holds or of the trajectory (source F3D_STRAIN_OF_FLOW / F3D_STRAIN_OF_TRAJECTORY):
+ * f3d_validate_displacement (include/f3d.h has the definition and what step, eps, threshold, min_neighbours and mode mean) into
+ * containers the driver keeps until f3d_flow_validate_end (or f3d_flow_destroy).  out[0] receives r, out[1..3] the validated u, v, w
+ * (width * height * depth floats each); a null out[0] leaves r out, null out[1..3] (all three or none) the displacement; at least one
+ * of the two is required.  fill_passes (needs out[1..3]): up to that many further passes over the result with threshold +inf, no mask
+ * and F3D_VALIDATE_REPLACE, each of which gives the undefined voxels with at least min_neighbours defined neighbours their median;
+ * they stop when no voxel is undefined or the count stops falling.  stats (nullable) are those of the first pass with replaced and
+ * undefined brought to the final state.  min_zncc is f3d_flow_motion_compute's: NaN for no mask; otherwise voxels whose zncc in the
+ * last f3d_flow_match_compute of the same pair is below it (or NaN) are absent -- rejected themselves and no neighbour of anyone; the
+ * call fails with a message when that zncc is not there, and when source is the trajectory.  A device library without
+ * f3d_validate_displacement still loads; then the call fails with a message naming the entry. */
+int f3d_flow_validate_compute(f3d_flow flow, int source, unsigned step, float eps, float threshold, unsigned min_neighbours,
+                              unsigned mode, unsigned fill_passes, float min_zncc, float* const out[4], f3d_validate_stats* stats);
+int f3d_flow_validate_end(f3d_flow flow);
 /* message of this thread's last call that failed in the host library itself; f3d_last_error() when there is none */
 const char* f3d_host_last_error(void);
 int f3d_flow_destroy(f3d_flow flow);
