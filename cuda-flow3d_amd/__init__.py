@@ -58,6 +58,14 @@ class PrincipalStats(C.Structure):  # f3d_principal_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PolarStats(C.Structure):  # f3d_polar_stats
+    _fields_ = [("defined", C.c_ulonglong), ("folded", C.c_ulonglong), ("theta_max", C.c_float), ("l1_max", C.c_float),
+                ("l3_min", C.c_float), ("theta_sum", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class InverseStats(C.Structure):  # f3d_inverse_stats
     _fields_ = [("defined", C.c_ulonglong), ("unconverged", C.c_ulonglong), ("steps_sum", C.c_ulonglong), ("err_max", C.c_float)]
 
@@ -281,6 +289,8 @@ def host():
         "f3d_flow_strain_end": [C.c_void_p],
         "f3d_flow_principal_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(PrincipalStats)],
         "f3d_flow_principal_end": [C.c_void_p],
+        "f3d_flow_polar_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(PolarStats)],
+        "f3d_flow_polar_end": [C.c_void_p],
         "f3d_flow_inverse_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_float, C.POINTER(_fp), C.POINTER(InverseStats)],
         "f3d_flow_inverse_end": [C.c_void_p],
         "f3d_flow_match_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_float, C.POINTER(_fp), C.POINTER(CorrelationStats)],
@@ -419,6 +429,11 @@ def _principal_entry():
                   "compute principal strains")
 
 
+def _polar_entry():
+    return _entry("f3d_polar_decomposition", [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(PolarStats)],
+                  "compute local rotations and stretches")
+
+
 def _inverse_entry():
     return _entry("f3d_invert_displacement", [_dp] * 7 + [_sz] * 3 + [C.c_uint, C.c_float, C.POINTER(InverseStats)],
                   "invert displacements")
@@ -514,6 +529,10 @@ _STRAIN_GROUP_OF = (1, 2, 2, 2, 2, 2, 2, 4)
 PRINCIPAL_NAMES = ("e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z")
 PRINCIPAL_GROUPS = {"val": 1, "shear": 2, "dir1": 4, "dir3": 8}
 _PRINCIPAL_GROUP_OF = (1, 1, 1, 2, 4, 4, 4, 8, 8, 8)
+# the seven outputs of f3d_polar_decomposition in ABI order, and the F3D_POLAR_* group of each
+POLAR_NAMES = ("theta", "rx", "ry", "rz", "l1", "l2", "l3")
+POLAR_GROUPS = {"angle": 1, "vector": 2, "stretch": 4}
+_POLAR_GROUP_OF = (1, 2, 2, 2, 4, 4, 4)
 # the four outputs of f3d_invert_displacement in ABI order, and the modes of f3d_carry_field
 INVERSE_NAMES = ("gu", "gv", "gw", "err")
 CARRY_MODES = {"linear": 1, "nearest": 2}
@@ -557,6 +576,10 @@ def _principal_mask(fields):
     return _mask(fields, PRINCIPAL_GROUPS, "principal strain")
 
 
+def _polar_mask(fields):
+    return _mask(fields, POLAR_GROUPS, "rotation")
+
+
 def _carry_mode(mode):
     if mode not in CARRY_MODES:
         raise ValueError(f"unknown carry mode {mode!r} (one of {', '.join(CARRY_MODES)})")
@@ -564,8 +587,8 @@ def _carry_mode(mode):
 
 
 def _grouped_fields(fn, what, u, v, w, mask, names, group_of, stats):
-    """f3d_flow_strain / f3d_principal_strain of (u, v, w) from anywhere: a dict name -> array of the outputs `mask` selects,
-    plus "stats" -> dict"""
+    """f3d_flow_strain / f3d_principal_strain / f3d_polar_decomposition of (u, v, w) from anywhere: a dict name -> array of the
+    outputs `mask` selects, plus "stats" -> dict"""
     with _on_device((u, v, w), "u, v and w must be three [z, y, x] volumes of one shape") as (box, p, dims):
         outs = [box.alloc() if mask & g else 0 for g in group_of]
         box.set_current()
@@ -592,6 +615,16 @@ def principal_strain(u, v, w, fields=("val", "shear")):
     fn = _principal_entry()
     return _grouped_fields(fn, "f3d_principal_strain", u, v, w, _principal_mask(fields), PRINCIPAL_NAMES, _PRINCIPAL_GROUP_OF,
                            PrincipalStats())
+
+
+def polar_decomposition(u, v, w, fields=("angle", "vector", "stretch")):
+    """Local rotation and principal stretches of a displacement on the device (include/f3d.h, f3d_polar_decomposition) for volumes
+    from anywhere: u, v, w numpy [z, y, x] float32 in voxel units.  fields: groups "angle" (theta, radians, of the R of F = R U),
+    "vector" (the rotation vector theta * axis as rx ry rz), "stretch" (l1 >= l2 >= l3, the principal stretches; np.log of them
+    are the Hencky strains).  Returns a dict name -> array for the selected outputs (NaN where the voxel is undefined or folded)
+    and "stats" -> dict (defined, folded, theta_max, l1_max, l3_min, theta_sum)."""
+    fn = _polar_entry()
+    return _grouped_fields(fn, "f3d_polar_decomposition", u, v, w, _polar_mask(fields), POLAR_NAMES, _POLAR_GROUP_OF, PolarStats())
 
 
 def invert_displacement(u, v, w, iterations=32, tolerance=1e-3):
@@ -1218,7 +1251,7 @@ class OpticalFlow:
     def trajectory_end(self):
         _host_check(host().f3d_flow_trajectory_end(self._h), "f3d_flow_trajectory_end")
 
-    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_{strain,principal,inverse,match,motion,validate}_*) ----
+    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_{strain,principal,polar,inverse,match,motion,validate}_*) ----
     def _derived(self, compute, src, selected, stats, *args, fit=None):
         """one f3d_flow_*_compute into fresh host arrays: a list with an array per selected output and None for the others
         (fit: the MotionFit f3d_flow_motion_compute takes between the arrays and the statistics)"""
@@ -1256,6 +1289,20 @@ class OpticalFlow:
     def principal_end(self):
         """free the principal strain containers (destroy() does too)"""
         _host_check(host().f3d_flow_principal_end(self._h), "f3d_flow_principal_end")
+
+    def rotation(self, source="flow", fields=("angle", "vector", "stretch")):
+        """Local rotation and principal stretches of the flow the driver holds (source="flow", after compute_resident) or of the
+        trajectory (source="trajectory", after trajectory_begin); same result shape as polar_decomposition().  Works between the
+        yields of compute_sequence, where the driver holds both."""
+        src, mask, stats = _source(source), _polar_mask(fields), PolarStats()
+        arrays = self._derived("f3d_flow_polar_compute", src, [mask & g for g in _POLAR_GROUP_OF], stats, mask)
+        res = {n: a for n, a in zip(POLAR_NAMES, arrays) if a is not None}
+        res["stats"] = stats.as_dict()
+        return res
+
+    def rotation_end(self):
+        """free the rotation and stretch containers (destroy() does too)"""
+        _host_check(host().f3d_flow_polar_end(self._h), "f3d_flow_polar_end")
 
     def inverse(self, source="flow", iterations=32, tolerance=1e-3):
         """The inverse displacement of the flow the driver holds (source="flow", after compute_resident) or of the trajectory

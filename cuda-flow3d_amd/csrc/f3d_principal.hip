@@ -10,14 +10,13 @@
 // volume and lanes of undefined voxels diagonalise the zero matrix and never hold their wave back.
 //
 // Statistics (optional): one partial per workgroup, folded in a fixed order by a one-workgroup kernel (f3d_partials.h).
+#include "f3d_jacobi3.h"
 #include "f3d_strain_grad.h"
 
 namespace {
 
 using namespace f3d_strain;
 using namespace f3d_partials;
-
-constexpr int kSweeps = 5;
 
 struct PrincipalPartial {
   unsigned long long defined;
@@ -36,33 +35,6 @@ struct PrincipalPartial {
 struct PrincipalOut {
   float* f[10];  // e1, e2, e3, gmax, d1x, d1y, d1z, d3x, d3y, d3z (null = not stored)
 };
-
-// include/f3d.h, f3d_principal_strain, rule 2: the rotation of the pair (p, q) with r the third index; vp / vq: columns p and q of V
-template <bool DIRS>
-__device__ __forceinline__ void rotate(float& app, float& aqq, float& apq, float& arp, float& arq, float (&vp)[3], float (&vq)[3])
-{
-  if (apq == 0.f) return;
-  const float theta = (aqq - app) / (2.f * apq);
-  float t = 1.f / (fabsf(theta) + sqrtf(theta * theta + 1.f));
-  if (theta < 0.f) t = -t;
-  const float c = 1.f / sqrtf(t * t + 1.f);
-  const float s = t * c;
-  const float h = t * apq;
-  app = app - h;
-  aqq = aqq + h;
-  apq = 0.f;
-  const float rp = arp, rq = arq;
-  arp = c * rp - s * rq;
-  arq = s * rp + c * rq;
-  if (DIRS) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float kp = vp[k], kq = vq[k];
-      vp[k] = c * kp - s * kq;
-      vq[k] = s * kp + c * kq;
-    }
-  }
-}
 
 // rule 3: value and column exchanged together when the first is strictly smaller
 template <bool DIRS>
@@ -118,13 +90,7 @@ __global__ __launch_bounds__(kBX* kBY) void k_principal_strain(const float* __re
     if (!def) a00 = a11 = a22 = a01 = a02 = a12 = 0.f;  // NaN in every output below; nothing to rotate meanwhile
     float v0[3] = {1.f, 0.f, 0.f}, v1[3] = {0.f, 1.f, 0.f}, v2[3] = {0.f, 0.f, 1.f};  // the columns of V
 
-    for (int sweep = 0; sweep < kSweeps; ++sweep) {
-      // rule 2: a sweep over three zero off-diagonals is the identity, so once that holds in every lane the rest can go
-      if (__ballot(a01 != 0.f || a02 != 0.f || a12 != 0.f) == 0) break;
-      rotate<DIRS>(a00, a11, a01, a02, a12, v0, v1);  // (0, 1), r = 2
-      rotate<DIRS>(a00, a22, a02, a01, a12, v0, v2);  // (0, 2), r = 1
-      rotate<DIRS>(a11, a22, a12, a01, a02, v1, v2);  // (1, 2), r = 0
-    }
+    f3d_jacobi3::sweeps<DIRS>(a00, a11, a22, a01, a02, a12, v0, v1, v2);  // rule 2
 
     order<DIRS>(a00, a11, v0, v1);
     order<DIRS>(a00, a22, v0, v2);

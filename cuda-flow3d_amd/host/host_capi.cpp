@@ -297,6 +297,15 @@ int f3d_flow_principal_compute(f3d_flow flow, int source, unsigned fields, float
 
 int f3d_flow_principal_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kPrincipal, "f3d_flow_principal_end: null driver"); }
 
+int f3d_flow_polar_compute(f3d_flow flow, int source, unsigned fields, float* const out[7], f3d_polar_stats* stats)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out != nullptr, "f3d_flow_polar_compute", &of)) return 1;
+  return DerivedDownload(flow, OpticalFlowE::kPolar, flow->driver.ComputePolar(of, fields, stats), out, fields);
+}
+
+int f3d_flow_polar_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kPolar, "f3d_flow_polar_end: null driver"); }
+
 int f3d_flow_inverse_compute(f3d_flow flow, int source, unsigned iterations, float tolerance, float* const out[4],
                              f3d_inverse_stats* stats)
 {

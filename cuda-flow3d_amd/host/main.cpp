@@ -5,7 +5,8 @@
 // flags:  flow3d --dims W H D --frames f0.raw f1.raw [f2.raw ...] [--f32] [--out prefix] [--levels N] [--scale s]
 //                [--outer N] [--inner N] [--alpha a] [--eps-smooth e] [--eps-data e] [--median r] [--sigma s]
 //                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
-//                [--strain vol,e,eq] [--principal val,shear,dir1,dir3] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]
+//                [--strain vol,e,eq] [--principal val,shear,dir1,dir3] [--rotation angle,vector,stretch] [--inverse]
+//                [--match warped,zncc,rmsd [--match-radius R]]
 //                [--detrend translation|rigid|affine [--detrend-min-zncc T]]
 //                [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]
 //                 [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]
@@ -29,6 +30,10 @@
 // val,shear,dir1,dir3) diagonalises the Green-Lagrange tensor of that displacement on the device (f3d_principal_strain) and writes
 // the selected fields as <tag>_principal-{e1,e2,e3 | gmax | d1x,d1y,d1z | d3x,d3y,d3z}-W-H-D.raw, and one line of statistics per
 // pair.
+// --rotation LIST (same conditions and the same source once more; LIST a comma-separated subset of angle,vector,stretch) takes the
+// rotation R of F = R U out of the local deformation gradient of that displacement on the device (f3d_polar_decomposition) and
+// writes the selected fields as <tag>_rotation-{theta | rx,ry,rz | l1,l2,l3}-W-H-D.raw (the angle in radians, the rotation vector
+// angle * axis, the principal stretches), and one line of statistics per pair.
 // --inverse (same conditions and the same source once more) inverts that displacement on the device (f3d_invert_displacement, 32
 // steps, tolerance 1e-3): <tag>_inverse-{u,v,w,err}-W-H-D.raw is the displacement on the LATER frame's grid that leads back to the
 // earlier one (NaN where the point comes from outside the volume) and the round-trip residual of it, and one line of statistics per
@@ -48,8 +53,8 @@
 // at least --validate-min-neighbours neighbours, default 9) to NaN (mark) or to the neighbour median (replace).  --validate-min-zncc Z
 // also rejects the voxels whose zncc of --match is below Z (conditions of --detrend-min-zncc); --validate-fill N runs up to N further
 // passes that give undefined voxels the median of their defined neighbours.  <tag>_validated-{r,u,v,w}-W-H-D.raw and one line per pair.
-// --use-validated makes --strain, --principal and --detrend take the validated displacement in place of the raw one; the validated
-// field is then computed before them, and after the match.
+// --use-validated makes --strain, --principal, --rotation and --detrend take the validated displacement in place of the raw one; the
+// validated field is then computed before them, and after the match.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -74,7 +79,7 @@ static void Usage()
               "              [--levels N] [--scale s] [--outer N] [--inner N] [--alpha a] [--eps-smooth e]\n"
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
               "              [--concurrent N] [--cumulative] [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
-              "              [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
+              "              [--rotation angle,vector,stretch] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
               "              [--detrend translation|rigid|affine [--detrend-min-zncc T]]\n"
               "              [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]\n"
               "               [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]\n");
@@ -90,6 +95,7 @@ int main(int argc, char** argv)
   size_t concurrent = 1;
   unsigned strain_fields = 0;     // --strain: F3D_STRAIN_* groups
   unsigned principal_fields = 0;  // --principal: F3D_PRINCIPAL_* groups
+  unsigned polar_fields = 0;      // --rotation: F3D_POLAR_* groups
   bool inverse = false;           // --inverse
   unsigned match_fields = 0;      // --match: OpticalFlowE::kMatch* bits
   unsigned match_radius = 3;      // --match-radius
@@ -177,6 +183,21 @@ int main(int argc, char** argv)
         else if (item == "shear") principal_fields |= F3D_PRINCIPAL_SHEAR;
         else if (item == "dir1") principal_fields |= F3D_PRINCIPAL_DIR1;
         else if (item == "dir3") principal_fields |= F3D_PRINCIPAL_DIR3;
+        else { Usage(); return 64; }
+        if (end == std::string::npos) break;
+        at = end + 1;
+      }
+    }
+    else if (a == "--rotation") {
+      need(1);
+      const std::string list = argv[++i];
+      size_t at = 0;
+      while (true) {
+        const size_t end = list.find(',', at);
+        const std::string item = list.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        if (item == "angle") polar_fields |= F3D_POLAR_ANGLE;
+        else if (item == "vector") polar_fields |= F3D_POLAR_VECTOR;
+        else if (item == "stretch") polar_fields |= F3D_POLAR_STRETCH;
         else { Usage(); return 64; }
         if (end == std::string::npos) break;
         at = end + 1;
@@ -280,6 +301,12 @@ int main(int argc, char** argv)
   }
   if (principal_fields && (use_partial_gpu || concurrent > 1)) {
     std::printf("--principal needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if (polar_fields && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--rotation needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
                 use_partial_gpu ? "--partial" : "--concurrent N > 1");
     Usage();
     return 64;
@@ -509,9 +536,9 @@ int main(int argc, char** argv)
     for (size_t i = 0; i < n; ++i) lost += std::isnan(u[i]) ? 1 : 0;
     std::printf("displacement frame 0 -> frame %zu: %zu of %zu voxels have left the volume\n", k + 1, lost, n);
   };
-  // --strain, --principal, --inverse: the derived fields of pair k (of its flow, or with --cumulative of the displacement frame 0 ->
-  // frame k+1) and the statistics the device computed with them; --match: always of the pair's flow and the pair's frames.  One
-  // descriptor per feature, in the order in which they run on the library stream and go down on the `down` queue.
+  // --strain, --principal, --rotation, --inverse: the derived fields of pair k (of its flow, or with --cumulative of the displacement
+  // frame 0 -> frame k+1) and the statistics the device computed with them; --match: always of the pair's flow and the pair's frames.
+  // One descriptor per feature; `order` below is the order in which they run on the library stream and go down on the `down` queue.
   struct DerivedField {
     const char* option;  // without the dashes; the files are <tag>_<option>-<name><suffix>
     OpticalFlowE::Derived which;
@@ -527,6 +554,7 @@ int main(int argc, char** argv)
   };
   static const char* const strain_names[8] = {"vol", "exx", "eyy", "ezz", "exy", "exz", "eyz", "eq"};
   static const char* const principal_names[10] = {"e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z"};
+  static const char* const polar_names[7] = {"theta", "rx", "ry", "rz", "l1", "l2", "l3"};
   static const char* const inverse_names[4] = {"u", "v", "w", "err"};
   static const char* const match_names[3] = {"warped", "zncc", "rmsd"};
   static const char* const motion_names[3] = {"u", "v", "w"};
@@ -535,12 +563,13 @@ int main(int argc, char** argv)
   const size_t voxels = width * height * depth;
   f3d_strain_stats strain_stats = {};
   f3d_principal_stats principal_stats = {};
+  f3d_polar_stats polar_stats = {};
   f3d_inverse_stats inverse_stats = {};
   f3d_correlation_stats match_stats = {};
   f3d_motion_fit motion_fit = {};
   f3d_motion_residual motion_residual = {};
   f3d_validate_stats validate_stats = {};
-  // --use-validated: what --strain, --principal and --detrend are computed of
+  // --use-validated: what --strain, --principal, --rotation and --detrend are computed of
   auto validated_or = [&](const OpticalFlowE::Displacement& of) {
     if (!use_validated) return of;
     const DevicePtr d[3] = {optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 1),
@@ -548,7 +577,7 @@ int main(int argc, char** argv)
                             optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 3)};
     return OpticalFlowE::Containers(d);
   };
-  DerivedField derived[6] = {
+  DerivedField derived[7] = {
       {"strain", OpticalFlowE::kStrain, strain_fields, strain_names, false,
        [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputeStrain(validated_or(of), strain_fields, &strain_stats); },
        [&](size_t k) {
@@ -626,13 +655,23 @@ int main(int argc, char** argv)
          std::printf("validate frame %zu -> frame %zu (%s, step %u): %llu tested, %llu outliers, %llu replaced, %llu undefined, r max %.6g "
                      "of %zu voxels\n", cumulative ? size_t(0) : k, k + 1, validate_mode == F3D_VALIDATE_MARK ? "mark" : "replace",
                      validate_step, st.tested, st.outliers, st.replaced, st.undefined, st.r_max, voxels);
+       }},
+      // listed last so that the indices above stay; it runs after the principal strains (`order` below)
+      {"rotation", OpticalFlowE::kPolar, polar_fields, polar_names, false,
+       [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputePolar(validated_or(of), polar_fields, &polar_stats); },
+       [&](size_t k) {
+         const f3d_polar_stats& st = polar_stats;
+         const double mean = st.defined ? st.theta_sum / static_cast<double>(st.defined) : std::nan("");
+         std::printf("rotation frame %zu -> frame %zu: angle max %.6g rad, mean %.6g rad, stretch max %.6g, min %.6g, %llu folded, %llu "
+                     "undefined of %zu voxels\n", cumulative ? size_t(0) : k, k + 1, st.theta_max, mean, st.l1_max, st.l3_min, st.folded,
+                     static_cast<unsigned long long>(voxels) - st.defined - st.folded, voxels);
        }}};
-  // the order in which the features run and their files and lines come out: as listed, or with --use-validated the match (whose zncc
-  // may be the mask) and the validated field first
-  DerivedField* order[6] = {&derived[0], &derived[1], &derived[2], &derived[3], &derived[4], &derived[5]};
+  // the order in which the features run and their files and lines come out: as listed, with the rotation after the principal strains,
+  // or with --use-validated the match (whose zncc may be the mask) and the validated field first
+  DerivedField* order[7] = {&derived[0], &derived[1], &derived[6], &derived[2], &derived[3], &derived[4], &derived[5]};
   if (use_validated) {
-    DerivedField* const first[6] = {&derived[3], &derived[5], &derived[0], &derived[1], &derived[2], &derived[4]};
-    for (int i = 0; i < 6; ++i) order[i] = first[i];
+    DerivedField* const first[7] = {&derived[3], &derived[5], &derived[0], &derived[1], &derived[6], &derived[2], &derived[4]};
+    for (int i = 0; i < 7; ++i) order[i] = first[i];
   }
   for (DerivedField& f : derived)
     for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)
@@ -718,8 +757,8 @@ int main(int argc, char** argv)
       if (CheckDeviceError(f3d_event_create(&composed)) || CheckDeviceError(f3d_event_create(&disp_down))) return 3;
       if (!optical_flow_e.ResetTrajectory()) return 3;
     }
-    // --strain, --principal, --inverse: the same pattern for each one's containers.  The kernel of pair k runs on the library stream
-    // right after compose k (or after TakeResult); its statistics wait for that kernel only.  The fields go down on `down` beside
+    // --strain, --principal, --rotation, --inverse: the same pattern for each one's containers.  The kernel of pair k runs on the library
+    // stream right after compose k (or after TakeResult); its statistics wait for that kernel only.  The fields go down on `down` beside
     // solve k+1 once the kernel is done (`done`), and the kernel of pair k+1, which rewrites the same containers, waits for that
     // download (`down`).
     // --match is the one reader of the frame containers after the solve: match k reads frames k and k+1, and the upload of frame k+3

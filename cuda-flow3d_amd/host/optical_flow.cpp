@@ -22,6 +22,8 @@ extern "C" int f3d_flow_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f
                                size_t height, size_t depth, f3d_strain_stats* stats) __attribute__((weak));
 extern "C" int f3d_principal_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[10], unsigned fields,
                                     size_t width, size_t height, size_t depth, f3d_principal_stats* stats) __attribute__((weak));
+extern "C" int f3d_polar_decomposition(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[7], unsigned fields,
+                                       size_t width, size_t height, size_t depth, f3d_polar_stats* stats) __attribute__((weak));
 extern "C" int f3d_invert_displacement(f3d_devptr d_u, f3d_devptr d_v, f3d_devptr d_w, f3d_devptr g_u, f3d_devptr g_v,
                                        f3d_devptr g_w, f3d_devptr err, size_t width, size_t height, size_t depth,
                                        unsigned iterations, float tolerance, f3d_inverse_stats* stats) __attribute__((weak));
@@ -100,6 +102,9 @@ const unsigned kPrincipalGroups[10] = {F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_VALUE
                                        F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR3,
                                        F3D_PRINCIPAL_DIR3,   F3D_PRINCIPAL_DIR3};
 const unsigned kPrincipalAll = F3D_PRINCIPAL_VALUES | F3D_PRINCIPAL_SHEAR | F3D_PRINCIPAL_DIR1 | F3D_PRINCIPAL_DIR3;
+const unsigned kPolarGroups[7] = {F3D_POLAR_ANGLE,   F3D_POLAR_VECTOR,  F3D_POLAR_VECTOR, F3D_POLAR_VECTOR,
+                                  F3D_POLAR_STRETCH, F3D_POLAR_STRETCH, F3D_POLAR_STRETCH};
+const unsigned kPolarAll = F3D_POLAR_ANGLE | F3D_POLAR_VECTOR | F3D_POLAR_STRETCH;
 const unsigned kMatchGroups[3] = {OpticalFlowE::kMatchWarped, OpticalFlowE::kMatchZncc, OpticalFlowE::kMatchRmsd};
 const unsigned kMatchAll = OpticalFlowE::kMatchWarped | OpticalFlowE::kMatchZncc | OpticalFlowE::kMatchRmsd;
 // r, u, v, w, and the second u, v, w the fill passes alternate with (a bit of its own, never downloaded)
@@ -107,9 +112,10 @@ const unsigned kValidatedSpare = 4u;
 const int kValidatedContainers = 7;
 const unsigned kValidatedGroups[kValidatedContainers] = {F3D_VALIDATE_R, F3D_VALIDATE_D, F3D_VALIDATE_D, F3D_VALIDATE_D,
                                                          kValidatedSpare,  kValidatedSpare,  kValidatedSpare};
-const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3, 4};
+const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3, 4, 7};
 const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr,
-                                                                     kMatchGroups,  nullptr,          kValidatedGroups};
+                                                                     kMatchGroups,  nullptr,          kValidatedGroups,
+                                                                     kPolarGroups};
 const char* const kTrajectoryNotStarted = "the trajectory was not started (ResetTrajectory first)";
 
 }  // namespace
@@ -138,7 +144,10 @@ OpticalFlowE::OpticalFlowE()
                 "the validated displacement's containers do not fit beside the driver's on the device",
                 "a requested field of the validated displacement has not been computed",
                 "no host volume for a requested field of the validated displacement",
-                "the device library has no f3d_validate_displacement (displacement validation)", "no displacement to validate"}}
+                "the device library has no f3d_validate_displacement (displacement validation)", "no displacement to validate"},
+               {this, kDerivedFields[kPolar], kPolarGroups, "the rotation and stretch containers do not fit beside the driver's on the device",
+                "a requested rotation or stretch field has not been computed", "no host volume for a requested rotation or stretch field",
+                "the device library has no f3d_polar_decomposition (local rotation and stretches)", "no displacement to differentiate"}}
 {
   // same initialisation order as the reference's forward_list built with push_front (optical_flow_e.cpp:34-39)
   cuda_operations_ = {&cuop_solve_, &cuop_resample_, &cuop_register_, &cuop_median_, &cuop_convolution_, &cuop_add_};
@@ -613,6 +622,19 @@ bool OpticalFlowE::ComputePrincipal(const Displacement& of, unsigned fields, f3d
   const f3d_size4 c = Container();
   return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
          set.Check(CheckDeviceError(f3d_principal_strain(d[0], d[1], d[2], set.ptr, fields, c.width, c.height, c.depth, stats)));
+}
+
+bool OpticalFlowE::ComputePolar(const Displacement& of, unsigned fields, f3d_polar_stats* stats)
+{
+  FieldSet& set = derived_[kPolar];
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, f3d_polar_decomposition != nullptr, d)) return false;
+  if (fields == 0 || (fields & ~kPolarAll))
+    return set.Fail("fields must be a non-empty combination of F3D_POLAR_ANGLE, F3D_POLAR_VECTOR, F3D_POLAR_STRETCH");
+  if (!set.Allocate(fields)) return false;
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         set.Check(CheckDeviceError(f3d_polar_decomposition(d[0], d[1], d[2], set.ptr, fields, c.width, c.height, c.depth, stats)));
 }
 
 bool OpticalFlowE::ComputeInverse(const Displacement& of, unsigned iterations, float tolerance, f3d_inverse_stats* stats)

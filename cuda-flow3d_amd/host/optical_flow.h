@@ -120,6 +120,8 @@ class OpticalFlowE : public OpticalFlowBase {
   //               exy, exz, eyz, eq, selected in groups by F3D_STRAIN_* bits.
   //   kPrincipal  f3d_principal_strain: e1 >= e2 >= e3 of E, maximum shear, the directions of e1 and e3.  Ten outputs in the order
   //               e1, e2, e3, gmax, d1x, d1y, d1z, d3x, d3y, d3z, selected by F3D_PRINCIPAL_VALUES / _SHEAR / _DIR1 / _DIR3.
+  //   kPolar      f3d_polar_decomposition: the rotation angle and rotation vector of the R of F = R U, and the principal stretches.
+  //               Seven outputs in the order theta, rx, ry, rz, l1, l2, l3, selected by F3D_POLAR_ANGLE / _VECTOR / _STRETCH.
   //   kInverse    f3d_invert_displacement: g on the deformed frame's grid with g(y) = -d(y + g(y)), and the round-trip residual
   //               of the stored g.  Four outputs g_u, g_v, g_w, err, always all of them (fields is ignored).
   //   kMatch      f3d_local_correlation of frame 0 against frame 1 carried onto frame 0's grid through the displacement
@@ -133,7 +135,7 @@ class OpticalFlowE : public OpticalFlowBase {
   // Each selected output gets a container of its own, allocated on first use and freed by ReleaseDerived() and Destroy().  Compute
   // enqueues on the library stream and waits only when stats is given.  Every call returns false with DerivedError() set when it
   // cannot run -- among other reasons when the device library lacks the entry point.
-  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kValidated, kDerivedCount };
+  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kValidated, kPolar, kDerivedCount };
   enum MatchField : unsigned { kMatchWarped = 1u, kMatchZncc = 2u, kMatchRmsd = 4u };
   // the displacement a derived field is computed of
   struct Displacement {
@@ -145,6 +147,7 @@ class OpticalFlowE : public OpticalFlowBase {
   static Displacement Containers(const DevicePtr (&d)[3]) { return {Displacement::kContainers, {d[0], d[1], d[2]}}; }  // TakeResult's
   bool ComputeStrain(const Displacement& of, unsigned fields, f3d_strain_stats* stats);
   bool ComputePrincipal(const Displacement& of, unsigned fields, f3d_principal_stats* stats);
+  bool ComputePolar(const Displacement& of, unsigned fields, f3d_polar_stats* stats);
   bool ComputeInverse(const Displacement& of, unsigned iterations, float tolerance, f3d_inverse_stats* stats);
   // frame_0 / frame_1: the containers of the two frames the displacement belongs to; 0 means the resident pair.  A trajectory is
   // refused: frame 0 of a sequence is not kept.
@@ -161,7 +164,7 @@ class OpticalFlowE : public OpticalFlowBase {
   // the absent voxels with enough present neighbours their median; they stop when no voxel is undefined or the count stops falling,
   // and they wait for the stream.  stats (nullable) are those of the first call with replaced and undefined brought to the final
   // state; r is that of the first call.  DerivedContainer(kValidated, 1 .. 3) is the validated displacement afterwards, which
-  // Containers() hands to the strain, principal strain and motion calls.
+  // Containers() hands to the strain, principal strain, polar and motion calls.
   bool ComputeValidated(const Displacement& of, DevicePtr weight, float weight_min, unsigned step, float eps, float threshold,
                         unsigned min_neighbours, unsigned mode, unsigned fill_passes, unsigned fields, f3d_validate_stats* stats);
   static int DerivedFieldCount(Derived which);

@@ -535,6 +535,57 @@ typedef struct f3d_principal_stats {
 int f3d_principal_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[10], unsigned fields, size_t width,
                          size_t height, size_t depth, f3d_principal_stats* stats /* nullable; non-null waits */);
 
+/* Polar decomposition F = R U of the local deformation gradient F = I + G of a displacement: the rotation of each material
+ * neighbourhood (to which E = 1/2 (F^T F - I) is blind by construction) as an angle and a rotation vector, and the principal
+ * stretches, in one stencil pass from d = (u, v, w); neither F nor R is stored.  Every operation float32, rounded on its own, in
+ * exactly the order written; only + - * / and sqrt occur, so float32 numpy agrees bit for bit.  Per voxel:
+ * 1. G, the missing-sample rules and the set of undefined voxels are exactly f3d_flow_strain's; vol and E (Exx Eyy Ezz Exy Exz Eyz)
+ *    are formed from G by exactly its expressions.  An undefined voxel is NaN in every output.
+ * 2. (A, V) = rule 2 of f3d_principal_strain unchanged: five cyclic Jacobi sweeps on A = E, V = I.
+ * 3. m_i = 2.f * a_ii + 1.f (i = 0, 1, 2): the eigenvalues of C = F^T F.  The voxel is FOLDED when vol <= -1.f or !(m_i > 0.f) for
+ *    any i: F has no rotation there (det R would be -1); a folded voxel is NaN in every output.  Otherwise lambda_i = sqrtf(m_i),
+ *    and l1, l2, l3 = the three lambda ordered by the compare-exchanges (0,1), (0,2), (1,2) of f3d_principal_strain's rule 3 (values
+ *    only, exchanged when strictly smaller).  Nothing below depends on that order.
+ * 4. q_i = 1.f / lambda_i
+ *    Uinv_rc = ((V_r0 * q_0) * V_c0 + (V_r1 * q_1) * V_c1) + (V_r2 * q_2) * V_c2            (all nine; r, c in {0,1,2})
+ *    Fm = G with 1.f added to G00, G11 and G22
+ *    R_rc = (Fm_r0 * Uinv_0c + Fm_r1 * Uinv_1c) + Fm_r2 * Uinv_2c
+ * 5. c = 0.5f * (((R00 + R11) + R22) - 1.f)
+ *    ax = 0.5f * (R21 - R12) ;  ay = 0.5f * (R02 - R20) ;  az = 0.5f * (R10 - R01)
+ *    s = sqrtf((ax*ax + ay*ay) + az*az)
+ *    theta = ATAN2(s, c)                                                                     (rule 6; 0 .. pi)
+ *    k = theta / s ;  (rx, ry, rz) = (k * ax, k * ay, k * az) ;  if s == 0: (rx, ry, rz) = (0, 0, 0)
+ *    The skew part of an exact half turn vanishes and gives no axis: there theta is pi and the rotation vector is 0.
+ * 6. ATAN2(s, c) for s >= 0, with K3, K5, K7, K9 the float32 nearest to 1/3, 1/5, 1/7, 1/9 (0x3EAAAAAB, 0x3E4CCCCD, 0x3E124925,
+ *    0x3DE38E39), PI_F = 0x40490FDB and HALFPI_F = 0x3FC90FDB:
+ *      big = fabsf(c) >= s
+ *      x = big ? s / c : c / s ;  if s == 0 and c == 0: x = 0.f
+ *      twice:  x = x / (1.f + sqrtf(x * x + 1.f))                        (the tangent of half the angle; |x| <= tan(pi/16) after it)
+ *      z = x * x
+ *      p = (((z * K9 - K7) * z + K5) * z - K3) * z + 1.f
+ *      t = 4.f * (x * p)
+ *      theta = big ? (c > 0.f ? t : PI_F + t) : HALFPI_F - t
+ * Outputs, in this order (out[0..6]), selected by group:
+ *   F3D_POLAR_ANGLE    out[0]    theta: the rotation angle in radians
+ *   F3D_POLAR_VECTOR   out[1..3] rx ry rz: the rotation vector theta * n, n the unit axis (right-handed, x y z components)
+ *   F3D_POLAR_STRETCH  out[4..6] l1 >= l2 >= l3: the principal stretches (the eigenvalues of U; their logarithms are the Hencky strains)
+ * Geometry from the current container (f3d_set_container), whole volume, library stream.  Entries of out for groups not selected
+ * are ignored and never written.  Refused: a null input; a null selected output; fields 0 or with unknown bits; a selected output
+ * that is also an input; two selected outputs that are the same container.
+ * stats (nullable; asking waits for the stream): folded = the folded voxels; over the others that are defined: defined = their
+ * number, theta_max, l1_max and l3_min = the exact max of theta, max of l1 and min of l3 (NaN when there is none), theta_sum = the sum
+ * of theta in double in the fixed order of the reduction (0 when there is none) -- all whether or not those fields are stored. */
+#define F3D_POLAR_ANGLE 1u
+#define F3D_POLAR_VECTOR 2u
+#define F3D_POLAR_STRETCH 4u
+typedef struct f3d_polar_stats {
+  unsigned long long defined, folded;
+  float theta_max, l1_max, l3_min;
+  double theta_sum;
+} f3d_polar_stats;
+int f3d_polar_decomposition(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[7], unsigned fields, size_t width,
+                            size_t height, size_t depth, f3d_polar_stats* stats /* nullable; non-null waits */);
+
 /* Inverse displacement (no reference counterpart).  d = (d_u, d_v, d_w) is the displacement of every voxel of frame 0 on frame 0's
  * grid (a pair's flow, or f3d_compose_flow's cumulative displacement), voxel units.  g = (g_u, g_v, g_w) is the map in the other
  * direction on frame k's grid: g(y) = -d(y + g(y)), by the fixed-point iteration g <- -d(y + g) of each voxel on its own.  With g a

@@ -108,6 +108,14 @@ int f3d_flow_strain_end(f3d_flow flow);
 int f3d_flow_principal_compute(f3d_flow flow, int source, unsigned fields, float* const out[10], f3d_principal_stats* stats);
 int f3d_flow_principal_end(f3d_flow flow);
 
+/* Local rotation and principal stretches (f3d_polar_decomposition of include/f3d.h has the definition) of the same two sources,
+ * F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY.  fields selects groups of the seven outputs theta, rx, ry, rz, l1, l2, l3
+ * (F3D_POLAR_ANGLE / _VECTOR / _STRETCH); out[i] of a selected output receives width * height * depth floats, entries of other
+ * outputs are ignored; stats is nullable.  The driver keeps a container per selected field until f3d_flow_polar_end (or
+ * f3d_flow_destroy).  A device library without f3d_polar_decomposition still loads; then the call fails with a message naming it. */
+int f3d_flow_polar_compute(f3d_flow flow, int source, unsigned fields, float* const out[7], f3d_polar_stats* stats);
+int f3d_flow_polar_end(f3d_flow flow);
+
 /* Inverse displacement (f3d_invert_displacement of include/f3d.h has the definition) of the same two sources, F3D_STRAIN_OF_FLOW or
  * F3D_STRAIN_OF_TRAJECTORY: out[0..3] = g_u, g_v, g_w, err receive width * height * depth floats each (all four required); stats is
  * nullable.  Blocks until the fields are on the host.  The driver keeps four containers until f3d_flow_inverse_end (or

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Resource report and instruction counts of the derived-field kernels (strain, principal strain, inverse / carry, trajectory),
+"""Resource report and instruction counts of the derived-field kernels (strain, principal strain, polar decomposition, inverse / carry, trajectory),
 read from the gfx950 assembly that the Makefile's flags give.  Runs on the CPU: hipcc only cross-compiles.
 
     python tools/derived_isa.py                     one line per kernel of this tree
@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))  # so that it als
 from median_isa import kernels  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ("f3d_strain", "f3d_principal", "f3d_inverse", "f3d_trajectory")
+FILES = ("f3d_strain", "f3d_principal", "f3d_polar", "f3d_inverse", "f3d_trajectory")
 FIGURES = ("vgprs", "lds", "scratch", "occupancy", "global_loads", "global_stores", "ds", "barriers", "cross_lane")
 CROSS = re.compile(r"\b(row_|quad_perm|wave_sh|wave_ro|bank_mask|v_permlane|ds_bpermute|ds_permute|ds_swizzle)")
 
@@ -58,13 +58,15 @@ def digest(body):
 
 
 def report(tree=ROOT):
-    """{kernel: {figure: value}} of the four device files of a tree"""
+    """{kernel: {figure: value}} of the device files of a tree (those of FILES that it has: an older checkout lacks the newer ones)"""
     res = {}
     with tempfile.TemporaryDirectory(prefix="f3d_derived_isa_") as tmp:
         for f in FILES:
+            src = os.path.join(tree, "cuda-flow3d_amd", "csrc", f + ".hip")
+            if not os.path.exists(src):
+                continue
             asm = os.path.join(tmp, f + ".s")
-            subprocess.run([*compiler(tree), "-S", "--cuda-device-only",
-                            os.path.join(tree, "cuda-flow3d_amd", "csrc", f + ".hip"), "-o", asm], check=True)
+            subprocess.run([*compiler(tree), "-S", "--cuda-device-only", src, "-o", asm], check=True)
             ks = {n: k for n, k in kernels(asm).items() if "occupancy" in k}
             for name, k in zip(demangled(list(ks)), ks.values()):
                 ops = [t.split()[0] for t in k["body"]]
