@@ -111,6 +111,14 @@ class MotionResidual(C.Structure):  # f3d_motion_residual
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class LabelInfo(C.Structure):  # f3d_label_info: every voxel of the volume in exactly one counter
+    _fields_ = [("background", C.c_ulonglong), ("foreign", C.c_ulonglong), ("absent", C.c_ulonglong), ("out_of_range", C.c_ulonglong),
+                ("used", C.c_ulonglong)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class ValidateStats(C.Structure):  # f3d_validate_stats
     _fields_ = [("present", C.c_ulonglong), ("tested", C.c_ulonglong), ("outliers", C.c_ulonglong), ("replaced", C.c_ulonglong),
                 ("undefined", C.c_ulonglong), ("r_max", C.c_float)]
@@ -296,9 +304,14 @@ def host():
         "f3d_flow_match_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_float, C.POINTER(_fp), C.POINTER(CorrelationStats)],
         "f3d_flow_match_end": [C.c_void_p],
         "f3d_motion_solve": [C.POINTER(MotionSums), C.c_int, C.POINTER(MotionFit)],
+        "f3d_motion_solve_labels": [C.POINTER(MotionSums), _sz, C.c_int, C.c_ulonglong, C.POINTER(C.c_double), C.POINTER(MotionFit),
+                                    C.POINTER(C.c_int)],
         "f3d_flow_motion_compute": [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(_fp), C.POINTER(MotionFit),
                                     C.POINTER(MotionResidual)],
         "f3d_flow_motion_end": [C.c_void_p],
+        "f3d_flow_label_motion_compute": [C.c_void_p, C.c_int, C.POINTER(C.c_int), _sz, C.c_int, C.c_ulonglong, C.POINTER(_fp),
+                                          C.POINTER(MotionFit), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(LabelInfo)],
+        "f3d_flow_label_motion_end": [C.c_void_p],
         "f3d_flow_validate_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_float, C.c_uint, C.c_uint, C.c_uint, C.c_float,
                                       C.POINTER(_fp), C.POINTER(ValidateStats)],
         "f3d_flow_validate_end": [C.c_void_p],
@@ -454,6 +467,24 @@ def _motion_entry():
     what = "fit or remove the motion of a displacement"
     return (_entry("f3d_motion_sums", [_dp] * 4 + [C.c_float] + [_sz] * 3 + [C.POINTER(MotionSums)], what),
             _entry("f3d_remove_motion", [_dp] * 6 + [C.POINTER(MotionFit)] + [_sz] * 3 + [C.POINTER(MotionResidual)], what))
+
+
+_LABEL_MOTION_WHAT = "fit or remove the motion of the labels of a segmentation"
+
+
+def _label_sums_entry():
+    return _entry("f3d_label_motion_sums", [_dp] * 4 + [_sz, _dp, C.c_float] + [_sz] * 3 + [C.POINTER(MotionSums), C.POINTER(LabelInfo)],
+                  _LABEL_MOTION_WHAT)
+
+
+def _label_remove_entry():
+    return _entry("f3d_remove_label_motion", [_dp] * 4 + [_sz, C.POINTER(MotionFit), C.POINTER(C.c_int)] + [_dp] * 3 + [_sz] * 3 +
+                  [C.POINTER(MotionResidual)], _LABEL_MOTION_WHAT)
+
+
+def _label_motion_entry():
+    """(f3d_label_motion_sums, f3d_remove_label_motion)"""
+    return _label_sums_entry(), _label_remove_entry()
 
 
 def _validate_entry():
@@ -717,6 +748,124 @@ def remove_motion(u, v, w, fit):
         stats = MotionResidual()
         check(fn(*p, *outs, C.byref(fit), *dims, C.byref(stats)), "f3d_remove_motion")
         return tuple(box.download(o, dims) for o in outs) + (stats.as_dict(),)
+
+
+# the status of a label after solve_label_motion (F3D_LABEL_*)
+LABEL_STATUS = ("ok", "empty", "small", "degenerate")
+MAX_LABELS = 1 << 22
+
+
+def _labels_as_float_bits(labels, n_labels):
+    """(the bits of the int32 labels as a float32 volume for the upload, n_labels): labels is any integer array; values that do not fit
+    int32 raise; n_labels None means labels.max()"""
+    labels = np.asarray(labels)
+    if labels.ndim != 3 or not (np.issubdtype(labels.dtype, np.integer) or labels.dtype == np.bool_):
+        raise ValueError("labels must be a [z, y, x] volume of integers")
+    if labels.dtype == np.bool_:
+        labels = labels.astype(np.int32)
+    if labels.size and (int(labels.min()) < -2 ** 31 or int(labels.max()) > 2 ** 31 - 1):
+        raise ValueError("labels do not fit int32")
+    if n_labels is None:
+        n_labels = int(labels.max()) if labels.size else 0
+    n_labels = int(n_labels)
+    if not 1 <= n_labels <= MAX_LABELS:
+        raise ValueError(f"n_labels must be 1 .. {MAX_LABELS}, not {n_labels}")
+    return np.ascontiguousarray(labels, dtype=np.int32).view(np.float32), n_labels
+
+
+def label_motion_sums(u, v, w, labels, n_labels=None, weight=None, weight_min=0.8):
+    """The exact moment sums of every label of a segmentation on the device (include/f3d.h, f3d_label_motion_sums): u, v, w numpy
+    [z, y, x] float32, labels an integer volume of the same shape (0 background, 1 .. n_labels the bodies, anything else ignored;
+    n_labels None means labels.max()), weight as in motion_sums.  Returns (sums, info): a ctypes array of n_labels MotionSums about the
+    centre of the volume (label L at index L - 1) and a dict of the voxel counts background, foreign, absent, out_of_range, used."""
+    fn = _label_sums_entry()
+    bits, n_labels = _labels_as_float_bits(labels, n_labels)
+    vols = (u, v, w, bits) if weight is None else (u, v, w, bits, weight)
+    with _on_device(vols, "u, v, w, labels and weight must be [z, y, x] volumes of one shape") as (box, p, dims):
+        box.set_current()
+        sums = (MotionSums * n_labels)()
+        info = LabelInfo()
+        check(fn(p[0], p[1], p[2], p[3], n_labels, p[4] if weight is not None else 0, weight_min, *dims, sums, C.byref(info)),
+              "f3d_label_motion_sums")
+    return sums, info.as_dict()
+
+
+class LabelMotion:
+    """The fit of every label (solve_label_motion): arrays over the labels, label L at index L - 1.  .status (0 ok, 1 empty, 2 small,
+    3 degenerate: LABEL_STATUS), .n, .centre (N, 3: the centroid of an ok label), .t (N, 3: the motion of the body at its centroid),
+    .matrix (N, 3, 3; rows = components), .cos_angle, .axial (N, 3) for the rigid model, .rms_before, and .rms_after (None until the
+    motion has been removed: remove_label_motion fills it in).  .fits and .status_c are the C arrays f3d_remove_label_motion takes."""
+
+    def __init__(self, fits, status, model):
+        self.fits, self.status_c, self.model = fits, status, model
+        n = len(fits)
+        self.status = np.array(list(status), np.int32).reshape(n)
+        self.n = np.array([f.n for f in fits], np.uint64)
+        self.centre = np.array([list(f.centre) for f in fits], np.float64).reshape(n, 3)
+        self.t = np.array([list(f.t) for f in fits], np.float64).reshape(n, 3)
+        self.matrix = np.array([list(f.M) for f in fits], np.float64).reshape(n, 3, 3)
+        self.cos_angle = np.array([f.cos_angle for f in fits], np.float64)
+        self.axial = np.array([list(f.axial) for f in fits], np.float64).reshape(n, 3)
+        self.rms_before = np.array([f.rms_before for f in fits], np.float64)
+        self.rms_after = None
+
+    def __len__(self):
+        return len(self.fits)
+
+    def as_table(self):
+        """one dict per label: label, status (a word of LABEL_STATUS), n, centre, t, matrix, cos_angle, axial, rms_before, rms_after"""
+        return [{"label": i + 1, "status": LABEL_STATUS[self.status[i]], "n": int(self.n[i]), "centre": self.centre[i].tolist(),
+                 "t": self.t[i].tolist(), "matrix": self.matrix[i].tolist(), "cos_angle": float(self.cos_angle[i]),
+                 "axial": self.axial[i].tolist(), "rms_before": float(self.rms_before[i]),
+                 "rms_after": None if self.rms_after is None else float(self.rms_after[i])} for i in range(len(self))]
+
+
+def solve_label_motion(sums, dims, model="rigid", min_voxels=27):
+    """f3d_motion_solve_labels (include/f3d_host.h; host code, no device): the LabelMotion of the array `sums` of label_motion_sums taken
+    over a (width, height, depth) volume.  A label with fewer than min_voxels voxels is not fitted."""
+    n = len(sums)
+    if not isinstance(sums, C.Array):
+        sums = (MotionSums * n)(*sums)
+    fits, status = (MotionFit * n)(), (C.c_int * n)()
+    centre = (C.c_double * 3)(*[(k - 1) / 2 for k in dims])
+    if int(min_voxels) < 0:
+        raise ValueError("min_voxels must not be negative")
+    _host_check(host().f3d_motion_solve_labels(sums, n, _motion_model(model), int(min_voxels), centre, fits, status),
+                "f3d_motion_solve_labels")
+    return LabelMotion(fits, status, model)
+
+
+def fit_label_motion(u, v, w, labels, model="rigid", n_labels=None, min_voxels=27, weight=None, weight_min=0.8):
+    """The translation, rigid motion or affine map of every label of a segmentation (least squares over the label's voxels that take
+    part, the displacement quantised to 2^-14 voxel): the exact sums on the device, the solves on the host.  Returns a LabelMotion;
+    .info holds the voxel counts of label_motion_sums."""
+    _motion_model(model)
+    d, h, w_ = np.shape(u)
+    sums, info = label_motion_sums(u, v, w, labels, n_labels, weight, weight_min)
+    motion = solve_label_motion(sums, (w_, h, d), model, min_voxels)
+    motion.info = info
+    return motion
+
+
+def remove_label_motion(u, v, w, labels, motion):
+    """A displacement with the fit of each voxel's label taken out on the device (include/f3d.h, f3d_remove_label_motion): returns
+    (ru, rv, rw, stats); NaN where the label is background, foreign or not fitted.  motion.rms_after receives the rms of the residual
+    of every label (NaN where there is none), from a second f3d_label_motion_sums of the residual."""
+    fn = _label_remove_entry()               # the entry this call is named after first: a library without it is reported by that name
+    sums_fn = _label_sums_entry()
+    n = len(motion)
+    bits, n = _labels_as_float_bits(labels, n)
+    with _on_device((u, v, w, bits), "u, v, w and labels must be [z, y, x] volumes of one shape") as (box, p, dims):
+        outs = [box.alloc() for _ in range(3)]
+        box.set_current()
+        stats = MotionResidual()
+        check(fn(*p, n, motion.fits, motion.status_c, *outs, *dims, C.byref(stats)), "f3d_remove_label_motion")
+        after = (MotionSums * n)()
+        check(sums_fn(*outs, p[3], n, 0, 0.0, *dims, after, None), "f3d_label_motion_sums")
+        res = tuple(box.download(o, dims) for o in outs)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        motion.rms_after = np.array([np.sqrt(((s.Sdd[0] + s.Sdd[1]) + s.Sdd[2]) / s.n) if s.n else np.nan for s in after], np.float64)
+    return res + (stats.as_dict(),)
 
 
 def validate_displacement(u, v, w, weight=None, weight_min=0.8, step=1, eps=0.1, threshold=2.0, min_neighbours=9, mode="replace",
@@ -1251,7 +1400,7 @@ class OpticalFlow:
     def trajectory_end(self):
         _host_check(host().f3d_flow_trajectory_end(self._h), "f3d_flow_trajectory_end")
 
-    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_{strain,principal,polar,inverse,match,motion,validate}_*) ----
+    # ---- derived fields of the held flow or the trajectory (include/f3d_host.h, f3d_flow_{strain,principal,polar,inverse,match,motion,label_motion,validate}_*) ----
     def _derived(self, compute, src, selected, stats, *args, fit=None):
         """one f3d_flow_*_compute into fresh host arrays: a list with an array per selected output and None for the others
         (fit: the MotionFit f3d_flow_motion_compute takes between the arrays and the statistics)"""
@@ -1346,6 +1495,41 @@ class OpticalFlow:
     def motion_end(self):
         """free the motion residual containers (destroy() does too)"""
         _host_check(host().f3d_flow_motion_end(self._h), "f3d_flow_motion_end")
+
+    def label_motion(self, labels, source="flow", model="rigid", min_voxels=27, n_labels=None):
+        """The motion of every label of a segmentation in the flow the driver holds (source="flow") or in the trajectory
+        (source="trajectory"), fitted and taken out on the device: a dict with the residual "u", "v", "w" (NaN where a voxel's label
+        has no fit), "motion" -> LabelMotion (with .rms_after and .info).  labels: an integer [z, y, x] volume on the grid of the
+        displacement, or None for the labels of the previous call, which the driver keeps on the device (n_labels is then required)."""
+        w, h, d = self.dims
+        if labels is None:
+            if n_labels is None:
+                raise ValueError("n_labels is required when the labels of the previous call are reused")
+            lab, ptr = None, None
+        else:
+            bits, n_labels = _labels_as_float_bits(labels, n_labels)
+            if bits.shape != (d, h, w):
+                raise ValueError(f"labels must be a [z, y, x] volume of shape {(d, h, w)}")
+            lab = bits.view(np.int32)
+            ptr = lab.ctypes.data_as(C.POINTER(C.c_int))
+        n = int(n_labels)
+        if not 1 <= n <= MAX_LABELS:
+            raise ValueError(f"n_labels must be 1 .. {MAX_LABELS}, not {n}")
+        fits, status, rms, info = (MotionFit * n)(), (C.c_int * n)(), (C.c_double * n)(), LabelInfo()
+        arrays = [np.empty((d, h, w), np.float32) for _ in range(3)]
+        ptrs = (_fp * 3)(*[a.ctypes.data_as(_fp) for a in arrays])
+        _host_check(host().f3d_flow_label_motion_compute(self._h, _source(source), ptr, n, _motion_model(model), int(min_voxels), ptrs,
+                                                         fits, status, rms, C.byref(info)), "f3d_flow_label_motion_compute")
+        motion = LabelMotion(fits, status, model)
+        motion.rms_after = np.array(list(rms), np.float64)
+        motion.info = info.as_dict()
+        res = dict(zip("uvw", arrays))
+        res["motion"] = motion
+        return res
+
+    def label_motion_end(self):
+        """free the containers of the per-label residual and of the labels (destroy() does too)"""
+        _host_check(host().f3d_flow_label_motion_end(self._h), "f3d_flow_label_motion_end")
 
     def validate(self, source="flow", step=1, eps=0.1, threshold=2.0, min_neighbours=9, mode="replace", fill_passes=0,
                  fields=("r", "d"), min_zncc=None):

@@ -344,6 +344,15 @@ int f3d_motion_solve(const struct f3d_motion_sums* sums, int model, f3d_motion_f
   return SolveMotion(*sums, model, fit, &why) ? 0 : HostFail(why.c_str());
 }
 
+int f3d_motion_solve_labels(const struct f3d_motion_sums* sums, size_t n_labels, int model, unsigned long long min_voxels,
+                            const double volume_centre[3], f3d_motion_fit* fits, int* status)
+{
+  g_host_error.clear();
+  if (!sums || !volume_centre || !fits || !status) return HostFail("f3d_motion_solve_labels: null argument");
+  std::string why;
+  return SolveLabelMotions(sums, n_labels, model, min_voxels, volume_centre, fits, status, &why) ? 0 : HostFail(why.c_str());
+}
+
 int f3d_flow_motion_compute(f3d_flow flow, int source, int model, float min_zncc, float* const out[3], f3d_motion_fit* fit,
                             f3d_motion_residual* residual)
 {
@@ -360,6 +369,23 @@ int f3d_flow_motion_compute(f3d_flow flow, int source, int model, float min_zncc
 }
 
 int f3d_flow_motion_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kMotion, "f3d_flow_motion_end: null driver"); }
+
+int f3d_flow_label_motion_compute(f3d_flow flow, int source, const int* labels, size_t n_labels, int model, unsigned long long min_voxels,
+                                  float* const out[3], f3d_motion_fit* fits, int* status, double* rms_after, f3d_label_info* info)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out && out[0] && out[1] && out[2] && fits && status, "f3d_flow_label_motion_compute", &of)) return 1;
+  OpticalFlowE& d = flow->driver;
+  if (labels && !d.UploadLabels(labels)) return HostFail(d.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  float* const four[4] = {out[0], out[1], out[2], nullptr};
+  return DerivedDownload(flow, OpticalFlowE::kLabelMotion, d.ComputeLabelMotion(of, n_labels, model, min_voxels, fits, status, rms_after, info),
+                         four, 1);
+}
+
+int f3d_flow_label_motion_end(f3d_flow flow)
+{
+  return DerivedEnd(flow, OpticalFlowE::kLabelMotion, "f3d_flow_label_motion_end: null driver");
+}
 
 int f3d_flow_validate_compute(f3d_flow flow, int source, unsigned step, float eps, float threshold, unsigned min_neighbours,
                               unsigned mode, unsigned fill_passes, float min_zncc, float* const out[4], f3d_validate_stats* stats)

@@ -10,6 +10,7 @@
 //                [--detrend translation|rigid|affine [--detrend-min-zncc T]]
 //                [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]
 //                 [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]
+//                [--labels FILE --label-motion translation|rigid|affine [--label-min-voxels K]]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -55,6 +56,13 @@
 // passes that give undefined voxels the median of their defined neighbours.  <tag>_validated-{r,u,v,w}-W-H-D.raw and one line per pair.
 // --use-validated makes --strain, --principal, --rotation and --detrend take the validated displacement in place of the raw one; the
 // validated field is then computed before them, and after the match.
+// --labels FILE --label-motion MODEL (same conditions and the same source as --detrend, --use-validated included) fits MODEL to the
+// voxels of every body of a segmentation on the device (f3d_label_motion_sums, f3d_motion_solve_labels) and takes each body's fit out of
+// its voxels (f3d_remove_label_motion).  FILE is raw little-endian int32 of W x H x D on frame 0's grid: 0 background, 1 .. max the
+// bodies; it is uploaded once.  With more than two frames it needs --cumulative: only the displacement from frame 0 lives on that grid.
+// A body with fewer than --label-min-voxels voxels (default 27) is not fitted.  <tag>_labelres-{u,v,w}-W-H-D.raw is what remains (NaN
+// where there is no fit), <tag>_labelmotion.csv has one row per label, and one line per pair sums it up.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -82,7 +90,8 @@ static void Usage()
               "              [--rotation angle,vector,stretch] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
               "              [--detrend translation|rigid|affine [--detrend-min-zncc T]]\n"
               "              [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]\n"
-              "               [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]\n");
+              "               [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]\n"
+              "              [--labels FILE --label-motion translation|rigid|affine [--label-min-voxels K]]\n");
 }
 
 int main(int argc, char** argv)
@@ -109,6 +118,10 @@ int main(int argc, char** argv)
   float validate_threshold = 2.0f, validate_eps = 0.1f;
   float validate_min_zncc = std::nanf("");  // --validate-min-zncc; NaN: no mask
   bool validate_min_given = false, validate_sub_given = false, use_validated = false;
+  std::string labels_file;        // --labels
+  int label_model = -1;           // --label-motion: F3D_MOTION_*
+  unsigned long long label_min_voxels = 27;
+  bool label_min_given = false;
   const unsigned inverse_iterations = 32;
   const float inverse_tolerance = 1e-3f;
 
@@ -283,6 +296,26 @@ int main(int argc, char** argv)
       validate_sub_given = true;
     }
     else if (a == "--use-validated") use_validated = true;
+    else if (a == "--labels") {
+      need(1);
+      labels_file = argv[++i];
+      if (labels_file.empty()) { Usage(); return 64; }
+    }
+    else if (a == "--label-motion") {
+      need(1);
+      const std::string model = argv[++i];
+      if (model == "translation") label_model = F3D_MOTION_TRANSLATION;
+      else if (model == "rigid") label_model = F3D_MOTION_RIGID;
+      else if (model == "affine") label_model = F3D_MOTION_AFFINE;
+      else { Usage(); return 64; }
+    }
+    else if (a == "--label-min-voxels") {
+      need(1);
+      char* rest = nullptr;
+      label_min_voxels = std::strtoull(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest || argv[i][0] == '-') { Usage(); return 64; }
+      label_min_given = true;
+    }
     else { Usage(); return 64; }
   }
   if (width == 0 || height == 0 || depth == 0 || (!synthetic && files.size() < 2)) {
@@ -362,6 +395,54 @@ int main(int argc, char** argv)
                            : "--validate-min-zncc needs --match with zncc in its list\n");
     Usage();
     return 64;
+  }
+  if (labels_file.empty() != (label_model < 0) || (label_min_given && label_model < 0)) {
+    std::printf("--labels and --label-motion need each other, and --label-min-voxels needs both\n");
+    Usage();
+    return 64;
+  }
+  if (label_model >= 0 && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--label-motion needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if (label_model >= 0 && !synthetic && files.size() > 2 && !cumulative) {
+    std::printf("--label-motion of more than two frames needs --cumulative: the labels live on frame 0's grid, and only the displacement "
+                "from frame 0 lives there too\n");
+    Usage();
+    return 64;
+  }
+  // the segmentation is read before any device is touched: a file of another size or without a body is an argument error
+  std::vector<int> label_volume;
+  size_t n_labels = 0;
+  if (label_model >= 0) {
+    const size_t count = width * height * depth;
+    std::FILE* f = std::fopen(labels_file.c_str(), "rb");
+    bool good = f != nullptr;
+    if (good) {
+      // the size first: nothing is allocated for a file that is not this volume
+      good = std::fseek(f, 0, SEEK_END) == 0 && static_cast<size_t>(std::ftell(f)) == count * sizeof(int);
+      if (good) {
+        std::rewind(f);
+        label_volume.resize(count);
+        good = std::fread(label_volume.data(), sizeof(int), count, f) == count;
+      }
+      std::fclose(f);
+    }
+    if (!good) {
+      std::printf("--labels %s: cannot read %zu x %zu x %zu int32 values (%zu bytes)\n", labels_file.c_str(), width, height, depth,
+                  count * sizeof(int));
+      Usage();
+      return 64;
+    }
+    const int largest = *std::max_element(label_volume.begin(), label_volume.end());
+    if (largest < 1 || largest > (1 << 22)) {
+      std::printf("--labels %s: the largest label is %d; it must be 1 .. %d\n", labels_file.c_str(), largest, 1 << 22);
+      Usage();
+      return 64;
+    }
+    n_labels = static_cast<size_t>(largest);
   }
 
   std::printf("//----------------------------------------------------------------------//\n");
@@ -494,6 +575,10 @@ int main(int argc, char** argv)
   }
   if (!optical_flow_e.AllocateResidentFrames()) return 3;
   std::printf("Mode: Full GPU mode \n");
+  if (label_model >= 0) {
+    if (!optical_flow_e.UploadLabels(label_volume.data())) return 3;
+    std::vector<int>().swap(label_volume);
+  }
   optical_flow_e.silent = silent_mode;
   optical_flow_e.collect_level_statistics = print_stats;
 
@@ -560,6 +645,13 @@ int main(int argc, char** argv)
   static const char* const motion_names[3] = {"u", "v", "w"};
   static const char* const motion_models[3] = {"translation", "rigid", "affine"};
   static const char* const validated_names[4] = {"r", "u", "v", "w"};
+  static const char* const labelres_names[4] = {"u", "v", "w", "labels"};
+  static const char* const label_status[4] = {"ok", "empty", "small", "degenerate"};
+  std::vector<f3d_motion_fit> label_fits(n_labels);
+  std::vector<int> label_state(n_labels);
+  std::vector<double> label_rms_after(n_labels);
+  f3d_label_info label_info = {};
+  bool label_table_failed = false;  // a <tag>_labelmotion.csv that could not be written: the run ends with 2 like an unreadable frame
   const size_t voxels = width * height * depth;
   f3d_strain_stats strain_stats = {};
   f3d_principal_stats principal_stats = {};
@@ -577,7 +669,7 @@ int main(int argc, char** argv)
                             optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 3)};
     return OpticalFlowE::Containers(d);
   };
-  DerivedField derived[7] = {
+  DerivedField derived[8] = {
       {"strain", OpticalFlowE::kStrain, strain_fields, strain_names, false,
        [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputeStrain(validated_or(of), strain_fields, &strain_stats); },
        [&](size_t k) {
@@ -665,13 +757,71 @@ int main(int argc, char** argv)
          std::printf("rotation frame %zu -> frame %zu: angle max %.6g rad, mean %.6g rad, stretch max %.6g, min %.6g, %llu folded, %llu "
                      "undefined of %zu voxels\n", cumulative ? size_t(0) : k, k + 1, st.theta_max, mean, st.l1_max, st.l3_min, st.folded,
                      static_cast<unsigned long long>(voxels) - st.defined - st.folded, voxels);
+       }},
+      // the same source as --detrend; the table of the labels is written with the line
+      {"labelres", OpticalFlowE::kLabelMotion, label_model >= 0 ? 1u : 0u, labelres_names, false,
+       [&](const OpticalFlowE::Displacement& of) {
+         return optical_flow_e.ComputeLabelMotion(validated_or(of), n_labels, label_model, label_min_voxels, label_fits.data(),
+                                                  label_state.data(), label_rms_after.data(), &label_info);
+       },
+       [&](size_t k) {
+         const double degrees = 180.0 / 3.14159265358979323846;
+         const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
+         std::FILE* csv = std::fopen((tag + "_labelmotion.csv").c_str(), "w");
+         if (csv) {
+           std::fprintf(csv, "label,status,n,cx,cy,cz,tx,ty,tz,%srms_before,rms_after\n",
+                        label_model == F3D_MOTION_RIGID ? "angle_deg,ax,ay,az,"
+                        : label_model == F3D_MOTION_AFFINE ? "m00,m01,m02,m10,m11,m12,m20,m21,m22," : "");
+         } else {
+           std::printf("Error: cannot write %s_labelmotion.csv\n", tag.c_str());
+           label_table_failed = true;
+         }
+         size_t count[4] = {0, 0, 0, 0};
+         std::vector<double> length;
+         double max_angle = 0.0;
+         for (size_t l = 0; l < n_labels; ++l) {
+           const f3d_motion_fit& f = label_fits[l];
+           const int state = label_state[l];
+           ++count[state];
+           const double sine = std::sqrt((f.axial[0] * f.axial[0] + f.axial[1] * f.axial[1]) + f.axial[2] * f.axial[2]);
+           const double unit = sine > 0 ? 1.0 / sine : 0.0;
+           const double angle = std::atan2(sine, f.cos_angle) * degrees;
+           if (state == F3D_LABEL_OK) {
+             length.push_back(std::sqrt((f.t[0] * f.t[0] + f.t[1] * f.t[1]) + f.t[2] * f.t[2]));
+             if (label_model == F3D_MOTION_RIGID) max_angle = std::max(max_angle, angle);
+           }
+           if (!csv) continue;
+           std::fprintf(csv, "%zu,%s,%llu,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,", l + 1, label_status[state], f.n, f.centre[0], f.centre[1],
+                        f.centre[2], f.t[0], f.t[1], f.t[2]);
+           if (label_model == F3D_MOTION_RIGID)
+             std::fprintf(csv, "%.9g,%.9g,%.9g,%.9g,", state == F3D_LABEL_OK ? angle : 0.0, f.axial[0] * unit, f.axial[1] * unit,
+                          f.axial[2] * unit);
+           else if (label_model == F3D_MOTION_AFFINE)
+             std::fprintf(csv, "%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,", f.M[0], f.M[1], f.M[2], f.M[3], f.M[4], f.M[5], f.M[6],
+                          f.M[7], f.M[8]);
+           std::fprintf(csv, "%.9g,%.9g\n", f.rms_before, label_rms_after[l]);
+         }
+         const bool write_error = csv && std::ferror(csv) != 0;
+         if (csv && (std::fclose(csv) != 0 || write_error)) {
+           std::printf("Error: cannot write %s_labelmotion.csv\n", tag.c_str());
+           label_table_failed = true;
+         }
+         double median = std::nan("");
+         if (!length.empty()) {
+           std::sort(length.begin(), length.end());
+           median = length.size() % 2 ? length[length.size() / 2] : 0.5 * (length[length.size() / 2 - 1] + length[length.size() / 2]);
+         }
+         std::printf("label motion frame %zu -> frame %zu (%s): %zu labels fitted, %zu empty, %zu small, %zu degenerate; median |t| %.6g, ",
+                     cumulative ? size_t(0) : k, k + 1, motion_models[label_model], count[0], count[1], count[2], count[3], median);
+         if (label_model == F3D_MOTION_RIGID) std::printf("max angle %.6g deg, ", max_angle);
+         std::printf("%llu foreign, %llu out of range voxels\n", label_info.foreign, label_info.out_of_range);
        }}};
   // the order in which the features run and their files and lines come out: as listed, with the rotation after the principal strains,
   // or with --use-validated the match (whose zncc may be the mask) and the validated field first
-  DerivedField* order[7] = {&derived[0], &derived[1], &derived[6], &derived[2], &derived[3], &derived[4], &derived[5]};
+  DerivedField* order[8] = {&derived[0], &derived[1], &derived[6], &derived[2], &derived[3], &derived[4], &derived[5], &derived[7]};
   if (use_validated) {
-    DerivedField* const first[7] = {&derived[3], &derived[5], &derived[0], &derived[1], &derived[6], &derived[2], &derived[4]};
-    for (int i = 0; i < 7; ++i) order[i] = first[i];
+    DerivedField* const first[8] = {&derived[3], &derived[5], &derived[0], &derived[1], &derived[6], &derived[2], &derived[4], &derived[7]};
+    for (int i = 0; i < 8; ++i) order[i] = first[i];
   }
   for (DerivedField& f : derived)
     for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)
@@ -847,5 +997,5 @@ int main(int argc, char** argv)
 
   optical_flow_e.Destroy();
   f3d_host_shutdown();
-  return 0;
+  return label_table_failed ? 2 : 0;
 }

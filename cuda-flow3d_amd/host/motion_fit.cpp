@@ -173,3 +173,34 @@ bool SolveMotion(const struct f3d_motion_sums& s, int model, f3d_motion_fit* fit
   }
   return true;
 }
+
+// include/f3d_host.h, f3d_motion_solve_labels: the definition stands there.
+bool SolveLabelMotions(const struct f3d_motion_sums* sums, size_t n_labels, int model, unsigned long long min_voxels,
+                       const double volume_centre[3], f3d_motion_fit* fits, int* status, std::string* error)
+{
+  if (model != F3D_MOTION_TRANSLATION && model != F3D_MOTION_RIGID && model != F3D_MOTION_AFFINE) {
+    if (error) *error = "f3d_motion_solve_labels: model must be F3D_MOTION_TRANSLATION, F3D_MOTION_RIGID or F3D_MOTION_AFFINE";
+    return false;
+  }
+  for (size_t l = 0; l < n_labels; ++l) {
+    const struct f3d_motion_sums& s = sums[l];
+    f3d_motion_fit fit = {};
+    fit.n = s.n;
+    fit.model = model;
+    if (s.n == 0) {
+      status[l] = F3D_LABEL_EMPTY;
+    } else if (s.n < min_voxels) {
+      status[l] = F3D_LABEL_SMALL;
+    } else if (!SolveMotion(s, model, &fit, nullptr)) {
+      status[l] = F3D_LABEL_DEGENERATE;
+    } else {
+      status[l] = F3D_LABEL_OK;
+      const double n = static_cast<double>(s.n);
+      const double xb[3] = {s.Sx[0] / n, s.Sx[1] / n, s.Sx[2] / n};
+      for (int a = 0; a < 3; ++a) fit.centre[a] = volume_centre[a] + xb[a];
+      for (int r = 0; r < 3; ++r) fit.t[r] = fit.t[r] + ((fit.M[3 * r] * xb[0] + fit.M[3 * r + 1] * xb[1]) + fit.M[3 * r + 2] * xb[2]);
+    }
+    fits[l] = fit;
+  }
+  return true;
+}

@@ -11,4 +11,9 @@
 // false with `error` set when the model cannot be determined from the sums (the fit is then untouched)
 bool SolveMotion(const struct f3d_motion_sums& sums, int model, f3d_motion_fit* fit, std::string* error);
 
+// f3d_motion_solve_labels of include/f3d_host.h: one SolveMotion per label about the volume centre, the status F3D_LABEL_* of each, and
+// an OK fit moved to the label's centroid.  false with `error` set for an unknown model only.
+bool SolveLabelMotions(const struct f3d_motion_sums* sums, size_t n_labels, int model, unsigned long long min_voxels,
+                       const double volume_centre[3], f3d_motion_fit* fits, int* status, std::string* error);
+
 #endif

@@ -37,6 +37,13 @@ extern "C" int f3d_motion_sums(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_dev
 extern "C" int f3d_remove_motion(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr out_u, f3d_devptr out_v, f3d_devptr out_w,
                                  const f3d_motion_fit* fit, size_t width, size_t height, size_t depth, f3d_motion_residual* stats)
     __attribute__((weak));
+extern "C" int f3d_label_motion_sums(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr labels, size_t n_labels, f3d_devptr weight,
+                                     float weight_min, size_t width, size_t height, size_t depth, struct f3d_motion_sums* out,
+                                     f3d_label_info* info) __attribute__((weak));
+extern "C" int f3d_remove_label_motion(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr labels, size_t n_labels,
+                                       const f3d_motion_fit* fits, const int* status, f3d_devptr out_u, f3d_devptr out_v,
+                                       f3d_devptr out_w, size_t width, size_t height, size_t depth, f3d_motion_residual* stats)
+    __attribute__((weak));
 extern "C" int f3d_validate_displacement(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr weight, float weight_min, unsigned step,
                                          float eps, float threshold, unsigned min_neighbours, unsigned mode, const f3d_devptr out[4],
                                          unsigned fields, size_t width, size_t height, size_t depth, f3d_validate_stats* stats)
@@ -112,10 +119,13 @@ const unsigned kValidatedSpare = 4u;
 const int kValidatedContainers = 7;
 const unsigned kValidatedGroups[kValidatedContainers] = {F3D_VALIDATE_R, F3D_VALIDATE_D, F3D_VALIDATE_D, F3D_VALIDATE_D,
                                                          kValidatedSpare,  kValidatedSpare,  kValidatedSpare};
-const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3, 4, 7};
+// the residual u, v, w of the per-label motion, and the container of the labels (a bit of its own, never downloaded)
+const unsigned kLabelResidual = 1u, kLabelLabels = 2u;
+const unsigned kLabelMotionGroups[4] = {kLabelResidual, kLabelResidual, kLabelResidual, kLabelLabels};
+const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3, 4, 7, 4};
 const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr,
                                                                      kMatchGroups,  nullptr,          kValidatedGroups,
-                                                                     kPolarGroups};
+                                                                     kPolarGroups,  kLabelMotionGroups};
 const char* const kTrajectoryNotStarted = "the trajectory was not started (ResetTrajectory first)";
 
 }  // namespace
@@ -147,7 +157,11 @@ OpticalFlowE::OpticalFlowE()
                 "the device library has no f3d_validate_displacement (displacement validation)", "no displacement to validate"},
                {this, kDerivedFields[kPolar], kPolarGroups, "the rotation and stretch containers do not fit beside the driver's on the device",
                 "a requested rotation or stretch field has not been computed", "no host volume for a requested rotation or stretch field",
-                "the device library has no f3d_polar_decomposition (local rotation and stretches)", "no displacement to differentiate"}}
+                "the device library has no f3d_polar_decomposition (local rotation and stretches)", "no displacement to differentiate"},
+               {this, kDerivedFields[kLabelMotion], kLabelMotionGroups,
+                "the containers of the per-label motion do not fit beside the driver's on the device",
+                "the residual of the per-label motion has not been computed", "no host volume for a field of the per-label residual",
+                "the device library has no f3d_label_motion_sums (per-label motion)", "no displacement to fit the motion of the labels to"}}
 {
   // same initialisation order as the reference's forward_list built with push_front (optical_flow_e.cpp:34-39)
   cuda_operations_ = {&cuop_solve_, &cuop_resample_, &cuop_register_, &cuop_median_, &cuop_convolution_, &cuop_add_};
@@ -701,6 +715,55 @@ bool OpticalFlowE::ComputeMotion(const Displacement& of, int model, DevicePtr we
                                                     c.depth, residual))))
     return false;
   *fit = solved;
+  return true;
+}
+
+bool OpticalFlowE::UploadLabels(const int* labels)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!labels) return set.Fail("no labels to upload");
+  if (!set.Allocate(kLabelLabels)) return false;
+  const DataSize4& c = dev_container_size_;
+  // the copy moves bytes: the int32 labels arrive as they are
+  return set.Check(CheckDeviceError(f3d_copy3d_h2d(set.ptr[3], c.pitch, c.height, 0, reinterpret_cast<const float*>(labels), c.width,
+                                                   c.height, c.depth)));
+}
+
+bool OpticalFlowE::ComputeLabelMotion(const Displacement& of, size_t n_labels, int model, unsigned long long min_voxels,
+                                      f3d_motion_fit* fits, int* status, double* rms_after, f3d_label_info* info)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, f3d_label_motion_sums != nullptr, d)) return false;
+  if (!f3d_remove_label_motion) return set.Fail("the device library has no f3d_remove_label_motion (per-label motion)");
+  if (!fits || !status) return set.Fail("no fits or status to write to");
+  if (n_labels == 0 || n_labels > (static_cast<size_t>(1) << 22)) return set.Fail("n_labels must be 1 .. 2^22");
+  const DevicePtr labels = set.ptr[3];
+  if (!labels) return set.Fail("no labels on the device (UploadLabels first)");
+  if (!set.Allocate(kLabelResidual)) return false;
+  const f3d_size4 c = Container();
+  std::vector<struct f3d_motion_sums> sums(n_labels);
+  if (!set.Check(CheckDeviceError(f3d_set_container(&c))) ||
+      !set.Check(CheckDeviceError(f3d_label_motion_sums(d[0], d[1], d[2], labels, n_labels, 0, 0.f, c.width, c.height, c.depth,
+                                                        sums.data(), info))))
+    return false;
+  const double centre[3] = {0.5 * static_cast<double>(c.width - 1), 0.5 * static_cast<double>(c.height - 1),
+                            0.5 * static_cast<double>(c.depth - 1)};
+  std::string why;
+  if (!SolveLabelMotions(sums.data(), n_labels, model, min_voxels, centre, fits, status, &why)) return set.Fail(why.c_str());
+  if (!set.Check(CheckDeviceError(f3d_remove_label_motion(d[0], d[1], d[2], labels, n_labels, fits, status, set.ptr[0], set.ptr[1],
+                                                          set.ptr[2], c.width, c.height, c.depth, nullptr))))
+    return false;
+  if (!rms_after) return true;
+  if (!set.Check(CheckDeviceError(f3d_label_motion_sums(set.ptr[0], set.ptr[1], set.ptr[2], labels, n_labels, 0, 0.f, c.width, c.height,
+                                                        c.depth, sums.data(), nullptr))))
+    return false;
+  for (size_t l = 0; l < n_labels; ++l) {
+    const struct f3d_motion_sums& s = sums[l];
+    rms_after[l] = s.n ? std::sqrt(((s.Sdd[0] + s.Sdd[1]) + s.Sdd[2]) / static_cast<double>(s.n)) : std::nan("");
+  }
   return true;
 }
 

@@ -132,10 +132,13 @@ class OpticalFlowE : public OpticalFlowBase {
   //               rigid motion or affine map taken out.  Three outputs, the residual u, v, w, always all of them.
   //   kValidated  f3d_validate_displacement: the normalised median test and the repair of what it rejects.  Four outputs r, u, v, w
   //               selected by F3D_VALIDATE_R (r) and F3D_VALIDATE_D (u, v, w); the fill passes keep a second u, v, w beside them.
+  //   kLabelMotion f3d_label_motion_sums, the host solve per label (motion_fit.h) and f3d_remove_label_motion: the displacement with the
+  //               fit of each voxel's label taken out.  Three outputs, the residual u, v, w, always all of them, and a fourth container
+  //               that holds the labels (UploadLabels; never downloaded).
   // Each selected output gets a container of its own, allocated on first use and freed by ReleaseDerived() and Destroy().  Compute
   // enqueues on the library stream and waits only when stats is given.  Every call returns false with DerivedError() set when it
   // cannot run -- among other reasons when the device library lacks the entry point.
-  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kValidated, kPolar, kDerivedCount };
+  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kValidated, kPolar, kLabelMotion, kDerivedCount };
   enum MatchField : unsigned { kMatchWarped = 1u, kMatchZncc = 2u, kMatchRmsd = 4u };
   // the displacement a derived field is computed of
   struct Displacement {
@@ -167,6 +170,15 @@ class OpticalFlowE : public OpticalFlowBase {
   // Containers() hands to the strain, principal strain, polar and motion calls.
   bool ComputeValidated(const Displacement& of, DevicePtr weight, float weight_min, unsigned step, float eps, float threshold,
                         unsigned min_neighbours, unsigned mode, unsigned fill_passes, unsigned fields, f3d_validate_stats* stats);
+  // Per-label motion.  UploadLabels: width * height * depth int32 on frame 0's grid (0 background, 1 .. n_labels the bodies) into a
+  // container the driver keeps until ReleaseDerived(kLabelMotion) or Destroy().  ComputeLabelMotion: the sums of every label, waits,
+  // the solves on the host (fits and status: n_labels entries each, required; a label with fewer than min_voxels voxels is not
+  // fitted), the subtraction, and -- when rms_after (n_labels entries) is given -- the sums of the residual and a second wait:
+  // rms_after[L-1] = sqrt((Sdd_u + Sdd_v + Sdd_w) / n) of label L's residual, NaN where the label has none.  info (nullable) are the
+  // voxel counts of the first sums.
+  bool UploadLabels(const int* labels);
+  bool ComputeLabelMotion(const Displacement& of, size_t n_labels, int model, unsigned long long min_voxels, f3d_motion_fit* fits,
+                          int* status, double* rms_after, f3d_label_info* info);
   static int DerivedFieldCount(Derived which);
   static bool DerivedSelected(Derived which, int field, unsigned fields);
   DevicePtr DerivedContainer(Derived which, int field) const { return derived_[which].ptr[field]; }  // 0 until computed

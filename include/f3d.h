@@ -742,6 +742,67 @@ int f3d_remove_motion(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr out_u
                       const f3d_motion_fit* fit, size_t width, size_t height, size_t depth,
                       f3d_motion_residual* stats /* nullable; non-null waits */);
 
+/* Per-label motion of a displacement (no reference counterpart: the samples of in-situ tomography are mostly many bodies -- grains,
+ * fibres, particles -- and what is asked of them is a table per body: how far it moved, how far it turned, how well a rigid motion
+ * explains its voxels).  A segmentation is a container like every other (same pitch, 4 bytes per voxel) whose voxels are read as
+ * int32; no float instruction touches them.  Label 0 is background, label L in 1 .. n_labels is body L, every other value (negative or
+ * above n_labels) is foreign and ignored.  Two device passes with a host solve between them (f3d_motion_solve_labels of
+ * include/f3d_host.h), as for the whole volume above.
+ *
+ * f3d_label_motion_sums.  out[L-1] receives the moment sums of label L about the centre of the volume.  A voxel takes part when it is
+ * inside the volume, its label is in 1 .. n_labels, none of u, v, w is NaN there, weight[i] >= weight_min when weight is not 0 (a NaN
+ * weight fails), and |d_j| < 1024 for every component.  info (nullable) counts every voxel of the volume exactly once, in this order:
+ *   background     its label is 0
+ *   foreign        its label is outside 0 .. n_labels
+ *   absent         its label is in range, but a component is NaN or the weight fails
+ *   out_of_range   it passes the above, but some |d_j| >= 1024 (an infinity included)
+ *   used           it takes part
+ * The sums are exact integers, so they depend on no summation order and the device adds them with integer atomics:
+ *   q_j = (int)rintf(d_j * 16384.0f)     the product is exact (a power of two, no overflow; a denormal gives 0 either way), the rounding
+ *                                        is to nearest, ties to even; |q_j| <= 2^24
+ *   x2  = the doubled coordinates (2x - (width-1), 2y - (height-1), 2z - (depth-1)), as in f3d_motion_sums
+ * and over the voxels of a label that take part
+ *   n,  sum x2_i,  sum x2_i x2_k  (xx yy zz xy xz yz)             as in f3d_motion_sums
+ *   Id_j = sum q_j      Ixd_ij = sum x2_i q_j      Idd_j = sum q_j^2
+ * Each integer is rounded to binary64 once, to nearest even, and then scaled by a power of two (exact):
+ *   Sx = 0.5 sum x2      Sxx = 0.25 sum x2 x2      Sd_j = 2^-14 Id_j      Sxd_ij = 2^-15 Ixd_ij  (Sxd[3*i + j])      Sdd_j = 2^-28 Idd_j
+ * so Sd, Sxd and Sdd are the sums of the displacement quantised to 2^-14 voxel.  A label with no voxel gives all zeros (+0).
+ * Widths: over one 64 x 4 x 32 tile (2^13 voxels) every sum fits signed 64 bits (q^2 < 2^48, |x2 q| < 2^40); over a label it does not
+ * (Idd reaches 2^81), so the fifteen displacement sums are carried across tiles in two signed 64-bit limbs: a value v adds
+ * v & 0xffffffff to lo and v >> 32 (arithmetic shift) to hi, and the total is hi 2^32 + lo as a 128-bit integer on the host (lo only
+ * receives addends in [0, 2^32), at most 2^32 of them per label, and is read as unsigned).  The ten
+ * coordinate sums are single 64-bit words under the size limits of f3d_motion_sums, which hold here too.
+ * n_labels is 1 .. 2^22 (the accumulator is 320 B per label in a grow-only buffer of the library's, cleared on the stream before the
+ * kernel and copied down after it).  Geometry from the current container, whole volume, library stream; the call waits for the
+ * stream.  Refused (status 1, a message, nothing written): a null u, v, w, labels or out; n_labels 0 or above 2^22; a NaN weight_min
+ * when weight is given; an empty or too large size. */
+typedef struct f3d_label_info {
+  unsigned long long background, foreign, absent, out_of_range, used;
+} f3d_label_info;
+int f3d_label_motion_sums(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr labels, size_t n_labels,
+                          f3d_devptr weight /* 0: none */, float weight_min, size_t width, size_t height, size_t depth,
+                          struct f3d_motion_sums* out /* n_labels entries, host */, f3d_label_info* info /* nullable */);
+
+/* f3d_remove_label_motion.  fits and status are host arrays of n_labels entries, what f3d_motion_solve_labels wrote: the fit of label L
+ * is fits[L-1] and is used when status[L-1] is F3D_LABEL_OK.  Per voxel (x, y, z) of label L and component r, with
+ * X = (double)x - centre_L[0], Y and Z likewise, in binary64, every operation rounded on its own, in f3d_remove_motion's order:
+ *   res_r = (float)((double)d_r - (t_r + ((M_r0 * X + M_r1 * Y) + M_r2 * Z)))
+ * All three outputs are NaN where the label is background or foreign and where the label's status is not F3D_LABEL_OK; NaN in, NaN out
+ * (per component).  In place (out_u == u, out_v == v, out_w == w) is allowed; any other aliasing between the six volumes, and the
+ * label container among them, is refused, and so are a null volume, fits or status, n_labels 0 or above 2^22, a non-finite entry of
+ * centre, t or M in a fit whose status is F3D_LABEL_OK, and an empty size; a refused call writes nothing.  The library uploads the
+ * table of the fits per call and waits for that copy.  stats (nullable; asking waits for the stream) are f3d_remove_motion's, of the
+ * stored residuals of the whole volume in the same fixed order.  The rms of one label's residual is sqrt((Sdd_u + Sdd_v + Sdd_w) / n)
+ * of f3d_label_motion_sums of the residual.  Geometry from the current container, whole volume, library stream. */
+#define F3D_LABEL_OK 0         /* fitted                                                              */
+#define F3D_LABEL_EMPTY 1      /* no voxel took part                                                  */
+#define F3D_LABEL_SMALL 2      /* fewer voxels than min_voxels                                        */
+#define F3D_LABEL_DEGENERATE 3 /* the model is not determined (f3d_motion_solve refuses these sums)   */
+int f3d_remove_label_motion(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr labels, size_t n_labels,
+                            const f3d_motion_fit* fits, const int* status /* n_labels each, host */, f3d_devptr out_u,
+                            f3d_devptr out_v, f3d_devptr out_w, size_t width, size_t height, size_t depth,
+                            f3d_motion_residual* stats /* nullable; non-null waits */);
+
 /* Validation of a displacement (no reference counterpart: the normalised median test of PIV and volume-correlation post-processing,
  * Westerweel & Scarano 2005, which a workflow applies between the displacement and the strain).  A vector is compared with the median
  * of its neighbours, scaled by the median residual of those neighbours; a rejected vector becomes NaN (which f3d_flow_strain and

@@ -160,6 +160,22 @@ int f3d_flow_match_end(f3d_flow flow);
  * and the fit untouched when refused. */
 int f3d_motion_solve(const struct f3d_motion_sums* sums, int model, f3d_motion_fit* fit);
 
+/* The solve between f3d_label_motion_sums and f3d_remove_label_motion (include/f3d.h, which also defines F3D_LABEL_*): one fit per
+ * label.  Host code, no device needed.  sums, fits and status have n_labels entries; label L is entry L-1.  status[L-1] is
+ *   F3D_LABEL_EMPTY       when n == 0
+ *   F3D_LABEL_SMALL       when n < min_voxels
+ *   F3D_LABEL_DEGENERATE  when f3d_motion_solve of these sums (about the volume centre) refuses
+ *   F3D_LABEL_OK          otherwise
+ * An OK fit is then moved from the centre of the volume to the centroid of the label, so that t is the motion of the body itself and
+ * not an extrapolation to the middle of the volume.  With xbar_a = Sx_a / n, in binary64, every operation rounded on its own, in
+ * exactly this order:
+ *   centre_a = volume_centre_a + xbar_a
+ *   t_r      = t_r + ((M_r0 * xbar_0 + M_r1 * xbar_1) + M_r2 * xbar_2)
+ * M and everything else f3d_motion_solve reports stay.  A label that is not OK gets a zeroed fit with n and model set.  Returns non-zero
+ * (f3d_host_last_error() set, nothing written) only for an unknown model or a null pointer. */
+int f3d_motion_solve_labels(const struct f3d_motion_sums* sums, size_t n_labels, int model, unsigned long long min_voxels,
+                            const double volume_centre[3], f3d_motion_fit* fits, int* status);
+
 /* Motion of the flow the driver holds or of the trajectory (source F3D_STRAIN_OF_FLOW / F3D_STRAIN_OF_TRAJECTORY): f3d_motion_sums on
  * the device, f3d_motion_solve, f3d_remove_motion into three containers the driver keeps until f3d_flow_motion_end (or
  * f3d_flow_destroy).  out[0..2] receive the residual u, v, w (width * height * depth floats each; all three required); fit receives the
@@ -171,6 +187,20 @@ int f3d_motion_solve(const struct f3d_motion_sums* sums, int model, f3d_motion_f
 int f3d_flow_motion_compute(f3d_flow flow, int source, int model, float min_zncc, float* const out[3], f3d_motion_fit* fit,
                             f3d_motion_residual* residual);
 int f3d_flow_motion_end(f3d_flow flow);
+
+/* Per-label motion of the flow the driver holds or of the trajectory (source F3D_STRAIN_OF_FLOW / F3D_STRAIN_OF_TRAJECTORY):
+ * f3d_label_motion_sums on the device, f3d_motion_solve_labels, f3d_remove_label_motion into three containers the driver keeps until
+ * f3d_flow_label_motion_end (or f3d_flow_destroy), and f3d_label_motion_sums of the residual.  labels: width * height * depth int32 on
+ * the grid of the displacement (frame 0's for the trajectory), 0 background, 1 .. n_labels the bodies; they are uploaded into a
+ * container the driver keeps, and a null labels reuses the ones uploaded by an earlier call.  out[0..2] receive the residual u, v, w
+ * (all three required; NaN where a voxel's label has no fit); fits and status (n_labels entries each, required) what
+ * f3d_motion_solve_labels writes; rms_after (nullable, n_labels entries) the rms of each label's residual, sqrt((Sdd_u + Sdd_v +
+ * Sdd_w) / n) of the sums of the residual, NaN where the label has none; info (nullable) the voxel counts of the first sums.  A device
+ * library without f3d_label_motion_sums or f3d_remove_label_motion still loads; then the call fails with a message naming the entry. */
+int f3d_flow_label_motion_compute(f3d_flow flow, int source, const int* labels, size_t n_labels, int model, unsigned long long min_voxels,
+                                  float* const out[3], f3d_motion_fit* fits, int* status, double* rms_after /* nullable */,
+                                  f3d_label_info* info /* nullable */);
+int f3d_flow_label_motion_end(f3d_flow flow);
 
 /* Validation of the flow the driver holds or of the trajectory (source F3D_STRAIN_OF_FLOW / F3D_STRAIN_OF_TRAJECTORY):
  * f3d_validate_displacement (include/f3d.h has the definition and what step, eps, threshold, min_neighbours and mode mean) into
