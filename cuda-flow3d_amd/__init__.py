@@ -345,6 +345,7 @@ def host():
         "f3d_op_solve_p_last": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz), C.POINTER(C.c_int)],
         "f3d_op_solve_p_fused_weights": [C.c_void_p, C.POINTER(C.c_int)],
         "f3d_plan_solve_piecemeal": [_sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5,
+        "f3d_plan_sweeps": [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2 + [C.c_int],
         "f3d_pflow_create": [C.POINTER(C.c_void_p)], "f3d_pflow_initialize": [C.c_void_p, _sz, _sz, _sz],
         "f3d_pflow_compute": [C.c_void_p, _fp, _fp, _sz, _sz, _sz, pp, C.c_int, _fp, _fp, _fp, _fp],
         "f3d_pflow_stats": [C.c_void_p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)], "f3d_pflow_destroy": [C.c_void_p],
@@ -1207,6 +1208,18 @@ def plan_solve_piecemeal(budget_bytes, width, height, depth, inner_iterations, o
     check(host().f3d_plan_solve_piecemeal(budget_bytes, width, height, depth, inner_iterations, outer_iterations,
                                           forced_outer_per_pass, overlap_mode, *[C.byref(o) for o in out]))
     return tuple(o.value for o in out)
+
+
+def plan_sweeps(inner, fused, tri, carry):
+    """[(sweeps, next_weights), ...]: the launches the solver drivers cut the `inner` sweeps of one outer iteration into (host
+    arithmetic).  fused / tri: the solve takes the fused / the three-stage launches; carry: another outer iteration follows and
+    the driver can take its weights along."""
+    cap = max(1, inner)
+    sweeps, weights = (C.c_int * cap)(), (C.c_int * cap)()
+    n = host().f3d_plan_sweeps(inner, int(bool(fused)), int(bool(tri)), int(bool(carry)), sweeps, weights, cap)
+    if n < 0:
+        raise F3dError("f3d_plan_sweeps failed")
+    return [(sweeps[i], bool(weights[i])) for i in range(n)]
 
 
 class Operation:

@@ -640,6 +640,17 @@ int f3d_plan_solve_piecemeal(size_t budget_bytes, size_t width, size_t height, i
   return 0;
 }
 
+int f3d_plan_sweeps(int inner, int fused, int tri, int carry, int* sweeps, int* next_weights, int capacity)
+{
+  const std::vector<SweepLaunch> cut = CutSweeps(inner, fused != 0, tri != 0, carry != 0);
+  if (static_cast<int>(cut.size()) > capacity || (!cut.empty() && (!sweeps || !next_weights))) return -1;
+  for (size_t i = 0; i < cut.size(); ++i) {
+    sweeps[i] = cut[i].sweeps;
+    next_weights[i] = cut[i].next_weights ? 1 : 0;
+  }
+  return static_cast<int>(cut.size());
+}
+
 size_t f3d_max_warp_level(size_t width, size_t height, size_t depth, float scale_factor)
 {
   return OpticalFlowBase::GetMaxWarpLevel(width, height, depth, scale_factor);

@@ -12,6 +12,7 @@
 
 #include "common_utils.h"
 #include "hip_utils.h"
+#include "solve_schedule.h"
 
 // Declared weak: the host library keeps loading against a device library that lacks the entry (the address is then null, and the
 // solve operator leaves the flow update to its caller, as before the entry existed).
@@ -474,7 +475,7 @@ void CudaOperationSolve::Execute(OperationParameters& params)
   GET_PARAM_OR_RETURN(params, float, hy, "hy");
   GET_PARAM_OR_RETURN(params, float, hz, "hz");
   GET_PARAM_OR_RETURN(params, DataSize4, data_size, "data_size");
-  NoteSolveWeights(equation_alpha, hx, hy, hz);
+  const bool fused = FusedSweepsEnabled() && SolveWeightsPlain(equation_alpha, hx, hy, hz);
   // Optional "flow_update" (bool*): its presence asks for flow += increments inside the solve.  Granted when the level ends with a launch
   // of ONE sweep and the device library has the entry (f3d_solve_sweep_add then writes the sums where that sweep would have written the increments); *flow_update tells the
   // caller whether dev_flow_d* (after the swaps) hold the sums -- true -- or the increments as always -- false, the caller adds.
@@ -508,51 +509,17 @@ void CudaOperationSolve::Execute(OperationParameters& params)
   }
 
   const size_t w = data_size.width, h = data_size.height, d = data_size.depth;
-  // Launch schedule of one outer iteration (the same bit pattern whichever way it is cut):
-  //   phi/ksi (first outer iteration of a level only), then the sweeps in fused groups -- three per launch on small and mid-size
-  //   levels (f3d_solve_sweep3), two per launch elsewhere (f3d_solve_sweep2) -- with one buffer swap per launch; when another outer
-  //   iteration follows, the last launch also computes the phi/ksi of the NEXT iteration into the second weight pair
-  //   (f3d_solve_sweep2_phi_ksi behind two sweeps, f3d_solve_sweep_phi_ksi behind one).  Defaults (5 sweeps): 2 launches per outer
-  //   iteration on levels up to ~144^3, 3 above, instead of the reference's 6.
-  const bool fuse_weights = FusedSweepsEnabled() && FusedPhiKsiEnabled() && outer_iterations_count > 1 &&
-                            dev_container_size_.pitch % 256 == 0 && EnsureWeightScratch();
-  // Small and mid-size levels take the three-stage launches (k_tri: no z-slab windows yet, frames not derivatives): with them the
-  // last launch of an outer iteration that is not the level's last can carry the next weights behind TWO sweeps, so the default five
-  // sweeps are (S, S, S) + (S, S, P); without them it carries them behind one, and only an odd count ends that way.
-  const bool tri = FusedSweepsEnabled() && slab_ == nullptr && dev_container_size_.pitch % 256 == 0 && inner_iterations_count >= 2 &&
-                   ThreeStageLaunchesPay(w, h, d);
-  // How the `inner` sweeps of an outer iteration are cut into launches: groups of 3 / 2 / 1 sweeps, the last group taking the next
-  // weights along when another outer iteration follows (`more`) and the group is 2 (three-stage) or 1 sweeps.
-  auto next_group = [&](size_t remaining, bool more) -> size_t {
-    if (!FusedSweepsEnabled()) return 1;
-    const bool weights_wanted = more && fuse_weights;
-    if (tri) {
-      if (weights_wanted) {
-        if (remaining == 2) return 2;                 // (S, S, P)
-        if (remaining == 3) return 1;                 // S, then (S, S, P)
-        if (remaining == 4) return 2;                 // (S, S), then (S, S, P)
-      }
-      if (remaining >= 3) return 3;
-    }
-    if (weights_wanted && remaining == 3 && !tri) return 2;   // (S, S), then (S, P)
-    return remaining >= 2 ? 2 : 1;
-  };
-  // the weights of the last outer iteration must end in the caller's dev_phi / dev_ksi (as in the reference): every outer iteration
-  // whose last group carries the next weights hands over to the other pair once; count the hand-overs and start on the right side
-  auto carries_weights = [&](size_t group, size_t remaining_after, bool more) {
-    return more && fuse_weights && remaining_after == 0 && ((tri && group == 2) || group == 1);
-  };
-  size_t hand_overs = 0;
-  for (size_t i = 0; i + 1 < outer_iterations_count; ++i) {
-    size_t remaining = inner_iterations_count, group = 0;
-    while (remaining > 0) {
-      group = next_group(remaining, true);
-      remaining -= group;
-    }
-    if (carries_weights(group, 0, true)) ++hand_overs;
-  }
+  const int K = static_cast<int>(inner_iterations_count);
+  // The launches of an outer iteration are CutSweeps' (solve_schedule.h); here: whether the last one can take the next weights along
+  // (a second weight pair), and whether the level takes the three-stage launches (k_tri: no z-slab windows yet, frames not derivatives).
+  const bool fuse_weights = fused && FusedPhiKsiEnabled() && outer_iterations_count > 1 && dev_container_size_.pitch % 256 == 0 &&
+                            EnsureWeightScratch();
+  const bool tri = fused && slab_ == nullptr && dev_container_size_.pitch % 256 == 0 && K >= 2 && ThreeStageLaunchesPay(w, h, d);
+  const std::vector<SweepLaunch> cut_more = CutSweeps(K, fused, tri, fuse_weights), cut_last = CutSweeps(K, fused, tri, false);
+  // the weights of the last outer iteration must end in the caller's dev_phi / dev_ksi (as in the reference): every outer iteration but
+  // the last hands over to the other pair once when its cut ends in a launch that carries; start on the side an odd count asks for
   DevicePtr phi_cur = dev_phi, ksi_cur = dev_ksi, phi_nxt = phi_alt_, ksi_nxt = ksi_alt_;
-  if (hand_overs % 2 == 1) {
+  if (!cut_more.empty() && cut_more.back().next_weights && (outer_iterations_count - 1) % 2 == 1) {
     std::swap(phi_cur, phi_nxt);
     std::swap(ksi_cur, ksi_nxt);
   }
@@ -561,7 +528,7 @@ void CudaOperationSolve::Execute(OperationParameters& params)
   // level instead of the frames (the reference recomputes them for every voxel in each of its 240 launches per level).
   // (thin volumes: the launches on frames march along y with all planes in the tile, two workgroups per CU -- faster than the z march
   // the derivative builds would take, so such a level stays on the frames)
-  const bool on_derivatives = !tri && FusedSweepsEnabled() && FrameDerivativesEnabled() && slab_ == nullptr && inner_iterations_count >= 2 &&
+  const bool on_derivatives = !tri && fused && FrameDerivativesEnabled() && slab_ == nullptr && K >= 2 &&
                               f3d_fused_launches_march_along_y(w, h, d) == 0 &&
                               dev_container_size_.pitch % 256 == 0 && EnsureDerivativeScratch() &&
                               !CheckDeviceError(f3d_frame_derivatives(dev_frame_0, dev_frame_1, w, h, d, hx, hy, hz, fder_[0], fder_[1],
@@ -573,9 +540,9 @@ void CudaOperationSolve::Execute(OperationParameters& params)
       return;
     weights_ready = false;
     const bool more = i + 1 < outer_iterations_count;
-    for (size_t j = 0; j < inner_iterations_count;) {
-      const size_t group = next_group(inner_iterations_count - j, more);
-      const bool with_weights = carries_weights(group, inner_iterations_count - j - group, more);
+    for (const SweepLaunch& launch : more ? cut_more : cut_last) {
+      const int group = launch.sweeps;
+      const bool with_weights = launch.next_weights;
       int status;
       if (group == 3)
         status = f3d_solve_sweep3(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_cur, ksi_cur,
@@ -598,7 +565,7 @@ void CudaOperationSolve::Execute(OperationParameters& params)
         status = f3d_solve_sweep_phi_ksi(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr,
                                          phi_cur, ksi_cur, w, h, d, hx, hy, hz, equation_alpha, equation_smoothness, equation_data,
                                          *tdu_ptr, *tdv_ptr, *tdw_ptr, phi_nxt, ksi_nxt, slab_);
-      else if (flow_update && f3d_solve_sweep_add && !more && j + 1 == inner_iterations_count) {  // the last launch of the level, and it is one sweep
+      else if (flow_update && f3d_solve_sweep_add && !more && launch.first + 1 == K) {  // the last launch of the level, and it is one sweep
         status = f3d_solve_sweep_add(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_cur,
                                      ksi_cur, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
         *flow_update = status == 0;
@@ -614,7 +581,6 @@ void CudaOperationSolve::Execute(OperationParameters& params)
         std::swap(ksi_cur, ksi_nxt);
         weights_ready = true;
       }
-      j += group;
     }
     if (!silent) {
       CheckDeviceError(f3d_stream_sync());

@@ -16,6 +16,7 @@
 #include "common_utils.h"
 #include "hip_utils.h"
 #include "slab_plan.h"
+#include "solve_schedule.h"
 
 namespace {
 
@@ -723,7 +724,7 @@ void CudaOperationSolveP::Execute(OperationParameters& params)
   GET_PARAM_OR_RETURN(params, float, hy, "hy");
   GET_PARAM_OR_RETURN(params, float, hz, "hz");
   GET_PARAM_OR_RETURN(params, DataSize4, data_size, "data_size");
-  NoteSolveWeights(equation_alpha, hx, hy, hz);
+  const bool fused = FusedSweepsEnabled() && SolveWeightsPlain(equation_alpha, hx, hy, hz);
 
   Data3D* fixed[5] = {p_frame_0, p_frame_1, p_flow_u, p_flow_v, p_flow_w};
   Data3D* inc[3] = {p_flow_du, p_flow_dv, p_flow_dw};
@@ -774,7 +775,8 @@ void CudaOperationSolveP::Execute(OperationParameters& params)
   // relative halos and more residencies -- 32.8 s of solver against 30.2 s with the 13.  So the fused launch is taken only where the
   // level fits the budget with all 15 fields (one residency, no halo: the device is what is left to save on); F3D_P_FUSED=1
   // forces it for chunked levels too (the tests run both).
-  bool fuse_weights = FusedSweepsEnabled() && FusedPhiKsiEnabled() && K % 2 == 1 && outer > 1;
+  // (wanted where the cut of an outer iteration that may carry the weights ends in a launch that does: an odd K)
+  bool fuse_weights = fused && FusedPhiKsiEnabled() && outer > 1 && CutSweeps(K, fused, false, true).back().next_weights;
   const bool fuse_when_chunked = std::getenv("F3D_P_FUSED") && std::atoi(std::getenv("F3D_P_FUSED")) == 1;
   auto make_plan = [&](int fields) {
     SolvePiecemealPlan p = PlanSolvePiecemeal(PiecemealBudgetBytes(), W, H, D, K, outer, forced, overlap_mode, fields);
@@ -864,7 +866,7 @@ void CudaOperationSolveP::Execute(OperationParameters& params)
     Utils::PrintProgressBar(0.f);
   }
   const size_t rows = static_cast<size_t>(planes) * H;
-  const bool fused = FusedSweepsEnabled();
+  const std::vector<SweepLaunch> cut_more = CutSweeps(K, fused, false, fuse_weights), cut_last = CutSweeps(K, fused, false, false);
   size_t chunk_counter = 0;
   // Overlapped schedule, every field in the chunk sets: the windows of two neighbouring chunks share 2 x reach planes, and for the five
   // fields nothing writes -- the two frames, u, v, w -- those planes are in the OTHER chunk set already when a chunk starts: they are
@@ -987,41 +989,32 @@ void CudaOperationSolveP::Execute(OperationParameters& params)
                                          equation_smoothness, equation_data, buf[PHI], buf[KSI], &pw)))
           return;
         weights_ready = false;
-        for (int s = 0; s < K;) {
-          const bool pair = fused && s + 2 <= K;
-          const f3d_slab sw = window(g + K - 1 - s - (pair ? 1 : 0));
-          if (fuse_weights && !pair && s == K - 1 && j + 1 < n) {
-            // The next outer iteration wants its weights on window(g - 1): this sweep's window shrunk by one plane wherever it does
-            // not end at a face of the volume (the weights of a plane need the new increments of both z neighbours).  The launch
-            // computes the sweep on those edge planes anyway and stores it there too (keep_below / keep_above).
-            const int lo_in = sw.z_lo > 0 ? 1 : 0, hi_in = sw.z_hi < D ? 1 : 0;
-            const f3d_slab ww = {sw.z_base, sw.z_lo + lo_in, sw.z_hi - hi_in};
-            if (ww.z_hi - ww.z_lo >= 1) {
-              if (CheckDeviceError(f3d_solve_sweep_phi_ksi_edges(buf[F0], buf[F1], buf[FU], buf[FV], buf[FW], buf[DU], buf[DV], buf[DW],
-                                                                 buf[PHI], buf[KSI], W, H, D, hx, hy, hz, equation_alpha,
-                                                                 equation_smoothness, equation_data, buf[TDU], buf[TDV], buf[TDW],
-                                                                 buf[PHI2], buf[KSI2], &ww, lo_in, hi_in)))
-                return;
-              std::swap(buf[DU], buf[TDU]);
-              std::swap(buf[DV], buf[TDV]);
-              std::swap(buf[DW], buf[TDW]);
-              std::swap(buf[PHI], buf[PHI2]);
-              std::swap(buf[KSI], buf[KSI2]);
-              weights_ready = true;
-              s += 1;
-              continue;
-            }
-          }
+        for (const SweepLaunch& launch : j + 1 < n ? cut_more : cut_last) {
+          const bool pair = launch.sweeps == 2;
+          const f3d_slab sw = window(g + K - 1 - launch.first - (pair ? 1 : 0));
+          // The next outer iteration wants its weights on window(g - 1): this sweep's window shrunk by one plane wherever it does
+          // not end at a face of the volume (the weights of a plane need the new increments of both z neighbours).  The launch
+          // computes the sweep on those edge planes anyway and stores it there too (keep_below / keep_above).
+          const int lo_in = sw.z_lo > 0 ? 1 : 0, hi_in = sw.z_hi < D ? 1 : 0;
+          const f3d_slab ww = {sw.z_base, sw.z_lo + lo_in, sw.z_hi - hi_in};
+          const bool with_weights = launch.next_weights && ww.z_hi - ww.z_lo >= 1;   // (a window too thin for that: the plain sweep)
           const int status =
-              pair ? f3d_solve_sweep2(buf[F0], buf[F1], buf[FU], buf[FV], buf[FW], buf[DU], buf[DV], buf[DW], buf[PHI], buf[KSI], W, H, D,
-                                      hx, hy, hz, equation_alpha, buf[TDU], buf[TDV], buf[TDW], &sw)
-                   : f3d_solve_sweep(buf[F0], buf[F1], buf[FU], buf[FV], buf[FW], buf[DU], buf[DV], buf[DW], buf[PHI], buf[KSI], W, H, D,
-                                     hx, hy, hz, equation_alpha, buf[TDU], buf[TDV], buf[TDW], &sw);
+              with_weights ? f3d_solve_sweep_phi_ksi_edges(buf[F0], buf[F1], buf[FU], buf[FV], buf[FW], buf[DU], buf[DV], buf[DW], buf[PHI],
+                                                           buf[KSI], W, H, D, hx, hy, hz, equation_alpha, equation_smoothness, equation_data,
+                                                           buf[TDU], buf[TDV], buf[TDW], buf[PHI2], buf[KSI2], &ww, lo_in, hi_in)
+              : pair ? f3d_solve_sweep2(buf[F0], buf[F1], buf[FU], buf[FV], buf[FW], buf[DU], buf[DV], buf[DW], buf[PHI], buf[KSI], W, H, D,
+                                        hx, hy, hz, equation_alpha, buf[TDU], buf[TDV], buf[TDW], &sw)
+                     : f3d_solve_sweep(buf[F0], buf[F1], buf[FU], buf[FV], buf[FW], buf[DU], buf[DV], buf[DW], buf[PHI], buf[KSI], W, H, D,
+                                       hx, hy, hz, equation_alpha, buf[TDU], buf[TDV], buf[TDW], &sw);
           if (CheckDeviceError(status)) return;
+          if (with_weights) {
+            std::swap(buf[PHI], buf[PHI2]);
+            std::swap(buf[KSI], buf[KSI2]);
+            weights_ready = true;
+          }
           std::swap(buf[DU], buf[TDU]);
           std::swap(buf[DV], buf[TDV]);
           std::swap(buf[DW], buf[TDW]);
-          s += pair ? 2 : 1;
         }
       }
       // the last residency of the chunk: the flow update on the device, on the planes the chunk owns (see add_increments_to_flow)

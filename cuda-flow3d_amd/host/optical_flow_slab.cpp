@@ -399,10 +399,10 @@ bool OpticalFlowSlab::CompleteWeights(Local& l, int lo, int hi, int D, size_t W,
 // fx, fy, fz, ft of the level on every plane a fused launch of this level computes a stage 1 on: the frames are valid on the slab
 // widened by `valid_halo` planes (the warp's window), a z derivative needs one plane more on either side, so the derivatives are
 // made on the slab widened by valid_halo - 1 (clipped at the faces of the volume, where the mirror plane is the rank's own)
-bool OpticalFlowSlab::FrameDerivatives(Local& l, int D, size_t W, size_t H, float hx, float hy, float hz, int valid_halo)
+bool OpticalFlowSlab::FrameDerivatives(Local& l, int D, size_t W, size_t H, float hx, float hy, float hz, int valid_halo, bool fused)
 {
   l.derivatives = false;
-  if (!l.buf[FDX] || !FusedSweepsEnabled() || local_container_.pitch % 256 != 0) return true;
+  if (!l.buf[FDX] || !fused || local_container_.pitch % 256 != 0) return true;
   const PlaneRange own = OwnedPlanes(D, l.rank, n_ranks_);
   if (own.empty() || valid_halo < 1) return true;
   f3d_slab win;
@@ -475,22 +475,13 @@ bool OpticalFlowSlab::SweepAndNextWeights(Local& l, const Role (&in)[3], const R
 //     the plain order, so the bits do not change (tests/test_gpu_slab_procs.py);
 //   * the interior's last sweep also writes the weights of the NEXT outer iteration for its planes (one launch, see
 //     SweepAndNextWeights); the next call then computes phi/ksi only for the two zones and the halo planes.
-bool OpticalFlowSlab::SweepsOverlapped(Local& l, int D, size_t W, size_t H, int K, float hx, float hy, float hz,
-                                       float equation_alpha, float equation_smoothness, float equation_data)
+bool OpticalFlowSlab::SweepsOverlapped(Local& l, int D, size_t W, size_t H, int K, const std::vector<SweepLaunch>& cut, float hx, float hy,
+                                       float hz, float equation_alpha, float equation_smoothness, float equation_data)
 {
   const PlaneRange own = OwnedPlanes(D, l.rank, n_ranks_);
   const int a = own.lo, b = own.hi, Hs = K + 1;
   const bool has_lo = a > 0, has_hi = b < D;
-  struct Stage {
-    bool pair;
-    int rest;  // sweeps still to come after this stage
-  };
-  std::vector<Stage> stages;
-  for (int j = 0; j < K;) {
-    const bool pair = FusedSweepsEnabled() && j + 2 <= K;
-    j += pair ? 2 : 1;
-    stages.push_back({pair, K - j});
-  }
+  auto rest = [&](size_t s) { return K - cut[s].first - cut[s].sweeps; };  // sweeps still to come after stage s
   auto slab = [&](int lo, int hi) {
     f3d_slab s;
     s.z_base = a - halo_;
@@ -514,12 +505,12 @@ bool OpticalFlowSlab::SweepsOverlapped(Local& l, int D, size_t W, size_t H, int 
   auto stage = [&](size_t s, const f3d_slab& win, bool to_edge) {
     const Role* in = (s % 2 == 0) ? cur : tmp;
     const Role* out = to_edge ? edge : ((s % 2 == 0) ? tmp : cur);
-    return Sweeps(l, stages[s].pair, in, out, W, H, D, hx, hy, hz, equation_alpha, win);
+    return Sweeps(l, cut[s].sweeps == 2, in, out, W, H, D, hx, hy, hz, equation_alpha, win);
   };
-  const size_t last = stages.size() - 1;
+  const size_t last = cut.size() - 1;
   const Role* final_out = (last % 2 == 0) ? tmp : cur;
-  // the last stage of the interior can take the next weights along when it is a single sweep (an exchange always follows here)
-  const bool fuse_last = fused_weights_ && FusedSweepsEnabled() && FusedPhiKsiEnabled() && !stages[last].pair;
+  // the last stage of the interior takes the next weights along where the cut says so (an exchange always follows here)
+  const bool fuse_last = cut[last].next_weights;
   const bool had_weights = l.weights_hi > l.weights_lo;
   if (fuse_last || had_weights) {
     if (!CompleteWeights(l, a - K, b + K, D, W, H, hx, hy, hz, equation_smoothness, equation_data)) return false;
@@ -529,13 +520,13 @@ bool OpticalFlowSlab::SweepsOverlapped(Local& l, int D, size_t W, size_t H, int 
     if ((z == LOW && !has_lo) || (z == HIGH && !has_hi)) continue;
     if (!weights_done && !phi(zone(z, K))) return false;
     for (size_t s = 0; s <= last; ++s)
-      if (!stage(s, zone(z, stages[s].rest), s == last)) return false;
+      if (!stage(s, zone(z, rest(s)), s == last)) return false;
   }
   f3d_comm_mark(0, 1);   // (timing runs only) an exchange whose transfer runs beside the interior's launches
   if (!ExchangeBegin(D, W, H, {edge[0], edge[1], edge[2]}, {final_out[0], final_out[1], final_out[2]}, Hs, Hs)) return false;
   if (!weights_done && !phi(zone(INNER, K))) return false;
   for (size_t s = 0; s <= last; ++s) {
-    const f3d_slab win = zone(INNER, stages[s].rest);
+    const f3d_slab win = zone(INNER, rest(s));
     if (s == last && fuse_last) {
       const Role* in = (s % 2 == 0) ? cur : tmp;
       bool launched = false;
@@ -805,8 +796,13 @@ bool OpticalFlowSlab::Pyramid(OperationParameters& params)
     // exchange after every solver stage: the deepest stage reads p_max planes of the increments and of the weights beyond the
     // slab, the weights p_max + 1 planes of everything else
     const bool per_stage = exchange_per_stage_ && n_ranks_ > 1;
-    NoteSolveWeights(equation_alpha, hx, hy, hz);
-    const int p_max = (FusedSweepsEnabled() && K >= 2) ? 2 : 1;
+    // the launches of an outer iteration of this level (solve_schedule.h): of one that is followed by another and may take its
+    // weights along, and of the level's last
+    const bool fused = FusedSweepsEnabled() && SolveWeightsPlain(equation_alpha, hx, hy, hz);
+    const std::vector<SweepLaunch> cut_more = CutSweeps(K, fused, false, fused_weights_ && FusedPhiKsiEnabled()),
+                                   cut_last = CutSweeps(K, fused, false, false);
+    int p_max = 1;
+    for (const SweepLaunch& launch : cut_last) p_max = std::max(p_max, launch.sweeps);
     if (per_stage) n_ex = 1;
     const int wide = per_stage ? p_max + 1 : n_ex * (K + 1);
     if (!Exchange(D, W, H, {FU, FV, FW, F0R}, wide, wide)) return false;
@@ -826,7 +822,7 @@ bool OpticalFlowSlab::Pyramid(OperationParameters& params)
     // the frame derivatives of the level, where the rank holds containers for them: both frames are valid on the slab widened by
     // `wide` planes now (the exchange of frame 0, the window of the warp)
     for (Local& l : locals_)
-      if (!FrameDerivatives(l, D, W, H, hx, hy, hz, wide)) return false;
+      if (!FrameDerivatives(l, D, W, H, hx, hy, hz, wide, fused)) return false;
 
     // solver: outer x (phi/ksi + K sweeps on shrinking windows), increments exchanged once per n_ex outer iterations
     for (Local& l : locals_) {
@@ -843,14 +839,8 @@ bool OpticalFlowSlab::Pyramid(OperationParameters& params)
                              own_here.size() >= std::max(overlap_min_planes_, 4 * K + 4) && (own_here.lo > 0 || own_here.hi < D);
     for (size_t i = 0; per_stage && i < outer_iterations_count; ++i) {
       // ---- one exchange per solver stage (F3D_SLAB_EXCHANGE=stage): every launch on the slab itself ----
-      struct Stage { bool pair; };
-      std::vector<Stage> stages;
-      for (int s = 0; s < K;) {
-        const bool pair = FusedSweepsEnabled() && s + 2 <= K;
-        stages.push_back({pair});
-        s += pair ? 2 : 1;
-      }
       const bool more = i + 1 < outer_iterations_count;
+      const std::vector<SweepLaunch>& stages = more ? cut_more : cut_last;
       for (Local& l : locals_) {
         const PlaneRange own = OwnedPlanes(D, l.rank, n_ranks_);
         if (own.empty()) continue;
@@ -866,11 +856,12 @@ bool OpticalFlowSlab::Pyramid(OperationParameters& params)
       bool hidden_any = false;
       for (size_t st = 0; hide_stage_exchanges && st < stages.size(); ++st) {
         const bool last = st + 1 == stages.size();
-        const int next = !last ? (stages[st + 1].pair ? 2 : 1) : (more ? p_max + 1 : 0);
+        const int next = !last ? stages[st + 1].sweeps : (more ? p_max + 1 : 0);
         Local& l = locals_[0];
         const int a = own0.lo, b = own0.hi;
         const bool has_lo = a > 0, has_hi = b < D;
         const Role from[3] = {DU, DV, DW}, to[3] = {TDU, TDV, TDW};
+        const bool pair = stages[st].sweeps == 2;
         auto part = [&](int lo, int hi) {
           f3d_slab s;
           s.z_base = a - halo_;
@@ -880,8 +871,8 @@ bool OpticalFlowSlab::Pyramid(OperationParameters& params)
         };
         const int cut_lo = (has_lo && next > 0) ? a + next : a, cut_hi = (has_hi && next > 0) ? b - next : b;
         // the two zones the neighbours need (plain launches of this stage), then the transfer, then the interior
-        if (cut_lo > a && !Sweeps(l, stages[st].pair, from, to, W, H, D, hx, hy, hz, equation_alpha, part(a, cut_lo))) return false;
-        if (cut_hi < b && !Sweeps(l, stages[st].pair, from, to, W, H, D, hx, hy, hz, equation_alpha, part(cut_hi, b))) return false;
+        if (cut_lo > a && !Sweeps(l, pair, from, to, W, H, D, hx, hy, hz, equation_alpha, part(a, cut_lo))) return false;
+        if (cut_hi < b && !Sweeps(l, pair, from, to, W, H, D, hx, hy, hz, equation_alpha, part(cut_hi, b))) return false;
         if (next > 0) {
           f3d_comm_mark(0, 1);
           if (!ExchangeBegin(D, W, H, {to[0], to[1], to[2]}, {to[0], to[1], to[2]}, next, next)) return false;
@@ -889,12 +880,10 @@ bool OpticalFlowSlab::Pyramid(OperationParameters& params)
           hidden_any = true;
         }
         bool launched = false;
-        if (last && !stages[st].pair && more && fused_weights_ && FusedSweepsEnabled() && FusedPhiKsiEnabled()) {
-          if (!SweepAndNextWeights(l, {DU, DV, DW}, {TDU, TDV, TDW}, cut_lo, cut_hi, D, W, H, hx, hy, hz, equation_alpha, equation_smoothness,
-                                   equation_data, launched))
-            return false;
-        }
-        if (!launched && !Sweeps(l, stages[st].pair, from, to, W, H, D, hx, hy, hz, equation_alpha, part(cut_lo, cut_hi))) return false;
+        if (stages[st].next_weights && !SweepAndNextWeights(l, {DU, DV, DW}, {TDU, TDV, TDW}, cut_lo, cut_hi, D, W, H, hx, hy, hz, equation_alpha,
+                                                            equation_smoothness, equation_data, launched))
+          return false;
+        if (!launched && !Sweeps(l, pair, from, to, W, H, D, hx, hy, hz, equation_alpha, part(cut_lo, cut_hi))) return false;
         if (next > 0) {
           if (!ExchangeEnd(W, H)) return false;
           f3d_comm_mark(1, 1);
@@ -911,21 +900,17 @@ bool OpticalFlowSlab::Pyramid(OperationParameters& params)
           if (own.empty()) continue;
           const f3d_slab sw = Window(D, l.rank, 0, 0);
           bool launched = false;
-          if (last && !stages[st].pair && more && fused_weights_ && FusedSweepsEnabled() && FusedPhiKsiEnabled()) {
-            if (!SweepAndNextWeights(l, {DU, DV, DW}, {TDU, TDV, TDW}, sw.z_lo, sw.z_hi, D, W, H, hx, hy, hz, equation_alpha,
-                                     equation_smoothness, equation_data, launched))
-              return false;
-          }
-          if (!launched) {
-            const Role from[3] = {DU, DV, DW}, to[3] = {TDU, TDV, TDW};
-            if (!Sweeps(l, stages[st].pair, from, to, W, H, D, hx, hy, hz, equation_alpha, sw)) return false;
-          }
+          if (stages[st].next_weights && !SweepAndNextWeights(l, {DU, DV, DW}, {TDU, TDV, TDW}, sw.z_lo, sw.z_hi, D, W, H, hx, hy, hz,
+                                                              equation_alpha, equation_smoothness, equation_data, launched))
+            return false;
+          const Role from[3] = {DU, DV, DW}, to[3] = {TDU, TDV, TDW};
+          if (!launched && !Sweeps(l, stages[st].sweeps == 2, from, to, W, H, D, hx, hy, hz, equation_alpha, sw)) return false;
           std::swap(l.buf[DU], l.buf[TDU]);
           std::swap(l.buf[DV], l.buf[TDV]);
           std::swap(l.buf[DW], l.buf[TDW]);
         }
         // as deep as what comes next reads: the sweeps of the next stage, or the weights of the next outer iteration
-        const int next = !last ? (stages[st + 1].pair ? 2 : 1) : (more ? p_max + 1 : 0);
+        const int next = !last ? stages[st + 1].sweeps : (more ? p_max + 1 : 0);
         if (next > 0) {
           if (!Exchange(D, W, H, {DU, DV, DW}, next, next)) return false;
           ++stage_exchanges_;
@@ -934,7 +919,7 @@ bool OpticalFlowSlab::Pyramid(OperationParameters& params)
     }
     for (size_t i = per_stage ? outer_iterations_count : 0; i < outer_iterations_count;) {
       if (can_overlap && i + 1 < outer_iterations_count) {
-        if (!SweepsOverlapped(locals_[0], D, W, H, K, hx, hy, hz, equation_alpha, equation_smoothness, equation_data)) return false;
+        if (!SweepsOverlapped(locals_[0], D, W, H, K, cut_more, hx, hy, hz, equation_alpha, equation_smoothness, equation_data)) return false;
         ++overlapped_iterations_;
         ++i;
         continue;
@@ -951,31 +936,21 @@ bool OpticalFlowSlab::Pyramid(OperationParameters& params)
           if (!CompleteWeights(l, own.lo - (g + K), own.hi + (g + K), D, W, H, hx, hy, hz, equation_smoothness, equation_data)) return false;
           // sweep s runs on the slab widened by g + K-1-s planes; a fused pair (s, s+1) is launched on the window of
           // sweep s+1 and computes sweep s on one plane more on either side by itself
-          for (int s = 0; s < K;) {
-            const bool pair = FusedSweepsEnabled() && s + 2 <= K;
-            const int shrink = g + K - 1 - s - (pair ? 1 : 0);
+          const bool more = i + static_cast<size_t>(j) + 1 < outer_iterations_count;
+          for (const SweepLaunch& launch : more ? cut_more : cut_last) {
+            const bool pair = launch.sweeps == 2;
+            const int shrink = g + K - 1 - launch.first - (pair ? 1 : 0);
             const f3d_slab sw = Window(D, l.rank, shrink, shrink);
             // the last sweep of an iteration that is not the level's last takes the next weights along (one launch)
-            if (!pair && s == K - 1 && i + static_cast<size_t>(j) + 1 < outer_iterations_count && fused_weights_ &&
-                FusedSweepsEnabled() && FusedPhiKsiEnabled()) {
-              bool launched = false;
-              if (!SweepAndNextWeights(l, {DU, DV, DW}, {TDU, TDV, TDW}, sw.z_lo, sw.z_hi, D, W, H, hx, hy, hz, equation_alpha,
-                                       equation_smoothness, equation_data, launched))
-                return false;
-              if (launched) {
-                std::swap(l.buf[DU], l.buf[TDU]);
-                std::swap(l.buf[DV], l.buf[TDV]);
-                std::swap(l.buf[DW], l.buf[TDW]);
-                s += 1;
-                continue;
-              }
-            }
+            bool launched = false;
+            if (launch.next_weights && !SweepAndNextWeights(l, {DU, DV, DW}, {TDU, TDV, TDW}, sw.z_lo, sw.z_hi, D, W, H, hx, hy, hz,
+                                                            equation_alpha, equation_smoothness, equation_data, launched))
+              return false;
             const Role from[3] = {DU, DV, DW}, to[3] = {TDU, TDV, TDW};
-            if (!Sweeps(l, pair, from, to, W, H, D, hx, hy, hz, equation_alpha, sw)) return false;
+            if (!launched && !Sweeps(l, pair, from, to, W, H, D, hx, hy, hz, equation_alpha, sw)) return false;
             std::swap(l.buf[DU], l.buf[TDU]);
             std::swap(l.buf[DV], l.buf[TDV]);
             std::swap(l.buf[DW], l.buf[TDW]);
-            s += pair ? 2 : 1;
           }
         }
       }

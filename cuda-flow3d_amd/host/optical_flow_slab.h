@@ -20,6 +20,7 @@
 
 #include "optical_flow.h"
 #include "slab_plan.h"
+#include "solve_schedule.h"
 
 class OpticalFlowSlab : public OpticalFlowBase {
  public:
@@ -66,7 +67,8 @@ class OpticalFlowSlab : public OpticalFlowBase {
   // the frame derivatives when `l.derivatives` says they are there.
   bool Sweeps(Local& l, bool pair, const Role* in, const Role* out, size_t W, size_t H, int D, float hx, float hy, float hz,
               float equation_alpha, const f3d_slab& win);
-  bool FrameDerivatives(Local& l, int D, size_t W, size_t H, float hx, float hy, float hz, int valid_halo);
+  // (`fused`: the solve of this level takes the fused launches -- without them nothing reads the derivatives)
+  bool FrameDerivatives(Local& l, int D, size_t W, size_t H, float hx, float hy, float hz, int valid_halo, bool fused);
 
   bool Pyramid(OperationParameters& params);
   int ZBase(int depth, int rank) const { return OwnedPlanes(depth, rank, n_ranks_).lo - halo_; }
@@ -78,9 +80,9 @@ class OpticalFlowSlab : public OpticalFlowBase {
   bool ExchangeBegin(int depth, size_t width, size_t height, const std::vector<Role>& send_roles,
                      const std::vector<Role>& recv_roles, int need_lo, int need_hi);
   bool ExchangeEnd(size_t width, size_t height);
-  // one outer iteration's sweeps with the halo exchange hidden behind the interior of the slab (see the .cpp)
-  bool SweepsOverlapped(Local& l, int D, size_t W, size_t H, int K, float hx, float hy, float hz, float equation_alpha,
-                        float equation_smoothness, float equation_data);
+  // one outer iteration's sweeps, cut into the stages `cut`, with the halo exchange hidden behind the interior of the slab (see the .cpp)
+  bool SweepsOverlapped(Local& l, int D, size_t W, size_t H, int K, const std::vector<SweepLaunch>& cut, float hx, float hy, float hz,
+                        float equation_alpha, float equation_smoothness, float equation_data);
   // phi / ksi on planes [lo, hi) of the level (clipped to it), skipping the planes that already hold them
   bool CompleteWeights(Local& l, int lo, int hi, int D, size_t W, size_t H, float hx, float hy, float hz, float equation_smoothness,
                        float equation_data);

@@ -258,6 +258,11 @@ int f3d_plan_solve_piecemeal(size_t budget_bytes, size_t width, size_t height, i
                              int forced_outer_per_pass, int overlap_mode, int* chunk, int* outer_per_pass, int* halo, int* max_planes,
                              int* overlapped);
 size_t f3d_piecemeal_budget_bytes(void);
+/* how the solver drivers cut the `inner` sweeps of ONE outer iteration into launches (pure host arithmetic, host/solve_schedule.h).
+ * fused: the solve takes the fused launches; tri: the three-stage launches too; carry: another outer iteration follows and the
+ * driver can take its weights along.  Fills up to `capacity` launches: sweeps[i] = 1 .. 3 sweeps in launch i, next_weights[i] = 1
+ * when it also writes the next phi / ksi; returns their number, or -1 if capacity is too small. */
+int f3d_plan_sweeps(int inner, int fused, int tri, int carry, int* sweeps, int* next_weights, int capacity);
 
 /* OpticalFlowP (src/optical_flow/optical_flow_p.h:35-57; ComputeFlow optical_flow_p.cpp:57-318): no pre-blur, no median */
 typedef struct f3d_pflow_s* f3d_pflow;

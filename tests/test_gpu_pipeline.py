@@ -237,6 +237,40 @@ def test_solve_operator_with_weights_the_fused_launches_refuse(f3d, oracle, alph
     cont.free()
 
 
+def test_a_solve_the_fused_launches_refuse_leaves_nothing_behind(f3d, oracle):
+    """One process, one thread: a resident OpticalFlow, then the solve operator with equation_alpha = -0.02 (which takes the one-sweep
+    launches, see above), then the same OpticalFlow again from a fresh driver.  Which launches a solve takes is decided per solve from
+    its own parameters, so the two flows are byte-identical, and equal to the oracle."""
+    W, H, D = 40, 36, 32
+    f0, f1 = f3d.synth_pair(W, H, D)
+    kw = dict(warp_levels_count=4, outer_iterations_count=3, inner_iterations_count=5)
+    before = run_flow(f3d, f0, f1, **kw)
+    rng = np.random.default_rng(6)
+    dims, cdims = (37, 21, 9), (64, 24, 12)
+    cont = f3d.Containers(*cdims)
+
+    def put(lo, hi):
+        c = np.full(cdims[::-1], np.nan, np.float32)
+        c[:dims[2], :dims[1], :dims[0]] = rng.uniform(lo, hi, size=dims[::-1]).astype(np.float32)
+        return cont.new(c)
+
+    ptrs = [put(*r) for r in [(0, 255), (0, 255), (-2, 2), (-2, 2), (-2, 2)]]
+    names = ["dev_flow_du", "dev_flow_dv", "dev_flow_dw", "dev_phi", "dev_ksi", "dev_temp_du", "dev_temp_dv", "dev_temp_dw"]
+    op = f3d.Operation("solve")
+    assert op.initialize(cont)
+    op.execute(dev_frame_0=ptrs[0], dev_frame_1=ptrs[1], dev_flow_u=ptrs[2], dev_flow_v=ptrs[3], dev_flow_w=ptrs[4],
+               outer_iterations_count=2, inner_iterations_count=3, equation_alpha=-0.02, equation_smoothness=0.001,
+               equation_data=0.001, hx=1.5, hy=1.2, hz=2.0, data_size=dims, **{n: cont.new() for n in names})
+    f3d.sync()
+    op.destroy()
+    cont.free()
+    after = run_flow(f3d, f0, f1, **kw)
+    for a, b in zip(before, after):
+        assert a.tobytes() == b.tobytes()
+    (exp, _) = oracle.compute_flow(f0, f1, **kw)
+    check3(after, exp, "40x36x32 synthetic after a solve on the one-sweep launches")
+
+
 def test_missing_key_is_reported_not_fatal(f3d, capfd):
     cont = f3d.Containers(16, 8, 8)
     p = cont.new()

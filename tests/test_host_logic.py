@@ -245,6 +245,79 @@ def test_piecemeal_solver_plan_properties(f3d):
     assert auto_small[0] >= 1 and auto_small[0] == auto_small[3] - 2 * auto_small[2] and (auto_small[3] == 40 or 20 <= auto_small[3] <= 13 * 40 // 21)
 
 
+def test_sweep_cut_equals_the_rules_each_driver_used_to_restate(f3d):
+    """CutSweeps (host/solve_schedule.cpp, through plan_sweeps) against the rules it replaced, restated here as they stood in the
+    three drivers before they shared it: the resident operator's next_group / carries_weights lambdas and its dry-run count of the
+    weight hand-overs, and the greedy-pair / trailing-single rule of the piecemeal operator and the z-slab driver.  Exhaustive:
+    every inner count 0 .. 12 with every combination of fused, tri and carry."""
+    f3d.host()
+
+    def resident(K, fused, tri, more, fuse_weights):
+        # `fused` was FusedSweepsEnabled(); fuse_weights and tri both had it as a factor
+        fuse_weights, tri = fuse_weights and fused, tri and fused
+
+        def next_group(remaining):
+            if not fused:
+                return 1
+            weights_wanted = more and fuse_weights
+            if tri:
+                if weights_wanted:
+                    if remaining == 2:
+                        return 2
+                    if remaining == 3:
+                        return 1
+                    if remaining == 4:
+                        return 2
+                if remaining >= 3:
+                    return 3
+            if weights_wanted and remaining == 3 and not tri:
+                return 2
+            return 2 if remaining >= 2 else 1
+
+        def carries_weights(group, remaining_after):
+            return bool(more and fuse_weights and remaining_after == 0 and ((tri and group == 2) or group == 1))
+
+        launches, j = [], 0
+        while j < K:
+            group = next_group(K - j)
+            launches.append((group, carries_weights(group, K - j - group)))
+            j += group
+        return launches
+
+    def resident_hand_overs(K, fused, tri, fuse_weights, outer):
+        # the dry run over all outer iterations but the last
+        return sum(1 for _ in range(max(outer - 1, 0)) if (resident(K, fused, tri, True, fuse_weights) or [(0, False)])[-1][1])
+
+    def greedy(K, fused, carry):
+        # operations_p.cpp / optical_flow_slab.cpp: `carry` stood for "another outer iteration follows && the fused-weights switches",
+        # of which FusedSweepsEnabled() was one
+        launches, s = [], 0
+        while s < K:
+            pair = fused and s + 2 <= K
+            launches.append((2 if pair else 1, bool(carry and fused and not pair and s == K - 1)))
+            s += 2 if pair else 1
+        return launches
+
+    for K in range(13):
+        for fused in (False, True):
+            for carry in (False, True):
+                for tri in (False, True):
+                    got = f3d.plan_sweeps(K, fused, tri, carry)
+                    assert got == resident(K, fused, tri, carry, True), (K, fused, tri, carry, got)
+                    assert got == resident(K, fused, tri, True, carry), (K, fused, tri, carry, got)
+                    assert sum(n for n, _ in got) == K and not any(w for _, w in got[:-1])
+                    assert tri or got == greedy(K, fused, carry), (K, fused, carry, got)
+                    # the closed form of the hand-overs: outer - 1 when the cut that may carry ends in a launch that does, else none
+                    for outer in range(6):
+                        closed = max(outer - 1, 0) if got and got[-1][1] else 0
+                        assert closed == resident_hand_overs(K, fused, tri, carry, outer), (K, fused, tri, carry, outer)
+                # the slab driver's deepest stage, and the piecemeal operator's "an odd inner count ends in a launch that carries"
+                assert max([n for n, _ in f3d.plan_sweeps(K, fused, False, False)] or [1]) == (2 if fused and K >= 2 else 1)
+                assert bool(K and f3d.plan_sweeps(K, fused, False, True)[-1][1]) == (fused and K % 2 == 1)
+    assert f3d.plan_sweeps(5, True, True, True) == [(3, False), (2, True)]      # the default five sweeps: (S, S, S) + (S, S, P)
+    assert f3d.plan_sweeps(5, True, False, True) == [(2, False), (2, False), (1, True)]
+
+
 @pytest.mark.parametrize("planes,forced,outer,inner", [(20, 1, 3, 5), (28, 2, 5, 5), (17, 0, 4, 3)])
 def test_piecemeal_solver_windows_reproduce_the_unsplit_solve(f3d, oracle, planes, forced, outer, inner):
     """The out-of-core solver's residency scheme on the CPU, with the ORACLE as the compute and the PRODUCT's plan

@@ -251,6 +251,27 @@ CASE = textwrap.dedent('''
         for o in ops.values():
             o.destroy()
         cont.free()
+    elif what == "stateless":
+        # what a driver reserves and reports at Initialize depends on the environment switches only, not on the solve the thread ran
+        # last: a solve whose alpha / h^2 the fused launches refuse (it takes the one-sweep launches) between two Initialize calls
+        first = pkg.OpticalFlow(); first.initialize(128, 64, 64); first.destroy()      # six scratch volumes of 2 MB each
+        rng = np.random.default_rng(6)
+        dims, cdims = (37, 21, 9), (64, 24, 12)
+        cont = pkg.Containers(*cdims)
+        def put(lo, hi):
+            c = np.zeros(cdims[::-1], np.float32)
+            c[:dims[2], :dims[1], :dims[0]] = rng.uniform(lo, hi, size=dims[::-1]).astype(np.float32)
+            return cont.new(c)
+        ptrs = [put(*r) for r in [(0, 255), (0, 255), (-2, 2), (-2, 2), (-2, 2)]]
+        names = ["dev_flow_du", "dev_flow_dv", "dev_flow_dw", "dev_phi", "dev_ksi", "dev_temp_du", "dev_temp_dv", "dev_temp_dw"]
+        op = pkg.Operation("solve")
+        assert op.initialize(cont)
+        op.execute(dev_frame_0=ptrs[0], dev_frame_1=ptrs[1], dev_flow_u=ptrs[2], dev_flow_v=ptrs[3], dev_flow_w=ptrs[4],
+                   outer_iterations_count=2, inner_iterations_count=3, equation_alpha=-0.02, equation_smoothness=0.001,
+                   equation_data=0.001, hx=1.5, hy=1.2, hz=2.0, data_size=dims, **{n: cont.new() for n in names})
+        pkg.sync()
+        op.destroy(); cont.free()
+        second = pkg.OpticalFlow(); second.initialize(128, 64, 64); second.destroy()
     pkg.shutdown()
     print("ok", what)
 ''')
@@ -273,6 +294,7 @@ def run_case(what, libdir, sanitized):
     out = subprocess.run([sys.executable, "-c", CASE, what], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and f"ok {what}" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
     assert "ERROR: AddressSanitizer" not in out.stderr and "runtime error:" not in out.stderr, out.stderr[-3000:]
+    return out.stdout
 
 
 @pytest.mark.parametrize("what", ["resident", "slabs", "piecemeal", "reinit", "gather", "batch", "solve_slab"])
@@ -283,6 +305,15 @@ def test_host_drivers_equal_the_oracle_on_the_cpu_backend(what):
 @pytest.mark.parametrize("what", ["resident", "slabs", "piecemeal", "reinit", "gather", "batch", "solve_slab"])
 def test_host_drivers_are_clean_under_asan_and_ubsan(what):
     run_case(what, build("asan"), sanitized=True)
+
+
+def test_initialize_reports_the_same_scratch_after_a_solve_the_fused_launches_refuse():
+    """The "(+ N MB optional solver scratch)" line of OpticalFlow.initialize before and after an Operation("solve") with
+    equation_alpha = -0.02 on the same thread: equal, and not zero -- which launches a solve takes is decided per solve, and leaves
+    nothing behind.  (When that decision was a per-thread flag set by the last solve, the second line said 0 MB.)"""
+    import re
+    lines = re.findall(r"\(\+ (\d+)MB optional solver scratch\)", run_case("stateless", build("all"), sanitized=False))
+    assert len(lines) == 2 and lines[0] == lines[1] and int(lines[0]) > 0, lines
 
 
 def test_out_of_core_operator_tests_on_the_cpu_backend():
