@@ -51,6 +51,14 @@ class StrainStats(C.Structure):  # f3d_strain_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class WindowStrainStats(C.Structure):  # f3d_window_strain_stats
+    _fields_ = [("defined", C.c_ulonglong), ("folded", C.c_ulonglong), ("lost", C.c_ulonglong), ("thin", C.c_ulonglong),
+                ("vol_min", C.c_float), ("vol_max", C.c_float), ("eq_max", C.c_float), ("vol_sum", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PrincipalStats(C.Structure):  # f3d_principal_stats
     _fields_ = [("defined", C.c_ulonglong), ("e1_max", C.c_float), ("e3_min", C.c_float), ("shear_max", C.c_float)]
 
@@ -295,6 +303,9 @@ def host():
         "f3d_flow_trajectory_end": [C.c_void_p],
         "f3d_flow_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(StrainStats)],
         "f3d_flow_strain_end": [C.c_void_p],
+        "f3d_flow_window_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(_fp),
+                                           C.POINTER(WindowStrainStats)],
+        "f3d_flow_window_strain_end": [C.c_void_p],
         "f3d_flow_principal_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(PrincipalStats)],
         "f3d_flow_principal_end": [C.c_void_p],
         "f3d_flow_polar_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(PolarStats)],
@@ -438,6 +449,11 @@ def _strain_entry():
     return _entry("f3d_flow_strain", [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(StrainStats)], "compute strain fields")
 
 
+def _window_strain_entry():
+    return _entry("f3d_window_strain", [_dp] * 3 + [_dpp, C.c_uint, C.c_uint, C.c_uint] + [_sz] * 3 + [C.POINTER(WindowStrainStats)],
+                  "compute strain fields over a window")
+
+
 def _principal_entry():
     return _entry("f3d_principal_strain", [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(PrincipalStats)],
                   "compute principal strains")
@@ -557,6 +573,10 @@ def compose_flow(acc, inc):
 STRAIN_NAMES = ("vol", "exx", "eyy", "ezz", "exy", "exz", "eyz", "eq")
 STRAIN_GROUPS = {"vol": 1, "e": 2, "eq": 4}
 _STRAIN_GROUP_OF = (1, 2, 2, 2, 2, 2, 2, 4)
+# the seventeen outputs of f3d_window_strain in ABI order, and the F3D_STRAIN_* / F3D_WSTRAIN_G group of each
+WINDOW_STRAIN_NAMES = STRAIN_NAMES + ("G00", "G01", "G02", "G10", "G11", "G12", "G20", "G21", "G22")
+WINDOW_STRAIN_GROUPS = {"vol": 1, "e": 2, "eq": 4, "grad": 8}
+_WINDOW_STRAIN_GROUP_OF = _STRAIN_GROUP_OF + (8,) * 9
 # the ten outputs of f3d_principal_strain in ABI order, and the F3D_PRINCIPAL_* group of each
 PRINCIPAL_NAMES = ("e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z")
 PRINCIPAL_GROUPS = {"val": 1, "shear": 2, "dir1": 4, "dir3": 8}
@@ -604,6 +624,15 @@ def _strain_mask(fields):
     return _mask(fields, STRAIN_GROUPS, "strain")
 
 
+def _window_strain_mask(fields):
+    return _mask(fields, WINDOW_STRAIN_GROUPS, "window strain")
+
+
+def _window_min_count(radius, min_count):
+    """min_count of f3d_window_strain; None: a quarter of the (2 radius + 1)^3 window, at least 4"""
+    return max(4, (2 * radius + 1) ** 3 // 4) if min_count is None else min_count
+
+
 def _principal_mask(fields):
     return _mask(fields, PRINCIPAL_GROUPS, "principal strain")
 
@@ -637,6 +666,25 @@ def flow_strain(u, v, w, fields=("vol", "e", "eq")):
     name -> array for the selected outputs and "stats" -> dict (defined, folded, vol_min, vol_max, eq_max, vol_sum)."""
     fn = _strain_entry()
     return _grouped_fields(fn, "f3d_flow_strain", u, v, w, _strain_mask(fields), STRAIN_NAMES, _STRAIN_GROUP_OF, StrainStats())
+
+
+def window_strain(u, v, w, radius=2, min_count=None, fields=("vol", "e", "eq")):
+    """Strain fields of a displacement over a strain window on the device (include/f3d.h, f3d_window_strain) for volumes from
+    anywhere: the gradient of a voxel is the slope of the least-squares plane through the present samples of its (2 radius + 1)^3
+    neighbourhood (radius 1 .. 3); a voxel with fewer than min_count of them (None: a quarter of the window, at least 4), or with
+    all of them in one plane, is undefined.  fields: the groups of flow_strain() and "grad", the nine entries G00 .. G22 of the
+    gradient.  Returns a dict name -> array for the selected outputs and "stats" -> dict (defined, folded, lost, thin, vol_min,
+    vol_max, eq_max, vol_sum)."""
+    fn = _window_strain_entry()
+    mask, stats = _window_strain_mask(fields), WindowStrainStats()
+    with _on_device((u, v, w), "u, v and w must be three [z, y, x] volumes of one shape") as (box, p, dims):
+        outs = [box.alloc() if mask & g else 0 for g in _WINDOW_STRAIN_GROUP_OF]
+        box.set_current()
+        check(fn(*p, (_dp * len(outs))(*outs), mask, radius, _window_min_count(radius, min_count), *dims, C.byref(stats)),
+              "f3d_window_strain")
+        res = {n: box.download(o, dims) for n, o in zip(WINDOW_STRAIN_NAMES, outs) if o}
+    res["stats"] = stats.as_dict()
+    return res
 
 
 def principal_strain(u, v, w, fields=("val", "shear")):
@@ -1437,6 +1485,21 @@ class OpticalFlow:
     def strain_end(self):
         """free the strain containers (destroy() does too)"""
         _host_check(host().f3d_flow_strain_end(self._h), "f3d_flow_strain_end")
+
+    def window_strain(self, source="flow", radius=2, min_count=None, fields=("vol", "e", "eq")):
+        """Strain fields over a strain window of the flow the driver holds (source="flow", after compute_resident) or of the
+        trajectory (source="trajectory", after trajectory_begin); same arguments and result shape as window_strain().  Works between
+        the yields of compute_sequence, where the driver holds both."""
+        src, mask, stats = _source(source), _window_strain_mask(fields), WindowStrainStats()
+        arrays = self._derived("f3d_flow_window_strain_compute", src, [mask & g for g in _WINDOW_STRAIN_GROUP_OF], stats, mask, radius,
+                               _window_min_count(radius, min_count))
+        res = {n: a for n, a in zip(WINDOW_STRAIN_NAMES, arrays) if a is not None}
+        res["stats"] = stats.as_dict()
+        return res
+
+    def window_strain_end(self):
+        """free the window strain containers (destroy() does too)"""
+        _host_check(host().f3d_flow_window_strain_end(self._h), "f3d_flow_window_strain_end")
 
     def principal(self, source="flow", fields=("val", "shear")):
         """Principal strains of the flow the driver holds (source="flow", after compute_resident) or of the trajectory

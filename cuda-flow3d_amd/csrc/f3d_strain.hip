@@ -56,17 +56,8 @@ __global__ __launch_bounds__(kBX* kBY) void k_flow_strain(const float* __restric
     const bool def = march_step(du, dv, dw, g, z, z_end, own, G);
     const auto& [G00, G01, G02, G10, G11, G12, G20, G21, G22] = G;
 
-    // include/f3d.h, f3d_flow_strain: the evaluation order is part of the ABI (contraction is off in this build)
-    const float I1 = (G00 + G11) + G22;
-    const float I2 = ((G00 * G11 - G01 * G10) + (G11 * G22 - G12 * G21)) + (G00 * G22 - G02 * G20);
-    const float I3 = (G00 * (G11 * G22 - G12 * G21) - G01 * (G10 * G22 - G12 * G20)) + G02 * (G10 * G21 - G11 * G20);
-    float vol = (I1 + I2) + I3;
-    float exx, eyy, ezz, exy, exz, eyz;
-    green_lagrange(G00, G01, G02, G10, G11, G12, G20, G21, G22, exx, eyy, ezz, exy, exz, eyz);
-    const float mean = ((exx + eyy) + ezz) / 3.f;
-    const float a = exx - mean, b = eyy - mean, c = ezz - mean;
-    const float s = ((a * a + b * b) + c * c) + 2.f * ((exy * exy + exz * exz) + eyz * eyz);
-    float eq = sqrtf(s / 1.5f);
+    float vol, exx, eyy, ezz, exy, exz, eyz, eq;
+    strain_fields(G00, G01, G02, G10, G11, G12, G20, G21, G22, vol, exx, eyy, ezz, exy, exz, eyz, eq);
     if (!def) {
       vol = exx = eyy = ezz = exy = exz = eyz = eq = __builtin_nanf("");
     }

@@ -68,6 +68,24 @@ __device__ __forceinline__ void green_lagrange(float G00, float G01, float G02, 
   eyz = 0.5f * ((G12 + G21) + ((G01 * G02 + G11 * G12) + G21 * G22));
 }
 
+// The eight outputs vol, exx, eyy, ezz, exy, exz, eyz, eq of f3d_flow_strain from a gradient: the one text f3d_flow_strain and
+// f3d_window_strain (f3d_window_strain.hip) both store.  include/f3d.h, f3d_flow_strain: the evaluation order is part of the ABI
+// (contraction is off in this build)
+__device__ __forceinline__ void strain_fields(float G00, float G01, float G02, float G10, float G11, float G12, float G20, float G21,
+                                              float G22, float& vol, float& exx, float& eyy, float& ezz, float& exy, float& exz,
+                                              float& eyz, float& eq)
+{
+  const float I1 = (G00 + G11) + G22;
+  const float I2 = ((G00 * G11 - G01 * G10) + (G11 * G22 - G12 * G21)) + (G00 * G22 - G02 * G20);
+  const float I3 = (G00 * (G11 * G22 - G12 * G21) - G01 * (G10 * G22 - G12 * G20)) + G02 * (G10 * G21 - G11 * G20);
+  vol = (I1 + I2) + I3;
+  green_lagrange(G00, G01, G02, G10, G11, G12, G20, G21, G22, exx, eyy, ezz, exy, exz, eyz);
+  const float mean = ((exx + eyy) + ezz) / 3.f;
+  const float a = exx - mean, b = eyy - mean, c = ezz - mean;
+  const float s = ((a * a + b * b) + c * c) + 2.f * ((exy * exy + exz * exz) + eyz * eyz);
+  eq = sqrtf(s / 1.5f);
+}
+
 // The geometry both kernels march over: a wave on kBX consecutive x of one row, a workgroup kBY rows, a run of kZ planes in z.
 constexpr int kBX = 64;
 constexpr int kBY = 4;

@@ -259,8 +259,8 @@ int DerivedDownload(f3d_flow flow, OpticalFlowE::Derived which, bool computed, f
   OpticalFlowE& d = flow->driver;
   if (!computed) return HostFail(d.DerivedError(which).c_str());
   const DataSize4& c = d.ContainerSize();
-  std::unique_ptr<Data3D> views[10];
-  Data3D* dst[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  std::unique_ptr<Data3D> views[OpticalFlowE::kMaxDerivedFields];
+  Data3D* dst[OpticalFlowE::kMaxDerivedFields] = {};
   for (int i = 0; i < OpticalFlowE::DerivedFieldCount(which); ++i)
     if (out[i]) {
       views[i].reset(new Data3D(out[i], c.width, c.height, c.depth));
@@ -287,6 +287,20 @@ int f3d_flow_strain_compute(f3d_flow flow, int source, unsigned fields, float* c
 }
 
 int f3d_flow_strain_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kStrain, "f3d_flow_strain_end: null driver"); }
+
+int f3d_flow_window_strain_compute(f3d_flow flow, int source, unsigned fields, unsigned radius, unsigned min_count,
+                                   float* const out[17], f3d_window_strain_stats* stats)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out != nullptr, "f3d_flow_window_strain_compute", &of)) return 1;
+  return DerivedDownload(flow, OpticalFlowE::kWindowStrain, flow->driver.ComputeWindowStrain(of, fields, radius, min_count, stats), out,
+                         fields);
+}
+
+int f3d_flow_window_strain_end(f3d_flow flow)
+{
+  return DerivedEnd(flow, OpticalFlowE::kWindowStrain, "f3d_flow_window_strain_end: null driver");
+}
 
 int f3d_flow_principal_compute(f3d_flow flow, int source, unsigned fields, float* const out[10], f3d_principal_stats* stats)
 {

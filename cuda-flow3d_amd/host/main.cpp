@@ -6,6 +6,7 @@
 //                [--outer N] [--inner N] [--alpha a] [--eps-smooth e] [--eps-data e] [--median r] [--sigma s]
 //                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
 //                [--strain vol,e,eq] [--principal val,shear,dir1,dir3] [--rotation angle,vector,stretch] [--inverse]
+//                [--window-strain vol,e,eq,grad [--window-radius R] [--window-min-count K]]
 //                [--match warped,zncc,rmsd [--match-radius R]]
 //                [--detrend translation|rigid|affine [--detrend-min-zncc T]]
 //                [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]
@@ -27,6 +28,11 @@
 // with --cumulative the displacement frame 0 -> frame k+1 instead -- on the device (f3d_flow_strain) and writes the selected fields
 // as <tag>_strain-{vol | exx,eyy,ezz,exy,exz,eyz | eq}-W-H-D.raw with the flow's (or the displacement's) tag, and one line of
 // statistics per pair.
+// --window-strain LIST (same conditions and the same source as --strain, --use-validated included; LIST a comma-separated subset of
+// vol,e,eq,grad) takes the gradient of that displacement as the slope of the least-squares plane through the (2R+1)^3 neighbourhood of
+// every voxel on the device (f3d_window_strain; --window-radius R, 1 .. 3, default 2) and forms the strain fields of --strain from it.
+// A voxel with fewer than --window-min-count present neighbours (default a quarter of the window, at least 4) is undefined.
+// <tag>_wstrain-{vol | exx,eyy,ezz,exy,exz,eyz | eq | G00 .. G22}-W-H-D.raw, and one line of statistics per pair.
 // --principal LIST (same conditions and the same source as --strain, with which it may be combined; LIST a comma-separated subset of
 // val,shear,dir1,dir3) diagonalises the Green-Lagrange tensor of that displacement on the device (f3d_principal_strain) and writes
 // the selected fields as <tag>_principal-{e1,e2,e3 | gmax | d1x,d1y,d1z | d3x,d3y,d3z}-W-H-D.raw, and one line of statistics per
@@ -88,6 +94,7 @@ static void Usage()
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
               "              [--concurrent N] [--cumulative] [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
               "              [--rotation angle,vector,stretch] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
+              "              [--window-strain vol,e,eq,grad [--window-radius R] [--window-min-count K]]\n"
               "              [--detrend translation|rigid|affine [--detrend-min-zncc T]]\n"
               "              [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]\n"
               "               [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]\n"
@@ -103,6 +110,10 @@ int main(int argc, char** argv)
   bool use_partial_gpu = false, partial_full = false, cumulative = false;
   size_t concurrent = 1;
   unsigned strain_fields = 0;     // --strain: F3D_STRAIN_* groups
+  unsigned wstrain_fields = 0;    // --window-strain: F3D_STRAIN_* groups and F3D_WSTRAIN_G
+  unsigned window_radius = 2;     // --window-radius
+  unsigned window_min_count = 0;  // --window-min-count; 0: a quarter of the window, at least 4
+  bool window_sub_given = false;
   unsigned principal_fields = 0;  // --principal: F3D_PRINCIPAL_* groups
   unsigned polar_fields = 0;      // --rotation: F3D_POLAR_* groups
   bool inverse = false;           // --inverse
@@ -184,6 +195,36 @@ int main(int argc, char** argv)
         if (end == std::string::npos) break;
         at = end + 1;
       }
+    }
+    else if (a == "--window-strain") {
+      need(1);
+      const std::string list = argv[++i];
+      size_t at = 0;
+      while (true) {
+        const size_t end = list.find(',', at);
+        const std::string item = list.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        if (item == "vol") wstrain_fields |= F3D_STRAIN_VOL;
+        else if (item == "e") wstrain_fields |= F3D_STRAIN_E;
+        else if (item == "eq") wstrain_fields |= F3D_STRAIN_EQ;
+        else if (item == "grad") wstrain_fields |= F3D_WSTRAIN_G;
+        else { Usage(); return 64; }
+        if (end == std::string::npos) break;
+        at = end + 1;
+      }
+    }
+    else if (a == "--window-radius" || a == "--window-min-count") {
+      need(1);
+      char* rest = nullptr;
+      const unsigned long n = std::strtoul(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest || argv[i][0] == '-') { Usage(); return 64; }
+      if (a == "--window-radius") {
+        if (n < 1 || n > 3) { Usage(); return 64; }
+        window_radius = static_cast<unsigned>(n);
+      } else {
+        if (n < 1 || n > 343) { Usage(); return 64; }
+        window_min_count = static_cast<unsigned>(n);
+      }
+      window_sub_given = true;
     }
     else if (a == "--principal") {
       need(1);
@@ -331,6 +372,26 @@ int main(int argc, char** argv)
     std::printf("--strain needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
                 use_partial_gpu ? "--partial" : "--concurrent N > 1");
     return 64;
+  }
+  if (window_sub_given && !wstrain_fields) {
+    std::printf("--window-radius and --window-min-count need --window-strain\n");
+    Usage();
+    return 64;
+  }
+  if (wstrain_fields && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--window-strain needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  {
+    const unsigned window = (2 * window_radius + 1) * (2 * window_radius + 1) * (2 * window_radius + 1);
+    if (window_min_count > window) {
+      std::printf("--window-min-count must be 1 .. %u at --window-radius %u\n", window, window_radius);
+      Usage();
+      return 64;
+    }
+    if (!window_min_count) window_min_count = std::max(4u, window / 4);
   }
   if (principal_fields && (use_partial_gpu || concurrent > 1)) {
     std::printf("--principal needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
@@ -632,12 +693,14 @@ int main(int argc, char** argv)
     bool of_pair;        // computed of the pair's flow also under --cumulative
     std::function<bool(const OpticalFlowE::Displacement&)> compute;
     std::function<void(size_t)> print;  // the statistics line of pair k
-    Data3D host[10];
-    Data3D* out[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Data3D host[OpticalFlowE::kMaxDerivedFields];
+    Data3D* out[OpticalFlowE::kMaxDerivedFields] = {};
     // sequence mode: the kernel of pair k has run (`done`); its fields have gone down, so pair k+1 may rewrite them (`down`)
     f3d_event done = nullptr, down = nullptr;
   };
   static const char* const strain_names[8] = {"vol", "exx", "eyy", "ezz", "exy", "exz", "eyz", "eq"};
+  static const char* const wstrain_names[17] = {"vol", "exx", "eyy", "ezz", "exy", "exz", "eyz", "eq", "G00",
+                                               "G01", "G02", "G10", "G11", "G12", "G20", "G21", "G22"};
   static const char* const principal_names[10] = {"e1", "e2", "e3", "gmax", "d1x", "d1y", "d1z", "d3x", "d3y", "d3z"};
   static const char* const polar_names[7] = {"theta", "rx", "ry", "rz", "l1", "l2", "l3"};
   static const char* const inverse_names[4] = {"u", "v", "w", "err"};
@@ -654,6 +717,7 @@ int main(int argc, char** argv)
   bool label_table_failed = false;  // a <tag>_labelmotion.csv that could not be written: the run ends with 2 like an unreadable frame
   const size_t voxels = width * height * depth;
   f3d_strain_stats strain_stats = {};
+  f3d_window_strain_stats wstrain_stats = {};
   f3d_principal_stats principal_stats = {};
   f3d_polar_stats polar_stats = {};
   f3d_inverse_stats inverse_stats = {};
@@ -661,7 +725,7 @@ int main(int argc, char** argv)
   f3d_motion_fit motion_fit = {};
   f3d_motion_residual motion_residual = {};
   f3d_validate_stats validate_stats = {};
-  // --use-validated: what --strain, --principal, --rotation and --detrend are computed of
+  // --use-validated: what --strain, --window-strain, --principal, --rotation and --detrend are computed of
   auto validated_or = [&](const OpticalFlowE::Displacement& of) {
     if (!use_validated) return of;
     const DevicePtr d[3] = {optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 1),
@@ -669,7 +733,7 @@ int main(int argc, char** argv)
                             optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 3)};
     return OpticalFlowE::Containers(d);
   };
-  DerivedField derived[8] = {
+  DerivedField derived[9] = {
       {"strain", OpticalFlowE::kStrain, strain_fields, strain_names, false,
        [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputeStrain(validated_or(of), strain_fields, &strain_stats); },
        [&](size_t k) {
@@ -815,13 +879,28 @@ int main(int argc, char** argv)
                      cumulative ? size_t(0) : k, k + 1, motion_models[label_model], count[0], count[1], count[2], count[3], median);
          if (label_model == F3D_MOTION_RIGID) std::printf("max angle %.6g deg, ", max_angle);
          std::printf("%llu foreign, %llu out of range voxels\n", label_info.foreign, label_info.out_of_range);
+       }},
+      // the same source as --strain, after which it runs (`order` below)
+      {"wstrain", OpticalFlowE::kWindowStrain, wstrain_fields, wstrain_names, false,
+       [&](const OpticalFlowE::Displacement& of) {
+         return optical_flow_e.ComputeWindowStrain(validated_or(of), wstrain_fields, window_radius, window_min_count, &wstrain_stats);
+       },
+       [&](size_t k) {
+         const f3d_window_strain_stats& st = wstrain_stats;
+         const double mean = st.defined ? st.vol_sum / static_cast<double>(st.defined) : std::nan("");
+         std::printf("window strain (r=%u) frame %zu -> frame %zu: vol min/mean/max %.6g/%.6g/%.6g, eq max %.6g, %llu folded, %llu thin, "
+                     "%llu lost of %zu voxels\n", window_radius, cumulative ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max,
+                     st.eq_max, st.folded, st.thin, st.lost, voxels);
        }}};
-  // the order in which the features run and their files and lines come out: as listed, with the rotation after the principal strains,
+  // the order in which the features run and their files and lines come out: as listed, with the window strain after the strain and the
+  // rotation after the principal strains,
   // or with --use-validated the match (whose zncc may be the mask) and the validated field first
-  DerivedField* order[8] = {&derived[0], &derived[1], &derived[6], &derived[2], &derived[3], &derived[4], &derived[5], &derived[7]};
+  DerivedField* order[9] = {&derived[0], &derived[8], &derived[1], &derived[6], &derived[2],
+                            &derived[3], &derived[4], &derived[5], &derived[7]};
   if (use_validated) {
-    DerivedField* const first[8] = {&derived[3], &derived[5], &derived[0], &derived[1], &derived[6], &derived[2], &derived[4], &derived[7]};
-    for (int i = 0; i < 8; ++i) order[i] = first[i];
+    DerivedField* const first[9] = {&derived[3], &derived[5], &derived[0], &derived[8], &derived[1],
+                                    &derived[6], &derived[2], &derived[4], &derived[7]};
+    for (int i = 0; i < 9; ++i) order[i] = first[i];
   }
   for (DerivedField& f : derived)
     for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)

@@ -20,6 +20,9 @@ extern "C" int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr a
     __attribute__((weak));
 extern "C" int f3d_flow_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[8], unsigned fields, size_t width,
                                size_t height, size_t depth, f3d_strain_stats* stats) __attribute__((weak));
+extern "C" int f3d_window_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[17], unsigned fields, unsigned radius,
+                                 unsigned min_count, size_t width, size_t height, size_t depth, f3d_window_strain_stats* stats)
+    __attribute__((weak));
 extern "C" int f3d_principal_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[10], unsigned fields,
                                     size_t width, size_t height, size_t depth, f3d_principal_stats* stats) __attribute__((weak));
 extern "C" int f3d_polar_decomposition(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[7], unsigned fields,
@@ -105,6 +108,10 @@ namespace {
 
 const unsigned kStrainGroups[8] = {F3D_STRAIN_VOL, F3D_STRAIN_E, F3D_STRAIN_E, F3D_STRAIN_E,
                                    F3D_STRAIN_E,   F3D_STRAIN_E, F3D_STRAIN_E, F3D_STRAIN_EQ};
+const unsigned kWindowStrainGroups[17] = {F3D_STRAIN_VOL, F3D_STRAIN_E,  F3D_STRAIN_E,  F3D_STRAIN_E,  F3D_STRAIN_E,  F3D_STRAIN_E,
+                                          F3D_STRAIN_E,   F3D_STRAIN_EQ, F3D_WSTRAIN_G, F3D_WSTRAIN_G, F3D_WSTRAIN_G, F3D_WSTRAIN_G,
+                                          F3D_WSTRAIN_G,  F3D_WSTRAIN_G, F3D_WSTRAIN_G, F3D_WSTRAIN_G, F3D_WSTRAIN_G};
+const unsigned kWindowStrainAll = F3D_STRAIN_VOL | F3D_STRAIN_E | F3D_STRAIN_EQ | F3D_WSTRAIN_G;
 const unsigned kPrincipalGroups[10] = {F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_SHEAR,
                                        F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR1,   F3D_PRINCIPAL_DIR3,
                                        F3D_PRINCIPAL_DIR3,   F3D_PRINCIPAL_DIR3};
@@ -122,10 +129,10 @@ const unsigned kValidatedGroups[kValidatedContainers] = {F3D_VALIDATE_R, F3D_VAL
 // the residual u, v, w of the per-label motion, and the container of the labels (a bit of its own, never downloaded)
 const unsigned kLabelResidual = 1u, kLabelLabels = 2u;
 const unsigned kLabelMotionGroups[4] = {kLabelResidual, kLabelResidual, kLabelResidual, kLabelLabels};
-const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3, 4, 7, 4};
+const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3, 4, 7, 4, 17};
 const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr,
                                                                      kMatchGroups,  nullptr,          kValidatedGroups,
-                                                                     kPolarGroups,  kLabelMotionGroups};
+                                                                     kPolarGroups,  kLabelMotionGroups, kWindowStrainGroups};
 const char* const kTrajectoryNotStarted = "the trajectory was not started (ResetTrajectory first)";
 
 }  // namespace
@@ -161,7 +168,11 @@ OpticalFlowE::OpticalFlowE()
                {this, kDerivedFields[kLabelMotion], kLabelMotionGroups,
                 "the containers of the per-label motion do not fit beside the driver's on the device",
                 "the residual of the per-label motion has not been computed", "no host volume for a field of the per-label residual",
-                "the device library has no f3d_label_motion_sums (per-label motion)", "no displacement to fit the motion of the labels to"}}
+                "the device library has no f3d_label_motion_sums (per-label motion)", "no displacement to fit the motion of the labels to"},
+               {this, kDerivedFields[kWindowStrain], kWindowStrainGroups,
+                "the window strain containers do not fit beside the driver's on the device",
+                "a requested window strain field has not been computed", "no host volume for a requested window strain field",
+                "the device library has no f3d_window_strain (strain over a window)", "no displacement to differentiate"}}
 {
   // same initialisation order as the reference's forward_list built with push_front (optical_flow_e.cpp:34-39)
   cuda_operations_ = {&cuop_solve_, &cuop_resample_, &cuop_register_, &cuop_median_, &cuop_convolution_, &cuop_add_};
@@ -622,6 +633,22 @@ bool OpticalFlowE::ComputeStrain(const Displacement& of, unsigned fields, f3d_st
   const f3d_size4 c = Container();
   return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
          set.Check(CheckDeviceError(f3d_flow_strain(d[0], d[1], d[2], set.ptr, fields, c.width, c.height, c.depth, stats)));
+}
+
+bool OpticalFlowE::ComputeWindowStrain(const Displacement& of, unsigned fields, unsigned radius, unsigned min_count,
+                                       f3d_window_strain_stats* stats)
+{
+  FieldSet& set = derived_[kWindowStrain];
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, f3d_window_strain != nullptr, d)) return false;
+  if (fields == 0 || (fields & ~kWindowStrainAll))
+    return set.Fail("fields must be a non-empty combination of F3D_STRAIN_VOL, F3D_STRAIN_E, F3D_STRAIN_EQ, F3D_WSTRAIN_G");
+  if (radius < 1 || radius > 3) return set.Fail("radius must be 1 .. 3");
+  if (!set.Allocate(fields)) return false;
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         set.Check(CheckDeviceError(f3d_window_strain(d[0], d[1], d[2], set.ptr, fields, radius, min_count, c.width, c.height, c.depth,
+                                                      stats)));
 }
 
 bool OpticalFlowE::ComputePrincipal(const Displacement& of, unsigned fields, f3d_principal_stats* stats)

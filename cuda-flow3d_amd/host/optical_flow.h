@@ -135,10 +135,14 @@ class OpticalFlowE : public OpticalFlowBase {
   //   kLabelMotion f3d_label_motion_sums, the host solve per label (motion_fit.h) and f3d_remove_label_motion: the displacement with the
   //               fit of each voxel's label taken out.  Three outputs, the residual u, v, w, always all of them, and a fourth container
   //               that holds the labels (UploadLabels; never downloaded).
+  //   kWindowStrain f3d_window_strain: the strain fields of kStrain from the least-squares gradient over a (2 radius + 1)^3 window, and
+  //               that gradient.  Seventeen outputs in the order vol, exx, eyy, ezz, exy, exz, eyz, eq, G00 .. G22, selected by
+  //               F3D_STRAIN_VOL / _E / _EQ and F3D_WSTRAIN_G.
   // Each selected output gets a container of its own, allocated on first use and freed by ReleaseDerived() and Destroy().  Compute
   // enqueues on the library stream and waits only when stats is given.  Every call returns false with DerivedError() set when it
   // cannot run -- among other reasons when the device library lacks the entry point.
-  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kValidated, kPolar, kLabelMotion, kDerivedCount };
+  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kValidated, kPolar, kLabelMotion, kWindowStrain, kDerivedCount };
+  static constexpr int kMaxDerivedFields = 17;  // the most outputs a Derived has (kWindowStrain)
   enum MatchField : unsigned { kMatchWarped = 1u, kMatchZncc = 2u, kMatchRmsd = 4u };
   // the displacement a derived field is computed of
   struct Displacement {
@@ -150,6 +154,9 @@ class OpticalFlowE : public OpticalFlowBase {
   static Displacement Containers(const DevicePtr (&d)[3]) { return {Displacement::kContainers, {d[0], d[1], d[2]}}; }  // TakeResult's
   bool ComputeStrain(const Displacement& of, unsigned fields, f3d_strain_stats* stats);
   bool ComputePrincipal(const Displacement& of, unsigned fields, f3d_principal_stats* stats);
+  // radius 1 .. 3; a voxel with fewer than min_count (1 .. (2 radius + 1)^3) present points in its window is undefined
+  bool ComputeWindowStrain(const Displacement& of, unsigned fields, unsigned radius, unsigned min_count,
+                           f3d_window_strain_stats* stats);
   bool ComputePolar(const Displacement& of, unsigned fields, f3d_polar_stats* stats);
   bool ComputeInverse(const Displacement& of, unsigned iterations, float tolerance, f3d_inverse_stats* stats);
   // frame_0 / frame_1: the containers of the two frames the displacement belongs to; 0 means the resident pair.  A trajectory is
@@ -214,7 +221,7 @@ class OpticalFlowE : public OpticalFlowBase {
     const char* no_volume;
     const char* no_entry;      // what Compute says when the device library lacks the entry point, and when there is no displacement
     const char* no_displacement;
-    DevicePtr ptr[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    DevicePtr ptr[kMaxDerivedFields] = {};
     std::string error;
 
     bool Selected(int field, unsigned mask) const { return !groups || (mask & groups[field]) != 0; }

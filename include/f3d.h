@@ -492,6 +492,51 @@ typedef struct f3d_strain_stats {
 int f3d_flow_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[8], unsigned fields, size_t width,
                     size_t height, size_t depth, f3d_strain_stats* stats /* nullable; non-null waits */);
 
+/* Strain fields of a displacement over a strain window: the displacement gradient G of a voxel is the slope of the unweighted
+ * least-squares plane through the displacement samples of its (2 radius + 1)^3 neighbourhood, and the strain fields are formed from
+ * that G by f3d_flow_strain's expressions.  It is a local affine fit of d itself, not a blur of strain fields: an affine displacement
+ * is reproduced whatever the pattern of missing samples, at radius 1 on a full window G[r][a] is the mean of the nine central
+ * differences around the voxel, and white noise of deviation s in d gives s / sqrt((2r+1)^2 sum i^2) in G (0.236 s, 0.063 s,
+ * 0.027 s at radius 1, 2, 3, against 0.707 s of f3d_flow_strain).  The arithmetic below is part of the ABI.
+ * Presence: a grid point is present when it lies inside the volume and none of u, v, w is NaN there (f3d_flow_strain's rule).  For
+ * voxel p, over the offsets (i, j, k) in [-r, r]^3 from p, with m = 1 at a present point and 0 elsewhere:
+ *   mask moments, exact integers:  n = sum m, Sx = sum i m, Sy = sum j m, Sz = sum k m, Sxx = sum i i m, Sxy = sum i j m, Sxz, Syy,
+ *     Syz, Szz
+ *   data sums in binary64, per component c of u, v, w, with t = (double)d_c at a present point and +0 elsewhere, formed separably
+ *     x, then y, then z; every sum as (((t[-r] + t[-r+1]) + ...) + t[r]) in ascending offset, every addition and every product by the
+ *     (double) integer offset rounded on its own, no running add / subtract sums (the discipline of f3d_local_correlation):
+ *       along x:  a0 = sum t,     a1 = sum (i * t)
+ *       along y:  b00 = sum a0,   b10 = sum a1,    b01 = sum (j * a0)
+ *       along z:  D0 = sum b00,   Dx = sum b10,    Dy = sum b01,   Dz = sum (k * b00)
+ *   normal matrix, exact integers:  C_ab = n S_ab - S_a S_b (symmetric 3 x 3); for an axis of size 1 C_aa = 1 (its off-diagonals and
+ *     right-hand side are 0 by themselves, so its column of G comes out 0, as in f3d_flow_strain).  adj = adjugate of C, and
+ *     det = C_00 adj_00 + C_01 adj_10 + C_02 adj_20 in int64.  |C| < 2^19, |adj| < 2^39 and det < 2^57 at radius <= 3; at radius 4
+ *     det leaves int64, so radius is 1 .. 3.
+ *   right-hand side and solution in binary64:  r_a = n * D_a - S_a * D0 (integers converted exactly),
+ *     num_a = (adj_a0 * r_0 + adj_a1 * r_1) + adj_a2 * r_2,  G[c][a] = (float)(num_a / (double)det): one IEEE binary64 division per
+ *     entry, nothing else in binary64 but + - *.
+ *   undefined voxel (every selected output NaN):  p absent (lost);  else n < min_count or det == 0, which is exact: the present
+ *     points are coplanar (thin).
+ * Outputs, in this order (out[0..16]), selected by group:
+ *   F3D_STRAIN_VOL  out[0] vol;  F3D_STRAIN_E  out[1..6] exx eyy ezz exy exz eyz;  F3D_STRAIN_EQ  out[7] eq: from this G by exactly
+ *                   the float32 expressions of f3d_flow_strain
+ *   F3D_WSTRAIN_G   out[8..16] G00 G01 G02 G10 G11 G12 G20 G21 G22 (row = component u v w, column = axis x y z)
+ * Geometry from the current container (f3d_set_container), whole volume, library stream.  Entries of out for groups not selected
+ * are ignored and never written.  Refused: a null input; a null selected output; fields 0 or with unknown bits; a selected output
+ * that is also an input; two selected outputs that are the same container; radius outside 1 .. 3; min_count outside
+ * 1 .. (2 radius + 1)^3; an empty or too large size.
+ * stats (nullable; asking waits for the stream): defined, folded, vol_min, vol_max, eq_max, vol_sum as in f3d_strain_stats, lost and
+ * thin as above.  vol and eq are computed for the statistics whether or not they are stored. */
+#define F3D_WSTRAIN_G 8u
+typedef struct f3d_window_strain_stats {
+  unsigned long long defined, folded, lost, thin;
+  float vol_min, vol_max, eq_max;
+  double vol_sum;
+} f3d_window_strain_stats;
+int f3d_window_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[17], unsigned fields, unsigned radius,
+                      unsigned min_count, size_t width, size_t height, size_t depth,
+                      f3d_window_strain_stats* stats /* nullable; non-null waits */);
+
 /* Principal strains of a displacement: the eigenvalues e1 >= e2 >= e3 of the Green-Lagrange tensor E of f3d_flow_strain (largest
  * extension, largest compaction, independent of how the sample sits in the grid), the maximum shear and the directions of e1 and
  * e3, in one stencil pass from d = (u, v, w); E itself is not stored.  Per voxel:

@@ -100,6 +100,14 @@ int f3d_flow_trajectory_end(f3d_flow flow);
 int f3d_flow_strain_compute(f3d_flow flow, int source, unsigned fields, float* const out[8], f3d_strain_stats* stats);
 int f3d_flow_strain_end(f3d_flow flow);
 
+/* Strain fields over a strain window (f3d_window_strain of include/f3d.h has the definition) of the same two sources,
+ * F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY.  fields selects groups of the seventeen outputs vol, exx, eyy, ezz, exy, exz, eyz, eq,
+ * G00 .. G22 (F3D_STRAIN_VOL / _E / _EQ, F3D_WSTRAIN_G); radius 1 .. 3; min_count 1 .. (2 radius + 1)^3.  Everything else as for
+ * f3d_flow_strain_compute; the containers live until f3d_flow_window_strain_end (or f3d_flow_destroy). */
+int f3d_flow_window_strain_compute(f3d_flow flow, int source, unsigned fields, unsigned radius, unsigned min_count,
+                                   float* const out[17], f3d_window_strain_stats* stats);
+int f3d_flow_window_strain_end(f3d_flow flow);
+
 /* Principal strains (f3d_principal_strain of include/f3d.h has the definition) of the same two sources, F3D_STRAIN_OF_FLOW or
  * F3D_STRAIN_OF_TRAJECTORY.  fields selects groups of the ten outputs e1, e2, e3, gmax, d1x, d1y, d1z, d3x, d3y, d3z
  * (F3D_PRINCIPAL_VALUES / _SHEAR / _DIR1 / _DIR3); out[i] of a selected output receives width * height * depth floats, entries of
