@@ -9,6 +9,7 @@ native handles raises -- build them with `python -c "import __graft_entry__ as g
 `make -C cuda-flow3d_amd`.
 """
 import atexit
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -357,6 +358,8 @@ def host():
         "f3d_op_solve_p_fused_weights": [C.c_void_p, C.POINTER(C.c_int)],
         "f3d_plan_solve_piecemeal": [_sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5,
         "f3d_plan_sweeps": [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2 + [C.c_int],
+        "f3d_pair8_plan": [C.c_int] * 7 + [C.POINTER(C.c_longlong)],
+        "f3d_pair8_decode": [C.c_int] * 4 + [C.POINTER(C.c_longlong)] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2,
         "f3d_pflow_create": [C.POINTER(C.c_void_p)], "f3d_pflow_initialize": [C.c_void_p, _sz, _sz, _sz],
         "f3d_pflow_compute": [C.c_void_p, _fp, _fp, _sz, _sz, _sz, pp, C.c_int, _fp, _fp, _fp, _fp],
         "f3d_pflow_stats": [C.c_void_p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)], "f3d_pflow_destroy": [C.c_void_p],
@@ -1268,6 +1271,30 @@ def plan_sweeps(inner, fused, tri, carry):
     if n < 0:
         raise F3dError("f3d_plan_sweeps failed")
     return [(sweeps[i], bool(weights[i])) for i in range(n)]
+
+
+Pair8Plan = collections.namedtuple("Pair8Plan", "A a b zc_a zc_b wgs cost tiles")
+
+
+def pair8_plan(width, rows, planes, ty, zc_limit=None, per_round=0, fold=False):
+    """How a fused solver launch of a width x rows x planes window with `ty` rows per tile is cut into workgroups (host arithmetic):
+    the first A tiles in `a` chunks of zc_a planes, the other tiles in `b` chunks of zc_b planes; A = 0 is the uniform plan.
+    per_round 0 = 256 (or F3D_PAIR8_ROUND); F3D_PAIR8_PLAN=0 gives the uniform plan."""
+    out = (C.c_longlong * 8)()
+    check(host().f3d_pair8_plan(width, rows, planes, ty, planes if zc_limit is None else zc_limit, per_round, int(bool(fold)), out))
+    return Pair8Plan(*[int(v) for v in out])
+
+
+def pair8_decode(width, rows, ty, fold, plan, xcd_remap, z_lo, z_hi):
+    """The kernel's decode of every workgroup number of a launch under `plan` (a Pair8Plan), run on the host: an int array
+    [grid, 6] of tile, tile column, tile row, folded, z0, z1 -- rows of -1 for the padding numbers of an XCD's run."""
+    cut = (C.c_longlong * 8)(*plan)
+    grid = C.c_int()
+    args = (width, rows, ty, int(bool(fold)), cut, int(bool(xcd_remap)), z_lo, z_hi)
+    check(host().f3d_pair8_decode(*args, 0, 0, None, C.byref(grid)))
+    out = np.empty((grid.value, 6), np.int32)
+    check(host().f3d_pair8_decode(*args, 0, grid.value, out.ctypes.data_as(C.POINTER(C.c_int)), None))
+    return out
 
 
 class Operation:

@@ -25,10 +25,12 @@
 #include <type_traits>
 
 #include "f3d_internal.h"
+#include "f3d_pair8_plan.h"
 
 namespace {
 
 constexpr int kLanes = 64;
+static_assert(kLanes == kPair8Lanes, "f3d_pair8_plan.h counts tile columns of one wave");
 
 // value held by the lane to the left / right (wave-wide shift by one lane; edge lanes keep their own value)
 __device__ __forceinline__ float lane_left(float v)

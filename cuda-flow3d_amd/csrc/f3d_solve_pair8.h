@@ -275,21 +275,7 @@ __device__ __forceinline__ void phi_ksi_stage2(const CarryP& k, const S3& xm, co
   }
 }
 
-// Tiles of a chunk, numbered x first.  With a folded last column (`fold`) a pair of tile rows (ty, ty + 1), ty even, is numbered: the
-// ntx - 1 regular tiles of row ty, the folded tile, the regular tiles of row ty + 1 -- so the folded tile marches in step with its y
-// neighbours; with nty odd the last row is alone with its folded tile (whose band B is empty).
-__host__ __device__ inline int pair8_tiles_per_chunk(int ntx, int nty, bool fold)
-{
-  return fold ? (ntx - 1) * nty + (nty + 1) / 2 : ntx * nty;
-}
-// F3D_PAIR8_FOLD=0 keeps one band per tile everywhere (A/B timing and the tests; read per call like F3D_PAIR8_TY): the same results
-inline bool pair8_folds(int width, int rows, int ty)
-{
-  const char* e = std::getenv("F3D_PAIR8_FOLD");
-  if (e && e[0] == '0') return false;
-  const int rem = width % kLanes;
-  return rem >= 1 && rem <= kLanes / 2 && width > kLanes && rows > ty;   // ntx >= 2, nty >= 2
-}
+// (the tile numbering, pair8_folds, the plan of a launch and the decode of a workgroup number: f3d_pair8_plan.h)
 
 // ABL (timing experiments only, wrong results): bit 0 = the loader issues nothing after the prologue, bit 1 = no stage
 // arithmetic (LDS traffic, barriers and stores stay), bit 2 = the compute waves only keep the barriers, bit 3 = arithmetic only behind the
@@ -311,7 +297,7 @@ inline bool pair8_folds(int width, int rows, int ty)
 // FOLDS: a build for the levels that fold (both tile kinds, one branch per workgroup).  The levels that do not fold keep the build
 // without it: with both bodies in every kernel a solve was 0.5 % slower where nothing folds (profiles/r13_pair8_fold_ab.txt).
 template <int MODE, int TY, int ABL, bool FD, bool YM, bool TIGHT, bool FOLDS = false>
-__device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, int zchunk, int ntx, int nty, int n_tiles, int xcd_remap)
+__device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, const Pair8Cut& cut, int ntx, int nty, int xcd_remap)
 {
   static_assert(!FOLDS || (!YM && !TIGHT && ABL == 0), "two row bands per tile: z-marching product builds only");
   static_assert(!(YM && FD), "the frame-derivative launchers march along z only");
@@ -333,26 +319,11 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
   __shared__ float hc1[2][3][2][32];        // the same for the two halo columns: [component][side][core row]
   __shared__ float img3[(ABL & 64) ? 3 : 1][(ABL & 64) ? NR : 1][(ABL & 64) ? kLanes : 1];  // lab: stage-2 results for a third stage
 
-  int tile = static_cast<int>(blockIdx.x);
-  if (xcd_remap) {
-    const int per_xcd = (n_tiles + 7) / 8;
-    tile = (tile % 8) * per_xcd + tile / 8;
-  }
-  if (tile >= n_tiles) return;
-  // the tile's place (FOLDS: the numbering described at pair8_tiles_per_chunk)
-  int tx = tile % ntx;
-  int ty = (tile / ntx) % nty;
-  int tz = tile / (ntx * nty);
-  bool folded = false;
-  if constexpr (FOLDS) {
-    const int per_chunk = pair8_tiles_per_chunk(ntx, nty, true);
-    tz = tile / per_chunk;
-    const int i = tile % per_chunk;
-    const int pair = i / (2 * ntx - 1), k = i % (2 * ntx - 1);
-    folded = k == ntx - 1;
-    tx = k < ntx ? k : k - ntx;
-    ty = k < ntx ? 2 * pair : 2 * pair + 1;
-  }
+  // the workgroup's tile and planes (f3d_pair8_plan.h: the function the host API decodes with); FOLDS: the numbering described there
+  Pair8Wg wg;
+  if (!pair8_decode(static_cast<int>(blockIdx.x), cut, ntx, nty, FOLDS, xcd_remap, m_lo, m_hi, (ABL & 64) ? 1 : 0, wg)) return;
+  const int tx = wg.tx, ty = wg.ty;
+  const bool folded = wg.folded;
 
   // ONE branch on the tile kind per workgroup: everything below exists twice in a build that folds, over the same LDS
   auto tile_body = [&](auto fold_c) __attribute__((always_inline)) {
@@ -361,8 +332,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
   const int r = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.y));
   const bool colw = r == NR;
   const bool loader = r == NR + 1;
-  const int z0 = m_lo + tz * zchunk;
-  const int z1 = min(z0 + zchunk + ((ABL & 64) ? 1 : 0), m_hi);   // (lab, bit 6: the third stage trails by one more plane)
+  const int z0 = wg.z0, z1 = wg.z1;   // (lab, bit 6: z1 is one plane further, the third stage trails by one more plane)
   const int qs = z0 > 0 ? z0 - 1 : 0;        // first and last plane of stage 1
   const int qe = z1 < MDIM ? z1 : MDIM - 1;
   const int q_end = z1 < MDIM ? qe : qe + 1;  // the top chunk takes one more step: stage 2 of plane D-1 alone
@@ -937,60 +907,24 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, i
 
 // the kernels: one body, two sets of launch attributes
 template <int MODE, int TY, int ABL = 0, bool FD = false, bool YM = false, bool FOLDS = false>
-__global__ __launch_bounds__(kLanes*(TY + 4)) void k_pair8(PairArgs a, F3dGeo g, int zchunk, int ntx, int nty, int n_tiles,
-                                                           int xcd_remap)
+__global__ __launch_bounds__(kLanes*(TY + 4)) void k_pair8(PairArgs a, F3dGeo g, Pair8Cut cut, int ntx, int nty, int xcd_remap)
 {
-  pair8_body<MODE, TY, ABL, FD, YM, false, FOLDS>(a, g, zchunk, ntx, nty, n_tiles, xcd_remap);
+  pair8_body<MODE, TY, ABL, FD, YM, false, FOLDS>(a, g, cut, ntx, nty, xcd_remap);
 }
 // ... a tile without halo rows (thin volumes marched along y, all planes in the tile): TY + 2 waves and ~50 KB of LDS per workgroup, held to
 // 128 registers so that TWO workgroups share a CU (four waves per SIMD) -- a level of BASELINE config 3 is then spread over twice as
 // many concurrent row waves
 template <int MODE, int TY>
-__global__ __launch_bounds__(kLanes*(TY + 2)) __attribute__((amdgpu_waves_per_eu(4))) void k_pair8t(PairArgs a, F3dGeo g, int zchunk, int ntx,
-                                                                                                   int nty, int n_tiles, int xcd_remap)
+__global__ __launch_bounds__(kLanes*(TY + 2)) __attribute__((amdgpu_waves_per_eu(4))) void k_pair8t(PairArgs a, F3dGeo g, Pair8Cut cut, int ntx,
+                                                                                                   int nty, int xcd_remap)
 {
-  pair8_body<MODE, TY, 0, false, true, true>(a, g, zchunk, ntx, nty, n_tiles, xcd_remap);
+  pair8_body<MODE, TY, 0, false, true, true>(a, g, cut, ntx, nty, xcd_remap);
 }
 
-// one workgroup per CU at a time: z-chunks by the round model of k_sweep7 (a chunk costs its planes plus ~7 steps of prologue
-// and repeated stage-1 planes, 256 workgroups run per round).  `cost` is in plane steps of ONE
-// workgroup; a step of a 16-wave workgroup (TY = 12) takes ~1.28 x a step of a 12-wave one (TY = 8) -- measured at 128^3 ... 512^3
-// (tools/kbench.py with F3D_PAIR8_TY): 12 rows win where the rows divide well (384^3: -9.5 %, 512^3: -4 %), 8 rows where one
-// round of workgroups covers the level (256^3: +6 %, 128^3: +6 %) -- so the caller compares cost x step.
-struct Pair8Plan {
-  int zchunk;
-  long cost;
-  long wgs = 0;
-};
-// `rows` / `planes`: extent along the tile rows and along the march (H and the z window; D and H for a y march)
-// `fold`: the last tile column holds two row bands per tile (pair8_folds; never for a y march)
-inline Pair8Plan pair8_plan_dims(int width, int rows, int planes, int ty, int zc_limit, long per_round = 256, bool fold = false)
-{
-  const long tiles = pair8_tiles_per_chunk((width + kLanes - 1) / kLanes, (rows + ty - 1) / ty, fold);
-  const int max_chunks = planes > 0 ? planes : 1;  // down to one plane per chunk: three steps instead of four where one round covers it
-  // what a chunk costs beside its planes, in plane steps (F3D_PAIR8_CHUNK_STEPS: launch-geometry experiments)
-  static const int extra = std::getenv("F3D_PAIR8_CHUNK_STEPS") ? std::atoi(std::getenv("F3D_PAIR8_CHUNK_STEPS")) : 7;
-  Pair8Plan p = {std::min(planes, zc_limit), -1};
-  for (int nzc = 1; nzc <= max_chunks; ++nzc) {
-    const int zc = (planes + nzc - 1) / nzc;
-    if (zc > zc_limit) continue;
-    const long wgs = tiles * ((planes + zc - 1) / zc);
-    const long cost = ((wgs + per_round - 1) / per_round) * (zc + extra);
-    if (p.cost < 0 || cost < p.cost) {
-      p.cost = cost;
-      p.zchunk = zc;
-      p.wgs = wgs;
-    }
-  }
-  if (p.cost < 0) {
-    p.cost = static_cast<long>((tiles + per_round - 1) / per_round) * (p.zchunk + extra);
-    p.wgs = tiles;
-  }
-  return p;
-}
+// the plan of a level window (f3d_pair8_plan.h); F3D_PAIR8_ROUND replaces the 256 workgroups of a round
 inline Pair8Plan pair8_plan(const F3dGeo& g, int ty, long per_round = 256)
 {
-  return pair8_plan_dims(g.W, g.H, g.z_hi - g.z_lo, ty, max_planes_per_chunk(g), per_round, pair8_folds(g.W, g.H, ty));
+  return pair8_plan_dims(g.W, g.H, g.z_hi - g.z_lo, ty, max_planes_per_chunk(g), pair8_per_round(per_round), pair8_folds(g.W, g.H, ty));
 }
 
 // Thin volumes march along y (YM, see the top of this file): the whole level in one launch, no slab window, every byte offset
@@ -1034,16 +968,12 @@ void launch_pair8(const PairArgs& args, const F3dGeo& g, int force_zchunk, int x
   constexpr int abl = 0;
 #endif
   const int fold = !YM && abl == 0 && pair8_folds(g.W, rows, TY) ? 1 : 0;   // (the timing builds of the lab keep one band per tile)
-  // (two workgroups of a tile without halo rows share a CU: 512 per round)
-  int zchunk = pair8_plan_dims(g.W, rows, planes, TY, zc_limit, TIGHT ? 512 : 256, fold != 0).zchunk;
-  if (force_zchunk > 0) zchunk = force_zchunk;
-  zchunk = std::min(zchunk, zc_limit);
-  const int nz = (planes + zchunk - 1) / zchunk;
-  const int n_tiles = pair8_tiles_per_chunk(ntx, nty, fold != 0) * nz;
-  const int per_xcd = (n_tiles + 7) / 8;
-  const int blocks = xcd_remap ? per_xcd * 8 : n_tiles;
-  const dim3 grid(blocks, 1, 1), block(kLanes, TY + (TIGHT ? 2 : 4), 1);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, f3d::stream(), a, g, zchunk, ntx, nty, n_tiles, xcd_remap); };
+  // (two workgroups of a tile without halo rows share a CU: 512 per round); the y marches keep the uniform plan
+  const int tiles = pair8_tiles_per_chunk(ntx, nty, fold != 0);
+  Pair8Cut cut = pair8_plan_dims(g.W, rows, planes, TY, zc_limit, pair8_per_round(TIGHT ? 512 : 256), fold != 0, !YM && abl == 0).cut;
+  if (force_zchunk > 0) cut = pair8_uniform_cut(tiles, planes, std::min(force_zchunk, zc_limit));   // F3D_ZCHUNK pins a uniform plan
+  const dim3 grid(pair8_cut_grid(cut, xcd_remap), 1, 1), block(kLanes, TY + (TIGHT ? 2 : 4), 1);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, f3d::stream(), a, g, cut, ntx, nty, xcd_remap); };
   if constexpr (!YM) {
     if (fold) return go(k_pair8<MODE, TY, 0, FD, false, true>);
   }

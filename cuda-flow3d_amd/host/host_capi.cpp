@@ -14,6 +14,7 @@
 #include "optical_flow_p.h"
 #include "optical_flow_slab.h"
 #include "synth.h"
+#include "../csrc/f3d_pair8_plan.h"
 
 struct f3d_flow_s {
   OpticalFlowE driver;
@@ -663,6 +664,40 @@ int f3d_plan_sweeps(int inner, int fused, int tri, int carry, int* sweeps, int* 
     next_weights[i] = cut[i].next_weights ? 1 : 0;
   }
   return static_cast<int>(cut.size());
+}
+
+int f3d_pair8_plan(int width, int rows, int planes, int ty, int zc_limit, int per_round, int fold, long long* plan)
+{
+  if (!plan || width < 1 || rows < 1 || planes < 1 || ty < 1 || zc_limit < 1) return 1;
+  const Pair8Plan p = pair8_plan_dims(width, rows, planes, ty, zc_limit, per_round > 0 ? per_round : pair8_per_round(256), fold != 0);
+  const long long v[8] = {p.cut.tiles_a, p.cut.chunks_a, p.cut.chunks_b, p.cut.zc_a, p.cut.zc_b, pair8_cut_wgs(p.cut), p.cost,
+                          p.cut.tiles_a + p.cut.tiles_b};
+  std::copy(v, v + 8, plan);
+  return 0;
+}
+
+int f3d_pair8_decode(int width, int rows, int ty, int fold, const long long* plan, int xcd_remap, int z_lo, int z_hi, int first,
+                     int count, int* out, int* grid)
+{
+  if (!plan || width < 1 || rows < 1 || ty < 1 || z_hi <= z_lo || first < 0 || count < 0 || (count && !out)) return 1;
+  const int ntx = (width + kPair8Lanes - 1) / kPair8Lanes, nty = (rows + ty - 1) / ty;
+  const int tiles = pair8_tiles_per_chunk(ntx, nty, fold != 0);
+  const Pair8Cut cut = {static_cast<int>(plan[0]), static_cast<int>(plan[1]), static_cast<int>(plan[3]),
+                        tiles - static_cast<int>(plan[0]), static_cast<int>(plan[2]), static_cast<int>(plan[4])};
+  if (cut.tiles_a < 0 || cut.tiles_b < 0 || (cut.tiles_a && (cut.chunks_a < 1 || cut.zc_a < 1)) ||
+      (cut.tiles_b && (cut.chunks_b < 1 || cut.zc_b < 1)))
+    return 1;
+  if (grid) *grid = pair8_cut_grid(cut, xcd_remap);
+  for (int i = 0; i < count; ++i) {
+    Pair8Wg w;
+    int* o = out + 6 * static_cast<size_t>(i);
+    if (pair8_decode(first + i, cut, ntx, nty, fold != 0, xcd_remap, z_lo, z_hi, 0, w)) {
+      o[0] = w.tile; o[1] = w.tx; o[2] = w.ty; o[3] = w.folded ? 1 : 0; o[4] = w.z0; o[5] = w.z1;
+    } else {
+      std::fill(o, o + 6, -1);
+    }
+  }
+  return 0;
 }
 
 size_t f3d_max_warp_level(size_t width, size_t height, size_t depth, float scale_factor)

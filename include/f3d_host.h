@@ -271,6 +271,17 @@ size_t f3d_piecemeal_budget_bytes(void);
  * driver can take its weights along.  Fills up to `capacity` launches: sweeps[i] = 1 .. 3 sweeps in launch i, next_weights[i] = 1
  * when it also writes the next phi / ksi; returns their number, or -1 if capacity is too small. */
 int f3d_plan_sweeps(int inner, int fused, int tri, int carry, int* sweeps, int* next_weights, int capacity);
+/* how a fused solver launch (k_pair8) of a level window is cut into workgroups (pure host arithmetic, csrc/f3d_pair8_plan.h; DESIGN.md
+ * section 3, "Launch shapes"): the first A tiles in a chunks of zc_a planes each, the other tiles in b chunks of zc_b planes; A = 0 is
+ * the uniform plan.  width, rows, planes: extents of the window; ty: rows per tile; zc_limit: planes a chunk may hold at most;
+ * per_round: workgroups that run at a time (<= 0: 256, or F3D_PAIR8_ROUND); fold: the last tile column holds two row bands per tile.
+ * plan[8] = A, a, b, zc_a, zc_b, workgroups, cost in plane steps, tiles.  F3D_PAIR8_PLAN=0 gives the uniform plan. */
+int f3d_pair8_plan(int width, int rows, int planes, int ty, int zc_limit, int per_round, int fold, long long* plan);
+/* the kernel's decode of workgroup numbers first .. first + count - 1 under plan[0 .. 4] (the same function, compiled for the host):
+ * out[6 i ..] = tile, tile column, tile row, folded, z0, z1 (planes [z0, z1) of [z_lo, z_hi)), or six times -1 for a padding number.
+ * *grid (if given) = workgroup numbers of the launch.  Returns 0, or 1 for arguments that make no plan. */
+int f3d_pair8_decode(int width, int rows, int ty, int fold, const long long* plan, int xcd_remap, int z_lo, int z_hi, int first,
+                     int count, int* out, int* grid);
 
 /* OpticalFlowP (src/optical_flow/optical_flow_p.h:35-57; ComputeFlow optical_flow_p.cpp:57-318): no pre-blur, no median */
 typedef struct f3d_pflow_s* f3d_pflow;
