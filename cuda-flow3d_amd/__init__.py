@@ -360,6 +360,8 @@ def host():
         "f3d_plan_sweeps": [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2 + [C.c_int],
         "f3d_pair8_plan": [C.c_int] * 7 + [C.POINTER(C.c_longlong)],
         "f3d_pair8_decode": [C.c_int] * 4 + [C.POINTER(C.c_longlong)] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2,
+        "f3d_pair8_plan_wide": [C.c_int] * 7 + [C.POINTER(C.c_longlong)],
+        "f3d_pair8_decode_wide": [C.c_int] * 4 + [C.POINTER(C.c_longlong)] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2,
         "f3d_pflow_create": [C.POINTER(C.c_void_p)], "f3d_pflow_initialize": [C.c_void_p, _sz, _sz, _sz],
         "f3d_pflow_compute": [C.c_void_p, _fp, _fp, _sz, _sz, _sz, pp, C.c_int, _fp, _fp, _fp, _fp],
         "f3d_pflow_stats": [C.c_void_p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)], "f3d_pflow_destroy": [C.c_void_p],
@@ -1294,6 +1296,31 @@ def pair8_decode(width, rows, ty, fold, plan, xcd_remap, z_lo, z_hi):
     check(host().f3d_pair8_decode(*args, 0, 0, None, C.byref(grid)))
     out = np.empty((grid.value, 6), np.int32)
     check(host().f3d_pair8_decode(*args, 0, grid.value, out.ctypes.data_as(C.POINTER(C.c_int)), None))
+    return out
+
+
+Pair8WidePlan = collections.namedtuple("Pair8WidePlan", "classes cost wgs tiles")
+
+
+def pair8_plan_wide(width, rows, planes, ty, zc_limit=None, per_round=0, fold=False):
+    """The plan the fused z-marching launches take (the launcher's own function, host arithmetic): `classes` is a tuple of up to three
+    (tiles, chunks, planes per chunk) in tile order, every class but the last filling whole rounds.  F3D_PAIR8_PLAN (read per
+    call) unset or 2 = the wide plan where it is strictly cheaper than pair8_plan's, 1 = pair8_plan's, 0 = the uniform plan."""
+    out = (C.c_longlong * 12)()
+    check(host().f3d_pair8_plan_wide(width, rows, planes, ty, planes if zc_limit is None else zc_limit, per_round, int(bool(fold)), out))
+    v = [int(x) for x in out]
+    return Pair8WidePlan(tuple(tuple(v[i:i + 3]) for i in (0, 3, 6) if v[i]), v[10], v[9], v[11])
+
+
+def pair8_decode_wide(width, rows, ty, fold, plan, xcd_remap, z_lo, z_hi):
+    """pair8_decode under a Pair8WidePlan"""
+    classes = [c for c in plan.classes] + [(0, 0, 0)] * (3 - len(plan.classes))
+    cut = (C.c_longlong * 9)(*[x for c in classes for x in c])
+    grid = C.c_int()
+    args = (width, rows, ty, int(bool(fold)), cut, int(bool(xcd_remap)), z_lo, z_hi)
+    check(host().f3d_pair8_decode_wide(*args, 0, 0, None, C.byref(grid)))
+    out = np.empty((grid.value, 6), np.int32)
+    check(host().f3d_pair8_decode_wide(*args, 0, grid.value, out.ctypes.data_as(C.POINTER(C.c_int)), None))
     return out
 
 

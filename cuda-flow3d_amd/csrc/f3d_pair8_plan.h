@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <vector>
 
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
@@ -15,6 +16,13 @@
 #endif
 
 constexpr int kPair8Lanes = 64;   // columns of a tile
+
+// a value that is the same in every lane of a wave, as a value (device: held in a scalar register; host: itself)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PAIR8_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
+#else
+#define PAIR8_UNIFORM(x) (x)
+#endif
 
 // Tiles of a level, numbered x first.  With a folded last column (`fold`) a pair of tile rows (ty, ty + 1), ty even, is numbered: the
 // ntx - 1 regular tiles of row ty, the folded tile, the regular tiles of row ty + 1 -- so the folded tile marches in step with its y
@@ -32,20 +40,25 @@ inline bool pair8_folds(int width, int rows, int ty)
   return rem >= 1 && rem <= kPair8Lanes / 2 && width > kPair8Lanes && rows > ty;   // ntx >= 2, nty >= 2
 }
 
-// The cut of a launch: two classes of tiles, in the tile numbering above.  Class A -- tiles 0 .. tiles_a-1 -- is cut into chunks_a
-// chunks of zc_a planes per tile, class B -- the other tiles_b tiles -- into chunks_b chunks of zc_b planes.  The uniform cut every
-// level had before is tiles_a = 0.  Handed to the kernel by value.
+// The cut of a launch: up to three classes of tiles, in the tile numbering above.  Class A -- tiles 0 .. tiles_a-1 -- is cut into chunks_a
+// chunks of zc_a planes per tile, class B -- the next tiles_b tiles -- into chunks_b chunks of zc_b planes, class C -- the last tiles_c
+// tiles -- into chunks_c chunks of zc_c planes.  An empty class has no tiles: the uniform cut is class B alone, the two-class cut A and B.
+// Handed to the kernel by value.
 struct Pair8Cut {
   int tiles_a, chunks_a, zc_a;
   int tiles_b, chunks_b, zc_b;
+  int tiles_c, chunks_c, zc_c;
 };
-__host__ __device__ inline int pair8_cut_wgs(const Pair8Cut& c) { return c.tiles_a * c.chunks_a + c.tiles_b * c.chunks_b; }
+__host__ __device__ inline int pair8_cut_wgs(const Pair8Cut& c)
+{
+  return c.tiles_a * c.chunks_a + c.tiles_b * c.chunks_b + c.tiles_c * c.chunks_c;
+}
 // Workgroups are dealt to the eight XCDs round-robin; with `xcd_remap` every XCD works on a contiguous run of a class (see
 // pair8_decode), which pads each class to a multiple of eight workgroup numbers.
 __host__ __device__ inline int pair8_cut_grid(const Pair8Cut& c, int xcd_remap)
 {
   if (!xcd_remap) return pair8_cut_wgs(c);
-  return 8 * ((c.tiles_a * c.chunks_a + 7) / 8 + (c.tiles_b * c.chunks_b + 7) / 8);
+  return 8 * ((c.tiles_a * c.chunks_a + 7) / 8 + (c.tiles_b * c.chunks_b + 7) / 8 + (c.tiles_c * c.chunks_c + 7) / 8);
 }
 
 struct Pair8Wg {
@@ -56,31 +69,36 @@ struct Pair8Wg {
 };
 
 // Workgroup number -> tile and planes; false for the padding numbers of an XCD's run.
-// Order.  Class A first, then class B; inside a class chunk-major (all tiles of the class at their first chunk, then the second
+// Order.  The classes in order (A, B, C); inside a class chunk-major (all tiles of the class at their first chunk, then the second
 // ...), tiles x first: workgroups that run together march the same planes of neighbouring tiles, so the rows of a plane are swept
 // across all memory channels and the halo rows and columns a tile fetches are its neighbours' core data of the same moment.
-// With xcd_remap, workgroup i runs on XCD i % 8: XCD x gets the x-th eighth of class A (a contiguous run, ceil(nA / 8) numbers) and
-// then the x-th eighth of class B -- its share of a round of whole columns first, as before its share of a round of chunks.
+// With xcd_remap, workgroup i runs on XCD i % 8: XCD x gets the x-th eighth of class A (a contiguous run, ceil(nA / 8) numbers),
+// then the x-th eighth of class B, then that of class C -- its share of each round of a class, the classes in the order they run.
 // `more`: planes a chunk marches beyond its own (timing builds of the lab only).
 __host__ __device__ inline bool pair8_decode(int wg, const Pair8Cut& c, int ntx, int nty, bool fold, int xcd_remap, int m_lo,
                                              int m_hi, int more, Pair8Wg& w)
 {
-  const int n_a = c.tiles_a * c.chunks_a, n_b = c.tiles_b * c.chunks_b;
-  bool in_a;
-  int item;
+  // (the nine numbers as values first: a choice among three fields of `c` by class number is otherwise compiled into an indexed read of
+  // a copy of `c` in scratch memory, per lane)
+  const int tiles_a = PAIR8_UNIFORM(c.tiles_a), tiles_b = PAIR8_UNIFORM(c.tiles_b), tiles_c = PAIR8_UNIFORM(c.tiles_c);
+  const int zc_a = PAIR8_UNIFORM(c.zc_a), zc_b = PAIR8_UNIFORM(c.zc_b), zc_c = PAIR8_UNIFORM(c.zc_c);
+  const int n_a = tiles_a * PAIR8_UNIFORM(c.chunks_a), n_b = tiles_b * PAIR8_UNIFORM(c.chunks_b), n_c = tiles_c * PAIR8_UNIFORM(c.chunks_c);
+  int cls;    // 0, 1, 2 = A, B, C
+  int item;   // chunk-major position inside the class
   if (xcd_remap) {
-    const int per_a = (n_a + 7) / 8, per_b = (n_b + 7) / 8;
+    const int per_a = (n_a + 7) / 8, per_b = (n_b + 7) / 8, per_c = (n_c + 7) / 8;
     const int xcd = wg % 8, s = wg / 8;
-    in_a = s < per_a;
-    item = in_a ? xcd * per_a + s : xcd * per_b + (s - per_a);
+    cls = s < per_a ? 0 : (s < per_a + per_b ? 1 : 2);
+    item = cls == 0 ? xcd * per_a + s : (cls == 1 ? xcd * per_b + (s - per_a) : xcd * per_c + (s - per_a - per_b));
   } else {
-    in_a = wg < n_a;
-    item = in_a ? wg : wg - n_a;
+    cls = wg < n_a ? 0 : (wg < n_a + n_b ? 1 : 2);
+    item = cls == 0 ? wg : (cls == 1 ? wg - n_a : wg - n_a - n_b);
   }
-  if (item >= (in_a ? n_a : n_b)) return false;
-  const int tiles = in_a ? c.tiles_a : c.tiles_b, zc = in_a ? c.zc_a : c.zc_b;
+  if (item >= (cls == 0 ? n_a : (cls == 1 ? n_b : n_c))) return false;
+  const int tiles = cls == 0 ? tiles_a : (cls == 1 ? tiles_b : tiles_c);
+  const int zc = cls == 0 ? zc_a : (cls == 1 ? zc_b : zc_c);
   const int chunk = item / tiles;
-  w.tile = item % tiles + (in_a ? 0 : c.tiles_a);
+  w.tile = item % tiles + (cls == 0 ? 0 : (cls == 1 ? tiles_a : tiles_a + tiles_b));
   w.z0 = m_lo + chunk * zc;
   w.z1 = w.z0 + zc + more < m_hi ? w.z0 + zc + more : m_hi;
   if (fold) {
@@ -114,7 +132,7 @@ struct Pair8Plan {
 };
 inline Pair8Cut pair8_uniform_cut(int tiles, int planes, int zchunk)
 {
-  return Pair8Cut{0, 0, 0, tiles, (planes + zchunk - 1) / zchunk, zchunk};
+  return Pair8Cut{0, 0, 0, tiles, (planes + zchunk - 1) / zchunk, zchunk, 0, 0, 0};
 }
 // F3D_PAIR8_ROUND=<n> overrides the workgroups per round (the tests reach both classes on tiny shapes with it); read per call
 inline long pair8_per_round(long standard)
@@ -125,14 +143,18 @@ inline long pair8_per_round(long standard)
 }
 // `rows` / `planes`: extent along the tile rows and along the march (H and the z window; D and H for a y march)
 // `fold`: the last tile column holds two row bands per tile (pair8_folds; never for a y march)
-// `two_class`: false keeps the uniform plan (the y-marching builds); F3D_PAIR8_PLAN=0 does so everywhere (A/B timing, tests; read per call)
-inline Pair8Plan pair8_plan_dims(int width, int rows, int planes, int ty, int zc_limit, long per_round = 256, bool fold = false,
-                                 bool two_class = true)
+// what a chunk costs beside its planes, in plane steps (F3D_PAIR8_CHUNK_STEPS: launch-geometry experiments)
+inline int pair8_chunk_steps()
+{
+  static const int extra = std::getenv("F3D_PAIR8_CHUNK_STEPS") ? std::atoi(std::getenv("F3D_PAIR8_CHUNK_STEPS")) : 7;
+  return extra;
+}
+// `two_class`: false gives the uniform plan.  Reads no switch: the same arguments give the same plan.
+inline Pair8Plan pair8_plan_two(int width, int rows, int planes, int ty, int zc_limit, long per_round, bool fold, bool two_class)
 {
   const long tiles = pair8_tiles_per_chunk((width + kPair8Lanes - 1) / kPair8Lanes, (rows + ty - 1) / ty, fold);
   const int max_chunks = planes > 0 ? planes : 1;  // down to one plane per chunk: three steps instead of four where one round covers it
-  // what a chunk costs beside its planes, in plane steps (F3D_PAIR8_CHUNK_STEPS: launch-geometry experiments)
-  static const int extra = std::getenv("F3D_PAIR8_CHUNK_STEPS") ? std::atoi(std::getenv("F3D_PAIR8_CHUNK_STEPS")) : 7;
+  const int extra = pair8_chunk_steps();
   auto rounds = [&](long wgs) { return (wgs + per_round - 1) / per_round; };
   Pair8Plan p = {std::min(planes, zc_limit), -1};
   for (int nzc = 1; nzc <= max_chunks; ++nzc) {
@@ -152,8 +174,7 @@ inline Pair8Plan pair8_plan_dims(int width, int rows, int planes, int ty, int zc
   }
   if (p.zchunk < 1) p.zchunk = 1;
   p.cut = pair8_uniform_cut(static_cast<int>(tiles), planes, p.zchunk);
-  const char* pe = std::getenv("F3D_PAIR8_PLAN");
-  if (!two_class || (pe && pe[0] == '0') || tiles <= per_round || planes < 1 || zc_limit < 1) return p;
+  if (!two_class || tiles <= per_round || planes < 1 || zc_limit < 1) return p;
   // class A: whole rounds of tiles (A x a a multiple of per_round) in as few chunks as the chunk limit allows, or one or two more;
   // class B: the other tiles in 1 .. planes chunks.  A strictly cheaper cut wins; on a tie the uniform plan stays.
   const int a0 = (planes + zc_limit - 1) / zc_limit;
@@ -179,12 +200,123 @@ inline Pair8Plan pair8_plan_dims(int width, int rows, int planes, int ty, int zc
         if (cost < p.cost) {
           p.cost = cost;
           p.wgs = A * a + (tiles - A) * b;
-          p.cut = Pair8Cut{static_cast<int>(A), a, zc_a, static_cast<int>(tiles - A), b, zc_b};
+          p.cut = Pair8Cut{static_cast<int>(A), a, zc_a, static_cast<int>(tiles - A), b, zc_b, 0, 0, 0};
         }
       }
     }
   }
   return p;
+}
+
+// `two_class`: false keeps the uniform plan (the y-marching builds); F3D_PAIR8_PLAN=0 does so everywhere (A/B timing, tests; read per call)
+inline Pair8Plan pair8_plan_dims(int width, int rows, int planes, int ty, int zc_limit, long per_round = 256, bool fold = false,
+                                 bool two_class = true)
+{
+  const char* pe = std::getenv("F3D_PAIR8_PLAN");
+  return pair8_plan_two(width, rows, planes, ty, zc_limit, per_round, fold, two_class && !(pe && pe[0] == '0'));
+}
+
+// The wide plan: up to three classes, also on levels one round covers.  The two-class plan above leaves two kinds of waste in the
+// round model.  A level of at most per_round tiles keeps one chunk length for every tile, although "most tiles in two chunks, the few
+// left over cut finely" fills the rounds better (307^3: 130 tiles in 3 chunks of 103 planes are two rounds of 110 steps less a
+// few; 128 tiles x 2 chunks of 154 planes are ONE full round of 161 steps and the two tiles left over one round of 10).  And what is
+// left beside class A is itself a level with a remainder (512^3: 88 tiles left, of which 64 x 4 chunks fill a round exactly).
+//   classes  up to three, in tile order; every class but the last fills whole rounds (tiles_i x chunks_i a multiple of per_round),
+//            the last class is the cheapest uniform cut of the tiles left;
+//   cost     sum over the classes of rounds(tiles_i x chunks_i) x (zc_i + extra);
+//   leading  a leading class takes one of the 16 smallest chunk counts the chunk limit allows;
+//   tie      taken only where strictly cheaper than pair8_plan_two's plan for the same arguments, which is returned otherwise --
+//            among wide plans the first found stays (fewer classes first, then fewer chunks, then fewer tiles in the leading class).
+// Pure arithmetic on its arguments: F3D_PAIR8_ROUND and F3D_PAIR8_PLAN are read by the callers, per call.
+inline Pair8Plan pair8_plan_wide(int width, int rows, int planes, int ty, int zc_limit, long per_round = 256, bool fold = false)
+{
+  Pair8Plan best = pair8_plan_two(width, rows, planes, ty, zc_limit, per_round, fold, true);
+  const int tiles = pair8_tiles_per_chunk((width + kPair8Lanes - 1) / kPair8Lanes, (rows + ty - 1) / ty, fold);
+  if (tiles < 2 || planes < 1 || zc_limit < 1 || per_round < 1) return best;
+  const int extra = pair8_chunk_steps();
+  auto rounds = [&](long wgs) { return (wgs + per_round - 1) / per_round; };
+
+  struct Class { int tiles, chunks, zc; };
+  // the chunkings a leading class may take, and the tile counts that fill whole rounds with each (multiples of `stride`)
+  struct Lead { int chunks, zc; long stride; };
+  Lead leads[16];
+  int n_leads = 0;
+  const int a0 = (planes + zc_limit - 1) / zc_limit;
+  for (int na = a0, seen = 0; na < a0 + 16 && na <= planes; ++na) {
+    const int zc = (planes + na - 1) / na;
+    if (zc > zc_limit || zc == seen) continue;
+    seen = zc;
+    const int a = (planes + zc - 1) / zc;
+    long g = a, r = per_round;
+    while (r) { const long t = g % r; g = r; r = t; }   // g = gcd(a, per_round)
+    leads[n_leads++] = Lead{a, zc, per_round / g};
+  }
+  // the cheapest uniform cut of n tiles (the first cheapest of 1 .. planes chunks, as in the uniform plan), and the cheapest cut of n
+  // tiles into a leading class and that; both remembered per n -- the tile counts left over are few (tiles minus multiples of a stride)
+  struct Tail { long cost = -1; Class lead = {0, 0, 0}, last = {0, 0, 0}; };
+  std::vector<Tail> one(tiles + 1), two(tiles + 1);
+  auto uniform = [&](int n) -> const Tail& {
+    Tail& t = one[n];
+    if (t.cost >= 0) return t;
+    for (int nzc = 1, seen = 0; nzc <= planes; ++nzc) {
+      const int zc = (planes + nzc - 1) / nzc;
+      if (zc > zc_limit || zc == seen) continue;
+      seen = zc;
+      const int b = (planes + zc - 1) / zc;
+      const long cost = rounds(static_cast<long>(n) * b) * (zc + extra);
+      if (t.cost < 0 || cost < t.cost) {
+        t.cost = cost;
+        t.last = Class{n, b, zc};
+      }
+    }
+    return t;
+  };
+  auto lead_and_uniform = [&](int n) -> const Tail& {
+    Tail& t = two[n];
+    if (t.cost >= 0) return t;
+    t = uniform(n);
+    for (int i = 0; i < n_leads; ++i) {
+      for (long A = leads[i].stride; A < n; A += leads[i].stride) {
+        const long cost_a = rounds(A * leads[i].chunks) * (leads[i].zc + extra);
+        if (cost_a >= t.cost) break;
+        const Tail& rest = uniform(n - static_cast<int>(A));
+        if (cost_a + rest.cost < t.cost) {
+          t.cost = cost_a + rest.cost;
+          t.lead = Class{static_cast<int>(A), leads[i].chunks, leads[i].zc};
+          t.last = rest.last;
+        }
+      }
+    }
+    return t;
+  };
+  auto take = [&](long cost, const Class& a, const Class& b, const Class& c) {
+    best.cost = cost;
+    best.cut = Pair8Cut{a.tiles, a.chunks, a.zc, b.tiles, b.chunks, b.zc, c.tiles, c.chunks, c.zc};
+    best.wgs = pair8_cut_wgs(best.cut);
+  };
+  {   // one or two classes
+    const Tail& t = lead_and_uniform(tiles);
+    if (t.cost < best.cost) take(t.cost, t.lead, t.last, Class{0, 0, 0});
+  }
+  for (int i = 0; i < n_leads; ++i) {   // three
+    for (long A = leads[i].stride; A < tiles; A += leads[i].stride) {
+      const long cost_a = rounds(A * leads[i].chunks) * (leads[i].zc + extra);
+      if (cost_a >= best.cost) break;
+      const Tail& rest = lead_and_uniform(tiles - static_cast<int>(A));
+      if (rest.lead.tiles && cost_a + rest.cost < best.cost)
+        take(cost_a + rest.cost, Class{static_cast<int>(A), leads[i].chunks, leads[i].zc}, rest.lead, rest.last);
+    }
+  }
+  return best;
+}
+
+// The plan a z-marching product launch takes: F3D_PAIR8_PLAN (read per call) unset or 2 = the wide plan, 1 = the two-class plan,
+// 0 = the uniform plan.
+inline Pair8Plan pair8_plan_launch(int width, int rows, int planes, int ty, int zc_limit, long per_round = 256, bool fold = false)
+{
+  const char* pe = std::getenv("F3D_PAIR8_PLAN");
+  if (pe && (pe[0] == '0' || pe[0] == '1')) return pair8_plan_two(width, rows, planes, ty, zc_limit, per_round, fold, pe[0] == '1');
+  return pair8_plan_wide(width, rows, planes, ty, zc_limit, per_round, fold);
 }
 
 #ifdef F3D_PAIR8_PLAN_OWN_QUALIFIERS

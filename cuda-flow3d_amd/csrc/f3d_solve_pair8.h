@@ -921,10 +921,37 @@ __global__ __launch_bounds__(kLanes*(TY + 2)) __attribute__((amdgpu_waves_per_eu
   pair8_body<MODE, TY, 0, false, true, true>(a, g, cut, ntx, nty, xcd_remap);
 }
 
+// pair8_plan_launch (f3d_pair8_plan.h: the wide plan, or what F3D_PAIR8_PLAN asks for) with the last answer per tile height kept: the
+// launches of a level ask for the same plans over and over -- pair8_rows prices three tile heights per launch -- and the wide
+// plan's enumeration costs up to 100 us at 512^3.  The key holds every argument and the switch, so this is the same pure function.
+inline Pair8Plan pair8_plan_launch_kept(int width, int rows, int planes, int ty, int zc_limit, long per_round, bool fold)
+{
+  struct Key {
+    int width, rows, planes, ty, zc_limit, fold, plan;
+    long per_round;
+    bool operator==(const Key& o) const
+    {
+      return width == o.width && rows == o.rows && planes == o.planes && ty == o.ty && zc_limit == o.zc_limit && fold == o.fold &&
+             plan == o.plan && per_round == o.per_round;
+    }
+  };
+  thread_local Key keys[3] = {};
+  thread_local Pair8Plan plans[3] = {};
+  const char* pe = std::getenv("F3D_PAIR8_PLAN");
+  const Key key = {width, rows, planes, ty, zc_limit, fold ? 1 : 0, pe ? pe[0] : 0, per_round};
+  const int slot = ty <= 4 ? 0 : (ty <= 8 ? 1 : 2);
+  if (!(keys[slot] == key)) {
+    plans[slot] = pair8_plan_launch(width, rows, planes, ty, zc_limit, per_round, fold);
+    keys[slot] = key;
+  }
+  return plans[slot];
+}
+
 // the plan of a level window (f3d_pair8_plan.h); F3D_PAIR8_ROUND replaces the 256 workgroups of a round
 inline Pair8Plan pair8_plan(const F3dGeo& g, int ty, long per_round = 256)
 {
-  return pair8_plan_dims(g.W, g.H, g.z_hi - g.z_lo, ty, max_planes_per_chunk(g), pair8_per_round(per_round), pair8_folds(g.W, g.H, ty));
+  return pair8_plan_launch_kept(g.W, g.H, g.z_hi - g.z_lo, ty, max_planes_per_chunk(g), pair8_per_round(per_round),
+                                pair8_folds(g.W, g.H, ty));
 }
 
 // Thin volumes march along y (YM, see the top of this file): the whole level in one launch, no slab window, every byte offset
@@ -968,9 +995,11 @@ void launch_pair8(const PairArgs& args, const F3dGeo& g, int force_zchunk, int x
   constexpr int abl = 0;
 #endif
   const int fold = !YM && abl == 0 && pair8_folds(g.W, rows, TY) ? 1 : 0;   // (the timing builds of the lab keep one band per tile)
-  // (two workgroups of a tile without halo rows share a CU: 512 per round); the y marches keep the uniform plan
+  // (two workgroups of a tile without halo rows share a CU: 512 per round); the y marches and the lab's timing builds keep the uniform plan
   const int tiles = pair8_tiles_per_chunk(ntx, nty, fold != 0);
-  Pair8Cut cut = pair8_plan_dims(g.W, rows, planes, TY, zc_limit, pair8_per_round(TIGHT ? 512 : 256), fold != 0, !YM && abl == 0).cut;
+  const long per_round = pair8_per_round(TIGHT ? 512 : 256);
+  Pair8Cut cut = !YM && abl == 0 ? pair8_plan_launch_kept(g.W, rows, planes, TY, zc_limit, per_round, fold != 0).cut
+                                 : pair8_plan_two(g.W, rows, planes, TY, zc_limit, per_round, fold != 0, false).cut;
   if (force_zchunk > 0) cut = pair8_uniform_cut(tiles, planes, std::min(force_zchunk, zc_limit));   // F3D_ZCHUNK pins a uniform plan
   const dim3 grid(pair8_cut_grid(cut, xcd_remap), 1, 1), block(kLanes, TY + (TIGHT ? 2 : 4), 1);
   auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, f3d::stream(), a, g, cut, ntx, nty, xcd_remap); };

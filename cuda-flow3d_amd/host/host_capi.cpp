@@ -683,10 +683,45 @@ int f3d_pair8_decode(int width, int rows, int ty, int fold, const long long* pla
   const int ntx = (width + kPair8Lanes - 1) / kPair8Lanes, nty = (rows + ty - 1) / ty;
   const int tiles = pair8_tiles_per_chunk(ntx, nty, fold != 0);
   const Pair8Cut cut = {static_cast<int>(plan[0]), static_cast<int>(plan[1]), static_cast<int>(plan[3]),
-                        tiles - static_cast<int>(plan[0]), static_cast<int>(plan[2]), static_cast<int>(plan[4])};
+                        tiles - static_cast<int>(plan[0]), static_cast<int>(plan[2]), static_cast<int>(plan[4]), 0, 0, 0};
   if (cut.tiles_a < 0 || cut.tiles_b < 0 || (cut.tiles_a && (cut.chunks_a < 1 || cut.zc_a < 1)) ||
       (cut.tiles_b && (cut.chunks_b < 1 || cut.zc_b < 1)))
     return 1;
+  if (grid) *grid = pair8_cut_grid(cut, xcd_remap);
+  for (int i = 0; i < count; ++i) {
+    Pair8Wg w;
+    int* o = out + 6 * static_cast<size_t>(i);
+    if (pair8_decode(first + i, cut, ntx, nty, fold != 0, xcd_remap, z_lo, z_hi, 0, w)) {
+      o[0] = w.tile; o[1] = w.tx; o[2] = w.ty; o[3] = w.folded ? 1 : 0; o[4] = w.z0; o[5] = w.z1;
+    } else {
+      std::fill(o, o + 6, -1);
+    }
+  }
+  return 0;
+}
+
+int f3d_pair8_plan_wide(int width, int rows, int planes, int ty, int zc_limit, int per_round, int fold, long long* plan)
+{
+  if (!plan || width < 1 || rows < 1 || planes < 1 || ty < 1 || zc_limit < 1) return 1;
+  const Pair8Plan p = pair8_plan_launch(width, rows, planes, ty, zc_limit, per_round > 0 ? per_round : pair8_per_round(256), fold != 0);
+  const Pair8Cut& c = p.cut;
+  const long long v[12] = {c.tiles_a, c.chunks_a, c.zc_a, c.tiles_b, c.chunks_b, c.zc_b, c.tiles_c, c.chunks_c, c.zc_c,
+                           pair8_cut_wgs(c), p.cost, c.tiles_a + c.tiles_b + c.tiles_c};
+  std::copy(v, v + 12, plan);
+  return 0;
+}
+
+int f3d_pair8_decode_wide(int width, int rows, int ty, int fold, const long long* plan, int xcd_remap, int z_lo, int z_hi, int first,
+                          int count, int* out, int* grid)
+{
+  if (!plan || width < 1 || rows < 1 || ty < 1 || z_hi <= z_lo || first < 0 || count < 0 || (count && !out)) return 1;
+  const int ntx = (width + kPair8Lanes - 1) / kPair8Lanes, nty = (rows + ty - 1) / ty;
+  int v[9];
+  for (int i = 0; i < 9; ++i) v[i] = static_cast<int>(plan[i]);
+  const Pair8Cut cut = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
+  for (int i = 0; i < 9; i += 3)   // a class is empty or has tiles, chunks and planes per chunk
+    if (v[i] < 0 || (v[i] && (v[i + 1] < 1 || v[i + 2] < 1))) return 1;
+  if (cut.tiles_a + cut.tiles_b + cut.tiles_c != pair8_tiles_per_chunk(ntx, nty, fold != 0)) return 1;
   if (grid) *grid = pair8_cut_grid(cut, xcd_remap);
   for (int i = 0; i < count; ++i) {
     Pair8Wg w;

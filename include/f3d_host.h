@@ -282,6 +282,15 @@ int f3d_pair8_plan(int width, int rows, int planes, int ty, int zc_limit, int pe
  * *grid (if given) = workgroup numbers of the launch.  Returns 0, or 1 for arguments that make no plan. */
 int f3d_pair8_decode(int width, int rows, int ty, int fold, const long long* plan, int xcd_remap, int z_lo, int z_hi, int first,
                      int count, int* out, int* grid);
+/* the plan the fused z-marching launches take (the launcher's own function): up to three classes of tiles in tile order, class i
+ * of tiles_i tiles in chunks_i chunks of zc_i planes, every class but the last filling whole rounds; an empty class has no tiles.
+ * F3D_PAIR8_PLAN (read per call) unset or 2: the wide plan, taken where it is strictly cheaper than f3d_pair8_plan's; 1: exactly
+ * f3d_pair8_plan's; 0: the uniform plan.  Arguments as for f3d_pair8_plan.
+ * plan[12] = tiles_a, chunks_a, zc_a, tiles_b, chunks_b, zc_b, tiles_c, chunks_c, zc_c, workgroups, cost in plane steps, tiles. */
+int f3d_pair8_plan_wide(int width, int rows, int planes, int ty, int zc_limit, int per_round, int fold, long long* plan);
+/* f3d_pair8_decode under plan[0 .. 8] of f3d_pair8_plan_wide */
+int f3d_pair8_decode_wide(int width, int rows, int ty, int fold, const long long* plan, int xcd_remap, int z_lo, int z_hi, int first,
+                          int count, int* out, int* grid);
 
 /* OpticalFlowP (src/optical_flow/optical_flow_p.h:35-57; ComputeFlow optical_flow_p.cpp:57-318): no pre-blur, no median */
 typedef struct f3d_pflow_s* f3d_pflow;
