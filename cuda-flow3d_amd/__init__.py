@@ -330,6 +330,11 @@ def host():
         "f3d_flow_principal_end": [C.c_void_p],
         "f3d_flow_polar_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(PolarStats)],
         "f3d_flow_polar_end": [C.c_void_p],
+        "f3d_flow_window_principal_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(_fp),
+                                              C.POINTER(PrincipalStats)],
+        "f3d_flow_window_principal_end": [C.c_void_p],
+        "f3d_flow_window_polar_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(_fp), C.POINTER(PolarStats)],
+        "f3d_flow_window_polar_end": [C.c_void_p],
         "f3d_flow_inverse_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_float, C.POINTER(_fp), C.POINTER(InverseStats)],
         "f3d_flow_inverse_end": [C.c_void_p],
         "f3d_flow_match_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_float, C.POINTER(_fp), C.POINTER(CorrelationStats)],
@@ -491,6 +496,16 @@ def _principal_entry():
 def _polar_entry():
     return _entry("f3d_polar_decomposition", [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(PolarStats)],
                   "compute local rotations and stretches")
+
+
+def _principal_from_gradient_entry():
+    return _entry("f3d_principal_from_gradient", [_dpp, _dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(PrincipalStats)],
+                  "compute principal strains of a stored gradient")
+
+
+def _polar_from_gradient_entry():
+    return _entry("f3d_polar_from_gradient", [_dpp, _dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(PolarStats)],
+                  "compute local rotations and stretches of a stored gradient")
 
 
 def _inverse_entry():
@@ -667,6 +682,18 @@ def _window_min_count(radius, min_count):
     return max(4, (2 * radius + 1) ** 3 // 4) if min_count is None else min_count
 
 
+def _window_args(radius, min_count):
+    """(radius, min_count) of a window call checked before anything touches the device: radius 1 .. 3, min_count (None:
+    _window_min_count's default) 1 .. (2 radius + 1)^3"""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= 3:
+        raise ValueError(f"radius must be 1, 2 or 3, not {radius!r}")
+    radius = int(radius)
+    count = _window_min_count(radius, min_count)
+    if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or not 1 <= count <= (2 * radius + 1) ** 3:
+        raise ValueError(f"min_count must be 1 .. {(2 * radius + 1) ** 3} at radius {radius}, not {min_count!r}")
+    return radius, int(count)
+
+
 def _principal_mask(fields):
     return _mask(fields, PRINCIPAL_GROUPS, "principal strain")
 
@@ -739,6 +766,89 @@ def polar_decomposition(u, v, w, fields=("angle", "vector", "stretch")):
     and "stats" -> dict (defined, folded, theta_max, l1_max, l3_min, theta_sum)."""
     fn = _polar_entry()
     return _grouped_fields(fn, "f3d_polar_decomposition", u, v, w, _polar_mask(fields), POLAR_NAMES, _POLAR_GROUP_OF, PolarStats())
+
+
+GRADIENT_NAMES = WINDOW_STRAIN_NAMES[8:]
+_GRADIENT_MISMATCH = "grad must be nine [z, y, x] volumes of one shape (G00 G01 G02 G10 G11 G12 G20 G21 G22) or a dict with those names"
+
+
+def _gradient_volumes(grad):
+    """the nine entries of `grad` in ABI order as contiguous float32 [z, y, x] arrays of one shape: from a sequence of nine, or by
+    name from the dict window_strain(..., fields=(..., "grad")) returns"""
+    if isinstance(grad, dict):
+        missing = [n for n in GRADIENT_NAMES if n not in grad]
+        if missing:
+            raise ValueError(f"grad has no {', '.join(missing)}: {_GRADIENT_MISMATCH}")
+        grad = [grad[n] for n in GRADIENT_NAMES]
+    try:
+        vols = [np.ascontiguousarray(a, dtype=np.float32) for a in grad]
+    except (TypeError, ValueError):
+        raise ValueError(_GRADIENT_MISMATCH) from None
+    if len(vols) != 9 or any(a.ndim != 3 or a.shape != vols[0].shape for a in vols):
+        raise ValueError(_GRADIENT_MISMATCH)
+    return vols
+
+
+def _from_gradient(fn, what, box, grad_ptrs, dims, mask, names, group_of, stats):
+    """the from-gradient entry `fn` on nine containers of `box` into fresh ones: a dict name -> array of the outputs `mask` selects,
+    plus "stats" -> dict"""
+    outs = [box.alloc() if mask & g else 0 for g in group_of]
+    box.set_current()
+    check(fn((_dp * 9)(*grad_ptrs), (_dp * len(outs))(*outs), mask, *dims, C.byref(stats)), what)
+    res = {n: box.download(o, dims) for n, o in zip(names, outs) if o}
+    res["stats"] = stats.as_dict()
+    return res
+
+
+def principal_from_gradient(grad, fields=("val", "shear")):
+    """Principal strains of a stored displacement gradient on the device (include/f3d.h, f3d_principal_from_gradient): grad is a
+    sequence of nine [z, y, x] arrays G00 G01 G02 G10 G11 G12 G20 G21 G22 (row = component u v w, column = axis x y z) or the dict
+    window_strain(..., fields=(..., "grad")) returns -- or a gradient from anywhere else, an FE solution, a filter of your own.  A
+    voxel with a NaN in any entry is undefined.  fields and the result as for principal_strain()."""
+    mask, vols = _principal_mask(fields), _gradient_volumes(grad)
+    fn = _principal_from_gradient_entry()
+    with _on_device(vols, _GRADIENT_MISMATCH) as (box, p, dims):
+        return _from_gradient(fn, "f3d_principal_from_gradient", box, p, dims, mask, PRINCIPAL_NAMES, _PRINCIPAL_GROUP_OF, PrincipalStats())
+
+
+def polar_from_gradient(grad, fields=("angle", "vector", "stretch")):
+    """Local rotation and principal stretches of a stored displacement gradient on the device (include/f3d.h,
+    f3d_polar_from_gradient): grad as for principal_from_gradient(), fields and the result as for polar_decomposition()."""
+    mask, vols = _polar_mask(fields), _gradient_volumes(grad)
+    fn = _polar_from_gradient_entry()
+    with _on_device(vols, _GRADIENT_MISMATCH) as (box, p, dims):
+        return _from_gradient(fn, "f3d_polar_from_gradient", box, p, dims, mask, POLAR_NAMES, _POLAR_GROUP_OF, PolarStats())
+
+
+def _window_then(fn, what, u, v, w, radius, min_count, mask, names, group_of, stats):
+    """one upload of (u, v, w), f3d_window_strain's gradient alone into nine containers, then the from-gradient entry `fn` on them:
+    nothing comes back to the host in between"""
+    window = _window_strain_entry()
+    with _on_device((u, v, w), "u, v and w must be three [z, y, x] volumes of one shape") as (box, p, dims):
+        grad = [box.alloc() for _ in range(9)]
+        box.set_current()
+        check(window(*p, (_dp * 17)(*([0] * 8 + grad)), WINDOW_STRAIN_GROUPS["grad"], radius, min_count, *dims, None), "f3d_window_strain")
+        return _from_gradient(fn, what, box, grad, dims, mask, names, group_of, stats)
+
+
+def window_principal(u, v, w, radius=2, min_count=None, fields=("val", "shear")):
+    """Principal strains of a displacement from its least-squares gradient over a strain window: window_strain()'s "grad" (radius,
+    min_count as there) handed to principal_from_gradient() on the device.  White noise in (u, v, w) biases e1, e3 and gmax of
+    principal_strain() upwards (the eigenvalues of a noisy tensor repel); the window's gradient carries a third (radius 1) to a
+    twenty-fifth (radius 3) of that noise.  fields and the result as for principal_strain()."""
+    mask, (radius, min_count) = _principal_mask(fields), _window_args(radius, min_count)
+    fn = _principal_from_gradient_entry()
+    return _window_then(fn, "f3d_principal_from_gradient", u, v, w, radius, min_count, mask, PRINCIPAL_NAMES, _PRINCIPAL_GROUP_OF,
+                        PrincipalStats())
+
+
+def window_rotation(u, v, w, radius=2, min_count=None, fields=("angle", "vector", "stretch")):
+    """Local rotation and principal stretches of a displacement from its least-squares gradient over a strain window:
+    window_strain()'s "grad" handed to polar_from_gradient() on the device.  radius, min_count as for window_strain(), fields and the
+    result as for polar_decomposition()."""
+    mask, (radius, min_count) = _polar_mask(fields), _window_args(radius, min_count)
+    fn = _polar_from_gradient_entry()
+    return _window_then(fn, "f3d_polar_from_gradient", u, v, w, radius, min_count, mask, POLAR_NAMES, _POLAR_GROUP_OF, PolarStats())
 
 
 def invert_displacement(u, v, w, iterations=32, tolerance=1e-3):
@@ -1701,6 +1811,36 @@ class OpticalFlow:
     def rotation_end(self):
         """free the rotation and stretch containers (destroy() does too)"""
         _host_check(host().f3d_flow_polar_end(self._h), "f3d_flow_polar_end")
+
+    def window_principal(self, source="flow", radius=2, min_count=None, fields=("val", "shear")):
+        """Principal strains from the least-squares gradient over a strain window of the flow the driver holds (source="flow") or of
+        the trajectory (source="trajectory"); same arguments and result shape as window_principal().  The call depends on its
+        arguments only: it needs no window_strain() before it and leaves that one's containers as they are."""
+        src, mask, stats = _source(source), _principal_mask(fields), PrincipalStats()
+        radius, min_count = _window_args(radius, min_count)
+        arrays = self._derived("f3d_flow_window_principal_compute", src, [mask & g for g in _PRINCIPAL_GROUP_OF], stats, mask, radius,
+                               min_count)
+        res = {n: a for n, a in zip(PRINCIPAL_NAMES, arrays) if a is not None}
+        res["stats"] = stats.as_dict()
+        return res
+
+    def window_principal_end(self):
+        """free the window principal strain containers, and the gradient's when window_rotation holds none (destroy() does too)"""
+        _host_check(host().f3d_flow_window_principal_end(self._h), "f3d_flow_window_principal_end")
+
+    def window_rotation(self, source="flow", radius=2, min_count=None, fields=("angle", "vector", "stretch")):
+        """Local rotation and principal stretches from the least-squares gradient over a strain window of the flow the driver holds
+        (source="flow") or of the trajectory (source="trajectory"); same arguments and result shape as window_rotation()."""
+        src, mask, stats = _source(source), _polar_mask(fields), PolarStats()
+        radius, min_count = _window_args(radius, min_count)
+        arrays = self._derived("f3d_flow_window_polar_compute", src, [mask & g for g in _POLAR_GROUP_OF], stats, mask, radius, min_count)
+        res = {n: a for n, a in zip(POLAR_NAMES, arrays) if a is not None}
+        res["stats"] = stats.as_dict()
+        return res
+
+    def window_rotation_end(self):
+        """free the window rotation and stretch containers, and the gradient's when window_principal holds none (destroy() does too)"""
+        _host_check(host().f3d_flow_window_polar_end(self._h), "f3d_flow_window_polar_end")
 
     def inverse(self, source="flow", iterations=32, tolerance=1e-3):
         """The inverse displacement of the flow the driver holds (source="flow", after compute_resident) or of the trajectory

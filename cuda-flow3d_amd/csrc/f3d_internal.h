@@ -30,6 +30,9 @@ bool make_geo(F3dGeo* g, size_t w, size_t h, size_t d, const f3d_slab* slab, con
 // null, is one of the inputs u, v, w (`reads` says why that cannot be), or is the container of an earlier one.
 bool select_outputs(const char* who, const char* reads, float** ptr, const f3d_devptr* out, int count, const char* const* names,
                     const unsigned* groups, unsigned fields, f3d_devptr u, f3d_devptr v, f3d_devptr w);
+// the same with the inputs as a list of n_inputs containers (f3d_*_from_gradient read nine)
+bool select_outputs(const char* who, const char* reads, float** ptr, const f3d_devptr* out, int count, const char* const* names,
+                    const unsigned* groups, unsigned fields, const f3d_devptr* inputs, int n_inputs);
 // conv taps live in host memory and are passed to the kernels by value
 struct ConvTaps { float k[51]; int count; };
 const ConvTaps& conv_taps();

@@ -10,70 +10,15 @@
 // volume and lanes of undefined voxels diagonalise the zero matrix and never hold their wave back.
 //
 // Statistics (optional): one partial per workgroup, folded in a fixed order by a one-workgroup kernel (f3d_partials.h).
-#include "f3d_jacobi3.h"
-#include "f3d_strain_grad.h"
+#include "f3d_tensor_tail.h"
 
 namespace {
-
-using namespace f3d_strain;
-using namespace f3d_partials;
-
-struct PrincipalPartial {
-  unsigned long long defined;
-  float e1_max, e3_min, shear_max, pad;
-
-  static __device__ __forceinline__ PrincipalPartial identity() { return {0ull, -INFINITY, INFINITY, -INFINITY, 0.f}; }
-  __device__ __forceinline__ void merge(const PrincipalPartial& q)
-  {
-    defined += q.defined;
-    e1_max = fmaxf(e1_max, q.e1_max);
-    e3_min = fminf(e3_min, q.e3_min);
-    shear_max = fmaxf(shear_max, q.shear_max);
-  }
-};
-
-struct PrincipalOut {
-  float* f[10];  // e1, e2, e3, gmax, d1x, d1y, d1z, d3x, d3y, d3z (null = not stored)
-};
-
-// rule 3: value and column exchanged together when the first is strictly smaller
-template <bool DIRS>
-__device__ __forceinline__ void order(float& li, float& lj, float (&vi)[3], float (&vj)[3])
-{
-  if (li < lj) {
-    const float l = li;
-    li = lj;
-    lj = l;
-    if (DIRS) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float x = vi[k];
-        vi[k] = vj[k];
-        vj[k] = x;
-      }
-    }
-  }
-}
-
-// rule 4: the component of largest magnitude (the first of x, y, z among equals) is made non-negative
-__device__ __forceinline__ void fix_sign(float (&d)[3])
-{
-  float lead = d[0];
-  if (fabsf(d[1]) > fabsf(lead)) lead = d[1];
-  if (fabsf(d[2]) > fabsf(lead)) lead = d[2];
-  if (lead < 0.f) {
-    d[0] = -d[0];
-    d[1] = -d[1];
-    d[2] = -d[2];
-  }
-}
 
 template <bool STATS, bool DIRS>
 __global__ __launch_bounds__(kBX* kBY) void k_principal_strain(const float* __restrict__ du, const float* __restrict__ dv,
                                                                const float* __restrict__ dw, PrincipalOut out, F3dGeo g,
                                                                PrincipalPartial* __restrict__ partials)
 {
-  const float nan = __builtin_nanf("");
   PrincipalPartial sum = PrincipalPartial::identity();  // this lane's voxels
 
   const int z_begin = blockIdx.z * kZ;
@@ -83,59 +28,11 @@ __global__ __launch_bounds__(kBX* kBY) void k_principal_strain(const float* __re
   for (int z = z_begin; z < z_end; ++z) {
     Gradient G;
     const bool def = march_step(du, dv, dw, g, z, z_end, own, G);
-    const auto& [G00, G01, G02, G10, G11, G12, G20, G21, G22] = G;
-
-    float a00, a11, a22, a01, a02, a12;
-    green_lagrange(G00, G01, G02, G10, G11, G12, G20, G21, G22, a00, a11, a22, a01, a02, a12);
-    if (!def) a00 = a11 = a22 = a01 = a02 = a12 = 0.f;  // NaN in every output below; nothing to rotate meanwhile
-    float v0[3] = {1.f, 0.f, 0.f}, v1[3] = {0.f, 1.f, 0.f}, v2[3] = {0.f, 0.f, 1.f};  // the columns of V
-
-    f3d_jacobi3::sweeps<DIRS>(a00, a11, a22, a01, a02, a12, v0, v1, v2);  // rule 2
-
-    order<DIRS>(a00, a11, v0, v1);
-    order<DIRS>(a00, a22, v0, v2);
-    order<DIRS>(a11, a22, v1, v2);
-    float e1 = a00, e2 = a11, e3 = a22;
-    float gmax = 0.5f * (e1 - e3);
-    if (DIRS) {
-      fix_sign(v0);
-      fix_sign(v2);
-    }
-    if (!def) {
-      e1 = e2 = e3 = gmax = nan;
-      v0[0] = v0[1] = v0[2] = v2[0] = v2[1] = v2[2] = nan;
-    }
-
-    if (march_owns(g)) {
-      const size_t i = own.row + march_x();
-      if (out.f[0]) out.f[0][i] = e1;
-      if (out.f[1]) out.f[1][i] = e2;
-      if (out.f[2]) out.f[2][i] = e3;
-      if (out.f[3]) out.f[3][i] = gmax;
-      if (DIRS) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          if (out.f[4 + k]) out.f[4 + k][i] = v0[k];
-          if (out.f[7 + k]) out.f[7 + k][i] = v2[k];
-        }
-      }
-    }
-    if (STATS && !isnan(e1)) {
-      ++sum.defined;
-      sum.e1_max = fmaxf(sum.e1_max, e1);
-      sum.e3_min = fminf(sum.e3_min, e3);
-      sum.shear_max = fmaxf(sum.shear_max, gmax);
-    }
+    principal_voxel<STATS, DIRS>(G, def, march_owns(g), own.row + march_x(), out, sum);  // f3d_tensor_tail.h
     march_advance(own);
   }
 
-  if (STATS) {
-    sum.defined = wave_sum(sum.defined);
-    sum.e1_max = wave_max(sum.e1_max);
-    sum.e3_min = wave_min(sum.e3_min);
-    sum.shear_max = wave_max(sum.shear_max);
-    block_partial<PrincipalPartial, kBY>(sum, partials);
-  }
+  if (STATS) principal_partial(sum, partials);
 }
 
 template <bool DIRS>
@@ -152,10 +49,7 @@ int launch(const float* u, const float* v, const float* w, const PrincipalOut& o
         hipLaunchKernelGGL((k_principal_strain<true, DIRS>), grid, dim3(kBX, kBY, 1), 0, f3d::stream(), u, v, w, o, g, d_part);
       }))
     return 1;
-  stats->defined = r.defined;
-  stats->e1_max = r.defined ? r.e1_max : __builtin_nanf("");
-  stats->e3_min = r.defined ? r.e3_min : __builtin_nanf("");
-  stats->shear_max = r.defined ? r.shear_max : __builtin_nanf("");
+  principal_stats_of(r, stats);
   return 0;
 }
 

@@ -130,6 +130,13 @@ bool make_geo(F3dGeo* g, size_t w, size_t h, size_t d, const f3d_slab* slab, con
 bool select_outputs(const char* who, const char* reads, float** ptr, const f3d_devptr* out, int count, const char* const* names,
                     const unsigned* groups, unsigned fields, f3d_devptr u, f3d_devptr v, f3d_devptr w)
 {
+  const f3d_devptr inputs[3] = {u, v, w};
+  return select_outputs(who, reads, ptr, out, count, names, groups, fields, inputs, 3);
+}
+
+bool select_outputs(const char* who, const char* reads, float** ptr, const f3d_devptr* out, int count, const char* const* names,
+                    const unsigned* groups, unsigned fields, const f3d_devptr* inputs, int n_inputs)
+{
   char a[32], b[32];
   auto label = [&](char* text, int f) {
     if (groups) std::snprintf(text, sizeof(a), "%d (%s)", f, names[f]);
@@ -140,7 +147,8 @@ bool select_outputs(const char* who, const char* reads, float** ptr, const f3d_d
     ptr[f] = nullptr;
     if (groups ? !(fields & groups[f]) : !out[f]) continue;
     if (!out[f]) return !fail("%s: output %s is selected but null", who, label(a, f));
-    if (out[f] == u || out[f] == v || out[f] == w) return !fail("%s: output %s is also an input (%s)", who, label(a, f), reads);
+    for (int i = 0; i < n_inputs; ++i)
+      if (out[f] == inputs[i]) return !fail("%s: output %s is also an input (%s)", who, label(a, f), reads);
     for (int e = 0; e < f; ++e)
       if (ptr[e] && out[e] == out[f])
         return !fail("%s: outputs %s and %s are the same container", who, label(a, e), label(b, f));

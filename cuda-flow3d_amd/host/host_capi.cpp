@@ -323,6 +323,34 @@ int f3d_flow_polar_compute(f3d_flow flow, int source, unsigned fields, float* co
 
 int f3d_flow_polar_end(f3d_flow flow) { return DerivedEnd(flow, OpticalFlowE::kPolar, "f3d_flow_polar_end: null driver"); }
 
+int f3d_flow_window_principal_compute(f3d_flow flow, int source, unsigned fields, unsigned radius, unsigned min_count,
+                                      float* const out[10], f3d_principal_stats* stats)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out != nullptr, "f3d_flow_window_principal_compute", &of)) return 1;
+  return DerivedDownload(flow, OpticalFlowE::kWindowPrincipal, flow->driver.ComputeWindowPrincipal(of, fields, radius, min_count, stats),
+                         out, fields);
+}
+
+int f3d_flow_window_principal_end(f3d_flow flow)
+{
+  return DerivedEnd(flow, OpticalFlowE::kWindowPrincipal, "f3d_flow_window_principal_end: null driver");
+}
+
+int f3d_flow_window_polar_compute(f3d_flow flow, int source, unsigned fields, unsigned radius, unsigned min_count, float* const out[7],
+                                  f3d_polar_stats* stats)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, out != nullptr, "f3d_flow_window_polar_compute", &of)) return 1;
+  return DerivedDownload(flow, OpticalFlowE::kWindowPolar, flow->driver.ComputeWindowPolar(of, fields, radius, min_count, stats), out,
+                         fields);
+}
+
+int f3d_flow_window_polar_end(f3d_flow flow)
+{
+  return DerivedEnd(flow, OpticalFlowE::kWindowPolar, "f3d_flow_window_polar_end: null driver");
+}
+
 int f3d_flow_inverse_compute(f3d_flow flow, int source, unsigned iterations, float tolerance, float* const out[4],
                              f3d_inverse_stats* stats)
 {

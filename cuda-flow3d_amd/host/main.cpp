@@ -7,6 +7,7 @@
 //                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
 //                [--strain vol,e,eq] [--principal val,shear,dir1,dir3] [--rotation angle,vector,stretch] [--inverse]
 //                [--window-strain vol,e,eq,grad [--window-radius R] [--window-min-count K]]
+//                [--window-principal val,shear,dir1,dir3] [--window-rotation angle,vector,stretch]
 //                [--match warped,zncc,rmsd [--match-radius R]]
 //                [--detrend translation|rigid|affine [--detrend-min-zncc T]]
 //                [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]
@@ -34,6 +35,11 @@
 // every voxel on the device (f3d_window_strain; --window-radius R, 1 .. 3, default 2) and forms the strain fields of --strain from it.
 // A voxel with fewer than --window-min-count present neighbours (default a quarter of the window, at least 4) is undefined.
 // <tag>_wstrain-{vol | exx,eyy,ezz,exy,exz,eyz | eq | G00 .. G22}-W-H-D.raw, and one line of statistics per pair.
+// --window-principal LIST and --window-rotation LIST (each on its own or with any of the others; the LISTs of --principal and
+// --rotation) compute those two from the window's gradient instead of central differences (f3d_window_strain's gradient, then
+// f3d_principal_from_gradient / f3d_polar_from_gradient), with the radius and minimum count of --window-radius / --window-min-count:
+// <tag>_wprincipal-{e1,e2,e3 | gmax | d1x,.. | d3x,..}-W-H-D.raw and <tag>_wrotation-{theta | rx,ry,rz | l1,l2,l3}-W-H-D.raw, and one
+// line of statistics each per pair.
 // --principal LIST (same conditions and the same source as --strain, with which it may be combined; LIST a comma-separated subset of
 // val,shear,dir1,dir3) diagonalises the Green-Lagrange tensor of that displacement on the device (f3d_principal_strain) and writes
 // the selected fields as <tag>_principal-{e1,e2,e3 | gmax | d1x,d1y,d1z | d3x,d3y,d3z}-W-H-D.raw, and one line of statistics per
@@ -102,6 +108,7 @@ static void Usage()
               "              [--concurrent N] [--cumulative] [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
               "              [--rotation angle,vector,stretch] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
               "              [--window-strain vol,e,eq,grad [--window-radius R] [--window-min-count K]]\n"
+              "              [--window-principal val,shear,dir1,dir3] [--window-rotation angle,vector,stretch]\n"
               "              [--detrend translation|rigid|affine [--detrend-min-zncc T]]\n"
               "              [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]\n"
               "               [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]\n"
@@ -123,6 +130,8 @@ int main(int argc, char** argv)
   unsigned window_min_count = 0;  // --window-min-count; 0: a quarter of the window, at least 4
   bool window_sub_given = false;
   unsigned principal_fields = 0;  // --principal: F3D_PRINCIPAL_* groups
+  unsigned wprincipal_fields = 0; // --window-principal: F3D_PRINCIPAL_* groups
+  unsigned wpolar_fields = 0;     // --window-rotation: F3D_POLAR_* groups
   unsigned polar_fields = 0;      // --rotation: F3D_POLAR_* groups
   bool inverse = false;           // --inverse
   unsigned match_fields = 0;      // --match: OpticalFlowE::kMatch* bits
@@ -236,6 +245,37 @@ int main(int argc, char** argv)
         window_min_count = static_cast<unsigned>(n);
       }
       window_sub_given = true;
+    }
+    else if (a == "--window-principal") {
+      need(1);
+      const std::string list = argv[++i];
+      size_t at = 0;
+      while (true) {
+        const size_t end = list.find(',', at);
+        const std::string item = list.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        if (item == "val") wprincipal_fields |= F3D_PRINCIPAL_VALUES;
+        else if (item == "shear") wprincipal_fields |= F3D_PRINCIPAL_SHEAR;
+        else if (item == "dir1") wprincipal_fields |= F3D_PRINCIPAL_DIR1;
+        else if (item == "dir3") wprincipal_fields |= F3D_PRINCIPAL_DIR3;
+        else { Usage(); return 64; }
+        if (end == std::string::npos) break;
+        at = end + 1;
+      }
+    }
+    else if (a == "--window-rotation") {
+      need(1);
+      const std::string list = argv[++i];
+      size_t at = 0;
+      while (true) {
+        const size_t end = list.find(',', at);
+        const std::string item = list.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        if (item == "angle") wpolar_fields |= F3D_POLAR_ANGLE;
+        else if (item == "vector") wpolar_fields |= F3D_POLAR_VECTOR;
+        else if (item == "stretch") wpolar_fields |= F3D_POLAR_STRETCH;
+        else { Usage(); return 64; }
+        if (end == std::string::npos) break;
+        at = end + 1;
+      }
     }
     else if (a == "--principal") {
       need(1);
@@ -392,8 +432,14 @@ int main(int argc, char** argv)
                 use_partial_gpu ? "--partial" : "--concurrent N > 1");
     return 64;
   }
-  if (window_sub_given && !wstrain_fields) {
-    std::printf("--window-radius and --window-min-count need --window-strain\n");
+  if (window_sub_given && !wstrain_fields && !wprincipal_fields && !wpolar_fields) {
+    std::printf("--window-radius and --window-min-count need --window-strain, --window-principal or --window-rotation\n");
+    Usage();
+    return 64;
+  }
+  if ((wprincipal_fields || wpolar_fields) && (use_partial_gpu || concurrent > 1)) {
+    std::printf("%s needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                wprincipal_fields ? "--window-principal" : "--window-rotation", use_partial_gpu ? "--partial" : "--concurrent N > 1");
     Usage();
     return 64;
   }
@@ -762,12 +808,15 @@ int main(int argc, char** argv)
   f3d_window_strain_stats wstrain_stats = {};
   f3d_principal_stats principal_stats = {};
   f3d_polar_stats polar_stats = {};
+  f3d_principal_stats wprincipal_stats = {};
+  f3d_polar_stats wpolar_stats = {};
   f3d_inverse_stats inverse_stats = {};
   f3d_correlation_stats match_stats = {};
   f3d_motion_fit motion_fit = {};
   f3d_motion_residual motion_residual = {};
   f3d_validate_stats validate_stats = {};
-  // --use-validated: what --strain, --window-strain, --principal, --rotation and --detrend are computed of
+  // --use-validated: what --strain, --window-strain, --window-principal, --window-rotation, --principal, --rotation and --detrend are
+  // computed of
   auto validated_or = [&](const OpticalFlowE::Displacement& of) {
     if (!use_validated) return of;
     const DevicePtr d[3] = {optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 1),
@@ -775,7 +824,7 @@ int main(int argc, char** argv)
                             optical_flow_e.DerivedContainer(OpticalFlowE::kValidated, 3)};
     return OpticalFlowE::Containers(d);
   };
-  DerivedField derived[9] = {
+  DerivedField derived[11] = {
       {"strain", OpticalFlowE::kStrain, strain_fields, strain_names, false,
        [&](const OpticalFlowE::Displacement& of) { return optical_flow_e.ComputeStrain(validated_or(of), strain_fields, &strain_stats); },
        [&](size_t k) {
@@ -933,6 +982,29 @@ int main(int argc, char** argv)
          std::printf("window strain (r=%u) frame %zu -> frame %zu: vol min/mean/max %.6g/%.6g/%.6g, eq max %.6g, %llu folded, %llu thin, "
                      "%llu lost of %zu voxels\n", window_radius, cumulative ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max,
                      st.eq_max, st.folded, st.thin, st.lost, voxels);
+       }},
+      // the principal strains and the rotation of the window's gradient: after the window strain, the lines of --principal / --rotation
+      {"wprincipal", OpticalFlowE::kWindowPrincipal, wprincipal_fields, principal_names, false,
+       [&](const OpticalFlowE::Displacement& of) {
+         return optical_flow_e.ComputeWindowPrincipal(validated_or(of), wprincipal_fields, window_radius, window_min_count,
+                                                      &wprincipal_stats);
+       },
+       [&](size_t k) {
+         const f3d_principal_stats& st = wprincipal_stats;
+         std::printf("window principal (r=%u) frame %zu -> frame %zu: e1 max %.6g, e3 min %.6g, shear max %.6g, %llu undefined of %zu "
+                     "voxels\n", window_radius, cumulative ? size_t(0) : k, k + 1, st.e1_max, st.e3_min, st.shear_max,
+                     static_cast<unsigned long long>(voxels) - st.defined, voxels);
+       }},
+      {"wrotation", OpticalFlowE::kWindowPolar, wpolar_fields, polar_names, false,
+       [&](const OpticalFlowE::Displacement& of) {
+         return optical_flow_e.ComputeWindowPolar(validated_or(of), wpolar_fields, window_radius, window_min_count, &wpolar_stats);
+       },
+       [&](size_t k) {
+         const f3d_polar_stats& st = wpolar_stats;
+         const double mean = st.defined ? st.theta_sum / static_cast<double>(st.defined) : std::nan("");
+         std::printf("window rotation (r=%u) frame %zu -> frame %zu: angle max %.6g rad, mean %.6g rad, stretch max %.6g, min %.6g, %llu "
+                     "folded, %llu undefined of %zu voxels\n", window_radius, cumulative ? size_t(0) : k, k + 1, st.theta_max, mean,
+                     st.l1_max, st.l3_min, st.folded, static_cast<unsigned long long>(voxels) - st.defined - st.folded, voxels);
        }}};
   // --contacts: no field of voxels, so no DerivedField: the table of pair k is computed after the derived fields of pair k (the fits of
   // --label-motion are then those of the same displacement) and written after their files
@@ -980,15 +1052,15 @@ int main(int argc, char** argv)
                 k + 1, contact_list.size(), n_bodies, n_bodies ? 2.0 * static_cast<double>(contact_list.size()) / static_cast<double>(n_bodies) : 0.0,
                 opening, closing, largest_slip, contact_info.contact, contact_info.jump_absent, contact_info.foreign);
   };
-  // the order in which the features run and their files and lines come out: as listed, with the window strain after the strain and the
-  // rotation after the principal strains,
+  // the order in which the features run and their files and lines come out: as listed, with the window strain and the two fields of
+  // the window's gradient after the strain and the rotation after the principal strains,
   // or with --use-validated the match (whose zncc may be the mask) and the validated field first
-  DerivedField* order[9] = {&derived[0], &derived[8], &derived[1], &derived[6], &derived[2],
-                            &derived[3], &derived[4], &derived[5], &derived[7]};
+  DerivedField* order[11] = {&derived[0], &derived[8], &derived[9], &derived[10], &derived[1], &derived[6],
+                             &derived[2], &derived[3], &derived[4],  &derived[5],  &derived[7]};
   if (use_validated) {
-    DerivedField* const first[9] = {&derived[3], &derived[5], &derived[0], &derived[8], &derived[1],
-                                    &derived[6], &derived[2], &derived[4], &derived[7]};
-    for (int i = 0; i < 9; ++i) order[i] = first[i];
+    DerivedField* const first[11] = {&derived[3], &derived[5], &derived[0], &derived[8], &derived[9], &derived[10],
+                                     &derived[1], &derived[6], &derived[2], &derived[4], &derived[7]};
+    for (int i = 0; i < 11; ++i) order[i] = first[i];
   }
   for (DerivedField& f : derived)
     for (int i = 0; i < OpticalFlowE::DerivedFieldCount(f.which); ++i)

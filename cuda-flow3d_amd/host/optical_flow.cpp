@@ -28,6 +28,10 @@ extern "C" int f3d_principal_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, co
                                     size_t width, size_t height, size_t depth, f3d_principal_stats* stats) __attribute__((weak));
 extern "C" int f3d_polar_decomposition(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[7], unsigned fields,
                                        size_t width, size_t height, size_t depth, f3d_polar_stats* stats) __attribute__((weak));
+extern "C" int f3d_principal_from_gradient(const f3d_devptr grad[9], const f3d_devptr out[10], unsigned fields, size_t width,
+                                           size_t height, size_t depth, f3d_principal_stats* stats) __attribute__((weak));
+extern "C" int f3d_polar_from_gradient(const f3d_devptr grad[9], const f3d_devptr out[7], unsigned fields, size_t width, size_t height,
+                                       size_t depth, f3d_polar_stats* stats) __attribute__((weak));
 extern "C" int f3d_invert_displacement(f3d_devptr d_u, f3d_devptr d_v, f3d_devptr d_w, f3d_devptr g_u, f3d_devptr g_v,
                                        f3d_devptr g_w, f3d_devptr err, size_t width, size_t height, size_t depth,
                                        unsigned iterations, float tolerance, f3d_inverse_stats* stats) __attribute__((weak));
@@ -132,10 +136,11 @@ const unsigned kValidatedGroups[kValidatedContainers] = {F3D_VALIDATE_R, F3D_VAL
 // the residual u, v, w of the per-label motion, and the container of the labels (a bit of its own, never downloaded)
 const unsigned kLabelResidual = 1u, kLabelLabels = 2u;
 const unsigned kLabelMotionGroups[4] = {kLabelResidual, kLabelResidual, kLabelResidual, kLabelLabels};
-const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3, 4, 7, 4, 17};
+const int kDerivedFields[OpticalFlowE::kDerivedCount] = {8, 10, 4, 3, 3, 4, 7, 4, 17, 10, 7};
 const unsigned* const kDerivedGroups[OpticalFlowE::kDerivedCount] = {kStrainGroups, kPrincipalGroups, nullptr,
                                                                      kMatchGroups,  nullptr,          kValidatedGroups,
-                                                                     kPolarGroups,  kLabelMotionGroups, kWindowStrainGroups};
+                                                                     kPolarGroups,  kLabelMotionGroups, kWindowStrainGroups,
+                                                                     kPrincipalGroups, kPolarGroups};
 const char* const kTrajectoryNotStarted = "the trajectory was not started (ResetTrajectory first)";
 
 }  // namespace
@@ -175,7 +180,19 @@ OpticalFlowE::OpticalFlowE()
                {this, kDerivedFields[kWindowStrain], kWindowStrainGroups,
                 "the window strain containers do not fit beside the driver's on the device",
                 "a requested window strain field has not been computed", "no host volume for a requested window strain field",
-                "the device library has no f3d_window_strain (strain over a window)", "no displacement to differentiate"}}
+                "the device library has no f3d_window_strain (strain over a window)", "no displacement to differentiate"},
+               {this, kDerivedFields[kWindowPrincipal], kPrincipalGroups,
+                "the window principal strain containers do not fit beside the driver's on the device",
+                "a requested window principal strain field has not been computed",
+                "no host volume for a requested window principal strain field",
+                "the device library has no f3d_principal_from_gradient (principal strains of a stored gradient)",
+                "no displacement to differentiate"},
+               {this, kDerivedFields[kWindowPolar], kPolarGroups,
+                "the window rotation and stretch containers do not fit beside the driver's on the device",
+                "a requested window rotation or stretch field has not been computed",
+                "no host volume for a requested window rotation or stretch field",
+                "the device library has no f3d_polar_from_gradient (local rotation and stretches of a stored gradient)",
+                "no displacement to differentiate"}}
 {
   // same initialisation order as the reference's forward_list built with push_front (optical_flow_e.cpp:34-39)
   cuda_operations_ = {&cuop_solve_, &cuop_resample_, &cuop_register_, &cuop_median_, &cuop_convolution_, &cuop_add_};
@@ -681,6 +698,76 @@ bool OpticalFlowE::ComputePolar(const Displacement& of, unsigned fields, f3d_pol
          set.Check(CheckDeviceError(f3d_polar_decomposition(d[0], d[1], d[2], set.ptr, fields, c.width, c.height, c.depth, stats)));
 }
 
+bool OpticalFlowE::ComputeWindowGradient(FieldSet& set, const Displacement& of, bool have_entry, unsigned radius, unsigned min_count)
+{
+  DevicePtr d[3];
+  if (!ResolveDisplacement(set, of, have_entry, d)) return false;
+  if (!f3d_window_strain) return set.Fail("the device library has no f3d_window_strain (strain over a window)");
+  if (radius < 1 || radius > 3) return set.Fail("radius must be 1 .. 3");
+  const DataSize4& s = dev_container_size_;
+  for (DevicePtr& p : window_gradient_) {
+    if (p) continue;
+    size_t pitch = 0;
+    if (f3d_alloc_pitched(&p, &pitch, s.width * sizeof(float), s.height * s.depth) != 0) p = 0;
+    if (!p || pitch != s.pitch) {
+      ReleaseWindowGradient();
+      return set.Fail("the nine containers of the window gradient do not fit beside the driver's on the device");
+    }
+  }
+  DevicePtr out[17] = {};
+  for (int k = 0; k < 9; ++k) out[8 + k] = window_gradient_[k];
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         set.Check(CheckDeviceError(f3d_window_strain(d[0], d[1], d[2], out, F3D_WSTRAIN_G, radius, min_count, c.width, c.height, c.depth,
+                                                      nullptr)));
+}
+
+void OpticalFlowE::ReleaseWindowGradient()
+{
+  for (DevicePtr& p : window_gradient_) {
+    if (p) CheckDeviceError(f3d_free(p));
+    p = 0;
+  }
+}
+
+void OpticalFlowE::ReleaseDerived(Derived which)
+{
+  derived_[which].Release();
+  if (which != kWindowPrincipal && which != kWindowPolar) return;
+  // the gradient goes with the last container of the two kinds that read it
+  for (const FieldSet* set : {&derived_[kWindowPrincipal], &derived_[kWindowPolar]})
+    for (DevicePtr p : set->ptr)
+      if (p) return;
+  ReleaseWindowGradient();
+}
+
+bool OpticalFlowE::ComputeWindowPrincipal(const Displacement& of, unsigned fields, unsigned radius, unsigned min_count,
+                                          f3d_principal_stats* stats)
+{
+  FieldSet& set = derived_[kWindowPrincipal];
+  set.error.clear();
+  if (fields == 0 || (fields & ~kPrincipalAll))
+    return set.Fail("fields must be a non-empty combination of F3D_PRINCIPAL_VALUES, F3D_PRINCIPAL_SHEAR, F3D_PRINCIPAL_DIR1, "
+                    "F3D_PRINCIPAL_DIR3");
+  if (!ComputeWindowGradient(set, of, f3d_principal_from_gradient != nullptr, radius, min_count)) return false;
+  if (!set.Allocate(fields)) return false;
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_principal_from_gradient(window_gradient_, set.ptr, fields, c.width, c.height, c.depth, stats)));
+}
+
+bool OpticalFlowE::ComputeWindowPolar(const Displacement& of, unsigned fields, unsigned radius, unsigned min_count,
+                                      f3d_polar_stats* stats)
+{
+  FieldSet& set = derived_[kWindowPolar];
+  set.error.clear();
+  if (fields == 0 || (fields & ~kPolarAll))
+    return set.Fail("fields must be a non-empty combination of F3D_POLAR_ANGLE, F3D_POLAR_VECTOR, F3D_POLAR_STRETCH");
+  if (!ComputeWindowGradient(set, of, f3d_polar_from_gradient != nullptr, radius, min_count)) return false;
+  if (!set.Allocate(fields)) return false;
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_polar_from_gradient(window_gradient_, set.ptr, fields, c.width, c.height, c.depth, stats)));
+}
+
 bool OpticalFlowE::ComputeInverse(const Displacement& of, unsigned iterations, float tolerance, f3d_inverse_stats* stats)
 {
   FieldSet& set = derived_[kInverse];
@@ -1038,6 +1125,7 @@ void OpticalFlowE::Destroy()
   ReleaseResult();
   trajectory_.Release();
   for (FieldSet& set : derived_) set.Release();
+  ReleaseWindowGradient();
   size_t freed = 0;
   while (!free_containers_.empty()) {
     CheckDeviceError(f3d_free(free_containers_.back()));

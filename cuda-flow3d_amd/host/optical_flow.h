@@ -138,10 +138,16 @@ class OpticalFlowE : public OpticalFlowBase {
   //   kWindowStrain f3d_window_strain: the strain fields of kStrain from the least-squares gradient over a (2 radius + 1)^3 window, and
   //               that gradient.  Seventeen outputs in the order vol, exx, eyy, ezz, exy, exz, eyz, eq, G00 .. G22, selected by
   //               F3D_STRAIN_VOL / _E / _EQ and F3D_WSTRAIN_G.
+  //   kWindowPrincipal f3d_window_strain's gradient (F3D_WSTRAIN_G alone) into nine containers the driver keeps to itself, then
+  //               f3d_principal_from_gradient on them: kPrincipal's ten outputs and bits from the least-squares gradient.
+  //   kWindowPolar the same with f3d_polar_from_gradient: kPolar's seven outputs and bits.  Both depend on their arguments only: no
+  //               earlier ComputeWindowStrain is needed, and what kWindowStrain holds is left as it is.  The nine gradient
+  //               containers are allocated on first use and freed when neither kind holds a container any more, and by Destroy().
   // Each selected output gets a container of its own, allocated on first use and freed by ReleaseDerived() and Destroy().  Compute
   // enqueues on the library stream and waits only when stats is given.  Every call returns false with DerivedError() set when it
   // cannot run -- among other reasons when the device library lacks the entry point.
-  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kValidated, kPolar, kLabelMotion, kWindowStrain, kDerivedCount };
+  enum Derived { kStrain = 0, kPrincipal, kInverse, kMatch, kMotion, kValidated, kPolar, kLabelMotion, kWindowStrain, kWindowPrincipal,
+                 kWindowPolar, kDerivedCount };
   static constexpr int kMaxDerivedFields = 17;  // the most outputs a Derived has (kWindowStrain)
   enum MatchField : unsigned { kMatchWarped = 1u, kMatchZncc = 2u, kMatchRmsd = 4u };
   // the displacement a derived field is computed of
@@ -158,6 +164,9 @@ class OpticalFlowE : public OpticalFlowBase {
   bool ComputeWindowStrain(const Displacement& of, unsigned fields, unsigned radius, unsigned min_count,
                            f3d_window_strain_stats* stats);
   bool ComputePolar(const Displacement& of, unsigned fields, f3d_polar_stats* stats);
+  // fields and stats as in ComputePrincipal / ComputePolar, radius and min_count as in ComputeWindowStrain
+  bool ComputeWindowPrincipal(const Displacement& of, unsigned fields, unsigned radius, unsigned min_count, f3d_principal_stats* stats);
+  bool ComputeWindowPolar(const Displacement& of, unsigned fields, unsigned radius, unsigned min_count, f3d_polar_stats* stats);
   bool ComputeInverse(const Displacement& of, unsigned iterations, float tolerance, f3d_inverse_stats* stats);
   // frame_0 / frame_1: the containers of the two frames the displacement belongs to; 0 means the resident pair.  A trajectory is
   // refused: frame 0 of a sequence is not kept.
@@ -194,7 +203,7 @@ class OpticalFlowE : public OpticalFlowBase {
   static bool DerivedSelected(Derived which, int field, unsigned fields);
   DevicePtr DerivedContainer(Derived which, int field) const { return derived_[which].ptr[field]; }  // 0 until computed
   bool DownloadDerived(Derived which, Data3D* const* out, unsigned fields) { return derived_[which].Download(out, fields); }
-  void ReleaseDerived(Derived which) { derived_[which].Release(); }
+  void ReleaseDerived(Derived which);
   const std::string& DerivedError(Derived which) const { return derived_[which].error; }
 
  private:
@@ -237,6 +246,11 @@ class OpticalFlowE : public OpticalFlowBase {
   };
   FieldSet trajectory_;
   FieldSet derived_[kDerivedCount];
+  // the gradient of kWindowPrincipal and kWindowPolar (G00 .. G22), never downloaded
+  DevicePtr window_gradient_[9] = {};
+  // the window pass of both: checks, the nine containers on first use, f3d_window_strain with F3D_WSTRAIN_G alone into them
+  bool ComputeWindowGradient(FieldSet& set, const Displacement& of, bool have_entry, unsigned radius, unsigned min_count);
+  void ReleaseWindowGradient();
   // clears set's error and gives the three containers of `of`, or fails with the text that says what is missing
   bool ResolveDisplacement(FieldSet& set, const Displacement& of, bool have_entry, DevicePtr (&disp)[3]);
   f3d_size4 Container() const;

@@ -631,6 +631,30 @@ typedef struct f3d_polar_stats {
 int f3d_polar_decomposition(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[7], unsigned fields, size_t width,
                             size_t height, size_t depth, f3d_polar_stats* stats /* nullable; non-null waits */);
 
+/* Principal strains and the polar decomposition of a STORED displacement gradient: what f3d_principal_strain and
+ * f3d_polar_decomposition compute, with G read from nine containers instead of formed by central differences -- the least-squares
+ * gradient of f3d_window_strain (its F3D_WSTRAIN_G group, whose noise is a third to a twenty-fifth of the stencil's, so the
+ * eigenvalues no longer repel), an FE solution, a filter of the caller's.  No new arithmetic; per voxel:
+ *   grad[0..8] = G00 G01 G02 G10 G11 G12 G20 G21 G22 (F3D_WSTRAIN_G's order: row = component u v w, column = axis x y z), float
+ *   containers of the current container geometry.  Two entries may be the same container.
+ *   The voxel is UNDEFINED iff any of its nine entries is NaN; an undefined voxel is NaN in every output.  Otherwise the arithmetic
+ *   runs as written (an infinity gives whatever the rules give): E from G by f3d_flow_strain's expressions (and vol, for the polar
+ *   entry), then
+ *     f3d_principal_from_gradient:  rules 2 - 4 of f3d_principal_strain, unchanged;
+ *     f3d_polar_from_gradient:      rules 2 - 6 of f3d_polar_decomposition, unchanged, the folded rule (vol <= -1.f or
+ *                                   !(m_i > 0.f)) included.
+ * Output order, groups (F3D_PRINCIPAL_* / F3D_POLAR_*), the statistics and their reduction order are those of
+ * f3d_principal_strain / f3d_polar_decomposition: the gradient f3d_flow_strain's rules give, with NaN at its undefined voxels, fed
+ * to these entries gives the outputs and statistics of those two bit for bit, theta_sum included.
+ * Geometry from the current container (f3d_set_container), whole volume, library stream.  Entries of out for groups not selected
+ * are ignored and never written.  Refused: a null grad or a null entry of it; a null selected output; fields 0 or with unknown
+ * bits; a selected output that is any of the nine inputs; two selected outputs that are the same container; an empty or too large
+ * size.  stats: nullable; asking waits for the stream. */
+int f3d_principal_from_gradient(const f3d_devptr grad[9], const f3d_devptr out[10], unsigned fields, size_t width, size_t height,
+                                size_t depth, f3d_principal_stats* stats /* nullable; non-null waits */);
+int f3d_polar_from_gradient(const f3d_devptr grad[9], const f3d_devptr out[7], unsigned fields, size_t width, size_t height,
+                            size_t depth, f3d_polar_stats* stats /* nullable; non-null waits */);
+
 /* Inverse displacement (no reference counterpart).  d = (d_u, d_v, d_w) is the displacement of every voxel of frame 0 on frame 0's
  * grid (a pair's flow, or f3d_compose_flow's cumulative displacement), voxel units.  g = (g_u, g_v, g_w) is the map in the other
  * direction on frame k's grid: g(y) = -d(y + g(y)), by the fixed-point iteration g <- -d(y + g) of each voxel on its own.  With g a

@@ -124,6 +124,20 @@ int f3d_flow_principal_end(f3d_flow flow);
 int f3d_flow_polar_compute(f3d_flow flow, int source, unsigned fields, float* const out[7], f3d_polar_stats* stats);
 int f3d_flow_polar_end(f3d_flow flow);
 
+/* Principal strains, and local rotation and principal stretches, of the least-squares gradient over a strain window: per call
+ * f3d_window_strain's F3D_WSTRAIN_G group into nine containers the driver keeps to itself, then f3d_principal_from_gradient /
+ * f3d_polar_from_gradient on them (include/f3d.h has the definitions), of the same two sources.  fields, out and stats as for
+ * f3d_flow_principal_compute / f3d_flow_polar_compute, radius and min_count as for f3d_flow_window_strain_compute.  A call depends on
+ * its arguments only: it needs no earlier f3d_flow_window_strain_compute and leaves what that holds as it is.  The output containers
+ * live until the kind's _end (or f3d_flow_destroy); the gradient's nine are freed when both kinds have ended.  A device library
+ * without f3d_principal_from_gradient / f3d_polar_from_gradient still loads; then the call fails with a message naming it. */
+int f3d_flow_window_principal_compute(f3d_flow flow, int source, unsigned fields, unsigned radius, unsigned min_count,
+                                      float* const out[10], f3d_principal_stats* stats);
+int f3d_flow_window_principal_end(f3d_flow flow);
+int f3d_flow_window_polar_compute(f3d_flow flow, int source, unsigned fields, unsigned radius, unsigned min_count, float* const out[7],
+                                  f3d_polar_stats* stats);
+int f3d_flow_window_polar_end(f3d_flow flow);
+
 /* Inverse displacement (f3d_invert_displacement of include/f3d.h has the definition) of the same two sources, F3D_STRAIN_OF_FLOW or
  * F3D_STRAIN_OF_TRAJECTORY: out[0..3] = g_u, g_v, g_w, err receive width * height * depth floats each (all four required); stats is
  * nullable.  Blocks until the fields are on the host.  The driver keeps four containers until f3d_flow_inverse_end (or
