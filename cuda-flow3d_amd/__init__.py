@@ -142,6 +142,14 @@ class ContactInfo(C.Structure):  # f3d_contact_info: every face of the volume in
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class ComponentInfo(C.Structure):  # f3d_component_info: every voxel of the box in exactly one of foreground and background
+    _fields_ = [(name, C.c_ulonglong) for name in ("foreground", "background", "nan", "n_components", "n_labels", "dropped_components",
+                                                   "dropped_voxels", "largest")]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class ContactKinematics(C.Structure):  # f3d_contact_kin
     _fields_ = [("point", C.c_double * 3), ("area", C.c_double), ("normal", C.c_double * 3), ("jump_normal", C.c_double),
                 ("jump_slip", C.c_double), ("fit_normal", C.c_double), ("fit_slip", C.c_double), ("status", C.c_uint)]
@@ -353,6 +361,9 @@ def host():
         "f3d_flow_contacts_compute": [C.c_void_p, C.c_int, C.POINTER(C.c_int), _sz, C.POINTER(C.POINTER(Contact)), C.POINTER(_sz),
                                       C.POINTER(ContactInfo)],
         "f3d_flow_contacts_end": [C.c_void_p],
+        "f3d_flow_labels_compute": [C.c_void_p, _dp, C.c_float, C.c_float, C.c_ulonglong, C.POINTER(C.POINTER(C.c_ulonglong)), C.POINTER(_sz),
+                                    C.POINTER(ComponentInfo)],
+        "f3d_flow_labels_end": [C.c_void_p], "f3d_flow_labels_download": [C.c_void_p, C.POINTER(C.c_int)],
         "f3d_flow_validate_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_float, C.c_uint, C.c_uint, C.c_uint, C.c_float,
                                       C.POINTER(_fp), C.POINTER(ValidateStats)],
         "f3d_flow_validate_end": [C.c_void_p],
@@ -551,6 +562,11 @@ def _label_motion_entry():
 def _contacts_entry():
     return _entry("f3d_label_contacts", [_dp] * 4 + [_sz] * 5 + [C.POINTER(Contact), C.POINTER(ContactInfo)],
                   "find the contacts between the labels of a segmentation")
+
+
+def _components_entry():
+    return _entry("f3d_label_components", [_dp, C.c_float, C.c_float, C.c_ulonglong, _dp] + [_sz] * 3 +
+                  [C.POINTER(C.c_ulonglong), _sz, C.POINTER(ComponentInfo)], "label the connected bodies of a thresholded volume")
 
 
 def _validate_entry():
@@ -1149,6 +1165,51 @@ def contact_kinematics(contacts, dims, motion=None, min_faces=4):
                 "f3d_contact_kinematics")
     assert C.sizeof(ContactKinematics) == _KINEMATICS_DTYPE.itemsize
     return np.frombuffer(out, dtype=_KINEMATICS_DTYPE, count=n).copy() if n else np.zeros(0, _KINEMATICS_DTYPE)
+
+
+class Components:
+    """The connected bodies of a thresholded volume (label_components, OpticalFlow.segment): .labels (int32 [d, h, w]: 0 for background
+    and for dropped bodies, 1 .. n_labels in ascending order of a body's smallest linear index), .sizes (uint64, the voxels of label L at
+    index L - 1), .n_labels and .info, the dict of f3d_component_info."""
+
+    def __init__(self, labels, sizes, info):
+        self.labels, self.sizes, self.info = labels, sizes, info
+        self.n_labels = int(info["n_labels"])
+
+    def __len__(self):
+        return self.n_labels
+
+
+def _component_range(lo, hi, min_voxels):
+    lo, hi, min_voxels = float(np.float32(lo)), float(np.float32(hi)), int(min_voxels)
+    if lo != lo or hi != hi or lo > hi:
+        raise ValueError(f"lo and hi must be numbers with lo <= hi, not {lo} and {hi}")
+    if not 1 <= min_voxels < 2 ** 64:
+        raise ValueError(f"min_voxels must be at least 1, not {min_voxels}")
+    return lo, hi, min_voxels
+
+
+def label_components(volume, lo=-np.inf, hi=np.inf, min_voxels=1):
+    """The connected bodies of a volume from anywhere on the device (include/f3d.h, f3d_label_components): volume numpy [z, y, x]
+    float32; a voxel is foreground when lo <= value <= hi (a NaN never is), bodies are joined over faces, and those of at least
+    min_voxels voxels are numbered in ascending order of their smallest linear index.  Returns a Components."""
+    fn = _components_entry()
+    lo, hi, min_voxels = _component_range(lo, hi, min_voxels)
+    volume = np.asarray(volume)
+    if volume.ndim != 3 or volume.size == 0:
+        raise ValueError("volume must be a non-empty [z, y, x] volume")
+    with _on_device((volume,), "volume must be a [z, y, x] volume") as (box, p, dims):
+        out = box.alloc()
+        box.set_current()
+        info = ComponentInfo()
+        check(fn(p[0], lo, hi, min_voxels, out, *dims, None, 0, C.byref(info)), "f3d_label_components")
+        n = int(info.n_labels)
+        sizes = np.zeros(n, np.uint64)
+        if n:                                                  # their number is known now: once more with room for all of them
+            check(fn(p[0], lo, hi, min_voxels, out, *dims, sizes.ctypes.data_as(C.POINTER(C.c_ulonglong)), n, C.byref(info)),
+                  "f3d_label_components")
+        labels = box.download(out, dims).view(np.int32)
+    return Components(labels, sizes, info.as_dict())
 
 
 def validate_displacement(u, v, w, weight=None, weight_min=0.8, step=1, eps=0.1, threshold=2.0, min_neighbours=9, mode="replace",
@@ -1919,6 +1980,24 @@ class OpticalFlow:
     def label_motion_end(self):
         """free the containers of the per-label residual and of the labels (destroy() does too)"""
         _host_check(host().f3d_flow_label_motion_end(self._h), "f3d_flow_label_motion_end")
+
+    def segment(self, lo=-np.inf, hi=np.inf, min_voxels=27):
+        """The connected bodies of the resident frame 0 (the raw frame of the last upload()), labelled on the device and left there: a
+        Components, after which label_motion(None, ..., n_labels=c.n_labels) and contacts(None, n_labels=c.n_labels) run on these
+        bodies.  lo, hi, min_voxels as in label_components."""
+        lo, hi, min_voxels = _component_range(lo, hi, min_voxels)
+        w, h, d = self.dims
+        sizes, count, info = C.POINTER(C.c_ulonglong)(), _sz(0), ComponentInfo()
+        _host_check(host().f3d_flow_labels_compute(self._h, 0, lo, hi, min_voxels, C.byref(sizes), C.byref(count), C.byref(info)),
+                    "f3d_flow_labels_compute")
+        own = np.array(sizes[:count.value], np.uint64)         # the driver owns its list: a copy outlives the next call
+        labels = np.empty((d, h, w), np.int32)
+        _host_check(host().f3d_flow_labels_download(self._h, labels.ctypes.data_as(C.POINTER(C.c_int))), "f3d_flow_labels_download")
+        return Components(labels, own, info.as_dict())
+
+    def segment_end(self):
+        """free the driver's list of sizes (the labels stay on the device until label_motion_end() or destroy())"""
+        _host_check(host().f3d_flow_labels_end(self._h), "f3d_flow_labels_end")
 
     def contacts(self, labels, source="flow", motion=None, n_labels=None, min_faces=4):
         """The contacts between the bodies of a segmentation in the flow the driver holds (source="flow") or in the trajectory

@@ -23,6 +23,7 @@ struct f3d_flow_s {
   bool trajectory_started = false;
   bool zncc_of_held_flow = false;  // the match container holds the zncc of the flow the driver holds (f3d_flow_motion_compute's mask)
   std::vector<f3d_contact> contacts;  // what f3d_flow_contacts_compute hands out
+  std::vector<unsigned long long> label_sizes;  // what f3d_flow_labels_compute hands out
 };
 
 struct f3d_slabflow_s {
@@ -460,6 +461,35 @@ int f3d_flow_contacts_end(f3d_flow flow)
   g_host_error.clear();
   if (!flow) return HostFail("f3d_flow_contacts_end: null driver");
   std::vector<f3d_contact>().swap(flow->contacts);
+  return 0;
+}
+
+int f3d_flow_labels_compute(f3d_flow flow, f3d_devptr frame, float lo, float hi, unsigned long long min_voxels,
+                            const unsigned long long** sizes, size_t* count, f3d_component_info* info)
+{
+  g_host_error.clear();
+  if (!flow || !sizes || !count || !info) return HostFail("f3d_flow_labels_compute: null argument");
+  OpticalFlowE& d = flow->driver;
+  if (!d.ComputeLabels(frame, lo, hi, min_voxels, &flow->label_sizes, info))
+    return HostFail(d.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  *sizes = flow->label_sizes.data();
+  *count = flow->label_sizes.size();
+  return 0;
+}
+
+int f3d_flow_labels_end(f3d_flow flow)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_labels_end: null driver");
+  std::vector<unsigned long long>().swap(flow->label_sizes);
+  return 0;
+}
+
+int f3d_flow_labels_download(f3d_flow flow, int* labels)
+{
+  g_host_error.clear();
+  if (!flow || !labels) return HostFail("f3d_flow_labels_download: null argument");
+  if (!flow->driver.DownloadLabels(labels)) return HostFail(flow->driver.DerivedError(OpticalFlowE::kLabelMotion).c_str());
   return 0;
 }
 

@@ -14,6 +14,7 @@
 //                 [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]
 //                [--labels FILE --label-motion translation|rigid|affine [--label-min-voxels K]]
 //                [--labels FILE --contacts [--contact-min-faces K]]
+//                [--segment LO:HI [--segment-min-voxels K]]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -81,6 +82,11 @@
 // the normal from lo to hi, the mean face centre, the opening and the slip of the displacement across the contact, and the same two from
 // the fits of --label-motion when that is given too (nan otherwise) -- and one line per pair sums it up.  A contact with fewer than
 // --contact-min-faces faces (default 4) is marked small and left out of that line's opening, closing and slip.
+// --segment LO:HI makes the labels on the device instead of reading them (f3d_label_components): the voxels of the raw frame 0 with
+// LO <= value <= HI, in the units of the frame as it is read (either side may be left empty for an open bound), joined over their faces
+// into bodies while the first pair is resident; a body of fewer than --segment-min-voxels voxels (default 27) gets no label.  It takes
+// the place of --labels FILE for --label-motion and --contacts, and may stand alone.  <tag>_labels.raw (tag of the first pair) is the
+// label volume in the format --labels reads, <tag>_bodies.csv has one row per body (label, voxels), and one line sums it up.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -113,7 +119,8 @@ static void Usage()
               "              [--validate mark|replace [--validate-step S] [--validate-threshold T] [--validate-eps E]\n"
               "               [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]\n"
               "              [--labels FILE --label-motion translation|rigid|affine [--label-min-voxels K]]\n"
-              "              [--labels FILE --contacts [--contact-min-faces K]]\n");
+              "              [--labels FILE --contacts [--contact-min-faces K]]\n"
+              "              [--segment LO:HI [--segment-min-voxels K]]\n");
 }
 
 int main(int argc, char** argv)
@@ -153,6 +160,10 @@ int main(int argc, char** argv)
   bool contacts = false;          // --contacts
   unsigned long long contact_min_faces = 4;
   bool contact_min_given = false;
+  bool segment = false;           // --segment LO:HI
+  float segment_lo = -INFINITY, segment_hi = INFINITY;
+  unsigned long long segment_min_voxels = 27;
+  bool segment_min_given = false;
   const unsigned inverse_iterations = 32;
   const float inverse_tolerance = 1e-3f;
 
@@ -409,6 +420,36 @@ int main(int argc, char** argv)
       label_min_given = true;
     }
     else if (a == "--contacts") contacts = true;
+    else if (a == "--segment") {
+      need(1);
+      // LO:HI, either side empty for an open bound; anything else, a NaN or LO > HI is malformed
+      const std::string range = argv[++i];
+      const size_t colon = range.find(':');
+      if (colon == std::string::npos || range.find(':', colon + 1) != std::string::npos) { Usage(); return 64; }
+      const std::string side[2] = {range.substr(0, colon), range.substr(colon + 1)};
+      float bound[2] = {-INFINITY, INFINITY};
+      for (int k = 0; k < 2; ++k) {
+        if (side[k].empty()) continue;
+        char* rest = nullptr;
+        bound[k] = std::strtof(side[k].c_str(), &rest);
+        if (rest == side[k].c_str() || *rest || bound[k] != bound[k]) { Usage(); return 64; }
+      }
+      if (bound[0] > bound[1]) {
+        std::printf("--segment %s: LO is above HI\n", range.c_str());
+        Usage();
+        return 64;
+      }
+      segment = true;
+      segment_lo = bound[0];
+      segment_hi = bound[1];
+    }
+    else if (a == "--segment-min-voxels") {
+      need(1);
+      char* rest = nullptr;
+      segment_min_voxels = std::strtoull(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest || argv[i][0] == '-' || segment_min_voxels == 0) { Usage(); return 64; }
+      segment_min_given = true;
+    }
     else if (a == "--contact-min-faces") {
       need(1);
       char* rest = nullptr;
@@ -522,7 +563,18 @@ int main(int argc, char** argv)
     Usage();
     return 64;
   }
-  if ((contacts && labels_file.empty()) || (contact_min_given && !contacts)) {
+  if ((segment && !labels_file.empty()) || (segment_min_given && !segment)) {
+    std::printf("--segment takes the place of --labels FILE: they cannot be combined, and --segment-min-voxels needs --segment\n");
+    Usage();
+    return 64;
+  }
+  if (segment && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--segment needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if ((contacts && labels_file.empty() && !segment) || (contact_min_given && !contacts)) {
     std::printf("--contacts needs --labels FILE, and --contact-min-faces needs --contacts\n");
     Usage();
     return 64;
@@ -539,7 +591,7 @@ int main(int argc, char** argv)
     Usage();
     return 64;
   }
-  if ((!contacts && labels_file.empty() != (label_model < 0)) || (label_min_given && label_model < 0)) {
+  if ((!contacts && !segment && labels_file.empty() != (label_model < 0)) || (label_min_given && label_model < 0)) {
     std::printf("--labels and --label-motion need each other, and --label-min-voxels needs both\n");
     Usage();
     return 64;
@@ -559,7 +611,7 @@ int main(int argc, char** argv)
   // the segmentation is read before any device is touched: a file of another size or without a body is an argument error
   std::vector<int> label_volume;
   size_t n_labels = 0, n_bodies = 0;  // the largest label, and how many of 1 .. n_labels occur
-  if (label_model >= 0 || contacts) {
+  if ((label_model >= 0 || contacts) && !segment) {
     const size_t count = width * height * depth;
     std::FILE* f = std::fopen(labels_file.c_str(), "rb");
     bool good = f != nullptr;
@@ -724,7 +776,7 @@ int main(int argc, char** argv)
   }
   if (!optical_flow_e.AllocateResidentFrames()) return 3;
   std::printf("Mode: Full GPU mode \n");
-  if (label_model >= 0 || contacts) {
+  if ((label_model >= 0 || contacts) && !segment) {
     if (!optical_flow_e.UploadLabels(label_volume.data())) return 3;
     std::vector<int>().swap(label_volume);
   }
@@ -1017,6 +1069,7 @@ int main(int argc, char** argv)
       return false;
     }
     contact_kin.resize(contact_list.size());
+    if (contact_list.empty()) return true;  // bodies that do not touch (those of --segment never do): nothing to project, and no array to pass
     const size_t dims[3] = {width, height, depth};
     const bool fitted = label_model >= 0;
     return f3d_contact_kinematics(contact_list.data(), contact_list.size(), dims, fitted ? label_fits.data() : nullptr,
@@ -1075,11 +1128,63 @@ int main(int argc, char** argv)
     f.print(k);
   };
 
+  // --segment: the labels of frame 0, made while the first pair is resident and before anything reads labels.  0: fine; otherwise
+  // the exit status.
+  auto segment_frame_0 = [&]() {
+    std::vector<unsigned long long> sizes;
+    f3d_component_info info = {};
+    if (!optical_flow_e.ComputeLabels(0, segment_lo, segment_hi, segment_min_voxels, &sizes, &info)) {
+      std::printf("Error: %s\n", optical_flow_e.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+      return 3;
+    }
+    std::printf("bodies frame 0: %llu bodies of %llu foreground voxels (largest %llu), %llu bodies of %llu voxels dropped below %llu, "
+                "%llu background, %llu NaN\n", info.n_labels, info.foreground, info.largest, info.dropped_components, info.dropped_voxels,
+                segment_min_voxels, info.background, info.nan);
+    const std::string tag = pairs > 1 ? prefix + "_0" : prefix;
+    std::vector<int> volume(width * height * depth);
+    if (!optical_flow_e.DownloadLabels(volume.data())) {
+      std::printf("Error: %s\n", optical_flow_e.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+      return 3;
+    }
+    std::FILE* raw = std::fopen((tag + "_labels.raw").c_str(), "wb");
+    const bool raw_good = raw && std::fwrite(volume.data(), sizeof(int), volume.size(), raw) == volume.size();
+    if ((raw && std::fclose(raw) != 0) || !raw_good) {
+      std::printf("Error: cannot write %s_labels.raw\n", tag.c_str());
+      return 2;
+    }
+    std::FILE* csv = std::fopen((tag + "_bodies.csv").c_str(), "w");
+    if (csv) {
+      std::fprintf(csv, "label,voxels\n");
+      for (size_t l = 0; l < sizes.size(); ++l) std::fprintf(csv, "%zu,%llu\n", l + 1, sizes[l]);
+    }
+    const bool csv_error = csv && std::ferror(csv) != 0;
+    if (!csv || std::fclose(csv) != 0 || csv_error) {
+      std::printf("Error: cannot write %s_bodies.csv\n", tag.c_str());
+      return 2;
+    }
+    if (label_model >= 0 || contacts) {
+      if (info.n_labels == 0 || info.n_labels > (1ull << 22)) {
+        std::printf(info.n_labels ? "Error: --segment found %llu bodies and --label-motion and --contacts take at most %d: raise "
+                                    "--segment-min-voxels (now %llu) so that the small ones get no label\n"
+                                  : "Error: --segment found no body (%llu) for --label-motion or --contacts; the most is %d, "
+                                    "--segment-min-voxels is %llu\n", info.n_labels, 1 << 22, segment_min_voxels);
+        return 3;
+      }
+      n_labels = n_bodies = static_cast<size_t>(info.n_labels);
+      label_fits.assign(n_labels, f3d_motion_fit());
+      label_state.assign(n_labels, 0);
+      label_rms_after.assign(n_labels, 0.0);
+    }
+    return 0;
+  };
+
   if (pairs == 1) {
     if (!synthetic && !load(frame_1, files[1])) return 2;
     optical_flow_e.UploadResidentFrames(frame_0, frame_1);
     optical_flow_e.ComputeFlowResident(params);
     if (print_stats) report();
+    if (segment)
+      if (const int status = segment_frame_0()) return status;
     optical_flow_e.DownloadFlow(flow_u, flow_v, flow_w);
     write_pair(0, flow_u, flow_v, flow_w);
     if (cumulative) {
@@ -1186,6 +1291,8 @@ int main(int argc, char** argv)
         pending_output = false;
       }
       optical_flow_e.EndComputeFlowResident();
+      if (segment && k == 0)  // frame 0 is still in its container: frame 3 overwrites it only beside the solve of pair 1
+        if (const int status = segment_frame_0()) return status;
       if (print_stats) report();
       std::printf("pair %zu of %zu: %.3f s on the device\n", k + 1, pairs, optical_flow_e.LastDeviceSeconds());
       if (!optical_flow_e.TakeResult(taken)) return 3;

@@ -199,6 +199,16 @@ class OpticalFlowE : public OpticalFlowBase {
   // 8 * n_labels (at most 2^20) and doubles until the table is complete; contacts receives them sorted by (lo, hi), info (required) the counters of
   // the call that sufficed.  Waits for the stream.  Errors are reported through DerivedError(kLabelMotion), whose labels these are.
   bool ComputeContacts(const Displacement& of, size_t n_labels, std::vector<f3d_contact>* contacts, f3d_contact_info* info);
+  // The labels made on the device instead of uploaded (f3d_label_components of include/f3d.h): the connected bodies of the voxels of
+  // `frame` with lo <= value <= hi, those of at least min_voxels voxels numbered 1 .. info->n_labels, into the container UploadLabels
+  // fills; ComputeLabelMotion and ComputeContacts then run on them with n_labels = info->n_labels.  frame 0 means the resident frame
+  // 0, the one ComputeMatch uses: the RAW frame as it was uploaded (the pre-blurred copies of the pyramid live in pooled containers and
+  // are not kept).  sizes (nullable) receives the size of every label, which costs a second run of the entry once their number is
+  // known; info is required.  Waits for the stream.  DownloadLabels copies the label container, however it was filled, to
+  // width * height * depth int32.  Errors of both are reported through DerivedError(kLabelMotion).
+  bool ComputeLabels(DevicePtr frame, float lo, float hi, unsigned long long min_voxels, std::vector<unsigned long long>* sizes,
+                     f3d_component_info* info);
+  bool DownloadLabels(int* labels);
   static int DerivedFieldCount(Derived which);
   static bool DerivedSelected(Derived which, int field, unsigned fields);
   DevicePtr DerivedContainer(Derived which, int field) const { return derived_[which].ptr[field]; }  // 0 until computed

@@ -932,6 +932,44 @@ int f3d_label_contacts(f3d_devptr u, f3d_devptr v, f3d_devptr w /* all three or 
                        size_t width, size_t height, size_t depth, size_t capacity,
                        struct f3d_contact* out /* capacity entries, host */, f3d_contact_info* info);
 
+/* Connected bodies of a thresholded volume (no reference counterpart: f3d_label_motion_sums and f3d_label_contacts start from a label
+ * volume, and a tomography user has grey values; this makes the labels where the frame already is).  The box is width x height x depth
+ * in the corner of the current container; src is a container of floats, labels_out a container read as int32 under the convention of
+ * f3d_label_motion_sums.  With W = width and H = height, the linear box index of the voxel (x, y, z) is x + W (y + H z).
+ *
+ * Foreground.  A voxel with value s is foreground when lo <= s && s <= hi in float compares.  A NaN voxel is therefore background, and
+ * it is counted in nan.  lo may be -inf and hi +inf (an infinite voxel is then foreground); -0.0f equals 0.0f; a denormal compares as
+ * its value.
+ * Connectivity.  Six neighbours: two voxels are connected when they share a face, the faces of f3d_label_contacts.  Voxels that share
+ * only an edge or a corner are not connected.
+ * Component.  A maximal face-connected set of foreground voxels.  Its root is the smallest linear box index among its voxels, its size
+ * is its voxel count.
+ * Kept and dropped.  A component is kept when its size is at least min_voxels (at least 1).  The kept components are numbered
+ * 1 .. n_labels in ascending order of root.  Every voxel of a kept component receives its number; every other voxel of the box receives
+ * 0.  Container padding is neither read nor written, and no float instruction touches a label.
+ * Sizes.  sizes[L - 1] is the size of label L, for L up to the smaller of n_labels and capacity; what lies beyond is not written.
+ * f3d_component_info:
+ *   foreground, background   every voxel of the box lies in exactly one of them
+ *   nan                      the NaN voxels, which are contained in background
+ *   n_components             kept and dropped components together
+ *   n_labels                 kept components; dropped_components = n_components - n_labels
+ *   dropped_voxels           the voxels of the dropped components; foreground - dropped_voxels voxels carry a label
+ *   largest                  the size of the largest component, kept or not (0 without foreground)
+ * Determinism.  Everything is a function of the input alone: two calls give the same bytes, whatever the schedule.
+ * Limits.  At most 32768 voxels along an axis and 2^31 - 1 in the box, because a parent index is one 32-bit word (1024^3 is inside).
+ * n_labels is not capped here; f3d_label_motion_sums and f3d_label_contacts keep their own limit of 2^22 labels.
+ * Scratch: a grow-only buffer of the library's, 8 B per voxel of the box, 20 B per 1024 voxels, and 4 B per size handed out.
+ * Refused (status 1, a message, nothing written): a null src, labels_out or info; src == labels_out; a NaN lo or hi, or lo > hi;
+ * min_voxels of 0; an empty box, or a box beyond the limits; a box larger than the current container; sizes given with capacity 0.
+ * Library stream; the call waits until info and sizes are on the host. */
+typedef struct f3d_component_info {
+  unsigned long long foreground, background, nan;
+  unsigned long long n_components, n_labels, dropped_components, dropped_voxels, largest;
+} f3d_component_info;
+int f3d_label_components(f3d_devptr src, float lo, float hi, unsigned long long min_voxels, f3d_devptr labels_out, size_t width,
+                         size_t height, size_t depth, unsigned long long* sizes /* host, nullable */, size_t capacity,
+                         f3d_component_info* info /* required */);
+
 /* Validation of a displacement (no reference counterpart: the normalised median test of PIV and volume-correlation post-processing,
  * Westerweel & Scarano 2005, which a workflow applies between the displacement and the strain).  A vector is compared with the median
  * of its neighbours, scaled by the median residual of those neighbours; a rejected vector becomes NaN (which f3d_flow_strain and

@@ -270,6 +270,20 @@ int f3d_flow_contacts_compute(f3d_flow flow, int source, const int* labels /* nu
                               const struct f3d_contact** contacts, size_t* count, f3d_contact_info* info);
 int f3d_flow_contacts_end(f3d_flow flow);
 
+/* The labels made on the device instead of uploaded: f3d_label_components (include/f3d.h has the definition of foreground, component,
+ * root, the numbering and every counter) of a frame into the label container of the driver, the one f3d_flow_label_motion_compute and
+ * f3d_flow_contacts_compute fill from their `labels` argument and reuse when that is null -- so a null labels and n_labels =
+ * info->n_labels afterwards run on these bodies.  frame: a device container of the driver's geometry, or 0 for the resident frame 0 (the
+ * raw frame 0 of the last f3d_flow_upload / f3d_flow_compute_resident, not a blurred copy).  *sizes receives a list of *count =
+ * info->n_labels sizes (label L at index L - 1) that the driver owns: it stays valid until the next call of this entry,
+ * f3d_flow_labels_end or f3d_flow_destroy.  info is required.  f3d_flow_labels_download copies the label container, however it was
+ * filled, to width * height * depth int32.  f3d_flow_labels_end frees the list of sizes; the labels stay on the device until
+ * f3d_flow_label_motion_end.  A device library without f3d_label_components still loads; then the call fails with a message naming it. */
+int f3d_flow_labels_compute(f3d_flow flow, f3d_devptr frame /* 0: the resident frame 0 */, float lo, float hi, unsigned long long min_voxels,
+                            const unsigned long long** sizes, size_t* count, f3d_component_info* info);
+int f3d_flow_labels_end(f3d_flow flow);
+int f3d_flow_labels_download(f3d_flow flow, int* labels);
+
 /* Validation of the flow the driver holds or of the trajectory (source F3D_STRAIN_OF_FLOW / F3D_STRAIN_OF_TRAJECTORY):
  * f3d_validate_displacement (include/f3d.h has the definition and what step, eps, threshold, min_neighbours and mode mean) into
  * containers the driver keeps until f3d_flow_validate_end (or f3d_flow_destroy).  out[0] receives r, out[1..3] the validated u, v, w
