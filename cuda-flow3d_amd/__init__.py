@@ -150,6 +150,22 @@ class ComponentInfo(C.Structure):  # f3d_component_info: every voxel of the box 
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class SplitInfo(C.Structure):  # f3d_split_info: f3d_component_info of the final classes, then what the split found on the way
+    _fields_ = [(name, C.c_ulonglong) for name in ("foreground", "background", "nan", "n_components", "n_labels", "dropped_components",
+                                                   "dropped_voxels", "largest", "connected_components", "core_voxels", "n_cores",
+                                                   "remainder_bodies", "remainder_voxels")]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class NearestInfo(C.Structure):  # f3d_nearest_info
+    _fields_ = [(name, C.c_ulonglong) for name in ("seeds", "d2_max", "unreached")]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class ContactKinematics(C.Structure):  # f3d_contact_kin
     _fields_ = [("point", C.c_double * 3), ("area", C.c_double), ("normal", C.c_double * 3), ("jump_normal", C.c_double),
                 ("jump_slip", C.c_double), ("fit_normal", C.c_double), ("fit_slip", C.c_double), ("status", C.c_uint)]
@@ -363,6 +379,8 @@ def host():
         "f3d_flow_contacts_end": [C.c_void_p],
         "f3d_flow_labels_compute": [C.c_void_p, _dp, C.c_float, C.c_float, C.c_ulonglong, C.POINTER(C.POINTER(C.c_ulonglong)), C.POINTER(_sz),
                                     C.POINTER(ComponentInfo)],
+        "f3d_flow_labels_split": [C.c_void_p, _dp, C.c_float, C.c_float, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.POINTER(C.c_ulonglong)),
+                                  C.POINTER(_sz), C.POINTER(SplitInfo)],
         "f3d_flow_labels_end": [C.c_void_p], "f3d_flow_labels_download": [C.c_void_p, C.POINTER(C.c_int)],
         "f3d_flow_validate_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_float, C.c_uint, C.c_uint, C.c_uint, C.c_float,
                                       C.POINTER(_fp), C.POINTER(ValidateStats)],
@@ -567,6 +585,16 @@ def _contacts_entry():
 def _components_entry():
     return _entry("f3d_label_components", [_dp, C.c_float, C.c_float, C.c_ulonglong, _dp] + [_sz] * 3 +
                   [C.POINTER(C.c_ulonglong), _sz, C.POINTER(ComponentInfo)], "label the connected bodies of a thresholded volume")
+
+
+def _nearest_entry():
+    return _entry("f3d_nearest_seed", [_dp, C.c_uint, C.c_uint] + [_dp] * 3 + [_sz] * 3 + [C.POINTER(NearestInfo)],
+                  "compute the exact distance and nearest-seed transform")
+
+
+def _split_entry():
+    return _entry("f3d_split_components", [_dp, C.c_float, C.c_float, C.c_ulonglong, C.c_ulonglong, _dp] + [_sz] * 3 +
+                  [C.POINTER(C.c_ulonglong), _sz, C.POINTER(SplitInfo)], "take the touching bodies of a thresholded volume apart")
 
 
 def _validate_entry():
@@ -1208,6 +1236,94 @@ def label_components(volume, lo=-np.inf, hi=np.inf, min_voxels=1):
         if n:                                                  # their number is known now: once more with room for all of them
             check(fn(p[0], lo, hi, min_voxels, out, *dims, sizes.ctypes.data_as(C.POINTER(C.c_ulonglong)), n, C.byref(info)),
                   "f3d_label_components")
+        labels = box.download(out, dims).view(np.int32)
+    return Components(labels, sizes, info.as_dict())
+
+
+# the modes, the flag and the outputs of f3d_nearest_seed in ABI order
+SEED_MODES = {"nonzero": 0, "zero": 1}
+NEAREST_D2_FLOAT = 1
+NEAREST_OUTPUTS = ("d2", "index", "value")
+
+
+def _int32_bits(labels, what):
+    """the bits of an integer (or bool) [z, y, x] volume as float32 for the upload; values that do not fit int32 raise"""
+    labels = np.asarray(labels)
+    if labels.ndim != 3 or labels.size == 0 or not (np.issubdtype(labels.dtype, np.integer) or labels.dtype == np.bool_):
+        raise ValueError(f"{what} must be a non-empty [z, y, x] volume of integers")
+    if labels.dtype != np.bool_ and (int(labels.min()) < -2 ** 31 or int(labels.max()) > 2 ** 31 - 1):
+        raise ValueError(f"{what} does not fit int32")
+    return np.ascontiguousarray(labels.astype(np.int32)).view(np.float32)
+
+
+def nearest_seed(labels, mode="nonzero", outputs=NEAREST_OUTPUTS, d2_float=False):
+    """The exact squared Euclidean distance and nearest-seed transform on the device (include/f3d.h, f3d_nearest_seed): labels an integer
+    [z, y, x] volume whose seeds are the voxels != 0 (mode "nonzero") or == 0 (mode "zero").  Returns (fields, info): fields a dict with
+    the asked-for ones of "d2" (squared distance to the nearest seed; float32 with d2_float), "index" (its x + W (y + H z), -1 without a
+    seed) and "value" (labels there), int32 [z, y, x] each; of several seeds at one distance the one with the smallest index wins.
+    info: the dict of f3d_nearest_info."""
+    fn = _nearest_entry()
+    if mode not in SEED_MODES:
+        raise ValueError(f"mode must be one of {sorted(SEED_MODES)}, not {mode!r}")
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outputs or any(o not in NEAREST_OUTPUTS for o in outputs) or len(set(outputs)) != len(outputs):
+        raise ValueError(f"outputs must be some of {NEAREST_OUTPUTS}, each once, not {outputs!r}")
+    bits = _int32_bits(labels, "labels")
+    with _on_device((bits,), "labels must be a [z, y, x] volume") as (box, p, dims):
+        out = [box.alloc() if name in outputs else 0 for name in NEAREST_OUTPUTS]
+        box.set_current()
+        info = NearestInfo()
+        check(fn(p[0], SEED_MODES[mode], NEAREST_D2_FLOAT if d2_float else 0, *out, *dims, C.byref(info)), "f3d_nearest_seed")
+        fields = {name: box.download(o, dims) for name, o in zip(NEAREST_OUTPUTS, out) if o}
+    return {name: a if name == "d2" and d2_float else a.view(np.int32) for name, a in fields.items()}, info.as_dict()
+
+
+def distance_transform(mask):
+    """The squared Euclidean distance of every voxel of mask (any [z, y, x] volume; a voxel counts where it is != 0) to the nearest voxel
+    where mask == 0, exactly, as int32 [z, y, x]: 0 outside the mask, 2^31 - 1 everywhere when the mask has no zero (nearest_seed in
+    mode "zero")."""
+    mask = np.asarray(mask)
+    if mask.ndim != 3 or mask.size == 0:
+        raise ValueError("mask must be a non-empty [z, y, x] volume")
+    return nearest_seed(mask != 0, mode="zero", outputs=("d2",))[0]["d2"]
+
+
+def _core_d2(radius, core_d2):
+    """the core_d2 of f3d_split_components from exactly one of a radius in voxels (ceil(radius^2)) and the exact integer"""
+    if (radius is None) == (core_d2 is None):
+        raise ValueError("give exactly one of radius and core_d2")
+    if radius is not None:
+        radius = float(radius)
+        if not (np.isfinite(radius) and radius > 0):
+            raise ValueError(f"radius must be finite and positive, not {radius}")
+        core_d2 = int(np.ceil(radius * radius))
+    if int(core_d2) != core_d2 or not 1 <= int(core_d2) < 2 ** 64:
+        raise ValueError(f"core_d2 must be an integer of at least 1, not {core_d2}")
+    return int(core_d2)
+
+
+def split_components(volume, lo=-np.inf, hi=np.inf, radius=None, core_d2=None, min_voxels=1):
+    """The bodies of a volume from anywhere with touching bodies taken apart, on the device (include/f3d.h, f3d_split_components): the
+    foreground (lo <= value <= hi) is eroded to the voxels whose squared distance to the background is at least core_d2 (or
+    ceil(radius^2); exactly one of the two is given), those cores are joined over faces, and every foreground voxel goes to the nearest
+    core voxel's body when that lies in its own connected component, else to the remainder of its component.  core_d2 = 1 is
+    label_components.  Returns a Components whose info is the dict of f3d_split_info."""
+    fn = _split_entry()
+    lo, hi, min_voxels = _component_range(lo, hi, min_voxels)
+    core_d2 = _core_d2(radius, core_d2)
+    volume = np.asarray(volume)
+    if volume.ndim != 3 or volume.size == 0:
+        raise ValueError("volume must be a non-empty [z, y, x] volume")
+    with _on_device((volume,), "volume must be a [z, y, x] volume") as (box, p, dims):
+        out = box.alloc()
+        box.set_current()
+        info = SplitInfo()
+        check(fn(p[0], lo, hi, core_d2, min_voxels, out, *dims, None, 0, C.byref(info)), "f3d_split_components")
+        n = int(info.n_labels)
+        sizes = np.zeros(n, np.uint64)
+        if n:                                                  # their number is known now: once more with room for all of them
+            check(fn(p[0], lo, hi, core_d2, min_voxels, out, *dims, sizes.ctypes.data_as(C.POINTER(C.c_ulonglong)), n, C.byref(info)),
+                  "f3d_split_components")
         labels = box.download(out, dims).view(np.int32)
     return Components(labels, sizes, info.as_dict())
 
@@ -1981,15 +2097,22 @@ class OpticalFlow:
         """free the containers of the per-label residual and of the labels (destroy() does too)"""
         _host_check(host().f3d_flow_label_motion_end(self._h), "f3d_flow_label_motion_end")
 
-    def segment(self, lo=-np.inf, hi=np.inf, min_voxels=27):
+    def segment(self, lo=-np.inf, hi=np.inf, min_voxels=27, split=None):
         """The connected bodies of the resident frame 0 (the raw frame of the last upload()), labelled on the device and left there: a
         Components, after which label_motion(None, ..., n_labels=c.n_labels) and contacts(None, n_labels=c.n_labels) run on these
-        bodies.  lo, hi, min_voxels as in label_components."""
+        bodies.  lo, hi, min_voxels as in label_components.  split: None, or the core_d2 of split_components (an integer of at least 1,
+        e.g. ceil(radius^2)), which takes touching bodies apart; the info is then that of f3d_split_info."""
         lo, hi, min_voxels = _component_range(lo, hi, min_voxels)
         w, h, d = self.dims
-        sizes, count, info = C.POINTER(C.c_ulonglong)(), _sz(0), ComponentInfo()
-        _host_check(host().f3d_flow_labels_compute(self._h, 0, lo, hi, min_voxels, C.byref(sizes), C.byref(count), C.byref(info)),
-                    "f3d_flow_labels_compute")
+        sizes, count = C.POINTER(C.c_ulonglong)(), _sz(0)
+        if split is None:
+            info = ComponentInfo()
+            _host_check(host().f3d_flow_labels_compute(self._h, 0, lo, hi, min_voxels, C.byref(sizes), C.byref(count), C.byref(info)),
+                        "f3d_flow_labels_compute")
+        else:
+            info = SplitInfo()
+            _host_check(host().f3d_flow_labels_split(self._h, 0, lo, hi, _core_d2(None, split), min_voxels, C.byref(sizes), C.byref(count),
+                                                     C.byref(info)), "f3d_flow_labels_split")
         own = np.array(sizes[:count.value], np.uint64)         # the driver owns its list: a copy outlives the next call
         labels = np.empty((d, h, w), np.int32)
         _host_check(host().f3d_flow_labels_download(self._h, labels.ctypes.data_as(C.POINTER(C.c_int))), "f3d_flow_labels_download")

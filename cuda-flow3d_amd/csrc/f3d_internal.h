@@ -37,6 +37,10 @@ bool select_outputs(const char* who, const char* reads, float** ptr, const f3d_d
 struct ConvTaps { float k[51]; int count; };
 const ConvTaps& conv_taps();
 
+// the calling thread's grow-only device buffer of at least `bytes`, shared by the labelled-body entries that run one after another on
+// the library stream (f3d_label_components.hip); 0 on success
+int scratch_buffer(size_t bytes, void** buffer);
+
 // per-kernel event timing
 void prof_begin(int kernel, size_t voxels);
 void prof_end(int kernel);

@@ -477,6 +477,19 @@ int f3d_flow_labels_compute(f3d_flow flow, f3d_devptr frame, float lo, float hi,
   return 0;
 }
 
+int f3d_flow_labels_split(f3d_flow flow, f3d_devptr frame, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
+                          const unsigned long long** sizes, size_t* count, f3d_split_info* info)
+{
+  g_host_error.clear();
+  if (!flow || !sizes || !count || !info) return HostFail("f3d_flow_labels_split: null argument");
+  OpticalFlowE& d = flow->driver;
+  if (!d.ComputeSplitLabels(frame, lo, hi, core_d2, min_voxels, &flow->label_sizes, info))
+    return HostFail(d.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  *sizes = flow->label_sizes.data();
+  *count = flow->label_sizes.size();
+  return 0;
+}
+
 int f3d_flow_labels_end(f3d_flow flow)
 {
   g_host_error.clear();

@@ -15,6 +15,7 @@
 //                [--labels FILE --label-motion translation|rigid|affine [--label-min-voxels K]]
 //                [--labels FILE --contacts [--contact-min-faces K]]
 //                [--segment LO:HI [--segment-min-voxels K]]
+//                [--segment-split R | --segment-split-d2 N]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -87,6 +88,9 @@
 // into bodies while the first pair is resident; a body of fewer than --segment-min-voxels voxels (default 27) gets no label.  It takes
 // the place of --labels FILE for --label-motion and --contacts, and may stand alone.  <tag>_labels.raw (tag of the first pair) is the
 // label volume in the format --labels reads, <tag>_bodies.csv has one row per body (label, voxels), and one line sums it up.
+// --segment-split R (or --segment-split-d2 N, the exact form: N = ceil(R^2)) takes touching bodies apart (f3d_split_components): the
+// cores are the foreground voxels at least R voxels deep below the surface, and every foreground voxel goes to the nearest core of its
+// connected body.  Same files; the line that sums up gains what the split found.  Only with --segment.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -120,7 +124,8 @@ static void Usage()
               "               [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]\n"
               "              [--labels FILE --label-motion translation|rigid|affine [--label-min-voxels K]]\n"
               "              [--labels FILE --contacts [--contact-min-faces K]]\n"
-              "              [--segment LO:HI [--segment-min-voxels K]]\n");
+              "              [--segment LO:HI [--segment-min-voxels K]]\n"
+              "              [--segment-split R | --segment-split-d2 N]\n");
 }
 
 int main(int argc, char** argv)
@@ -164,6 +169,8 @@ int main(int argc, char** argv)
   float segment_lo = -INFINITY, segment_hi = INFINITY;
   unsigned long long segment_min_voxels = 27;
   bool segment_min_given = false;
+  int segment_split_given = 0;            // --segment-split R and --segment-split-d2 N, counted
+  unsigned long long segment_core_d2 = 0;  // 0: no split
   const unsigned inverse_iterations = 32;
   const float inverse_tolerance = 1e-3f;
 
@@ -450,6 +457,21 @@ int main(int argc, char** argv)
       if (rest == argv[i] || *rest || argv[i][0] == '-' || segment_min_voxels == 0) { Usage(); return 64; }
       segment_min_given = true;
     }
+    else if (a == "--segment-split") {
+      need(1);
+      char* rest = nullptr;
+      const double radius = std::strtod(argv[++i], &rest);
+      if (rest == argv[i] || *rest || !std::isfinite(radius) || !(radius > 0) || radius > 65536.0) { Usage(); return 64; }
+      segment_core_d2 = static_cast<unsigned long long>(std::ceil(radius * radius));
+      ++segment_split_given;
+    }
+    else if (a == "--segment-split-d2") {
+      need(1);
+      char* rest = nullptr;
+      segment_core_d2 = std::strtoull(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest || argv[i][0] == '-' || segment_core_d2 == 0) { Usage(); return 64; }
+      ++segment_split_given;
+    }
     else if (a == "--contact-min-faces") {
       need(1);
       char* rest = nullptr;
@@ -565,6 +587,11 @@ int main(int argc, char** argv)
   }
   if ((segment && !labels_file.empty()) || (segment_min_given && !segment)) {
     std::printf("--segment takes the place of --labels FILE: they cannot be combined, and --segment-min-voxels needs --segment\n");
+    Usage();
+    return 64;
+  }
+  if (segment_split_given > 1 || (segment_split_given && (!segment || !labels_file.empty()))) {
+    std::printf("--segment-split R and --segment-split-d2 N are two forms of one option: give one, and only with --segment\n");
     Usage();
     return 64;
   }
@@ -1133,13 +1160,24 @@ int main(int argc, char** argv)
   auto segment_frame_0 = [&]() {
     std::vector<unsigned long long> sizes;
     f3d_component_info info = {};
-    if (!optical_flow_e.ComputeLabels(0, segment_lo, segment_hi, segment_min_voxels, &sizes, &info)) {
+    f3d_split_info split = {};
+    const bool labelled = segment_core_d2 ? optical_flow_e.ComputeSplitLabels(0, segment_lo, segment_hi, segment_core_d2, segment_min_voxels, &sizes, &split)
+                                          : optical_flow_e.ComputeLabels(0, segment_lo, segment_hi, segment_min_voxels, &sizes, &info);
+    if (!labelled) {
       std::printf("Error: %s\n", optical_flow_e.DerivedError(OpticalFlowE::kLabelMotion).c_str());
       return 3;
+    }
+    if (segment_core_d2) {  // the first eight counters are those of the classes
+      const f3d_component_info classes = {split.foreground, split.background, split.nan, split.n_components, split.n_labels,
+                                          split.dropped_components, split.dropped_voxels, split.largest};
+      info = classes;
     }
     std::printf("bodies frame 0: %llu bodies of %llu foreground voxels (largest %llu), %llu bodies of %llu voxels dropped below %llu, "
                 "%llu background, %llu NaN\n", info.n_labels, info.foreground, info.largest, info.dropped_components, info.dropped_voxels,
                 segment_min_voxels, info.background, info.nan);
+    if (segment_core_d2)
+      std::printf("split at d2 >= %llu: %llu components, %llu cores, %llu remainder bodies of %llu voxels\n", segment_core_d2,
+                  split.connected_components, split.n_cores, split.remainder_bodies, split.remainder_voxels);
     const std::string tag = pairs > 1 ? prefix + "_0" : prefix;
     std::vector<int> volume(width * height * depth);
     if (!optical_flow_e.DownloadLabels(volume.data())) {

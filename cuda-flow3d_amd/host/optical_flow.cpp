@@ -57,6 +57,9 @@ extern "C" int f3d_label_contacts(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_
 extern "C" int f3d_label_components(f3d_devptr src, float lo, float hi, unsigned long long min_voxels, f3d_devptr labels_out, size_t width,
                                     size_t height, size_t depth, unsigned long long* sizes, size_t capacity, f3d_component_info* info)
     __attribute__((weak));
+extern "C" int f3d_split_components(f3d_devptr src, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
+                                    f3d_devptr labels_out, size_t width, size_t height, size_t depth, unsigned long long* sizes, size_t capacity,
+                                    f3d_split_info* info) __attribute__((weak));
 extern "C" int f3d_validate_displacement(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr weight, float weight_min, unsigned step,
                                          float eps, float threshold, unsigned min_neighbours, unsigned mode, const f3d_devptr out[4],
                                          unsigned fields, size_t width, size_t height, size_t depth, f3d_validate_stats* stats)
@@ -887,6 +890,29 @@ bool OpticalFlowE::ComputeLabels(DevicePtr frame, float lo, float hi, unsigned l
   sizes->resize(static_cast<size_t>(info->n_labels));
   return set.Check(CheckDeviceError(f3d_label_components(frame, lo, hi, min_voxels, set.ptr[3], c.width, c.height, c.depth, sizes->data(),
                                                          sizes->size(), info)));
+}
+
+bool OpticalFlowE::ComputeSplitLabels(DevicePtr frame, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
+                                      std::vector<unsigned long long>* sizes, f3d_split_info* info)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!f3d_split_components) return set.Fail("the device library has no f3d_split_components (bodies of a thresholded volume, touching bodies apart)");
+  if (!info) return set.Fail("no info to write to");
+  if (!frame) frame = resident_frame_[0];
+  if (!frame) return set.Fail("no frame on the device (AllocateResidentFrames and UploadResidentFrames first)");
+  if (!set.Allocate(kLabelLabels)) return false;
+  const f3d_size4 c = Container();
+  if (!set.Check(CheckDeviceError(f3d_set_container(&c)))) return false;
+  // as in ComputeLabels: the number of bodies is known only afterwards, and the labels are the same bytes both times
+  if (sizes) sizes->clear();
+  if (!set.Check(CheckDeviceError(f3d_split_components(frame, lo, hi, core_d2, min_voxels, set.ptr[3], c.width, c.height, c.depth, nullptr, 0, info))))
+    return false;
+  if (!sizes || info->n_labels == 0) return true;
+  sizes->resize(static_cast<size_t>(info->n_labels));
+  return set.Check(CheckDeviceError(f3d_split_components(frame, lo, hi, core_d2, min_voxels, set.ptr[3], c.width, c.height, c.depth,
+                                                         sizes->data(), sizes->size(), info)));
 }
 
 bool OpticalFlowE::ComputeLabelMotion(const Displacement& of, size_t n_labels, int model, unsigned long long min_voxels,

@@ -208,6 +208,11 @@ class OpticalFlowE : public OpticalFlowBase {
   // width * height * depth int32.  Errors of both are reported through DerivedError(kLabelMotion).
   bool ComputeLabels(DevicePtr frame, float lo, float hi, unsigned long long min_voxels, std::vector<unsigned long long>* sizes,
                      f3d_component_info* info);
+  // The same with touching bodies taken apart (f3d_split_components of include/f3d.h): the cores are the foreground voxels whose
+  // squared distance to the background is at least core_d2, and every foreground voxel goes to the nearest core of its component.  It
+  // fills the same label container, so ComputeLabelMotion and ComputeContacts run on it unchanged.
+  bool ComputeSplitLabels(DevicePtr frame, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
+                          std::vector<unsigned long long>* sizes, f3d_split_info* info);
   bool DownloadLabels(int* labels);
   static int DerivedFieldCount(Derived which);
   static bool DerivedSelected(Derived which, int field, unsigned fields);

@@ -970,6 +970,80 @@ int f3d_label_components(f3d_devptr src, float lo, float hi, unsigned long long 
                          size_t height, size_t depth, unsigned long long* sizes /* host, nullable */, size_t capacity,
                          f3d_component_info* info /* required */);
 
+/* Exact squared Euclidean distance and nearest-seed (feature) transform (no reference counterpart: the primitive under a split of
+ * touching bodies, and alone the depth of every voxel below a surface).  The box is width x height x depth in the corner of the current
+ * container, the box index of the voxel (x, y, z) is x + W (y + H z) as for f3d_label_components, and seeds is a container read as int32
+ * under the convention of f3d_label_motion_sums.
+ *
+ * Seeds.  mode F3D_SEED_NONZERO: the voxels of the box with value != 0.  F3D_SEED_ZERO: those with value == 0 (the classic distance
+ * to the background of a label volume or mask).  Voxels outside the box do not exist: they are neither seeds nor background.
+ * Nearest seed.  The squared distance of the voxels p and s is (px - sx)^2 + (py - sy)^2 + (pz - sz)^2, an integer.  The nearest
+ * seed of p is the seed that minimises the pair (squared distance, box index) lexicographically: of several seeds at the same distance
+ * the one with the smallest box index wins.  A seed is its own nearest seed at distance 0.
+ * Outputs, each nullable, at least one required, each a container written inside the box only:
+ *   d2_out     int32, the squared distance to the nearest seed.  With F3D_NEAREST_D2_FLOAT in flags it is stored as (float)d2 rounded
+ *              to nearest even instead, so that it can be f3d_label_components' src; the conversion is monotone (a <= b gives
+ *              (float)a <= (float)b), so thresholds on it select the same voxels up to the rounding of the bound, and exact below 2^24
+ *   index_out  int32, the box index of the nearest seed
+ *   value_out  int32, seeds[] at the nearest seed (0 in mode F3D_SEED_ZERO)
+ * Without any seed in the box every voxel gets d2 = 2^31 - 1 (its float form with the flag), index = -1, value = 0.
+ * f3d_nearest_info: seeds, the seeds in the box; d2_max, the largest stored d2 (2^31 - 1 without a seed); unreached, the voxels
+ * without a nearest seed: the voxel count of the box when seeds == 0 and 0 otherwise.
+ * Exactness and determinism.  No float instruction touches a distance; the float form of d2_out is one final conversion.  Every output
+ * is a function of the input alone: two calls give the same bytes, whatever the schedule.
+ * Limits.  At most 32768 voxels along an axis and 2^31 - 1 in the box, and in addition W^2 + H^2 + D^2 <= 2^31 - 1 so that every
+ * distance fits (a cube of up to 26754 along the edge is inside; 32768 x 32768 x 1 is not).
+ * Scratch: a grow-only buffer of the library's, 12 B per voxel of the box.  Container padding is neither read nor written.
+ * Refused (status 1, a message, nothing written): a null seeds or info; no output selected; an output that is the container of seeds
+ * or of another output; an unknown mode or flag; an empty box, a box beyond the limits, a box larger than the current container.
+ * Library stream; the call waits until info is on the host. */
+#define F3D_SEED_NONZERO 0u
+#define F3D_SEED_ZERO 1u
+#define F3D_NEAREST_D2_FLOAT 1u
+typedef struct f3d_nearest_info {
+  unsigned long long seeds, d2_max, unreached;
+} f3d_nearest_info;
+int f3d_nearest_seed(f3d_devptr seeds, unsigned mode, unsigned flags, f3d_devptr d2_out /* nullable */, f3d_devptr index_out /* nullable */,
+                     f3d_devptr value_out /* nullable */, size_t width, size_t height, size_t depth, f3d_nearest_info* info /* required */);
+
+/* Bodies of a thresholded volume with touching bodies taken apart (no reference counterpart: f3d_label_components joins everything
+ * that shares a face, so a packed granular sample, a foam or a fibre mat is one component and has no contact; this splits it at its
+ * necks).  Arguments, box, box index, foreground rule, sizes and capacity are f3d_label_components'; core_d2 >= 1 is added.
+ *   1. F is the foreground: lo <= s && s <= hi, a NaN is background.
+ *   2. C is the set of face-connected components of F, all of them.
+ *   3. d2(p), p in F, is the squared distance to the nearest voxel of the box that is not in F: f3d_nearest_seed in mode F3D_SEED_ZERO
+ *      on the mask, 2^31 - 1 when F is the whole box (voxels outside the box do not exist and are not background).
+ *   4. The core voxels are those of F with d2 >= core_d2 (compared as 64-bit integers).  M is the set of face-connected components of
+ *      the core mask, the core bodies.
+ *   5. For p in F let s be the core voxel nearest to p in f3d_nearest_seed's order (squared distance, then box index), over ALL core
+ *      voxels.  If there is none, or s lies in another component of C than p, p belongs to the remainder of its component; otherwise
+ *      to the core body of s.
+ *   6. The classes are the core bodies and, per component that has remainder voxels, its remainder.  The root of a class is the
+ *      smallest box index among its voxels, its size their number.  The classes of at least min_voxels voxels are numbered
+ *      1 .. n_labels in ascending order of root; every other voxel of the box receives 0.
+ * Consequences.  With core_d2 = 1 every foreground voxel is a core voxel and its own nearest one, and labels_out, sizes and the first
+ * eight counters equal f3d_label_components' byte for byte.  The assignment is Euclidean, not geodesic: a class need not be
+ * face-connected, and a core body reaches exactly as far as its voxels are the nearest core voxels inside the component.
+ * f3d_split_info: the eight fields of f3d_component_info with "component" read as class (n_components: kept and dropped classes,
+ * largest: the largest class), and then
+ *   connected_components   the components of C (f3d_label_components' n_components with min_voxels = 1)
+ *   core_voxels, n_cores   the core voxels and the core bodies M
+ *   remainder_bodies       the classes that are a remainder;  n_components = n_cores + remainder_bodies
+ *   remainder_voxels       their voxels
+ * Determinism and exactness as for the two entries it is made of: integers only, the same bytes on every call.
+ * Limits: f3d_nearest_seed's.  Scratch: the library's grow-only buffer, 32 B per voxel of the box (4.3 GB at 512^3), 20 B per 1024
+ * voxels and 4 B per size handed out.
+ * Refused (status 1, a message, nothing written): what f3d_label_components refuses, core_d2 of 0, and a box whose squared diagonal
+ * W^2 + H^2 + D^2 exceeds 2^31 - 1.  Library stream; the call waits until info and sizes are on the host. */
+typedef struct f3d_split_info {
+  unsigned long long foreground, background, nan;
+  unsigned long long n_components, n_labels, dropped_components, dropped_voxels, largest;
+  unsigned long long connected_components, core_voxels, n_cores, remainder_bodies, remainder_voxels;
+} f3d_split_info;
+int f3d_split_components(f3d_devptr src, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
+                         f3d_devptr labels_out, size_t width, size_t height, size_t depth, unsigned long long* sizes /* host, nullable */,
+                         size_t capacity, f3d_split_info* info /* required */);
+
 /* Validation of a displacement (no reference counterpart: the normalised median test of PIV and volume-correlation post-processing,
  * Westerweel & Scarano 2005, which a workflow applies between the displacement and the strain).  A vector is compared with the median
  * of its neighbours, scaled by the median residual of those neighbours; a rejected vector becomes NaN (which f3d_flow_strain and

@@ -281,6 +281,10 @@ int f3d_flow_contacts_end(f3d_flow flow);
  * f3d_flow_label_motion_end.  A device library without f3d_label_components still loads; then the call fails with a message naming it. */
 int f3d_flow_labels_compute(f3d_flow flow, f3d_devptr frame /* 0: the resident frame 0 */, float lo, float hi, unsigned long long min_voxels,
                             const unsigned long long** sizes, size_t* count, f3d_component_info* info);
+/* f3d_flow_labels_split: the same through f3d_split_components (include/f3d.h), which takes touching bodies apart at core_d2; same label
+ * container, same list of sizes, and the same failure naming the entry when the device library has none. */
+int f3d_flow_labels_split(f3d_flow flow, f3d_devptr frame /* 0: the resident frame 0 */, float lo, float hi, unsigned long long core_d2,
+                          unsigned long long min_voxels, const unsigned long long** sizes, size_t* count, f3d_split_info* info);
 int f3d_flow_labels_end(f3d_flow flow);
 int f3d_flow_labels_download(f3d_flow flow, int* labels);
 
