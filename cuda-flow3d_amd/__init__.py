@@ -416,6 +416,7 @@ def host():
         "f3d_op_solve_p_fused_weights": [C.c_void_p, C.POINTER(C.c_int)],
         "f3d_plan_solve_piecemeal": [_sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5,
         "f3d_plan_sweeps": [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2 + [C.c_int],
+        "f3d_plan_sweeps_weights_first": [C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.c_int],
         "f3d_pair8_plan": [C.c_int] * 7 + [C.POINTER(C.c_longlong)],
         "f3d_pair8_decode": [C.c_int] * 4 + [C.POINTER(C.c_longlong)] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2,
         "f3d_pair8_plan_wide": [C.c_int] * 7 + [C.POINTER(C.c_longlong)],
@@ -502,6 +503,18 @@ def solve_sweep_add_entry():
     """f3d_solve_sweep_add (include/f3d.h): the last sweep of a level that stores flow + increments; arguments of f3d_solve_sweep"""
     return _entry("f3d_solve_sweep_add", [_dp] * 10 + [_sz] * 3 + [C.c_float] * 4 + [_dp] * 3 + [_slabp],
                   "add the increments to the flow inside the last sweep")
+
+
+def solve_phi_ksi_sweep_fd_entry():
+    """f3d_solve_phi_ksi_sweep_fd (include/f3d.h): phi / ksi of an outer iteration and its first sweep in one launch"""
+    return _entry("f3d_solve_phi_ksi_sweep_fd", [_dp] * 10 + [_sz] * 3 + [C.c_float] * 6 + [_dp] * 5 + [_slabp],
+                  "compute the weights in front of a sweep")
+
+
+def solve_sweep2_add_fd_entry():
+    """f3d_solve_sweep2_add_fd (include/f3d.h): two sweeps that store flow + increments; arguments of f3d_solve_sweep2_fd"""
+    return _entry("f3d_solve_sweep2_add_fd", [_dp] * 12 + [_sz] * 3 + [C.c_float] * 4 + [_dp] * 3 + [_slabp],
+                  "add the increments to the flow inside the last two sweeps")
 
 
 def _compose_entry():
@@ -1679,6 +1692,18 @@ def plan_sweeps(inner, fused, tri, carry):
     if n < 0:
         raise F3dError("f3d_plan_sweeps failed")
     return [(sweeps[i], bool(weights[i])) for i in range(n)]
+
+
+def plan_sweeps_weights_first(inner):
+    """[(first, sweeps, weights_first, next_weights), ...]: the weights-first cut of the `inner` sweeps of one outer iteration (host
+    arithmetic; first = index of the launch's first sweep): launch 0 computes the iteration's phi / ksi in front of its first sweep, pairs follow, a single sweep ends an even
+    count."""
+    cap = max(1, inner)
+    start, sweeps, first, nxt = (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
+    n = host().f3d_plan_sweeps_weights_first(inner, start, sweeps, first, nxt, cap)
+    if n < 0:
+        raise F3dError("f3d_plan_sweeps_weights_first failed")
+    return [(start[i], sweeps[i], bool(first[i]), bool(nxt[i])) for i in range(n)]
 
 
 Pair8Plan = collections.namedtuple("Pair8Plan", "A a b zc_a zc_b wgs cost tiles")

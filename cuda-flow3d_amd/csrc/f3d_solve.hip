@@ -1672,6 +1672,78 @@ int f3d_solve_sweep_phi_ksi_edges_fd(f3d_devptr fx, f3d_devptr fy, f3d_devptr fz
                   equation_data, out, slab, keep_below, keep_above);
 }
 
+namespace {
+// The weights-first launch (phi / ksi of an outer iteration and its first sweep) and the two sweeps that store flow + increments:
+// k_wpair8, whole level only.  They DECLINE (status 1, a text in f3d_last_error, nothing launched) where they do not apply -- a z-slab
+// window, a level the fused launches march along y, a pitch that is no multiple of 256 floats, face weights that are not plain, an output
+// that is also an input -- and the caller takes the launches it took before.
+int wpair8_fd(const char* who, bool weights_first, const f3d_devptr (&in)[12], size_t width, size_t height, size_t depth, float hx, float hy,
+              float hz, float alpha, float eps_s, float eps_d, const f3d_devptr (&out)[5], const f3d_slab* slab)
+{
+  if (slab) return f3d::fail("%s: whole levels only (no z-slab window)", who);
+  F3dGeo g;
+  if (!f3d::make_geo(&g, width, height, depth, nullptr, who)) return 1;
+  if (g.W < 2 || g.H < 2 || g.D < 2) return f3d::fail("%s: every dimension must be at least 2", who);
+  if (!pair_weights_finite(hx, hy, hz, alpha)) return f3d::fail("%s: alpha / h^2 must be finite and not negative (alpha %g, h %g %g %g)", who, alpha, hx, hy, hz);
+  if (g.pitch % 256 != 0) return f3d::fail("%s: the container pitch must be a multiple of 256 floats", who);
+  if (!pair8_enabled() || pair8_ymarch_rows(g) != 0) return f3d::fail("%s: the fused launches march along y on this level", who);
+  for (int i = 0; i < 5; ++i)
+    for (int k = 0; k < 12; ++k)
+      if (out[i] && out[i] == in[k]) return f3d::fail("%s: an output buffer is also an input (other tiles still read it)", who);
+  for (int i = 0; i < 5; ++i)
+    for (int k = i + 1; k < 5; ++k)
+      if (out[i] && out[i] == out[k]) return f3d::fail("%s: two outputs are the same buffer", who);
+  PairArgs a = {};
+  static const int plain_division = std::getenv("F3D_UDIV") && std::atoi(std::getenv("F3D_UDIV")) == 0;
+  a.plain_division = plain_division;
+  for (int i = 0; i < 12; ++i) a.in[i] = f3d_ptr<const float>(in[i]);
+  for (int i = 0; i < 5; ++i) a.out[i] = f3d_ptr<float>(out[i]);
+  a.hx = hx; a.hy = hy; a.hz = hz;
+  a.alpha = alpha;
+  a.eps_s = eps_s;
+  a.eps_d = eps_d;
+  const int kid = weights_first ? F3D_K_SWEEP_PHI_KSI : F3D_K_SWEEP2;
+  f3d::prof_begin(kid, static_cast<size_t>(g.W) * g.H * (g.z_hi - g.z_lo));
+  const int rows = pair8_rows(g);
+  if (weights_first) {
+    if (rows == 12) launch_pair8<PAIR_PS, 12, true>(a, g, tuning().zchunk, tuning().xcd_remap);
+    else if (rows == 4) launch_pair8<PAIR_PS, 4, true>(a, g, tuning().zchunk, tuning().xcd_remap);
+    else launch_pair8<PAIR_PS, 8, true>(a, g, tuning().zchunk, tuning().xcd_remap);
+  } else {
+    if (rows == 12) launch_pair8<PAIR_SSA, 12, true>(a, g, tuning().zchunk, tuning().xcd_remap);
+    else if (rows == 4) launch_pair8<PAIR_SSA, 4, true>(a, g, tuning().zchunk, tuning().xcd_remap);
+    else launch_pair8<PAIR_SSA, 8, true>(a, g, tuning().zchunk, tuning().xcd_remap);
+  }
+  f3d::prof_end(kid);
+  F3D_HIP(hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+int f3d_solve_phi_ksi_sweep_fd(f3d_devptr fx, f3d_devptr fy, f3d_devptr fz, f3d_devptr ft, f3d_devptr flow_u, f3d_devptr flow_v,
+                               f3d_devptr flow_w, f3d_devptr flow_du, f3d_devptr flow_dv, f3d_devptr flow_dw, size_t width, size_t height,
+                               size_t depth, float hx, float hy, float hz, float equation_alpha, float equation_smoothness,
+                               float equation_data, f3d_devptr phi_out, f3d_devptr ksi_out, f3d_devptr temp_du, f3d_devptr temp_dv,
+                               f3d_devptr temp_dw, const f3d_slab* slab)
+{
+  F3D_REQUIRE_READY("f3d_solve_phi_ksi_sweep_fd");
+  const f3d_devptr in[12] = {fx, fy, flow_u, flow_v, flow_w, flow_du, flow_dv, flow_dw, 0, 0, fz, ft};
+  const f3d_devptr out[5] = {temp_du, temp_dv, temp_dw, phi_out, ksi_out};
+  return wpair8_fd("f3d_solve_phi_ksi_sweep_fd", true, in, width, height, depth, hx, hy, hz, equation_alpha, equation_smoothness,
+                   equation_data, out, slab);
+}
+
+int f3d_solve_sweep2_add_fd(f3d_devptr fx, f3d_devptr fy, f3d_devptr fz, f3d_devptr ft, f3d_devptr flow_u, f3d_devptr flow_v,
+                            f3d_devptr flow_w, f3d_devptr flow_du, f3d_devptr flow_dv, f3d_devptr flow_dw, f3d_devptr phi, f3d_devptr ksi,
+                            size_t width, size_t height, size_t depth, float hx, float hy, float hz, float equation_alpha, f3d_devptr sum_u,
+                            f3d_devptr sum_v, f3d_devptr sum_w, const f3d_slab* slab)
+{
+  F3D_REQUIRE_READY("f3d_solve_sweep2_add_fd");
+  const f3d_devptr in[12] = {fx, fy, flow_u, flow_v, flow_w, flow_du, flow_dv, flow_dw, phi, ksi, fz, ft};
+  const f3d_devptr out[5] = {sum_u, sum_v, sum_w, 0, 0};
+  return wpair8_fd("f3d_solve_sweep2_add_fd", false, in, width, height, depth, hx, hy, hz, equation_alpha, 0.f, 0.f, out, slab);
+}
+
 int f3d_fused_launches_march_along_y(size_t width, size_t height, size_t depth)
 {
   // (no device needed: the launchers' own rule on the level's geometry, for a caller that has to choose between the entry points on

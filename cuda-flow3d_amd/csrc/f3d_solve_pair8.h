@@ -52,7 +52,11 @@
 // planes are mirrored by address, as before).  Halo pieces of tiles at an x face are fetched from columns inside the row
 // (their values are never used) so that no address leaves the container.
 
-enum { PAIR_SS = 0, PAIR_SP = 1 };
+// ... and two more, on the frame-derivative z-marching builds only, under a kernel name of their own (k_wpair8, below):
+//   PAIR_PS  stage 1 = phi/ksi of THIS outer iteration, stage 2 = its first sweep   -- f3d_solve_phi_ksi_sweep_fd (compute_phi_ksi_3d
+//            and the first solve_3d launch of an outer iteration): the weights are outputs only, so phi and ksi leave the rings
+//   PAIR_SSA PAIR_SS whose stage 2 stores flow + increments                         -- f3d_solve_sweep2_add_fd (the level's last launch)
+enum { PAIR_SS = 0, PAIR_SP = 1, PAIR_PS = 2, PAIR_SSA = 3 };
 
 struct PairArgs {
   // f0, f1(warped), u, v, w, du, dv, dw, phi, ksi; on precomputed frame derivatives (FD): fx, fy in place of f0, f1 and
@@ -116,13 +120,15 @@ inline void pair_consts(PairArgs& a)
 // TIGHT (y-marching builds whose tile holds ALL rows of the volume, i.e. every z plane of a thin volume): the two halo row waves and the
 // four halo ring rows would only hold mirror images of rows the tile has anyway, so they are left out -- TY row waves, TY ring rows,
 // the mirrored neighbour of a face row is read from the opposite row -- and two such workgroups share a CU.
-template <int TY, int NA = 10, bool FD = false, bool TIGHT = false>
+// WF (PAIR_PS, weights first): phi and ksi are not inputs -- six stencilled arrays, four centre-only ones -- and stage 1 of the halo
+// rows and of the column wave is phi alone, which looks at no centre-only value: the centre ring holds the TY core rows and no halo columns.
+template <int TY, int NA = 10, bool FD = false, bool TIGHT = false, bool WF = false>
 struct Pair8Lds {
   static constexpr int NR = TY + (TIGHT ? 0 : 2);     // row waves
   static constexpr int NJ = TY + (TIGHT ? 0 : 4);     // ring rows: y0-2 .. y0+TY+1 (TIGHT: y0 .. y0+TY-1)
   static constexpr int NK = (NJ + 3) / 4;             // row pieces (4 rows x 64 floats = 1 KiB) per array and plane
   static constexpr int NJP = NJ;                      // rows per array in the ring (a partial last piece masks its surplus lanes)
-  static constexpr int NS = FD ? 7 : NA;              // arrays in the three-slot ring
+  static constexpr int NS = FD ? (WF ? 6 : 7) : NA;   // arrays in the three-slot ring
   static constexpr int kHaloLanes = NS * 2 * NJ;      // 16-byte x-halo pieces per plane: [array][side][row]
   static constexpr int NH = (kHaloLanes + 63) / 64;   // halo instructions per plane
   static constexpr int kRowFloats = NS * NJP * 64;
@@ -139,10 +145,10 @@ struct Pair8Lds {
   static constexpr int kPerPlane = NS * NK + NH;
   static_assert(kPerPlane <= 63, "s_waitcnt vmcnt(kPerPlane): the counter has six bits");
   // the centre-only ring of the FD builds
-  static constexpr int NC = FD ? 5 : 0;               // fx, fy, ksi, fz, ft
-  static constexpr int NRC = TY + 2;                  // rows y0-1 .. y0+TY
+  static constexpr int NC = FD ? (WF ? 4 : 5) : 0;    // fx, fy, ksi, fz, ft (WF: fx, fy, fz, ft)
+  static constexpr int NRC = WF ? TY : TY + 2;        // rows y0-1 .. y0+TY (WF: y0 .. y0+TY-1)
   static constexpr int NKC = (NRC + 3) / 4;
-  static constexpr int kCHaloLanes = NC * 2 * TY;     // [array][side][core row]
+  static constexpr int kCHaloLanes = WF ? 0 : NC * 2 * TY;   // [array][side][core row]
   static constexpr int NHC = (kCHaloLanes + 63) / 64;
   static constexpr int kCRowFloats = NC * NRC * 64;
   static constexpr int kCHaloOff = kCRowFloats;
@@ -275,6 +281,52 @@ __device__ __forceinline__ void phi_ksi_stage2(const CarryP& k, const S3& xm, co
   }
 }
 
+// A.3 for one voxel from its nine complete numerators ((U[+1] - U[-1]) + dU[+1]) - dU[-1] (PAIR_PS, stage 1): phi_ksi_stage2's
+// operations behind the numerators.  with_ksi (wave-uniform): the rows that own voxels; the halo rows and the column wave make phi alone.
+__device__ __forceinline__ void weights_first_stage1(float (&q)[9], bool with_ksi, float fx, float fy, float fz, float ft, float du,
+                                                     float dv_c, float dw, const SolveDivs& dv, float eps_s2, float eps_d2, float& phi,
+                                                     float& ksi, bool counts, bool fast_weights)
+{
+  if (__builtin_expect(dv.ok && udiv_all_safe(q), 1)) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      q[3 * c + 0] = udiv(q[3 * c + 0], dv.x2);
+      q[3 * c + 1] = udiv(q[3 * c + 1], dv.y2);
+      q[3 * c + 2] = udiv(q[3 * c + 2], dv.z2);
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      q[3 * c + 0] = q[3 * c + 0] / dv.x2.d;
+      q[3 * c + 1] = q[3 * c + 1] / dv.y2.d;
+      q[3 * c + 2] = q[3 * c + 2] / dv.z2.d;
+    }
+  }
+  const float dux = q[0], duy = q[1], duz = q[2], dvx = q[3], dvy = q[4], dvz = q[5], dwx = q[6], dwy = q[7], dwz = q[8];
+  const float a_phi = dux * dux + duy * duy + duz * duz + dvx * dvx + dvy * dvy + dvz * dvz + dwx * dwx + dwy * dwy + dwz * dwz + eps_s2;
+  float s_phi, s_ksi = 1.f, a_ksi = 1.f, w_ksi = 0.f;
+  const float w_phi = weight_fast(a_phi, s_phi);
+  bool lane_ok = weight_fast_ok(a_phi, s_phi);
+  if (with_ksi) {
+    const float J11 = fx * fx, J22 = fy * fy, J33 = fz * fz;
+    const float J12 = fx * fy, J13 = fx * fz, J23 = fy * fz;
+    const float J14 = fx * ft, J24 = fy * ft, J34 = fz * ft, J44 = ft * ft;
+    float s = (J11 * du + J12 * dv_c + J13 * dw + J14) * du + (J12 * du + J22 * dv_c + J23 * dw + J24) * dv_c +
+              (J13 * du + J23 * dv_c + J33 * dw + J34) * dw + (J14 * du + J24 * dv_c + J34 * dw + J44);
+    s = static_cast<float>(s > 0) * s;
+    a_ksi = s + eps_d2;
+    w_ksi = weight_fast(a_ksi, s_ksi);
+    lane_ok = lane_ok && weight_fast_ok(a_ksi, s_ksi);
+  }
+  if (__builtin_expect(fast_weights && __builtin_amdgcn_ballot_w64(counts && !lane_ok) == 0, 1)) {
+    phi = w_phi;
+    ksi = w_ksi;
+  } else {
+    phi = weight_ieee(a_phi);
+    ksi = with_ksi ? weight_ieee(a_ksi) : 0.f;
+  }
+}
+
 // (the tile numbering, pair8_folds, the plan of a launch and the decode of a workgroup number: f3d_pair8_plan.h)
 
 // ABL (timing experiments only, wrong results): bit 0 = the loader issues nothing after the prologue, bit 1 = no stage
@@ -302,21 +354,25 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
   static_assert(!FOLDS || (!YM && !TIGHT && ABL == 0), "two row bands per tile: z-marching product builds only");
   static_assert(!(YM && FD), "the frame-derivative launchers march along z only");
   static_assert(!TIGHT || (YM && ABL == 0), "a tile without halo rows holds every row of the volume: thin volumes marched along y");
+  constexpr bool PS = MODE == PAIR_PS;                       // weights first
+  constexpr bool SSM = MODE == PAIR_SS || MODE == PAIR_SSA;  // two sweeps
+  static_assert((!PS && MODE != PAIR_SSA) || (FD && !YM && !TIGHT && ABL == 0), "k_wpair8: frame-derivative z-marching product builds only");
   constexpr int RH = TIGHT ? 0 : 1;   // halo rows on either side of the tile's rows that get a row wave (and twice that many ring rows)
   // rows of a tile / march direction: (y, z) or, for thin volumes, (z, y).  YM launches cover the whole volume (no slab window).
   const int RDIM = YM ? g.D : g.H;   // extent along the tile's rows
   const int MDIM = YM ? g.H : g.D;   // extent along the march
   const int m_lo = YM ? 0 : g.z_lo, m_hi = YM ? g.H : g.z_hi;
   constexpr int NA = FD ? 12 : 10;
-  using L = Pair8Lds<TY, NA, FD, TIGHT>;
+  using L = Pair8Lds<TY, NA, FD, TIGHT, PS>;
   constexpr int NR = L::NR, NJ = L::NJ, NK = L::NK, NJP = L::NJP, NH = L::NH;
   static_assert(TY <= 32, "the column wave holds one halo voxel per lane: 2 x TY <= 64");
   __shared__ __attribute__((aligned(16))) float ring[L::kSlots][L::kSlotFloats];
   __shared__ __attribute__((aligned(16))) float cring[L::kCSlots][L::kCSlotFloats];  // FD: the centre-only inputs (4 floats otherwise)
   // FD: ring index of a stencilled input (u .. phi are inputs 2 .. 8) and centre-ring index of fx, fy, ksi, fz, ft (inputs 0, 1, 9, 10, 11)
   constexpr int SB = FD ? 2 : 0;   // ring array = input - SB
-  __shared__ float img1[2][3][NR][kLanes];  // stage-1 results of the row waves: S = U + dU' (SS) or dU' (SP)
-  __shared__ float hc1[2][3][2][32];        // the same for the two halo columns: [component][side][core row]
+  constexpr int NI = PS ? 4 : 3;   // PS: S = U + dU and phi
+  __shared__ float img1[2][NI][NR][kLanes];  // stage-1 results of the row waves: S = U + dU' (SS) or dU' (SP)
+  __shared__ float hc1[2][NI][2][32];        // the same for the two halo columns: [component][side][core row]
   __shared__ float img3[(ABL & 64) ? 3 : 1][(ABL & 64) ? NR : 1][(ABL & 64) ? kLanes : 1];  // lab: stage-2 results for a third stage
 
   // the workgroup's tile and planes (f3d_pair8_plan.h: the function the host API decodes with); FOLDS: the numbering described there
@@ -361,7 +417,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     __builtin_amdgcn_s_setprio(3);
     const float* base[NA];
 #pragma unroll
-    for (int i = 0; i < NA; ++i) base[i] = uniform_ptr(a.in[i] + base_off);
+    for (int i = 0; i < NA; ++i) base[i] = (PS && (i == 8 || i == 9)) ? nullptr : uniform_ptr(a.in[i] + base_off);   // PS: no phi, no ksi
     // row pieces: lane -> (row 4k + lane/16, floats 4 (lane%16) ..); FOLD: the upper eight lanes of a row fetch band B's row
     const bool bandb = FOLD && (lane & 15) >= 8;
     const int seg = bandb ? (lane & 15) - 8 : (lane & 15);
@@ -414,8 +470,9 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
         if (hv[h]) dma16_lane(hptr[h] + (poff >> 2), slot + L::kHaloOff + h * 256);
     };
     // FD: the centre-only inputs of plane p into centre slot (p - qs) mod 2: rows y0-1 .. y0+TY and the halo columns of the core rows
-    constexpr int NKC = FD ? L::NKC : 1, NHC = FD ? L::NHC : 1;
-    constexpr int kCIn[5] = {0, 1, 9, 10, 11};
+    constexpr int NKC = FD ? L::NKC : 1, NHC = FD && L::NHC > 0 ? L::NHC : 1;
+    constexpr int kCIn[5] = {0, 1, PS ? 10 : 9, PS ? 11 : 10, 11};
+    constexpr int CR0 = PS ? 0 : 1;   // halo rows in front of the centre ring's first row
     unsigned crowb[NKC];
     bool crowv[NKC];
     const float* chptr[NHC];
@@ -425,7 +482,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
       for (int k = 0; k < NKC; ++k) {
         const int j = 4 * k + (lane >> 4);
         crowv[k] = j < L::NRC;
-        const int yrow = f3d_clampi(f3d_mir(y0 + (bandb ? TY : 0) - 1 + (crowv[k] ? j : 0), RDIM), 0, RDIM - 1);
+        const int yrow = f3d_clampi(f3d_mir(y0 + (bandb ? TY : 0) - CR0 + (crowv[k] ? j : 0), RDIM), 0, RDIM - 1);
         crowb[k] = static_cast<unsigned>(yrow) * row_b + static_cast<unsigned>(x0 + 4 * seg) * 4u;
       }
 #pragma unroll
@@ -438,7 +495,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
         const int j = lq % TY;
         const float* b = base[kCIn[0]];
 #pragma unroll
-        for (int i = 1; i < 5; ++i)
+        for (int i = 1; i < (FD ? L::NC : 1); ++i)
           if (arr == i) b = base[kCIn[i]];
         const int yrow = f3d_clampi(f3d_mir(y0 + (FOLD && s ? TY : 0) + j, RDIM), 0, RDIM - 1);
         const int xc = FOLD ? x0 - 4 : s == 0 ? (left_face ? 0 : x0 - 4) : (right_face ? x0 + kLanes - 4 : x0 + kLanes);
@@ -451,7 +508,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
         const int zz = f3d_mir(p, MDIM);
         const unsigned poff = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<unsigned>(zz - zb) * plane_b)));
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
+        for (int i = 0; i < L::NC; ++i) {
 #pragma unroll
           for (int k = 0; k < NKC; ++k)
             if (L::NRC % 4 == 0 || crowv[k]) dma16(base[kCIn[i]], crowb[k] + poff, slot + (i * L::NRC + 4 * k) * kLanes);
@@ -497,7 +554,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
   fdivs.x4 = UDiv{a.r4[0], a.d4[0]}; fdivs.y4 = UDiv{a.r4[1], a.d4[1]}; fdivs.z4 = UDiv{a.r4[2], a.d4[2]};
   fdivs.ok = a.fdivs_ok != 0;
   SolveDivs sdivs = {};
-  if (MODE == PAIR_SP) {
+  if (MODE == PAIR_SP || PS) {
     sdivs.x2 = UDiv{a.r2[0], a.d2[0]}; sdivs.y2 = UDiv{a.r2[1], a.d2[1]}; sdivs.z2 = UDiv{a.r2[2], a.d2[2]};
     sdivs.x4 = fdivs.x4; sdivs.y4 = fdivs.y4; sdivs.z4 = fdivs.z4;
     sdivs.ok = a.sdivs_ok != 0;
@@ -543,7 +600,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
 
   float* obase[5];
 #pragma unroll
-  for (int i = 0; i < 5; ++i) obase[i] = (i < 3 || MODE == PAIR_SP) ? uniform_ptr(a.out[i] + base_off) : nullptr;
+  for (int i = 0; i < 5; ++i) obase[i] = (i < 3 || MODE == PAIR_SP || PS) ? uniform_ptr(a.out[i] + base_off) : nullptr;
   auto rowoff = [&](int yrow, int zz) __attribute__((always_inline)) {
     return static_cast<unsigned>(__builtin_amdgcn_readfirstlane(
         static_cast<int>(static_cast<unsigned>(zz - zb) * plane_b + static_cast<unsigned>(yrow) * row_b)));
@@ -765,7 +822,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
       }
     }
     // what a neighbour reads of this voxel in stage 2: SS U + dU', SP dU'
-    const S3 sN = MODE == PAIR_SS ? S3{C.u + r_du, C.v + r_dv, C.w + r_dw} : S3{r_du, r_dv, r_dw};
+    const S3 sN = SSM ? S3{C.u + r_du, C.v + r_dv, C.w + r_dw} : S3{r_du, r_dv, r_dw};
     if (do1 && !(ABL & 8)) {
       if constexpr (CW) {
         if (cactive) {
@@ -822,9 +879,15 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
         o0 = xm.u + xp.v + ym.w + kC.J12;
         o1 = yp.u + zm.v + zp.w + kC.d1;
         o2 = xm.w + yp.v + zp.u + kC.pw[0] + hC_dv + hC_dw;
-      } else if (MODE == PAIR_SS)   // (ym, yp) = row neighbours, (zm, zp) = march neighbours: handed over in their geometric roles
+      } else if (SSM)   // (ym, yp) = row neighbours, (zm, zp) = march neighbours: handed over in their geometric roles
+      {
         sweep_stage2(kC, xm, xp, YM ? zm : ym, YM ? zp : yp, YM ? ym : zm, YM ? yp : zp, hC_dv, hC_dw, o0, o1, o2);
-      else
+        if constexpr (MODE == PAIR_SSA) {   // the level's last launch: flow + increments
+          o0 = kC.U + o0;
+          o1 = kC.V + o1;
+          o2 = kC.W + o2;
+        }
+      } else
         phi_ksi_stage2(pC, xm, xp, YM ? zm : ym, YM ? zp : yp, YM ? ym : zm, YM ? yp : zp, hC.u, hC.v, hC.w, sdivs, a.eps_s2,
                        a.eps_d2, o0, o1, owner, a.plain_division == 0);
     }
@@ -855,7 +918,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     pC = pN;
     if (do2 && owner) {
       const unsigned off = xb + rowoff(yy, t);
-      if (MODE == PAIR_SS) {
+      if (SSM) {
         gst(obase[0], off, o0);
         gst(obase[1], off, o1);
         gst(obase[2], off, o2);
@@ -867,6 +930,177 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     fetch_neighbours(colw_c, Sp);  // for step q+1
   };
 
+
+  // ================================== weights first (PAIR_PS): stage 1 = phi / ksi, stage 2 = the sweep ==================================
+  // Stage 1 of plane q looks at RAW values only: u, v, w and du, dv, dw of the six neighbours (phi) and the voxel's own increments and
+  // frame derivatives (ksi: core rows alone).  MIND THE NAMES of PlaneRegs in this mode: `su` holds the raw du as read and becomes
+  // u + du in plane_finish, as everywhere; `ksi` is NOT a weight here but the raw du kept beside it (phi needs u and du of the plane
+  // neighbours apart, and ksi is no input); `phi` is unused -- the computed weights travel in phi_q / phC / phM / ksC.  What stage 2 --
+  // the whole sweep of plane q-1 -- reads of its neighbours is finished S = U + dU and phi: published to the images by every stage-1
+  // wave (S without arithmetic), handed over between lanes by DPP and between planes in registers (hM / phM: plane q-2, M / phC: q-1).
+  auto row_raw_ps = [&](PlaneRegs& p, const float* slot, int j, bool centre, const float* cs) __attribute__((always_inline)) {
+    const float* d = slot + j * kLanes + lane;
+    constexpr int st = NJP * kLanes;
+    p.u = d[0 * st]; p.v = d[1 * st]; p.w = d[2 * st];
+    p.su = d[3 * st]; p.dv = d[4 * st]; p.dw = d[5 * st];
+    p.ksi = p.su;
+    if (centre) {   // core rows: ring row j is centre row j - 2
+      const float* c = cs + (j - 2) * kLanes + lane;
+      constexpr int ct = L::NRC * kLanes;
+      p.f0 = c[0 * ct]; p.f1 = c[1 * ct]; p.fz = c[2 * ct]; p.ft = c[3 * ct];   // fx, fy, fz, ft
+    }
+  };
+  auto halo_raw_ps = [&](PlaneRegs& p, const float* slot, int s, int j, int e) __attribute__((always_inline)) {
+    const float* d = slot + L::kHaloOff + (s * NJ + j) * 4 + e;
+    constexpr int st = 2 * NJ * 4;
+    p.u = d[0 * st]; p.v = d[1 * st]; p.w = d[2 * st];
+    p.su = d[3 * st]; p.dv = d[4 * st]; p.dw = d[5 * st];
+    p.ksi = p.su;
+  };
+  S3 nXd = {0.f, 0.f, 0.f}, nInd = {0.f, 0.f, 0.f};   // raw du, dv, dw of the halo column / of the tile's edge column (column wave)
+  float phM = 0.f, phC = 0.f, ksC = 0.f;             // phi of planes q-2 and q-1, ksi of plane q-1
+  // raw neighbours of the next step's plane: the y numerators ((U[y+1] - U[y-1]) + dU[y+1]) - dU[y-1] complete, the x halo raw
+  auto fetch_ps = [&](auto colw_c, const float* S) __attribute__((always_inline)) {
+    constexpr bool CW = decltype(colw_c)::value;
+    PlaneRegs T0, T1, T2;
+    if constexpr (CW) {
+      PlaneRegs T;
+      const float* d = S + jc * kLanes + (side ? (FOLD ? 32 : kLanes - 1) : 0);
+      constexpr int st = NJP * kLanes;
+      T.u = d[0 * st]; T.v = d[1 * st]; T.w = d[2 * st]; T.su = d[3 * st]; T.dv = d[4 * st]; T.dw = d[5 * st];
+      nInr = {T.u, T.v, T.w};
+      nInd = {T.su, T.dv, T.dw};
+      halo_raw_ps(T0, S, side, jc_m, e_near);
+      halo_raw_ps(T1, S, side, jc_p, e_near);
+      halo_raw_ps(T2, S, side, jc, e_far);
+    } else {
+      row_raw_ps(T0, S, jr_m, false, nullptr);
+      row_raw_ps(T1, S, jr_p, false, nullptr);
+      halo_raw_ps(T2, S, side, jr, e_near);
+    }
+    nDy = {((T1.u - T0.u) + T1.su) - T0.su, ((T1.v - T0.v) + T1.dv) - T0.dv, ((T1.w - T0.w) + T1.dw) - T0.dw};
+    nXr = {T2.u, T2.v, T2.w};
+    nXd = {T2.su, T2.dv, T2.dw};
+  };
+  auto step_ps = [&](auto colw_c, auto slot_c, PlaneRegs& M, PlaneRegs& C, PlaneRegs& P, int q) __attribute__((always_inline)) {
+    constexpr bool CW = decltype(colw_c)::value;
+    constexpr int SLOT = decltype(slot_c)::value;
+    if constexpr (TY > 8) lane = fresh_lane();
+    const int band = FOLD ? lane >> 5 : 0;
+    __syncthreads();  // B_q: plane q+1 is in the ring, img1 / hc1 of plane q-1 are complete
+    const float* Sp = &ring[SLOT][0];
+    const float* Cp = &cring[(q + 1 - qs) & 1][0];
+    const bool do1 = q <= qe;
+    const int b = q & 1;
+    if constexpr (CW) halo_raw_ps(P, Sp, side, jc, e_near);
+    else row_raw_ps(P, Sp, jr, core, Cp);
+    plane_finish(P);
+
+    // ---- stage 1 of plane q: the weights
+    S3 rxm, rxp, dxm, dxp;   // raw u, v, w and du, dv, dw of the x neighbours
+    int vx, vy;
+    if constexpr (CW) {
+      rxm = !FOLD && side ? nInr : nXr;
+      rxp = !FOLD && side ? nXr : nInr;
+      dxm = !FOLD && side ? nInd : nXd;
+      dxp = !FOLD && side ? nXd : nInd;
+      vx = cx;
+      vy = cy;
+      if (cx == g.W - 1) {   // the halo column is the last column of the volume (W = 64 k + 1)
+        rxp = rxm;
+        dxp = dxm;
+      }
+    } else {
+      rxm = {left_or(C.u, nXr.u), left_or(C.v, nXr.v), left_or(C.w, nXr.w)};
+      rxp = {lane_right_or(C.u, nXr.u), lane_right_or(C.v, nXr.v), lane_right_or(C.w, nXr.w)};
+      dxm = {left_or(C.ksi, nXd.u), left_or(C.dv, nXd.v), left_or(C.dw, nXd.w)};
+      dxp = {lane_right_or(C.ksi, nXd.u), lane_right_or(C.dv, nXd.v), lane_right_or(C.dw, nXd.w)};
+      vx = x;
+      vy = band ? y + TY : y;
+      if (tile_at_x_face) {   // mirror rule at the x faces of the volume
+        if (x == 0) {
+          rxm = rxp;
+          dxm = dxp;
+        }
+        if (x == g.W - 1) {
+          rxp = rxm;
+          dxp = dxm;
+        }
+      }
+    }
+    float nq[9] = {((rxp.u - rxm.u) + dxp.u) - dxm.u, nDy.u, ((P.u - M.u) + P.ksi) - M.ksi,
+                   ((rxp.v - rxm.v) + dxp.v) - dxm.v, nDy.v, ((P.v - M.v) + P.dv) - M.dv,
+                   ((rxp.w - rxm.w) + dxp.w) - dxm.w, nDy.w, ((P.w - M.w) + P.dw) - M.dw};
+    // a lane counts where a stage 2 can look at its weights: inside the volume (padding must not send the wave down the slow roads), and
+    // not in the extra step of the top chunk (q = MDIM: stage 1 runs on whatever the ring holds and nobody looks at its results)
+    const bool counts = do1 && vx >= 0 && vx < g.W && vy >= 0 && vy < RDIM && (!CW || cactive);
+    float phi_q = 0.f, ksi_q = 0.f;
+    weights_first_stage1(nq, !CW && core, C.f0, C.f1, C.fz, C.ft, C.ksi, C.dv, C.dw, sdivs, a.eps_s2, a.eps_d2, phi_q, ksi_q, counts,
+                         a.plain_division == 0);
+    if (do1) {
+      if constexpr (CW) {
+        if (cactive) {
+          hc1[b][0][side][crow] = C.su;
+          hc1[b][1][side][crow] = C.sv;
+          hc1[b][2][side][crow] = C.sw;
+          hc1[b][3][side][crow] = phi_q;
+        }
+      } else {
+        img1[b][0][r][lane] = C.su;
+        img1[b][1][r][lane] = C.sv;
+        img1[b][2][r][lane] = C.sw;
+        img1[b][3][r][lane] = phi_q;
+      }
+    }
+    if (!CW && do1 && owner && q >= z0 && q < z1) {   // the weights of the planes this chunk owns
+      const unsigned off = xb + rowoff(yy, q);
+      gst(obase[3], off, phi_q);
+      gst(obase[4], off, ksi_q);
+    }
+
+    // ---- stage 2 of plane t = q - 1: the sweep, on the owned rows
+    const int t = q - 1;
+    const bool do2 = !CW && core && t >= z0;
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+    if (do2) {
+      const int pb = t & 1;
+      const int im = band ? r_ymb : r_ym, ip = band ? r_ypb : r_yp;
+      Face6 ym = {}, yp = {}, xm = {}, xp = {}, zm = {}, zp = {}, cf = {};
+      ym.v[LSU] = img1[pb][0][im][lane]; ym.v[LSV] = img1[pb][1][im][lane]; ym.v[LSW] = img1[pb][2][im][lane]; ym.v[LPHI] = img1[pb][3][im][lane];
+      yp.v[LSU] = img1[pb][0][ip][lane]; yp.v[LSV] = img1[pb][1][ip][lane]; yp.v[LSW] = img1[pb][2][ip][lane]; yp.v[LPHI] = img1[pb][3][ip][lane];
+      const float eu = hc1[pb][0][side][r - RH], ev = hc1[pb][1][side][r - RH], ew = hc1[pb][2][side][r - RH], ep = hc1[pb][3][side][r - RH];
+      cf.v[LSU] = M.su; cf.v[LSV] = M.sv; cf.v[LSW] = M.sw; cf.v[LPHI] = phC;
+      xm.v[LSU] = left_or(M.su, eu); xm.v[LSV] = left_or(M.sv, ev); xm.v[LSW] = left_or(M.sw, ew); xm.v[LPHI] = left_or(phC, ep);
+      xp.v[LSU] = lane_right_or(M.su, eu); xp.v[LSV] = lane_right_or(M.sv, ev); xp.v[LSW] = lane_right_or(M.sw, ew);
+      xp.v[LPHI] = lane_right_or(phC, ep);
+      zm.v[LSU] = hM.u; zm.v[LSV] = hM.v; zm.v[LSW] = hM.w; zm.v[LPHI] = phM;
+      zp.v[LSU] = C.su; zp.v[LSV] = C.sv; zp.v[LSW] = C.sw; zp.v[LPHI] = phi_q;
+      // mirror rule at the faces of the volume: the missing neighbour is the opposite one
+      if (tile_at_x_face) {
+        if (x == 0) xm = xp;
+        if (x == g.W - 1) xp = xm;
+      }
+      if (t == 0) zm = zp;
+      if (t == MDIM - 1) zp = zm;
+      Carry kU;
+      sweep_stage1<true, true>(xm, xp, ym, yp, zm, zp, cf.v, M.u, M.v, M.w, M.dv, M.dw, ksC, a.hx, a.hy, a.hz, fdivs, a.alpha, vx < g.W - 1,
+                               vx > 0, vy < RDIM - 1, vy > 0, t < MDIM - 1, t > 0, o0, o1, o2, kU, M.f0, M.f1, M.fz, M.ft, tile_at_x_face,
+                               a.w[0], a.w[1], a.w[2]);
+    }
+    asm volatile("" ::"v"(o0), "v"(o1), "v"(o2), "v"(phi_q));
+    hM = {M.su, M.sv, M.sw};
+    phM = phC;
+    phC = phi_q;
+    ksC = ksi_q;
+    if (do2 && owner) {
+      const unsigned off = xb + rowoff(yy, t);
+      gst(obase[0], off, o0);
+      gst(obase[1], off, o1);
+      gst(obase[2], off, o2);
+    }
+    fetch_ps(colw_c, Sp);  // for step q+1
+  };
+
   __syncthreads();  // prologue barrier: planes qs-1, qs, qs+1 are in the ring
   PlaneRegs A = {}, B = {}, Cc = {};
   const float* Sm = &ring[0][0];  // plane qs-1
@@ -876,7 +1110,15 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
   using Slot2 = std::integral_constant<int, 2>;
   auto march = [&](auto colw_c) __attribute__((always_inline)) {
     constexpr bool CW = decltype(colw_c)::value;
-    if constexpr (CW) {
+    if constexpr (PS) {
+      if constexpr (CW) {
+        halo_raw_ps(A, Sm, side, jc, e_near);
+        halo_raw_ps(B, S0, side, jc, e_near);
+      } else {
+        row_raw_ps(A, Sm, jr, false, nullptr);
+        row_raw_ps(B, S0, jr, core, &cring[0][0]);
+      }
+    } else if constexpr (CW) {
       halo_raw(A, Sm, side, jc, e_near, false);
       halo_raw(B, S0, side, jc, e_near, true, &cring[0][0]);   // plane qs sits in centre slot 0
     } else {
@@ -885,15 +1127,26 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     }
     plane_finish(A);
     plane_finish(B);
-    fetch_neighbours(colw_c, S0);
     int q = qs;
-    for (; q + 2 <= q_end; q += 3) {  // step q reads plane q+1 from slot (q - qs + 2) mod 3
-      step(colw_c, Slot2{}, A, B, Cc, q);
-      step(colw_c, Slot0{}, B, Cc, A, q + 1);
-      step(colw_c, Slot1{}, Cc, A, B, q + 2);
+    if constexpr (PS) {
+      fetch_ps(colw_c, S0);
+      for (; q + 2 <= q_end; q += 3) {
+        step_ps(colw_c, Slot2{}, A, B, Cc, q);
+        step_ps(colw_c, Slot0{}, B, Cc, A, q + 1);
+        step_ps(colw_c, Slot1{}, Cc, A, B, q + 2);
+      }
+      if (q <= q_end) step_ps(colw_c, Slot2{}, A, B, Cc, q);
+      if (q + 1 <= q_end) step_ps(colw_c, Slot0{}, B, Cc, A, q + 1);
+    } else {
+      fetch_neighbours(colw_c, S0);
+      for (; q + 2 <= q_end; q += 3) {  // step q reads plane q+1 from slot (q - qs + 2) mod 3
+        step(colw_c, Slot2{}, A, B, Cc, q);
+        step(colw_c, Slot0{}, B, Cc, A, q + 1);
+        step(colw_c, Slot1{}, Cc, A, B, q + 2);
+      }
+      if (q <= q_end) step(colw_c, Slot2{}, A, B, Cc, q);
+      if (q + 1 <= q_end) step(colw_c, Slot0{}, B, Cc, A, q + 1);
     }
-    if (q <= q_end) step(colw_c, Slot2{}, A, B, Cc, q);
-    if (q + 1 <= q_end) step(colw_c, Slot0{}, B, Cc, A, q + 1);
   };
   if (colw) march(std::true_type{});
   else march(std::false_type{});
@@ -910,6 +1163,12 @@ template <int MODE, int TY, int ABL = 0, bool FD = false, bool YM = false, bool 
 __global__ __launch_bounds__(kLanes*(TY + 4)) void k_pair8(PairArgs a, F3dGeo g, Pair8Cut cut, int ntx, int nty, int xcd_remap)
 {
   pair8_body<MODE, TY, ABL, FD, YM, false, FOLDS>(a, g, cut, ntx, nty, xcd_remap);
+}
+// the weights-first launch and the two sweeps that store flow + increments (PAIR_PS, PAIR_SSA): frame derivatives, z march
+template <int MODE, int TY, bool FOLDS>
+__global__ __launch_bounds__(kLanes*(TY + 4)) void k_wpair8(PairArgs a, F3dGeo g, Pair8Cut cut, int ntx, int nty, int xcd_remap)
+{
+  pair8_body<MODE, TY, 0, true, false, false, FOLDS>(a, g, cut, ntx, nty, xcd_remap);
 }
 // ... a tile without halo rows (thin volumes marched along y, all planes in the tile): TY + 2 waves and ~50 KB of LDS per workgroup, held to
 // 128 registers so that TWO workgroups share a CU (four waves per SIMD) -- a level of BASELINE config 3 is then spread over twice as
@@ -1003,31 +1262,38 @@ void launch_pair8(const PairArgs& args, const F3dGeo& g, int force_zchunk, int x
   if (force_zchunk > 0) cut = pair8_uniform_cut(tiles, planes, std::min(force_zchunk, zc_limit));   // F3D_ZCHUNK pins a uniform plan
   const dim3 grid(pair8_cut_grid(cut, xcd_remap), 1, 1), block(kLanes, TY + (TIGHT ? 2 : 4), 1);
   auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, f3d::stream(), a, g, cut, ntx, nty, xcd_remap); };
-  if constexpr (!YM) {
-    if (fold) return go(k_pair8<MODE, TY, 0, FD, false, true>);
-  }
-  if constexpr (YM && TIGHT) return go(k_pair8t<MODE, TY>);
-  else if constexpr (YM) return go(k_pair8<MODE, TY, 0, false, true>);
-  else if constexpr (FD) return go(k_pair8<MODE, TY, 0, true>);
-  else {
+  if constexpr (MODE == PAIR_PS || MODE == PAIR_SSA) {
+    static_assert(FD && !YM && !TIGHT, "k_wpair8");
+    if (fold) return go(k_wpair8<MODE, TY, true>);
+    return go(k_wpair8<MODE, TY, false>);
+  } else {
+    // (under `else`: a plain return above would still instantiate k_pair8<MODE, ...> for the two modes that have a kernel of their own)
+    if constexpr (!YM) {
+      if (fold) return go(k_pair8<MODE, TY, 0, FD, false, true>);
+    }
+    if constexpr (YM && TIGHT) return go(k_pair8t<MODE, TY>);
+    else if constexpr (YM) return go(k_pair8<MODE, TY, 0, false, true>);
+    else if constexpr (FD) return go(k_pair8<MODE, TY, 0, true>);
+    else {
 #ifdef F3D_LAB  // timing builds that skip parts of the work (WRONG results): only in lib/lab/libf3d_hip.so (make lab, tools/kbench.py
-                // --ablate); the shipped library has no switch that changes a result and no ABL != 0 instantiation
-    if constexpr (TY == 12) {
-      if (abl == 16) return go(k_pair8<MODE, TY, 16>);
-    }
-    if constexpr (MODE == PAIR_SS) {
-      if (abl == 1) return go(k_pair8<MODE, TY, 1>);
-      if (abl == 2) return go(k_pair8<MODE, TY, 2>);
-      if (abl == 3) return go(k_pair8<MODE, TY, 3>);
-      if (abl == 4) return go(k_pair8<MODE, TY, 4>);
-      if (abl == 8) return go(k_pair8<MODE, TY, 8>);
-      if (abl == 40) return go(k_pair8<MODE, TY, 40>);
-      if constexpr (TY <= 8) {
-        if (abl == 64) return go(k_pair8<MODE, TY, 64>);
+                  // --ablate); the shipped library has no switch that changes a result and no ABL != 0 instantiation
+      if constexpr (TY == 12) {
+        if (abl == 16) return go(k_pair8<MODE, TY, 16>);
       }
-    }
+      if constexpr (MODE == PAIR_SS) {
+        if (abl == 1) return go(k_pair8<MODE, TY, 1>);
+        if (abl == 2) return go(k_pair8<MODE, TY, 2>);
+        if (abl == 3) return go(k_pair8<MODE, TY, 3>);
+        if (abl == 4) return go(k_pair8<MODE, TY, 4>);
+        if (abl == 8) return go(k_pair8<MODE, TY, 8>);
+        if (abl == 40) return go(k_pair8<MODE, TY, 40>);
+        if constexpr (TY <= 8) {
+          if (abl == 64) return go(k_pair8<MODE, TY, 64>);
+        }
+      }
 #endif
-    go(k_pair8<MODE, TY, 0>);
+      go(k_pair8<MODE, TY, 0>);
+    }
   }
 }
 

@@ -47,6 +47,13 @@ bool FusedPhiKsiEnabled()
   return on;
 }
 
+bool WeightsFirstEnabled()
+{
+  // read per solve: the tests run both schedules in one process
+  const char* e = std::getenv("F3D_WEIGHTS_FIRST");
+  return !(e && e[0] == '0');
+}
+
 bool FrameDerivativesEnabled()
 {
   static const bool on = [] {

@@ -42,6 +42,9 @@ bool FusedPhiKsiEnabled();
 // default: measured on the MI355X it trades a seventh of the stage-1 arithmetic for a fifth more bytes through the loader and
 // comes out even; the launchers stay tested because they need 36 registers fewer.
 bool FrameDerivativesEnabled();
+// F3D_WEIGHTS_FIRST (default on; 0 = the schedule that ends an outer iteration in sweep + next phi/ksi): the resident solve operator
+// starts every outer iteration of a level on frame derivatives with the weights-first launch (host/solve_schedule.h)
+bool WeightsFirstEnabled();
 // small and mid-size levels: an outer iteration as (sweep, sweep, sweep) + (sweep, sweep, next phi/ksi) -- two launches instead of three
 bool ThreeStageLaunchesPay(size_t width, size_t height, size_t depth);
 

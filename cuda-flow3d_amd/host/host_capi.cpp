@@ -770,6 +770,19 @@ int f3d_plan_sweeps(int inner, int fused, int tri, int carry, int* sweeps, int* 
   return static_cast<int>(cut.size());
 }
 
+int f3d_plan_sweeps_weights_first(int inner, int* first, int* sweeps, int* weights_first, int* next_weights, int capacity)
+{
+  const std::vector<SweepLaunch> cut = CutSweepsWeightsFirst(inner);
+  if (static_cast<int>(cut.size()) > capacity || (!cut.empty() && (!first || !sweeps || !weights_first || !next_weights))) return -1;
+  for (size_t i = 0; i < cut.size(); ++i) {
+    first[i] = cut[i].first;
+    sweeps[i] = cut[i].sweeps;
+    weights_first[i] = cut[i].weights_first ? 1 : 0;
+    next_weights[i] = cut[i].next_weights ? 1 : 0;
+  }
+  return static_cast<int>(cut.size());
+}
+
 int f3d_pair8_plan(int width, int rows, int planes, int ty, int zc_limit, int per_round, int fold, long long* plan)
 {
   if (!plan || width < 1 || rows < 1 || planes < 1 || ty < 1 || zc_limit < 1) return 1;

@@ -21,6 +21,20 @@ extern "C" int f3d_solve_sweep_add(f3d_devptr frame_0, f3d_devptr frame_1, f3d_d
                                    size_t width, size_t height, size_t depth, float hx, float hy, float hz, float equation_alpha,
                                    f3d_devptr sum_u, f3d_devptr sum_v, f3d_devptr sum_w, const f3d_slab* slab) __attribute__((weak));
 
+// The weights-first launch and the two sweeps with the flow update (k_wpair8), weak for the same reason: without them the solve keeps
+// the schedule that ends an outer iteration in sweep + next phi/ksi.
+extern "C" int f3d_solve_phi_ksi_sweep_fd(f3d_devptr fx, f3d_devptr fy, f3d_devptr fz, f3d_devptr ft, f3d_devptr flow_u, f3d_devptr flow_v,
+                                          f3d_devptr flow_w, f3d_devptr flow_du, f3d_devptr flow_dv, f3d_devptr flow_dw, size_t width,
+                                          size_t height, size_t depth, float hx, float hy, float hz, float equation_alpha,
+                                          float equation_smoothness, float equation_data, f3d_devptr phi_out, f3d_devptr ksi_out,
+                                          f3d_devptr temp_du, f3d_devptr temp_dv, f3d_devptr temp_dw, const f3d_slab* slab)
+    __attribute__((weak));
+extern "C" int f3d_solve_sweep2_add_fd(f3d_devptr fx, f3d_devptr fy, f3d_devptr fz, f3d_devptr ft, f3d_devptr flow_u, f3d_devptr flow_v,
+                                       f3d_devptr flow_w, f3d_devptr flow_du, f3d_devptr flow_dv, f3d_devptr flow_dw, f3d_devptr phi,
+                                       f3d_devptr ksi, size_t width, size_t height, size_t depth, float hx, float hy, float hz,
+                                       float equation_alpha, f3d_devptr sum_u, f3d_devptr sum_v, f3d_devptr sum_w, const f3d_slab* slab)
+    __attribute__((weak));
+
 // ---- base ------------------------------------------------------------------------------------------------
 
 bool CudaOperationBase::IsInitialized() const
@@ -533,46 +547,70 @@ void CudaOperationSolve::Execute(OperationParameters& params)
                               dev_container_size_.pitch % 256 == 0 && EnsureDerivativeScratch() &&
                               !CheckDeviceError(f3d_frame_derivatives(dev_frame_0, dev_frame_1, w, h, d, hx, hy, hz, fder_[0], fder_[1],
                                                                       fder_[2], fder_[3], nullptr));
-  for (size_t i = 0; i < outer_iterations_count; ++i) {
-    if (!weights_ready &&
-        CheckDeviceError(f3d_phi_ksi(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, w, h, d,
-                                     hx, hy, hz, equation_smoothness, equation_data, phi_cur, ksi_cur, slab_)))
-      return;
-    weights_ready = false;
+  // Weights first (solve_schedule.h: CutSweepsWeightsFirst): on a level that reads frame derivatives every outer iteration starts
+  // with phi / ksi and its first sweep in one launch, the weights land in the caller's pair, and the level's last launch -- two sweeps
+  // or one -- can carry the flow update.  If the level's first launch declines, the level runs the other schedule.
+  // (on_derivatives implies the fused launches, no slab window and K >= 2: with one sweep per outer iteration a level stays on the frames)
+  bool weights_first = on_derivatives && WeightsFirstEnabled() && f3d_solve_phi_ksi_sweep_fd && f3d_solve_sweep2_add_fd;
+  const std::vector<SweepLaunch> cut_first = CutSweepsWeightsFirst(K);
+  enum { kDone, kFailed, kDeclined };
+  // one outer iteration on either schedule: the launches of its cut, one buffer swap per launch
+  auto iteration = [&](size_t i, bool first) -> int {
     const bool more = i + 1 < outer_iterations_count;
-    for (const SweepLaunch& launch : more ? cut_more : cut_last) {
+    // weights first: always the caller's pair, no hand-over between iterations
+    const DevicePtr phi_use = first ? dev_phi : phi_cur, ksi_use = first ? dev_ksi : ksi_cur;
+    if (!first && !weights_ready &&
+        CheckDeviceError(f3d_phi_ksi(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, w, h, d,
+                                     hx, hy, hz, equation_smoothness, equation_data, phi_use, ksi_use, slab_)))
+      return kFailed;
+    weights_ready = false;
+    for (const SweepLaunch& launch : first ? cut_first : more ? cut_more : cut_last) {
       const int group = launch.sweeps;
       const bool with_weights = launch.next_weights;
+      const bool last_launch = !more && launch.first + launch.sweeps == K;   // the last launch of the level
       int status;
-      if (group == 3)
-        status = f3d_solve_sweep3(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_cur, ksi_cur,
+      if (launch.weights_first) {
+        status = f3d_solve_phi_ksi_sweep_fd(fder_[0], fder_[1], fder_[2], fder_[3], dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr,
+                                            *dw_ptr, w, h, d, hx, hy, hz, equation_alpha, equation_smoothness, equation_data, phi_use,
+                                            ksi_use, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
+        if (status != 0 && i == 0) return kDeclined;   // the level's first launch: nothing has been launched or swapped yet
+      } else if (group == 3)
+        status = f3d_solve_sweep3(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_use, ksi_use,
                                   w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
       else if (group == 2 && with_weights)
-        status = f3d_solve_sweep2_phi_ksi(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_cur,
-                                          ksi_cur, w, h, d, hx, hy, hz, equation_alpha, equation_smoothness, equation_data, *tdu_ptr,
+        status = f3d_solve_sweep2_phi_ksi(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_use,
+                                          ksi_use, w, h, d, hx, hy, hz, equation_alpha, equation_smoothness, equation_data, *tdu_ptr,
                                           *tdv_ptr, *tdw_ptr, phi_nxt, ksi_nxt, slab_);
-      else if (group == 2 && on_derivatives)
-        status = f3d_solve_sweep2_fd(fder_[0], fder_[1], fder_[2], fder_[3], dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr,
-                                     *dw_ptr, phi_cur, ksi_cur, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
-      else if (group == 2)
-        status = f3d_solve_sweep2(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_cur,
-                                  ksi_cur, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
+      else if (group == 2 && on_derivatives) {
+        status = 1;
+        if (first && flow_update && last_launch) {   // weights first with an odd K: the level ends in two sweeps that carry the update
+          status = f3d_solve_sweep2_add_fd(fder_[0], fder_[1], fder_[2], fder_[3], dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr,
+                                           *dw_ptr, phi_use, ksi_use, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr,
+                                           slab_);
+          *flow_update = status == 0;
+        }
+        if (status != 0)
+          status = f3d_solve_sweep2_fd(fder_[0], fder_[1], fder_[2], fder_[3], dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr,
+                                       *dw_ptr, phi_use, ksi_use, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
+      } else if (group == 2)
+        status = f3d_solve_sweep2(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_use,
+                                  ksi_use, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
       else if (with_weights && on_derivatives)
         status = f3d_solve_sweep_phi_ksi_fd(fder_[0], fder_[1], fder_[2], fder_[3], dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr,
-                                            *dv_ptr, *dw_ptr, phi_cur, ksi_cur, w, h, d, hx, hy, hz, equation_alpha,
+                                            *dv_ptr, *dw_ptr, phi_use, ksi_use, w, h, d, hx, hy, hz, equation_alpha,
                                             equation_smoothness, equation_data, *tdu_ptr, *tdv_ptr, *tdw_ptr, phi_nxt, ksi_nxt, slab_);
       else if (with_weights)
         status = f3d_solve_sweep_phi_ksi(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr,
-                                         phi_cur, ksi_cur, w, h, d, hx, hy, hz, equation_alpha, equation_smoothness, equation_data,
+                                         phi_use, ksi_use, w, h, d, hx, hy, hz, equation_alpha, equation_smoothness, equation_data,
                                          *tdu_ptr, *tdv_ptr, *tdw_ptr, phi_nxt, ksi_nxt, slab_);
-      else if (flow_update && f3d_solve_sweep_add && !more && launch.first + 1 == K) {  // the last launch of the level, and it is one sweep
-        status = f3d_solve_sweep_add(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_cur,
-                                     ksi_cur, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
+      else if (flow_update && f3d_solve_sweep_add && last_launch) {  // the last launch of the level, and it is one sweep
+        status = f3d_solve_sweep_add(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_use,
+                                     ksi_use, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
         *flow_update = status == 0;
       } else
-        status = f3d_solve_sweep(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_cur,
-                                 ksi_cur, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
-      if (CheckDeviceError(status)) return;
+        status = f3d_solve_sweep(dev_frame_0, dev_frame_1, dev_flow_u, dev_flow_v, dev_flow_w, *du_ptr, *dv_ptr, *dw_ptr, phi_use,
+                                 ksi_use, w, h, d, hx, hy, hz, equation_alpha, *tdu_ptr, *tdv_ptr, *tdw_ptr, slab_);
+      if (CheckDeviceError(status)) return kFailed;
       std::swap(*du_ptr, *tdu_ptr);
       std::swap(*dv_ptr, *tdv_ptr);
       std::swap(*dw_ptr, *tdw_ptr);
@@ -582,6 +620,15 @@ void CudaOperationSolve::Execute(OperationParameters& params)
         weights_ready = true;
       }
     }
+    return kDone;
+  };
+  for (size_t i = 0; i < outer_iterations_count; ++i) {
+    int outcome = iteration(i, weights_first);
+    if (outcome == kDeclined) {
+      weights_first = false;
+      outcome = iteration(i, false);
+    }
+    if (outcome != kDone) return;
     if (!silent) {
       CheckDeviceError(f3d_stream_sync());
       const float complete = static_cast<float>(i + 1) / static_cast<float>(outer_iterations_count);

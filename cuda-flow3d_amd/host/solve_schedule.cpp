@@ -25,3 +25,16 @@ std::vector<SweepLaunch> CutSweeps(int K, bool fused, bool tri, bool carry)
   if (fused && carry && !cut.empty()) cut.back().next_weights = cut.back().sweeps == 1 || (tri && cut.back().sweeps == 2);
   return cut;
 }
+
+std::vector<SweepLaunch> CutSweepsWeightsFirst(int K)
+{
+  std::vector<SweepLaunch> cut;
+  if (K < 1) return cut;
+  cut.push_back({0, 1, false, true});
+  for (int first = 1; first < K;) {
+    const int sweeps = std::min(K - first, 2);
+    cut.push_back({first, sweeps, false, false});
+    first += sweeps;
+  }
+  return cut;
+}

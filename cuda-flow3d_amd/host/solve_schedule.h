@@ -17,6 +17,7 @@ struct SweepLaunch {
   int first;          // index of the launch's first sweep within the outer iteration
   int sweeps;         // 1, 2 or 3 sweeps in this launch
   bool next_weights;  // the launch also computes the phi / ksi of the NEXT outer iteration (into the second weight pair)
+  bool weights_first = false;  // the launch computes the phi / ksi of THIS outer iteration in front of its sweep (CutSweepsWeightsFirst)
 };
 
 // The K sweeps of ONE outer iteration (the same bit pattern whichever way they are cut), one buffer swap per launch:
@@ -30,5 +31,11 @@ struct SweepLaunch {
 // tri alone: a level of `outer` iterations makes outer - 1 hand-overs when CutSweeps(K, fused, tri, true) ends in a launch that
 // carries, and none otherwise.
 std::vector<SweepLaunch> CutSweeps(int K, bool fused, bool tri, bool carry);
+
+// The same K sweeps cut the other way, for a driver that has the weights-first launch: the first launch of EVERY outer iteration is
+// (P, S) -- the phi / ksi of this iteration and its first sweep --, then two sweeps per launch, then a single one for an even K.  No
+// launch takes the next weights along (they are made where they are used, into the caller's pair: no second pair, no swap parity), so
+// the cut is the same whether or not another outer iteration follows.  K < 1: empty.
+std::vector<SweepLaunch> CutSweepsWeightsFirst(int K);
 
 #endif

@@ -270,6 +270,24 @@ int f3d_solve_sweep_phi_ksi_edges_fd(f3d_devptr fx, f3d_devptr fy, f3d_devptr fz
                                      f3d_devptr temp_dv, f3d_devptr temp_dw, f3d_devptr phi_next, f3d_devptr ksi_next,
                                      const f3d_slab* slab, int keep_below, int keep_above);
 
+/* WEIGHTS FIRST: compute_phi_ksi_3d of an outer iteration AND its first solve_3d sweep in one launch (k_wpair8): phi_out / ksi_out
+ * receive what f3d_phi_ksi computes from flow_* and flow_d*, temp_d* what f3d_solve_sweep then computes with those weights -- bit for
+ * bit.  The weights are outputs only: the launch reads ten volumes and writes five.  Whole levels only.  The entry DECLINES -- status 1,
+ * f3d_last_error says why, nothing is launched or written -- on a slab window, on a level the fused launches march along y
+ * (f3d_fused_launches_march_along_y), on a container pitch that is not a multiple of 256 floats, on face weights that are not plain
+ * (the fused-entry restriction above) and when an output is also an input; the caller then takes f3d_phi_ksi and the sweeps. */
+int f3d_solve_phi_ksi_sweep_fd(f3d_devptr fx, f3d_devptr fy, f3d_devptr fz, f3d_devptr ft, f3d_devptr flow_u, f3d_devptr flow_v,
+                               f3d_devptr flow_w, f3d_devptr flow_du, f3d_devptr flow_dv, f3d_devptr flow_dw, size_t width, size_t height,
+                               size_t depth, float hx, float hy, float hz, float equation_alpha, float equation_smoothness,
+                               float equation_data, f3d_devptr phi_out, f3d_devptr ksi_out, f3d_devptr temp_du, f3d_devptr temp_dv,
+                               f3d_devptr temp_dw, const f3d_slab* slab);
+/* f3d_solve_sweep2_fd whose outputs receive flow_u + du'', flow_v + dv'', flow_w + dw'' (one binary32 add each): the last launch of a
+ * level with the flow update in it, the two-sweep counterpart of f3d_solve_sweep_add.  Declines as the entry above does. */
+int f3d_solve_sweep2_add_fd(f3d_devptr fx, f3d_devptr fy, f3d_devptr fz, f3d_devptr ft, f3d_devptr flow_u, f3d_devptr flow_v,
+                            f3d_devptr flow_w, f3d_devptr flow_du, f3d_devptr flow_dv, f3d_devptr flow_dw, f3d_devptr phi, f3d_devptr ksi,
+                            size_t width, size_t height, size_t depth, float hx, float hy, float hz, float equation_alpha, f3d_devptr sum_u,
+                            f3d_devptr sum_v, f3d_devptr sum_w, const f3d_slab* slab);
+
 /* registration_3d, 12 args: cuda_operation_registration.cpp:110-122; kernel src/kernels/registration_3d.cu:28-82.
  * output must not be frame_1 (every voxel gathers from other voxels of it; refused, as cuda_operation_registration.cpp:100-103 does).
  * output may be frame_0: a voxel reads only its own voxel of frame_0, before it writes, and the reference's operator allows it. */
@@ -356,6 +374,8 @@ int f3d_range_pop(void);
 
 enum { F3D_K_PHI_KSI = 0, F3D_K_SWEEP = 1, F3D_K_SWEEP2 = 2, F3D_K_SWEEP_PHI_KSI = 3, F3D_K_SWEEP3 = 4, F3D_K_SWEEP2_PHI_KSI = 5,
        F3D_K_COUNT = 6 };
+/* (id 3 is "a sweep and a phi/ksi in one launch", 92 algorithmic bytes per voxel, in either order: f3d_solve_sweep_phi_ksi* and
+ * f3d_solve_phi_ksi_sweep_fd; id 2 is two sweeps, f3d_solve_sweep2* and f3d_solve_sweep2_add_fd) */
 /* enable = 1 brackets every launch of the solver kernels (phi/ksi, one sweep, two fused sweeps) with events on the library stream */
 int f3d_prof_enable(int enable);
 int f3d_prof_reset(void);

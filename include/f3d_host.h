@@ -349,6 +349,11 @@ size_t f3d_piecemeal_budget_bytes(void);
  * driver can take its weights along.  Fills up to `capacity` launches: sweeps[i] = 1 .. 3 sweeps in launch i, next_weights[i] = 1
  * when it also writes the next phi / ksi; returns their number, or -1 if capacity is too small. */
 int f3d_plan_sweeps(int inner, int fused, int tri, int carry, int* sweeps, int* next_weights, int capacity);
+/* the weights-first cut of the same sweeps (the resident solve operator on levels that take f3d_solve_phi_ksi_sweep_fd): launch 0 is
+ * (phi/ksi of this outer iteration, sweep) -- weights_first[0] = 1 --, then two sweeps per launch, then one for an even `inner`; no
+ * launch writes the next weights.  first[i] = index of launch i's first sweep within the outer iteration (the operator finds the level's
+ * last launch by first + sweeps = inner).  Same return convention. */
+int f3d_plan_sweeps_weights_first(int inner, int* first, int* sweeps, int* weights_first, int* next_weights, int capacity);
 /* how a fused solver launch (k_pair8) of a level window is cut into workgroups (pure host arithmetic, csrc/f3d_pair8_plan.h; DESIGN.md
  * section 3, "Launch shapes"): the first A tiles in a chunks of zc_a planes each, the other tiles in b chunks of zc_b planes; A = 0 is
  * the uniform plan.  width, rows, planes: extents of the window; ty: rows per tile; zc_limit: planes a chunk may hold at most;

@@ -38,6 +38,8 @@ where a DMA instruction sits (every piece of a plane has at least one live lane 
       compute waves before it has landed);
   P5  no ds_read is reachable from the kernel entry without crossing a workgroup barrier (the prologue planes);
   P6  the hand-issued global_store_dword of the compute waves are followed by `s_waitcnt vmcnt(0)` before s_endpgm.
+k_wpair8 (the weights-first launch and the two sweeps with the flow update, the same skeleton): run_wpair8() applies P1 .. P6 with the
+pieces per plane computed here from 6 stencilled + 4 centre-only arrays (weights first) or 7 + 5, and reports VGPRs and LDS bytes.
 Usage: isa_hazards.py [file.s]   (without an argument the source is compiled with the product's flags)
 """
 import os
@@ -201,6 +203,59 @@ def tri_params(name):
 def tri_per_plane(ty):
     """DMA instructions per plane: ten inputs, ring rows y0-3 .. y0+TY+2 in pieces of four rows"""
     return 10 * ((ty + 6 + 3) // 4)
+
+
+# ---- k_wpair8: the weights-first launch and the two sweeps with the flow update (csrc/f3d_solve_pair8.h, PAIR_PS / PAIR_SSA) --------
+
+WPAIR8 = "k_wpair8"
+LDS_LIMIT = 160 * 1024
+
+
+def wpair8_params(name):
+    """(MODE, TY, FOLDS) from the mangled name ..k_wpair8ILi<MODE>ELi<TY>ELb<FOLDS>EE..; MODE 2 = weights first, 3 = two sweeps + flow"""
+    m = re.search(r"k_wpair8ILi(\d+)ELi(\d+)ELb([01])E", name)
+    return tuple(int(g) for g in m.groups()) if m else None
+
+
+def wpair8_arrays(mode):
+    """(stencilled, centre-only) inputs: weights first reads neither phi (stencilled) nor ksi (centre-only)"""
+    return (6, 4) if mode == 2 else (7, 5)
+
+
+def wpair8_per_plane(mode, ty):
+    """DMA instructions per plane of the three-slot ring: ring rows y0-2 .. y0+TY+1 in pieces of four rows, and the x-halo pieces"""
+    stencilled, _ = wpair8_arrays(mode)
+    nj = ty + 4
+    return stencilled * ((nj + 3) // 4) + (stencilled * 2 * nj + 63) // 64
+
+
+def wpair8_centre_per_plane(mode, ty):
+    """... of the two-slot centre-only ring.  Weights first: stage 1 of the halo rows and of the column wave is phi alone, which looks at
+    no centre-only value, so the ring holds the TY core rows and no halo columns; two sweeps + flow: as the frame-derivative k_pair8"""
+    _, centre = wpair8_arrays(mode)
+    if mode == 2:
+        return centre * ((ty + 3) // 4)
+    return centre * ((ty + 2 + 3) // 4) + (centre * 2 * ty + 63) // 64
+
+
+def run_wpair8(path=None):
+    """{kernel: violations} for every k_wpair8 instantiation (all of them ship) and {kernel: {scratch, vgprs, lds}}"""
+    path = path or compile_to_asm()
+    report, resources = {}, {}
+    cur = None
+    for line in open(path):
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            cur = m.group(1)
+        for key, field in (("ScratchSize", "scratch"), ("NumVgprs", "vgprs"), ("LDSByteSize", "lds")):
+            m = re.search(r";\s*%s:\s*(\d+)" % key, line)
+            if m and cur and WPAIR8 in cur:
+                resources.setdefault(cur, {})[field] = int(m.group(1))
+    for name, body in pair8_kernels(path, WPAIR8):
+        prm = wpair8_params(name)
+        if prm is not None:
+            report[name] = check_pair8(body, wpair8_per_plane(prm[0], prm[1]), wpair8_centre_per_plane(prm[0], prm[1]))
+    return report, resources
 
 
 def instructions(body):
@@ -482,7 +537,17 @@ if __name__ == "__main__":
     rep3, scratch3 = run_tri(asm)
     rep.update(rep3)
     scratch.update(scratch3)
+    repw, resw = run_wpair8(asm)
+    rep.update(repw)
+    scratch.update({k: v.get("scratch", 0) for k, v in resw.items()})
+    for name, r in resw.items():
+        print(f"{name}: {r.get('vgprs')} VGPRs, {r.get('lds')} bytes of LDS, {r.get('scratch')} bytes of scratch")
+        if r.get("lds", 0) > LDS_LIMIT or (wpair8_params(name) or (0, 0, 0))[1] == 12 and r.get("vgprs", 0) > 128:
+            print("    over the limit (160 KB of LDS per CU; 128 VGPRs for four waves per SIMD on 12-row tiles)")
     rc = 0
+    for name, r in resw.items():
+        if r.get("lds", 0) > LDS_LIMIT or ((wpair8_params(name) or (0, 0, 0))[1] == 12 and r.get("vgprs", 0) > 128):
+            rc = 1
     for name, bad in rep.items():
         print(f"{name}: {len(bad)} violation(s)")
         for b in bad[:20]:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark: times f3d_phi_ksi / f3d_solve_sweep on one W x H x D level with HIP events
 (f3d_prof_*), on random data.  Used for tuning and for the rocprofv3 / PMC runs whose summaries live in profiles/.
-   python tools/kbench.py [--size 512 | --dims W H D] [--reps 20] [--kernel sweep|sweep2|sweeppk|sweep2fd|sweeppkfd|sweep3|sweep2pk|tri|phi|both|bothfd|all]
-                          [--ablate N]
+   python tools/kbench.py [--size 512 | --dims W H D] [--reps 20] [--kernel sweep|sweep2|sweeppk|sweep2fd|sweeppkfd|pksweepfd|sweep2addfd|sweep3|sweep2pk|tri|phi|both|bothfd|all]
+                          [--ablate N] [--container-width FLOATS]
 --ablate N: timing-only builds of the solver kernels that skip parts of the work (WRONG results; N as described at k_pair8 / k_sweep7 /
 k_sweep6).  They exist only in the LAB library (make -C cuda-flow3d_amd lab -> lib/lab/), which this option loads instead of the
 product; the shipped library has no such switch.
@@ -25,6 +25,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--kernel", default="both")
     ap.add_argument("--ablate", type=int, default=0)
+    ap.add_argument("--container-width", type=int, default=0,
+                    help="width of the containers in floats (default: the level's; pksweepfd / sweep2addfd want a pitch that is a multiple of 256 floats)")
     a = ap.parse_args()
     if a.ablate:
         lab = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cuda-flow3d_amd", "lib", "lab")
@@ -36,7 +38,7 @@ def main():
     W, H, D = a.dims if a.dims else (a.size,) * 3
     pkg = importlib.import_module("cuda-flow3d_amd")
     hip = pkg.hip()
-    cont = pkg.Containers(W, H, D)
+    cont = pkg.Containers(max(W, a.container_width), H, D)
     rng = np.random.default_rng(1)
     plane = lambda lo, hi: rng.uniform(lo, hi, size=(1, H, W)).astype(np.float32)
     ptr = []
@@ -70,6 +72,10 @@ def main():
             pkg.check(hip.f3d_solve_sweep2_fd(*fd, *ptr[2:], phi, ksi, W, H, D, *h, 7.5, *out, None))
         if a.kernel in ("sweeppkfd", "bothfd", "all"):
             pkg.check(hip.f3d_solve_sweep_phi_ksi_fd(*fd, *ptr[2:], phi, ksi, W, H, D, *h, 7.5, 0.001, 0.001, *out, phi2, ksi2, None))
+        if a.kernel == "pksweepfd":      # weights first: phi/ksi + the sweep (kernel id 3, like sweeppk: a sweep and a phi/ksi)
+            pkg.check(pkg.solve_phi_ksi_sweep_fd_entry()(*fd, *ptr[2:], W, H, D, *h, 7.5, 0.001, 0.001, phi2, ksi2, *out, None))
+        if a.kernel == "sweep2addfd":    # two sweeps that store flow + increments (kernel id 2)
+            pkg.check(pkg.solve_sweep2_add_fd_entry()(*fd, *ptr[2:], phi, ksi, W, H, D, *h, 7.5, *out, None))
         if a.kernel in ("sweep3", "tri"):
             pkg.check(hip.f3d_solve_sweep3(*ptr, phi, ksi, W, H, D, *h, 7.5, *out, None))
         if a.kernel in ("sweep2pk", "tri"):

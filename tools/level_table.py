@@ -5,11 +5,11 @@ The drivers launch exactly one warp (`k_warp`) per level and rank, so dispatches
 every `--warps-per-level`-th `k_warp` (1 for the resident driver, the rank count for the one-process z-slab driver); the solves
 of a trace are told apart by the level counter wrapping at --levels.  Prints a table and writes JSON:
   python3 tools/level_table.py trace.csv [--warps-per-level 8] [--levels 40] [--skip-solves 1] [--out file.json]
-Columns: microseconds per level of the two-sweep launches (k_pair8<0>), sweep + next phi/ksi (k_pair8<1>), phi/ksi alone,
-one sweep, everything else; `n` = solver launches."""
+Columns: microseconds per level of the two-sweep launches (k_pair8<0>, k_wpair8<3>), sweep + next phi/ksi (k_pair8<1>), phi/ksi + sweep
+(k_wpair8<2>), phi/ksi alone, one sweep, everything else; `n` = solver launches."""
 import argparse, collections, csv, json, sys
 
-CLASSES = (("k_pair8<0", "pair_ss"), ("k_pair8<1", "pair_sp"), ("k_pair8t<0", "pair_ss"), ("k_pair8t<1", "pair_sp"), ("k_phiksi6", "phi_ksi"), ("k_sweep6", "sweep"), ("k_sweep7", "pair7"))
+CLASSES = (("k_wpair8<2", "pair_ps"), ("k_wpair8<3", "pair_ss"), ("k_pair8<0", "pair_ss"), ("k_pair8<1", "pair_sp"), ("k_pair8t<0", "pair_ss"), ("k_pair8t<1", "pair_sp"), ("k_phiksi6", "phi_ksi"), ("k_sweep6", "sweep"), ("k_sweep7", "pair7"))
 
 
 def classify(name):
@@ -67,10 +67,10 @@ def main():
     a = ap.parse_args()
     table, n = levels_of(a.trace, a.warps_per_level, a.levels, a.skip_solves)
     print(f"# {a.trace}: {n} solve(s) averaged; level 0 = coarsest")
-    print("| level | pair SS us | pair SP us | phi/ksi us | sweep us | other us | total us | solver launches |")
-    print("|---|---|---|---|---|---|---|---|")
+    print("| level | pair SS us | pair SP us | pair PS us | phi/ksi us | sweep us | other us | total us | solver launches |")
+    print("|---|---|---|---|---|---|---|---|---|")
     for r in table:
-        print(f"| {r['level_index']} | {r['pair_ss_us']} | {r['pair_sp_us']} | {r['phi_ksi_us']} | {r['sweep_us']} | "
+        print(f"| {r['level_index']} | {r['pair_ss_us']} | {r['pair_sp_us']} | {r['pair_ps_us']} | {r['phi_ksi_us']} | {r['sweep_us']} | "
               f"{round(r['other_us'] + r['pair7_us'], 1)} | {r['total_us']} | {r['solver_launches']} |")
     if a.out:
         json.dump({"trace": a.trace, "solves": n, "levels": table}, open(a.out, "w"), indent=1)
