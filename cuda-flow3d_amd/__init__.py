@@ -159,6 +159,24 @@ class SplitInfo(C.Structure):  # f3d_split_info: f3d_component_info of the final
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class HistogramInfo(C.Structure):  # f3d_histogram_info: every voxel of the volume in exactly one counter, tried in this order
+    _fields_ = [(name, C.c_ulonglong) for name in ("masked", "nan", "below", "above", "used")]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RangeInfo(C.Structure):  # f3d_range_info: every voxel of the volume in exactly one counter, tried in this order
+    _fields_ = [(name, C.c_ulonglong) for name in ("masked", "nan", "infinite", "finite")]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class OtsuInfo(C.Structure):  # f3d_otsu_info
+    _fields_ = [("status", C.c_int), ("populations", C.c_ulonglong * 3), ("objective", C.c_double)]
+
+
 class NearestInfo(C.Structure):  # f3d_nearest_info
     _fields_ = [(name, C.c_ulonglong) for name in ("seeds", "d2_max", "unreached")]
 
@@ -382,6 +400,10 @@ def host():
         "f3d_flow_labels_split": [C.c_void_p, _dp, C.c_float, C.c_float, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.POINTER(C.c_ulonglong)),
                                   C.POINTER(_sz), C.POINTER(SplitInfo)],
         "f3d_flow_labels_end": [C.c_void_p], "f3d_flow_labels_download": [C.c_void_p, C.POINTER(C.c_int)],
+        "f3d_histogram_edge": [C.c_float, C.c_float, _sz, _sz, _fp],
+        "f3d_otsu": [C.POINTER(C.c_ulonglong), _sz, C.c_int, C.POINTER(C.c_uint), C.POINTER(OtsuInfo)],
+        "f3d_histogram_rank": [C.POINTER(C.c_ulonglong), _sz, C.c_ulonglong, C.POINTER(C.c_uint)],
+        "f3d_flow_histogram": [C.c_void_p, _dp, _fp, _sz, C.POINTER(C.c_ulonglong), C.POINTER(HistogramInfo), _fp, _fp],
         "f3d_flow_validate_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_float, C.c_uint, C.c_uint, C.c_uint, C.c_float,
                                       C.POINTER(_fp), C.POINTER(ValidateStats)],
         "f3d_flow_validate_end": [C.c_void_p],
@@ -598,6 +620,16 @@ def _contacts_entry():
 def _components_entry():
     return _entry("f3d_label_components", [_dp, C.c_float, C.c_float, C.c_ulonglong, _dp] + [_sz] * 3 +
                   [C.POINTER(C.c_ulonglong), _sz, C.POINTER(ComponentInfo)], "label the connected bodies of a thresholded volume")
+
+
+def _histogram_entry():
+    return _entry("f3d_histogram", [_dp, _dp, C.c_float, C.c_float] + [_sz] * 4 + [C.POINTER(C.c_ulonglong), C.POINTER(HistogramInfo)],
+                  "count the grey values of a volume")
+
+
+def _value_range_entry():
+    return _entry("f3d_value_range", [_dp, _dp] + [_sz] * 3 + [_fp, _fp, C.POINTER(RangeInfo)],
+                  "find the finite minimum and maximum of a volume")
 
 
 def _nearest_entry():
@@ -1251,6 +1283,140 @@ def label_components(volume, lo=-np.inf, hi=np.inf, min_voxels=1):
                   "f3d_label_components")
         labels = box.download(out, dims).view(np.int32)
     return Components(labels, sizes, info.as_dict())
+
+
+MAX_BINS = 4096
+OTSU_OK, OTSU_DEGENERATE = 0, 1
+OTSU_TOKENS = {"otsu": (2, 0), "otsu1": (3, 0), "otsu2": (3, 1)}    # what OpticalFlow.segment takes for lo or hi: (classes, which cut)
+
+
+def _bins(bins):
+    if int(bins) != bins or not 1 <= int(bins) <= MAX_BINS:
+        raise ValueError(f"bins must be an integer in 1 .. {MAX_BINS}, not {bins}")
+    return int(bins)
+
+
+def _bin_range(value_range):
+    """(lo, hi) as float32 values of a (lo, hi) pair: both finite, lo < hi"""
+    try:
+        lo, hi = value_range
+        lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    except (TypeError, ValueError):
+        raise ValueError(f"range must be a pair (lo, hi) of numbers, not {value_range!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"range must be finite with lo < hi, not ({lo}, {hi})")
+    return lo, hi
+
+
+class Otsu:
+    """The Otsu cuts of a Histogram: .status (OTSU_OK, or OTSU_DEGENERATE when fewer bins are occupied than classes: cuts and values are
+    then empty), .cuts (the first bin of every class but the lowest), .values (float32: the edge of each cut, so that class j is
+    values[j - 1] <= s < values[j]), .populations (uint64, the voxels of every class) and .objective."""
+
+    def __init__(self, status, cuts, values, populations, objective):
+        self.status, self.cuts, self.values, self.populations, self.objective = status, cuts, values, populations, objective
+
+
+class Histogram:
+    """The grey-value histogram of a volume (histogram, OpticalFlow.histogram): .counts (uint64 [bins]), .lo and .hi (the float32 bounds
+    the bins are laid over), .info (the dict of f3d_histogram_info; info["used"] == counts.sum()) and .bins.  The bin rule is
+    include/f3d.h's; edge, otsu, rank and quantile are the exact host functions of include/f3d_host.h."""
+
+    def __init__(self, counts, lo, hi, info):
+        self.counts, self.lo, self.hi, self.info = counts, float(lo), float(hi), info
+        self.bins = len(counts)
+
+    def _counts(self):
+        counts = np.ascontiguousarray(self.counts, dtype=np.uint64)
+        return counts, counts.ctypes.data_as(C.POINTER(C.c_ulonglong))
+
+    def edge(self, k):
+        """the smallest float32 value whose bin is at least k: label_components(volume, lo=h.edge(k), hi=h.hi) has counts[k:].sum()
+        foreground voxels"""
+        edge = C.c_float()
+        _host_check(host().f3d_histogram_edge(self.lo, self.hi, self.bins, int(k), C.byref(edge)), "f3d_histogram_edge")
+        return np.float32(edge.value)
+
+    def otsu(self, classes=2):
+        if classes not in (2, 3):
+            raise ValueError(f"classes must be 2 or 3, not {classes}")
+        counts, ptr = self._counts()
+        cuts, info = (C.c_uint * 2)(), OtsuInfo()
+        _host_check(host().f3d_otsu(ptr, self.bins, classes, cuts, C.byref(info)), "f3d_otsu")
+        if info.status != OTSU_OK:
+            return Otsu(info.status, np.zeros(0, np.uint32), np.zeros(0, np.float32), np.zeros(classes, np.uint64), 0.0)
+        found = np.array(cuts[:classes - 1], np.uint32)
+        return Otsu(info.status, found, np.array([self.edge(k) for k in found], np.float32),
+                    np.array(info.populations[:classes], np.uint64), info.objective)
+
+    def rank(self, r):
+        """the bin that holds the r-th smallest counted voxel (0-based)"""
+        if int(r) != r or not 0 <= int(r) < 2 ** 64:
+            raise ValueError(f"r must be a non-negative integer, not {r}")
+        counts, ptr = self._counts()
+        found = C.c_uint()
+        _host_check(host().f3d_histogram_rank(ptr, self.bins, int(r), C.byref(found)), "f3d_histogram_rank")
+        return found.value
+
+    def quantile(self, q):
+        """the bin of rank floor(q * (used - 1)), q in [0, 1]"""
+        used = int(np.asarray(self.counts, np.uint64).sum())
+        if not 0 <= q <= 1:
+            raise ValueError(f"q must lie in [0, 1], not {q}")
+        if used == 0:
+            raise ValueError("the histogram is empty: it has no quantile")
+        return self.rank(int(np.floor(q * (used - 1))))
+
+
+@contextlib.contextmanager
+def _volume_and_mask(volume, mask):
+    """volume (and mask, an integer or bool [z, y, x] volume of its shape, or None) in containers of their own: yields
+    (source pointer, mask pointer or 0, (w, h, d)) with the container geometry set"""
+    volume = np.asarray(volume)
+    if volume.ndim != 3 or volume.size == 0:
+        raise ValueError("volume must be a non-empty [z, y, x] volume")
+    vols = [volume]
+    if mask is not None:
+        bits = _int32_bits(mask, "mask")
+        if bits.shape != volume.shape:
+            raise ValueError(f"mask must have the shape of the volume, {volume.shape}")
+        vols.append(bits)
+    with _on_device(vols, "volume must be a [z, y, x] volume") as (box, p, dims):
+        box.set_current()
+        yield p[0], (p[1] if mask is not None else 0), dims
+
+
+def value_range(volume, mask=None):
+    """The smallest and the largest finite value of a volume on the device (include/f3d.h, f3d_value_range): volume numpy [z, y, x]
+    float32, mask an integer volume whose zeros leave voxels out.  Returns (min, max, info): float32 values (+inf and -inf when nothing
+    is finite; -0.0 is below +0.0) and the dict of f3d_range_info."""
+    fn = _value_range_entry()
+    with _volume_and_mask(volume, mask) as (src, msk, dims):
+        lo, hi, info = C.c_float(), C.c_float(), RangeInfo()
+        check(fn(src, msk, *dims, C.byref(lo), C.byref(hi), C.byref(info)), "f3d_value_range")
+    return np.float32(lo.value), np.float32(hi.value), info.as_dict()
+
+
+def histogram(volume, bins=256, range=None, mask=None):
+    """The grey-value histogram of a volume on the device (include/f3d.h, f3d_histogram): bins 1 .. 4096 laid over range = (lo, hi), or
+    over the volume's finite minimum and maximum under the mask when range is None (ValueError when there is no finite voxel or only
+    one value).  mask: an integer volume whose zeros leave voxels out.  Returns a Histogram."""
+    fn, bins = _histogram_entry(), _bins(bins)
+    bounds = None if range is None else _bin_range(range)
+    find = _value_range_entry() if bounds is None else None
+    with _volume_and_mask(volume, mask) as (src, msk, dims):
+        if bounds is None:
+            lo, hi, found = C.c_float(), C.c_float(), RangeInfo()
+            check(find(src, msk, *dims, C.byref(lo), C.byref(hi), C.byref(found)), "f3d_value_range")
+            if found.finite == 0:
+                raise ValueError("the volume has no finite voxel: there is no range to lay the bins over")
+            if not lo.value < hi.value:
+                raise ValueError(f"the volume is constant ({lo.value}): there is no range to lay the bins over")
+            bounds = (lo.value, hi.value)
+        counts, info = np.zeros(bins, np.uint64), HistogramInfo()
+        check(fn(src, msk, bounds[0], bounds[1], bins, *dims, counts.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(info)),
+              "f3d_histogram")
+    return Histogram(counts, bounds[0], bounds[1], info.as_dict())
 
 
 # the modes, the flag and the outputs of f3d_nearest_seed in ABI order
@@ -2122,11 +2288,47 @@ class OpticalFlow:
         """free the containers of the per-label residual and of the labels (destroy() does too)"""
         _host_check(host().f3d_flow_label_motion_end(self._h), "f3d_flow_label_motion_end")
 
-    def segment(self, lo=-np.inf, hi=np.inf, min_voxels=27, split=None):
+    def histogram(self, bins=256, range=None):
+        """The grey-value histogram of the resident frame 0, the frame segment() thresholds (include/f3d_host.h, f3d_flow_histogram): a
+        Histogram over range = (lo, hi), or over the frame's finite minimum and maximum when range is None."""
+        bins = _bins(bins)
+        bounds = None if range is None else (C.c_float * 2)(*_bin_range(range))
+        counts, info, lo, hi = np.zeros(bins, np.uint64), HistogramInfo(), C.c_float(), C.c_float()
+        _host_check(host().f3d_flow_histogram(self._h, 0, bounds, bins, counts.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(info),
+                                              C.byref(lo), C.byref(hi)), "f3d_flow_histogram")
+        return Histogram(counts, lo.value, hi.value, info.as_dict())
+
+    def _otsu_bounds(self, lo, hi, bins, value_range):
+        """lo and hi of segment() with the strings of OTSU_TOKENS replaced: on the lo side by the edge e of the cut (s >= e), on the hi
+        side by the largest float32 below it (s < e)"""
+        tokens = [b for b in (lo, hi) if isinstance(b, str)]
+        if not tokens:
+            return lo, hi
+        for t in tokens:
+            if t not in OTSU_TOKENS:
+                raise ValueError(f"lo and hi must be numbers or one of {sorted(OTSU_TOKENS)}, not {t!r}")
+        classes = {OTSU_TOKENS[t][0] for t in tokens}
+        if len(classes) != 1:
+            raise ValueError("'otsu' is the cut of two classes, 'otsu1' and 'otsu2' are the cuts of three: they cannot be mixed")
+        if len(tokens) == 2 and OTSU_TOKENS[lo][1] >= OTSU_TOKENS[hi][1]:
+            raise ValueError(f"lo {lo!r} is above hi {hi!r}")
+        found = self.histogram(bins, value_range).otsu(classes.pop())
+        if found.status != OTSU_OK:
+            raise F3dError("segment: fewer bins of the frame's histogram are occupied than classes: there is no Otsu cut")
+        if isinstance(lo, str):
+            lo = found.values[OTSU_TOKENS[lo][1]]
+        if isinstance(hi, str):
+            hi = np.nextafter(found.values[OTSU_TOKENS[hi][1]], np.float32(-np.inf))
+        return lo, hi
+
+    def segment(self, lo=-np.inf, hi=np.inf, min_voxels=27, split=None, bins=256, value_range=None):
         """The connected bodies of the resident frame 0 (the raw frame of the last upload()), labelled on the device and left there: a
         Components, after which label_motion(None, ..., n_labels=c.n_labels) and contacts(None, n_labels=c.n_labels) run on these
         bodies.  lo, hi, min_voxels as in label_components.  split: None, or the core_d2 of split_components (an integer of at least 1,
-        e.g. ceil(radius^2)), which takes touching bodies apart; the info is then that of f3d_split_info."""
+        e.g. ceil(radius^2)), which takes touching bodies apart; the info is then that of f3d_split_info.  lo or hi may also be "otsu"
+        (the cut of two classes) or "otsu1" / "otsu2" (the lower and upper cut of three) of histogram(bins, value_range): as lo the
+        foreground starts at the cut, as hi it ends below it."""
+        lo, hi = self._otsu_bounds(lo, hi, bins, value_range)
         lo, hi, min_voxels = _component_range(lo, hi, min_voxels)
         w, h, d = self.dims
         sizes, count = C.POINTER(C.c_ulonglong)(), _sz(0)

@@ -15,6 +15,7 @@
 #include "optical_flow_p.h"
 #include "optical_flow_slab.h"
 #include "synth.h"
+#include "threshold_select.h"
 #include "../csrc/f3d_pair8_plan.h"
 
 struct f3d_flow_s {
@@ -503,6 +504,38 @@ int f3d_flow_labels_download(f3d_flow flow, int* labels)
   g_host_error.clear();
   if (!flow || !labels) return HostFail("f3d_flow_labels_download: null argument");
   if (!flow->driver.DownloadLabels(labels)) return HostFail(flow->driver.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  return 0;
+}
+
+int f3d_histogram_edge(float lo, float hi, size_t bins, size_t k, float* edge)
+{
+  g_host_error.clear();
+  std::string why;
+  return HistogramEdge(lo, hi, bins, k, edge, &why) ? 0 : HostFail(("f3d_histogram_edge: " + why).c_str());
+}
+
+int f3d_otsu(const unsigned long long* counts, size_t bins, int classes, unsigned* cuts, f3d_otsu_info* info)
+{
+  g_host_error.clear();
+  std::string why;
+  return OtsuCuts(counts, bins, classes, cuts, info, &why) ? 0 : HostFail(("f3d_otsu: " + why).c_str());
+}
+
+int f3d_histogram_rank(const unsigned long long* counts, size_t bins, unsigned long long r, unsigned* bin)
+{
+  g_host_error.clear();
+  std::string why;
+  return HistogramRank(counts, bins, r, bin, &why) ? 0 : HostFail(("f3d_histogram_rank: " + why).c_str());
+}
+
+int f3d_flow_histogram(f3d_flow flow, f3d_devptr frame, const float* range, size_t bins, unsigned long long* counts,
+                       f3d_histogram_info* info, float* lo_used, float* hi_used)
+{
+  g_host_error.clear();
+  if (!flow || !counts || !info) return HostFail("f3d_flow_histogram: null argument");
+  OpticalFlowE& d = flow->driver;
+  if (!d.ComputeHistogram(frame, range, bins, counts, info, lo_used, hi_used))
+    return HostFail(d.DerivedError(OpticalFlowE::kLabelMotion).c_str());
   return 0;
 }
 

@@ -16,6 +16,7 @@
 //                [--labels FILE --contacts [--contact-min-faces K]]
 //                [--segment LO:HI [--segment-min-voxels K]]
 //                [--segment-split R | --segment-split-d2 N]
+//                [--segment otsu|otsu1|otsu2 on either side of the colon] [--segment-bins B] [--segment-range A:B] [--histogram]
 // More than two frames make a sequence: the driver, its containers and operators are set up once (the reference does
 // Initialize / Destroy per pair, src/main.cpp:150,184) and the flow of every consecutive pair is written as
 // <prefix>_<k>_flow-{u,v,w}-W-H-D.raw.  --partial runs the out-of-core driver (the reference's use_partial_gpu branch,
@@ -91,6 +92,13 @@
 // --segment-split R (or --segment-split-d2 N, the exact form: N = ceil(R^2)) takes touching bodies apart (f3d_split_components): the
 // cores are the foreground voxels at least R voxels deep below the surface, and every foreground voxel goes to the nearest core of its
 // connected body.  Same files; the line that sums up gains what the split found.  Only with --segment.
+// Either side of --segment LO:HI may be a token instead of a number: otsu is the cut of two classes, otsu1 and otsu2 the lower and the
+// upper cut of three (f3d_histogram of frame 0 on the device, f3d_otsu and f3d_histogram_edge on the host).  On the LO side a token
+// stands for the float32 edge e of the cut bin, so the foreground is s >= e; on the HI side for the largest float below e, so it is
+// s < e: otsu1:otsu2 is exactly the middle phase, and :otsu and otsu: partition the voxels inside the range.  --segment-bins B (1 ..
+// 4096, default 256) and --segment-range A:B (default: the finite minimum and maximum of frame 0) lay the bins; one line says what was
+// chosen and the run goes on exactly as if the numbers had been given.  --histogram, alone or with --segment, writes
+// <tag>_histogram.csv (bin, lower edge with %.9g, count) and prints one line.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -125,7 +133,9 @@ static void Usage()
               "              [--labels FILE --label-motion translation|rigid|affine [--label-min-voxels K]]\n"
               "              [--labels FILE --contacts [--contact-min-faces K]]\n"
               "              [--segment LO:HI [--segment-min-voxels K]]\n"
-              "              [--segment-split R | --segment-split-d2 N]\n");
+              "              [--segment-split R | --segment-split-d2 N]\n"
+              "              [--segment with otsu, or otsu1 / otsu2, in place of LO or HI] [--segment-bins B] [--segment-range A:B]\n"
+              "              [--histogram]\n");
 }
 
 int main(int argc, char** argv)
@@ -169,6 +179,12 @@ int main(int argc, char** argv)
   float segment_lo = -INFINITY, segment_hi = INFINITY;
   unsigned long long segment_min_voxels = 27;
   bool segment_min_given = false;
+  int segment_token[2] = {0, 0};   // what stands for LO and for HI: 0 a number, 1 otsu, 2 otsu1, 3 otsu2
+  size_t segment_bins = 256;       // --segment-bins B
+  bool segment_bins_given = false;
+  float segment_range[2] = {0.f, 0.f};  // --segment-range A:B
+  bool segment_range_given = false;
+  bool histogram = false;          // --histogram
   int segment_split_given = 0;            // --segment-split R and --segment-split-d2 N, counted
   unsigned long long segment_core_d2 = 0;  // 0: no split
   const unsigned inverse_iterations = 32;
@@ -436,10 +452,28 @@ int main(int argc, char** argv)
       const std::string side[2] = {range.substr(0, colon), range.substr(colon + 1)};
       float bound[2] = {-INFINITY, INFINITY};
       for (int k = 0; k < 2; ++k) {
+        segment_token[k] = 0;
         if (side[k].empty()) continue;
+        // a token stands for a cut of frame 0's histogram; the bound stays open until the frame is there
+        if (side[k] == "otsu" || side[k] == "otsu1" || side[k] == "otsu2") {
+          segment_token[k] = side[k] == "otsu" ? 1 : side[k] == "otsu1" ? 2 : 3;
+          continue;
+        }
         char* rest = nullptr;
         bound[k] = std::strtof(side[k].c_str(), &rest);
         if (rest == side[k].c_str() || *rest || bound[k] != bound[k]) { Usage(); return 64; }
+      }
+      if (segment_token[0] && segment_token[1]) {
+        if ((segment_token[0] == 1) != (segment_token[1] == 1)) {
+          std::printf("--segment %s: otsu is the cut of two classes, otsu1 and otsu2 are the cuts of three: they cannot be mixed\n", range.c_str());
+          Usage();
+          return 64;
+        }
+        if (segment_token[0] >= segment_token[1]) {  // HI stands for the largest value below its cut
+          std::printf("--segment %s: LO is above HI\n", range.c_str());
+          Usage();
+          return 64;
+        }
       }
       if (bound[0] > bound[1]) {
         std::printf("--segment %s: LO is above HI\n", range.c_str());
@@ -450,6 +484,34 @@ int main(int argc, char** argv)
       segment_lo = bound[0];
       segment_hi = bound[1];
     }
+    else if (a == "--segment-bins") {
+      need(1);
+      char* rest = nullptr;
+      const unsigned long long b = std::strtoull(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest || argv[i][0] == '-' || b < 1 || b > 4096) { Usage(); return 64; }
+      segment_bins = static_cast<size_t>(b);
+      segment_bins_given = true;
+    }
+    else if (a == "--segment-range") {
+      need(1);
+      // A:B, both finite numbers with A < B
+      const std::string range = argv[++i];
+      const size_t colon = range.find(':');
+      if (colon == std::string::npos || range.find(':', colon + 1) != std::string::npos) { Usage(); return 64; }
+      const std::string side[2] = {range.substr(0, colon), range.substr(colon + 1)};
+      for (int k = 0; k < 2; ++k) {
+        char* rest = nullptr;
+        segment_range[k] = std::strtof(side[k].c_str(), &rest);
+        if (side[k].empty() || rest == side[k].c_str() || *rest || !std::isfinite(segment_range[k])) { Usage(); return 64; }
+      }
+      if (!(segment_range[0] < segment_range[1])) {
+        std::printf("--segment-range %s: A must be below B\n", range.c_str());
+        Usage();
+        return 64;
+      }
+      segment_range_given = true;
+    }
+    else if (a == "--histogram") histogram = true;
     else if (a == "--segment-min-voxels") {
       need(1);
       char* rest = nullptr;
@@ -592,6 +654,17 @@ int main(int argc, char** argv)
   }
   if (segment_split_given > 1 || (segment_split_given && (!segment || !labels_file.empty()))) {
     std::printf("--segment-split R and --segment-split-d2 N are two forms of one option: give one, and only with --segment\n");
+    Usage();
+    return 64;
+  }
+  if ((segment_bins_given || segment_range_given) && !segment_token[0] && !segment_token[1] && !histogram) {
+    std::printf("--segment-bins and --segment-range lay the bins of a histogram: they need otsu, otsu1 or otsu2 in --segment, or --histogram\n");
+    Usage();
+    return 64;
+  }
+  if (histogram && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--histogram needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
     Usage();
     return 64;
   }
@@ -1158,6 +1231,78 @@ int main(int argc, char** argv)
   // --segment: the labels of frame 0, made while the first pair is resident and before anything reads labels.  0: fine; otherwise
   // the exit status.
   auto segment_frame_0 = [&]() {
+    const std::string tag_0 = pairs > 1 ? prefix + "_0" : prefix;
+    if (histogram || segment_token[0] || segment_token[1]) {
+      std::vector<unsigned long long> counts(segment_bins);
+      f3d_histogram_info counted = {};
+      float range_lo = 0.f, range_hi = 0.f;
+      if (!optical_flow_e.ComputeHistogram(0, segment_range_given ? segment_range : nullptr, segment_bins, counts.data(), &counted, &range_lo,
+                                           &range_hi)) {
+        std::printf("Error: %s\n", optical_flow_e.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+        return 3;
+      }
+      const double a = static_cast<double>(range_lo), b = static_cast<double>(range_hi);
+      if (histogram) {
+        std::FILE* csv = std::fopen((tag_0 + "_histogram.csv").c_str(), "w");
+        if (csv) {
+          std::fprintf(csv, "bin,lower_edge,count\n");
+          for (size_t k = 0; k < segment_bins; ++k) {
+            float edge = 0.f;
+            if (f3d_histogram_edge(range_lo, range_hi, segment_bins, k, &edge)) {
+              std::printf("Error: %s\n", f3d_host_last_error());
+              std::fclose(csv);
+              return 3;
+            }
+            std::fprintf(csv, "%zu,%.9g,%llu\n", k, static_cast<double>(edge), counts[k]);
+          }
+        }
+        const bool csv_error = csv && std::ferror(csv) != 0;
+        if (!csv || std::fclose(csv) != 0 || csv_error) {
+          std::printf("Error: cannot write %s_histogram.csv\n", tag_0.c_str());
+          return 2;
+        }
+        std::printf("histogram frame 0: %zu bins of [%.9g, %.9g]: %llu voxels counted, %llu NaN, %llu outside the range\n", segment_bins, a, b,
+                    counted.used, counted.nan, counted.below + counted.above);
+      }
+      if (segment_token[0] || segment_token[1]) {
+        const int classes = (segment_token[0] == 1 || segment_token[1] == 1) ? 2 : 3;
+        unsigned cuts[2] = {0, 0};
+        f3d_otsu_info chosen = {};
+        if (f3d_otsu(counts.data(), segment_bins, classes, cuts, &chosen)) {
+          std::printf("Error: %s\n", f3d_host_last_error());
+          return 3;
+        }
+        if (chosen.status != F3D_OTSU_OK) {
+          std::printf("Error: --segment otsu: fewer than %d of the %zu bins of [%.9g, %.9g] are occupied (%llu voxels counted): there is no "
+                      "cut of %d classes\n", classes, segment_bins, a, b, counted.used, classes);
+          return 3;
+        }
+        float edges[2] = {0.f, 0.f};
+        for (int j = 0; j < classes - 1; ++j)
+          if (f3d_histogram_edge(range_lo, range_hi, segment_bins, cuts[j], &edges[j])) {
+            std::printf("Error: %s\n", f3d_host_last_error());
+            return 3;
+          }
+        if (classes == 2)
+          std::printf("threshold frame 0: otsu, 2 classes over %zu bins of [%.9g, %.9g]: cut at bin %u = %.9g (%llu | %llu voxels), %llu NaN, "
+                      "%llu outside the range\n", segment_bins, a, b, cuts[0], static_cast<double>(edges[0]), chosen.populations[0],
+                      chosen.populations[1], counted.nan, counted.below + counted.above);
+        else
+          std::printf("threshold frame 0: otsu, 3 classes over %zu bins of [%.9g, %.9g]: cuts at bins %u, %u = %.9g, %.9g (%llu | %llu | %llu "
+                      "voxels), %llu NaN, %llu outside the range\n", segment_bins, a, b, cuts[0], cuts[1], static_cast<double>(edges[0]),
+                      static_cast<double>(edges[1]), chosen.populations[0], chosen.populations[1], chosen.populations[2], counted.nan,
+                      counted.below + counted.above);
+        // LO is the edge itself (s >= e), HI the largest float below it (s < e)
+        if (segment_token[0]) segment_lo = edges[segment_token[0] == 3 ? 1 : 0];
+        if (segment_token[1]) segment_hi = std::nextafterf(edges[segment_token[1] == 3 ? 1 : 0], -INFINITY);
+        if (segment_lo > segment_hi) {
+          std::printf("Error: --segment: with the cut the range is [%.9g, %.9g]: LO is above HI\n", static_cast<double>(segment_lo),
+                      static_cast<double>(segment_hi));
+          return 3;
+        }
+      }
+      if (!segment) return 0;
+    }
     std::vector<unsigned long long> sizes;
     f3d_component_info info = {};
     f3d_split_info split = {};
@@ -1221,7 +1366,7 @@ int main(int argc, char** argv)
     optical_flow_e.UploadResidentFrames(frame_0, frame_1);
     optical_flow_e.ComputeFlowResident(params);
     if (print_stats) report();
-    if (segment)
+    if (segment || histogram)
       if (const int status = segment_frame_0()) return status;
     optical_flow_e.DownloadFlow(flow_u, flow_v, flow_w);
     write_pair(0, flow_u, flow_v, flow_w);
@@ -1329,7 +1474,7 @@ int main(int argc, char** argv)
         pending_output = false;
       }
       optical_flow_e.EndComputeFlowResident();
-      if (segment && k == 0)  // frame 0 is still in its container: frame 3 overwrites it only beside the solve of pair 1
+      if ((segment || histogram) && k == 0)  // frame 0 is still in its container: frame 3 overwrites it only beside the solve of pair 1
         if (const int status = segment_frame_0()) return status;
       if (print_stats) report();
       std::printf("pair %zu of %zu: %.3f s on the device\n", k + 1, pairs, optical_flow_e.LastDeviceSeconds());

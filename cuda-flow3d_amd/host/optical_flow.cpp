@@ -60,6 +60,10 @@ extern "C" int f3d_label_components(f3d_devptr src, float lo, float hi, unsigned
 extern "C" int f3d_split_components(f3d_devptr src, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
                                     f3d_devptr labels_out, size_t width, size_t height, size_t depth, unsigned long long* sizes, size_t capacity,
                                     f3d_split_info* info) __attribute__((weak));
+extern "C" int f3d_value_range(f3d_devptr src, f3d_devptr mask, size_t width, size_t height, size_t depth, float* min, float* max,
+                               f3d_range_info* info) __attribute__((weak));
+extern "C" int f3d_histogram(f3d_devptr src, f3d_devptr mask, float lo, float hi, size_t bins, size_t width, size_t height, size_t depth,
+                             unsigned long long* counts, f3d_histogram_info* info) __attribute__((weak));
 extern "C" int f3d_validate_displacement(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr weight, float weight_min, unsigned step,
                                          float eps, float threshold, unsigned min_neighbours, unsigned mode, const f3d_devptr out[4],
                                          unsigned fields, size_t width, size_t height, size_t depth, f3d_validate_stats* stats)
@@ -913,6 +917,40 @@ bool OpticalFlowE::ComputeSplitLabels(DevicePtr frame, float lo, float hi, unsig
   sizes->resize(static_cast<size_t>(info->n_labels));
   return set.Check(CheckDeviceError(f3d_split_components(frame, lo, hi, core_d2, min_voxels, set.ptr[3], c.width, c.height, c.depth,
                                                          sizes->data(), sizes->size(), info)));
+}
+
+bool OpticalFlowE::ComputeHistogram(DevicePtr frame, const float* range, size_t bins, unsigned long long* counts, f3d_histogram_info* info,
+                                    float* lo_used, float* hi_used)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!f3d_histogram) return set.Fail("the device library has no f3d_histogram (grey-value histogram of a frame)");
+  if (!range && !f3d_value_range) return set.Fail("the device library has no f3d_value_range (finite minimum and maximum of a frame)");
+  if (!counts || !info) return set.Fail("no counts or info to write to");
+  if (!frame) frame = resident_frame_[0];
+  if (!frame) return set.Fail("no frame on the device (AllocateResidentFrames and UploadResidentFrames first)");
+  const f3d_size4 c = Container();
+  if (!set.Check(CheckDeviceError(f3d_set_container(&c)))) return false;
+  float lo = 0.f, hi = 0.f;
+  if (range) {
+    lo = range[0];
+    hi = range[1];
+  } else {
+    f3d_range_info found = {};
+    if (!set.Check(CheckDeviceError(f3d_value_range(frame, 0, c.width, c.height, c.depth, &lo, &hi, &found)))) return false;
+    if (found.finite == 0) return set.Fail("the frame has no finite voxel: there is no range to lay the bins over");
+    if (!(lo < hi)) {
+      char text[160];
+      std::snprintf(text, sizeof(text), "the frame is constant (every finite voxel is %.9g): there is no range to lay the bins over",
+                    static_cast<double>(lo));
+      return set.Fail(text);
+    }
+  }
+  if (!set.Check(CheckDeviceError(f3d_histogram(frame, 0, lo, hi, bins, c.width, c.height, c.depth, counts, info)))) return false;
+  if (lo_used) *lo_used = lo;
+  if (hi_used) *hi_used = hi;
+  return true;
 }
 
 bool OpticalFlowE::ComputeLabelMotion(const Displacement& of, size_t n_labels, int model, unsigned long long min_voxels,

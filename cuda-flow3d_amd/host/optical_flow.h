@@ -214,6 +214,12 @@ class OpticalFlowE : public OpticalFlowBase {
   bool ComputeSplitLabels(DevicePtr frame, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
                           std::vector<unsigned long long>* sizes, f3d_split_info* info);
   bool DownloadLabels(int* labels);
+  // The histogram of the frame ComputeLabels thresholds (f3d_histogram of include/f3d.h; frame 0 means the resident frame 0).  range:
+  // {lo, hi}, or null for the frame's finite minimum and maximum (f3d_value_range); a constant frame and one without a finite voxel
+  // then fail with a message that says which.  counts has bins entries, info is required, *lo_used and *hi_used (nullable) receive the
+  // bounds the bins were laid over.  Waits for the stream.  Errors are reported through DerivedError(kLabelMotion).
+  bool ComputeHistogram(DevicePtr frame, const float* range, size_t bins, unsigned long long* counts, f3d_histogram_info* info,
+                        float* lo_used, float* hi_used);
   static int DerivedFieldCount(Derived which);
   static bool DerivedSelected(Derived which, int field, unsigned fields);
   DevicePtr DerivedContainer(Derived which, int field) const { return derived_[which].ptr[field]; }  // 0 until computed

@@ -1064,6 +1064,45 @@ int f3d_split_components(f3d_devptr src, float lo, float hi, unsigned long long 
                          f3d_devptr labels_out, size_t width, size_t height, size_t depth, unsigned long long* sizes /* host, nullable */,
                          size_t capacity, f3d_split_info* info /* required */);
 
+/* Grey-value histogram and finite value range of a volume (no reference counterpart: what a user needs before f3d_label_components,
+ * whose lo and hi have to come from somewhere, and the exact counts and ranks of any derived field).  The volume is width x height x
+ * depth; src is a container of floats; mask is 0 for none, or a container read as int32: where it is 0 the voxel is masked, every
+ * other value (a negative one too) lets it through.  Container padding is not read.
+ *
+ * The bin rule (csrc/f3d_histogram_bin.h, one text for the kernel and the host).  With lo < hi both finite, bins in 1 .. 4096 and
+ * scale = (float)bins / (hi - lo) formed once in float32 on the host, a voxel value s takes part when lo <= s && s <= hi in float
+ * compares; a NaN never takes part.  Its bin is min((int)((s - lo) * scale), bins - 1): the subtraction and the product are each
+ * rounded to float32 (contraction is off) and the conversion truncates.  Each step is monotone in s, so every bin is an interval of
+ * floats, and s == hi lands in the last bin.  -0.0f equals 0.0f; a denormal counts as its value.
+ * f3d_histogram_info counts every voxel of the volume exactly once, tried in this order:
+ *   masked   the mask is 0 there
+ *   nan      s is a NaN
+ *   below    s < lo (-inf included)
+ *   above    s > hi (+inf included)
+ *   used     the voxel is counted in counts[its bin]:  sum(counts) == used
+ * f3d_value_range gives the smallest and the largest FINITE value of the voxels the mask lets through.  Values are compared by the
+ * totally ordered integer key of their bits (sign-magnitude folded to an unsigned), so -0.0f is below +0.0f, a denormal keeps its value
+ * and the result does not depend on the schedule.  f3d_range_info counts every voxel exactly once, in this order: masked, nan, infinite,
+ * finite.  With finite == 0, min is +inf and max is -inf.
+ * Determinism.  Counts and counters are integers added with integer atomics, min and max a maximum over integer keys: two calls give
+ * the same bytes, whatever the schedule.  Workgroups count in LDS in 32-bit words (the lanes of a wave first merge their runs of equal
+ * bins, so a constant row costs one add) and add what is non-zero to a 64-bit accumulator of `bins` words in a grow-only buffer of
+ * the library's, cleared on the stream before the kernel.  No lane waits for another.
+ * Limits: f3d_label_contacts'.  At most 32768 voxels along an axis and 2^33 in all.
+ * Refused (status 1, a message, nothing written): a null src, counts, info, min or max; lo >= hi, a bound that is not finite, a hi - lo
+ * or a scale that is not finite and positive in float32, bins outside 1 .. 4096; an empty volume, one beyond the limits or larger
+ * than the current container.  Geometry from the current container, whole volume, library stream; the call waits for the stream. */
+typedef struct f3d_histogram_info {
+  unsigned long long masked, nan, below, above, used;
+} f3d_histogram_info;
+typedef struct f3d_range_info {
+  unsigned long long masked, nan, infinite, finite;
+} f3d_range_info;
+int f3d_value_range(f3d_devptr src, f3d_devptr mask /* 0: none */, size_t width, size_t height, size_t depth, float* min, float* max,
+                    f3d_range_info* info);
+int f3d_histogram(f3d_devptr src, f3d_devptr mask /* 0: none */, float lo, float hi, size_t bins, size_t width, size_t height, size_t depth,
+                  unsigned long long* counts /* bins entries, host */, f3d_histogram_info* info);
+
 /* Validation of a displacement (no reference counterpart: the normalised median test of PIV and volume-correlation post-processing,
  * Westerweel & Scarano 2005, which a workflow applies between the displacement and the strain).  A vector is compared with the median
  * of its neighbours, scaled by the median residual of those neighbours; a rejected vector becomes NaN (which f3d_flow_strain and

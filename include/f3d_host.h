@@ -288,6 +288,45 @@ int f3d_flow_labels_split(f3d_flow flow, f3d_devptr frame /* 0: the resident fra
 int f3d_flow_labels_end(f3d_flow flow);
 int f3d_flow_labels_download(f3d_flow flow, int* labels);
 
+/* Exact selection on a histogram of f3d_histogram (include/f3d.h has the bin rule).  Host code, no device needed.  Each returns
+ * non-zero (f3d_host_last_error() set, nothing written) when it refuses its arguments.
+ *
+ * f3d_histogram_edge: the smallest float32 s in [lo, hi] whose bin is at least k, found by bisection over the ordered bit patterns with
+ * the bin function the kernel runs.  k == 0 gives lo; k >= bins is refused, and so is what f3d_histogram refuses of lo, hi and bins.
+ * By monotonicity {s in [lo, hi] : s >= edge} is exactly the set of bins k .., so f3d_label_components(lo = edge, hi).foreground equals
+ * sum(counts[k:]) by construction, and with hi = the largest float below edge (nextafterf(edge, -inf)) and lo its foreground is
+ * sum(counts[:k]).
+ *
+ * f3d_otsu: the cuts of classes = 2 or 3 that maximise the between-class variance, exactly specified.  With N(a,b) = sum h_i and
+ * M(a,b) = sum i h_i over a <= i < b (exact integers; counts that add up to more than 2^33 are refused, so M < 2^45), a candidate is
+ * 0 < c_1 (< c_2) < bins, its classes are the bins [0, c_1), [c_1, c_2), [c_2, bins), and its objective is the binary64 sum, left to
+ * right in class order, of (double)M * (double)M / (double)N, every operation rounded on its own.  A candidate with an empty class is
+ * skipped.  Candidates are walked in lexicographic order and replaced only on strict >, so ties go to the smallest cut.  cuts receives
+ * classes - 1 bins: class j starts at bin cuts[j - 1], i.e. at the value f3d_histogram_edge(.., cuts[j - 1]).  info: status
+ * F3D_OTSU_OK with the class populations and the objective, or F3D_OTSU_DEGENERATE when fewer bins are occupied than classes; then
+ * nothing is written to cuts and populations and objective are 0.
+ *
+ * f3d_histogram_rank: the bin holding the r-th smallest used voxel (0-based), the first bin whose cumulative count exceeds r; refused
+ * at r >= used. */
+#define F3D_OTSU_OK 0
+#define F3D_OTSU_DEGENERATE 1
+typedef struct f3d_otsu_info {
+  int status;
+  unsigned long long populations[3];
+  double objective;
+} f3d_otsu_info;
+int f3d_histogram_edge(float lo, float hi, size_t bins, size_t k, float* edge);
+int f3d_otsu(const unsigned long long* counts, size_t bins, int classes /* 2 or 3 */, unsigned* cuts /* classes - 1 */, f3d_otsu_info* info);
+int f3d_histogram_rank(const unsigned long long* counts, size_t bins, unsigned long long r, unsigned* bin);
+
+/* Histogram of a frame on the device: f3d_histogram (include/f3d.h) of `frame`, a device container of the driver's geometry, or 0 for the
+ * resident frame 0 that f3d_flow_labels_compute thresholds.  range: {lo, hi}, or null for the finite minimum and maximum of the frame
+ * (f3d_value_range); the bounds used come back in *lo_used and *hi_used.  counts has bins entries; info is required.  The call fails
+ * with a message that says which when the frame is constant or has no finite voxel (only with a null range).  A device library
+ * without f3d_histogram or f3d_value_range still loads; then the call fails with a message naming the entry. */
+int f3d_flow_histogram(f3d_flow flow, f3d_devptr frame /* 0: the resident frame 0 */, const float* range /* nullable: {lo, hi} */,
+                       size_t bins, unsigned long long* counts, f3d_histogram_info* info, float* lo_used, float* hi_used);
+
 /* Validation of the flow the driver holds or of the trajectory (source F3D_STRAIN_OF_FLOW / F3D_STRAIN_OF_TRAJECTORY):
  * f3d_validate_displacement (include/f3d.h has the definition and what step, eps, threshold, min_neighbours and mode mean) into
  * containers the driver keeps until f3d_flow_validate_end (or f3d_flow_destroy).  out[0] receives r, out[1..3] the validated u, v, w
