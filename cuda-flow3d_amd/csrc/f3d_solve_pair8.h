@@ -283,11 +283,24 @@ __device__ __forceinline__ void phi_ksi_stage2(const CarryP& k, const S3& xm, co
 
 // A.3 for one voxel from its nine complete numerators ((U[+1] - U[-1]) + dU[+1]) - dU[-1] (PAIR_PS, stage 1): phi_ksi_stage2's
 // operations behind the numerators.  with_ksi (wave-uniform): the rows that own voxels; the halo rows and the column wave make phi alone.
+//
+// No tiny-numerator guard in front of the nine quotients (udiv_all_safe: nine keys, four three-way minima, a compare, a ballot and a
+// branch per step and wave).  The guard sends a wave down the IEEE road when a numerator has 0 < |x| < 2^-100, because only there can
+// q = (float)((double)x * R) differ from x / d: a quotient in the subnormal range can be a tie.  Here every quotient is looked at
+// ONLY as q * q inside a_phi, and for such a numerator both roads square to the same float:
+//   * the divisors are in range (dv.ok, wave-uniform, still tested: udiv_divisor_ok, d >= 2^-20), so |x / d| < 2^-100 * 2^20 = 2^-80,
+//     and R = RN64(1 / d) <= 2^20 gives |(double)x * R| <= 2^-80 as well (the product of a double below 2^-100 and one of at most
+//     2^20 rounds to at most 2^-80), whatever the conversion to float then does to it;
+//   * the square of a float of magnitude at most 2^-80 is at most 2^-160, below half the smallest subnormal (2^-150): it rounds to +0
+//     on both roads (and is +0 as well if the quotient itself was flushed), so the term of a_phi is the same +0 and a_phi the same float;
+//   * numerators of at least 2^-100 give the same quotient on both roads (the argument at udiv), +-0, Inf and NaN always did.
+// tests/test_udiv_square_cpu.py walks every binade below 2^-100 for the divisors of the default pyramid.  phi_ksi_voxel and
+// phi_ksi_stage2 keep the guard: they belong to other kernels, and the former divides frame numerators whose quotients are not squared.
 __device__ __forceinline__ void weights_first_stage1(float (&q)[9], bool with_ksi, float fx, float fy, float fz, float ft, float du,
                                                      float dv_c, float dw, const SolveDivs& dv, float eps_s2, float eps_d2, float& phi,
                                                      float& ksi, bool counts, bool fast_weights)
 {
-  if (__builtin_expect(dv.ok && udiv_all_safe(q), 1)) {
+  if (__builtin_expect(dv.ok, 1)) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       q[3 * c + 0] = udiv(q[3 * c + 0], dv.x2);
@@ -958,6 +971,12 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     p.ksi = p.su;
   };
   S3 nXd = {0.f, 0.f, 0.f}, nInd = {0.f, 0.f, 0.f};   // raw du, dv, dw of the halo column / of the tile's edge column (column wave)
+  // Row waves of a tile with one band: the two halo columns in registers of their own (nXr / nXd: the LEFT one in every lane, nXrR / nXdR:
+  // the RIGHT one).  A lane shift takes its edge value as the `old` operand, which the instruction overwrites: one register that holds
+  // the left value in lanes 0-31 and the right one in lanes 32-63 serves the two shifts of a quantity only through a copy -- six
+  // v_mov_b32 per step here and four in stage 2 -- where a second (broadcast) LDS read costs the vector unit nothing.  A folded tile has
+  // two LEFT halos and no right one: it keeps the register selected by `side`.
+  S3 nXrR = {0.f, 0.f, 0.f}, nXdR = {0.f, 0.f, 0.f};
   float phM = 0.f, phC = 0.f, ksC = 0.f;             // phi of planes q-2 and q-1, ksi of plane q-1
   // raw neighbours of the next step's plane: the y numerators ((U[y+1] - U[y-1]) + dU[y+1]) - dU[y-1] complete, the x halo raw
   auto fetch_ps = [&](auto colw_c, const float* S) __attribute__((always_inline)) {
@@ -976,7 +995,15 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     } else {
       row_raw_ps(T0, S, jr_m, false, nullptr);
       row_raw_ps(T1, S, jr_p, false, nullptr);
-      halo_raw_ps(T2, S, side, jr, e_near);
+      if constexpr (FOLD) {
+        halo_raw_ps(T2, S, side, jr, e_near);
+      } else {
+        PlaneRegs T3;
+        halo_raw_ps(T2, S, 0, jr, 3);
+        halo_raw_ps(T3, S, 1, jr, 0);
+        nXrR = {T3.u, T3.v, T3.w};
+        nXdR = {T3.su, T3.dv, T3.dw};
+      }
     }
     nDy = {((T1.u - T0.u) + T1.su) - T0.su, ((T1.v - T0.v) + T1.dv) - T0.dv, ((T1.w - T0.w) + T1.dw) - T0.dw};
     nXr = {T2.u, T2.v, T2.w};
@@ -1011,10 +1038,11 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
         dxp = dxm;
       }
     } else {
+      const S3 eR = FOLD ? nXr : nXrR, edR = FOLD ? nXd : nXdR;   // (a folded tile's shift to the right never looks at its edge value)
       rxm = {left_or(C.u, nXr.u), left_or(C.v, nXr.v), left_or(C.w, nXr.w)};
-      rxp = {lane_right_or(C.u, nXr.u), lane_right_or(C.v, nXr.v), lane_right_or(C.w, nXr.w)};
+      rxp = {lane_right_or(C.u, eR.u), lane_right_or(C.v, eR.v), lane_right_or(C.w, eR.w)};
       dxm = {left_or(C.ksi, nXd.u), left_or(C.dv, nXd.v), left_or(C.dw, nXd.w)};
-      dxp = {lane_right_or(C.ksi, nXd.u), lane_right_or(C.dv, nXd.v), lane_right_or(C.dw, nXd.w)};
+      dxp = {lane_right_or(C.ksi, edR.u), lane_right_or(C.dv, edR.v), lane_right_or(C.dw, edR.w)};
       vx = x;
       vy = band ? y + TY : y;
       if (tile_at_x_face) {   // mirror rule at the x faces of the volume
@@ -1061,18 +1089,22 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     // ---- stage 2 of plane t = q - 1: the sweep, on the owned rows
     const int t = q - 1;
     const bool do2 = !CW && core && t >= z0;
-    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+    // (the results live and are stored inside this branch: declared outside it they were three zeros made per step by every wave)
     if (do2) {
+      float o0, o1, o2;
       const int pb = t & 1;
       const int im = band ? r_ymb : r_ym, ip = band ? r_ypb : r_yp;
       Face6 ym = {}, yp = {}, xm = {}, xp = {}, zm = {}, zp = {}, cf = {};
       ym.v[LSU] = img1[pb][0][im][lane]; ym.v[LSV] = img1[pb][1][im][lane]; ym.v[LSW] = img1[pb][2][im][lane]; ym.v[LPHI] = img1[pb][3][im][lane];
       yp.v[LSU] = img1[pb][0][ip][lane]; yp.v[LSV] = img1[pb][1][ip][lane]; yp.v[LSW] = img1[pb][2][ip][lane]; yp.v[LPHI] = img1[pb][3][ip][lane];
-      const float eu = hc1[pb][0][side][r - RH], ev = hc1[pb][1][side][r - RH], ew = hc1[pb][2][side][r - RH], ep = hc1[pb][3][side][r - RH];
+      // the halo columns' stage-1 results: left and right in registers of their own, as the raw ones above (FOLD: both are `side`'s)
+      const int sl = FOLD ? side : 0, sr = FOLD ? side : 1;
+      const float eu = hc1[pb][0][sl][r - RH], ev = hc1[pb][1][sl][r - RH], ew = hc1[pb][2][sl][r - RH], ep = hc1[pb][3][sl][r - RH];
+      const float fu = hc1[pb][0][sr][r - RH], fv = hc1[pb][1][sr][r - RH], fw = hc1[pb][2][sr][r - RH], fp = hc1[pb][3][sr][r - RH];
       cf.v[LSU] = M.su; cf.v[LSV] = M.sv; cf.v[LSW] = M.sw; cf.v[LPHI] = phC;
       xm.v[LSU] = left_or(M.su, eu); xm.v[LSV] = left_or(M.sv, ev); xm.v[LSW] = left_or(M.sw, ew); xm.v[LPHI] = left_or(phC, ep);
-      xp.v[LSU] = lane_right_or(M.su, eu); xp.v[LSV] = lane_right_or(M.sv, ev); xp.v[LSW] = lane_right_or(M.sw, ew);
-      xp.v[LPHI] = lane_right_or(phC, ep);
+      xp.v[LSU] = lane_right_or(M.su, fu); xp.v[LSV] = lane_right_or(M.sv, fv); xp.v[LSW] = lane_right_or(M.sw, fw);
+      xp.v[LPHI] = lane_right_or(phC, fp);
       zm.v[LSU] = hM.u; zm.v[LSV] = hM.v; zm.v[LSW] = hM.w; zm.v[LPHI] = phM;
       zp.v[LSU] = C.su; zp.v[LSV] = C.sv; zp.v[LSW] = C.sw; zp.v[LPHI] = phi_q;
       // mirror rule at the faces of the volume: the missing neighbour is the opposite one
@@ -1086,18 +1118,18 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
       sweep_stage1<true, true>(xm, xp, ym, yp, zm, zp, cf.v, M.u, M.v, M.w, M.dv, M.dw, ksC, a.hx, a.hy, a.hz, fdivs, a.alpha, vx < g.W - 1,
                                vx > 0, vy < RDIM - 1, vy > 0, t < MDIM - 1, t > 0, o0, o1, o2, kU, M.f0, M.f1, M.fz, M.ft, tile_at_x_face,
                                a.w[0], a.w[1], a.w[2]);
+      asm volatile("" ::"v"(o0), "v"(o1), "v"(o2), "v"(phi_q));
+      if (owner) {
+        const unsigned off = xb + rowoff(yy, t);
+        gst(obase[0], off, o0);
+        gst(obase[1], off, o1);
+        gst(obase[2], off, o2);
+      }
     }
-    asm volatile("" ::"v"(o0), "v"(o1), "v"(o2), "v"(phi_q));
     hM = {M.su, M.sv, M.sw};
     phM = phC;
     phC = phi_q;
     ksC = ksi_q;
-    if (do2 && owner) {
-      const unsigned off = xb + rowoff(yy, t);
-      gst(obase[0], off, o0);
-      gst(obase[1], off, o1);
-      gst(obase[2], off, o2);
-    }
     fetch_ps(colw_c, Sp);  // for step q+1
   };
 
