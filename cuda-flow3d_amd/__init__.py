@@ -142,6 +142,26 @@ class ContactInfo(C.Structure):  # f3d_contact_info: every face of the volume in
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class LabelShapeSums(C.Structure):  # struct f3d_label_shape_sums: the 36 exact sums of one label
+    _fields_ = [("n", C.c_ulonglong), ("lo", C.c_longlong * 3), ("hi", C.c_longlong * 3), ("s1", C.c_ulonglong * 3),
+                ("s2", C.c_ulonglong * 6), ("pairs", C.c_ulonglong * 13), ("squares", C.c_ulonglong * 3), ("cubes", C.c_ulonglong),
+                ("border", C.c_ulonglong * 3)]
+
+
+class LabelShapeInfo(C.Structure):  # f3d_label_shape_info: every voxel of the box in exactly one counter
+    _fields_ = [("background", C.c_ulonglong), ("foreign", C.c_ulonglong), ("labelled", C.c_ulonglong)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class LabelShape(C.Structure):  # f3d_label_shape
+    _fields_ = [("status", C.c_int), ("voxels", C.c_ulonglong), ("box_lo", C.c_longlong * 3), ("box_hi", C.c_longlong * 3),
+                ("border", C.c_ulonglong * 3), ("centroid", C.c_double * 3), ("diameter", C.c_double), ("semi_axes", C.c_double * 3),
+                ("axes", C.c_double * 9), ("faces", C.c_ulonglong), ("surface", C.c_double), ("sphericity", C.c_double),
+                ("euler", C.c_longlong)]
+
+
 class ComponentInfo(C.Structure):  # f3d_component_info: every voxel of the box in exactly one of foreground and background
     _fields_ = [(name, C.c_ulonglong) for name in ("foreground", "background", "nan", "n_components", "n_labels", "dropped_components",
                                                    "dropped_voxels", "largest")]
@@ -395,6 +415,8 @@ def host():
         "f3d_flow_contacts_compute": [C.c_void_p, C.c_int, C.POINTER(C.c_int), _sz, C.POINTER(C.POINTER(Contact)), C.POINTER(_sz),
                                       C.POINTER(ContactInfo)],
         "f3d_flow_contacts_end": [C.c_void_p],
+        "f3d_label_shape_solve": [C.POINTER(LabelShapeSums), _sz, C.POINTER(LabelShape)],
+        "f3d_flow_label_shapes_compute": [C.c_void_p, C.POINTER(C.c_int), _sz, C.POINTER(LabelShape), C.POINTER(LabelShapeInfo)],
         "f3d_flow_labels_compute": [C.c_void_p, _dp, C.c_float, C.c_float, C.c_ulonglong, C.POINTER(C.POINTER(C.c_ulonglong)), C.POINTER(_sz),
                                     C.POINTER(ComponentInfo)],
         "f3d_flow_labels_split": [C.c_void_p, _dp, C.c_float, C.c_float, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.POINTER(C.c_ulonglong)),
@@ -615,6 +637,11 @@ def _label_motion_entry():
 def _contacts_entry():
     return _entry("f3d_label_contacts", [_dp] * 4 + [_sz] * 5 + [C.POINTER(Contact), C.POINTER(ContactInfo)],
                   "find the contacts between the labels of a segmentation")
+
+
+def _label_shape_entry():
+    return _entry("f3d_label_shape_sums", [_dp] + [_sz] * 4 + [C.POINTER(LabelShapeSums), C.POINTER(LabelShapeInfo)],
+                  "sum the shapes of the labels of a segmentation")
 
 
 def _components_entry():
@@ -1238,6 +1265,91 @@ def contact_kinematics(contacts, dims, motion=None, min_faces=4):
                 "f3d_contact_kinematics")
     assert C.sizeof(ContactKinematics) == _KINEMATICS_DTYPE.itemsize
     return np.frombuffer(out, dtype=_KINEMATICS_DTYPE, count=n).copy() if n else np.zeros(0, _KINEMATICS_DTYPE)
+
+
+_SHAPE_SUMS_DTYPE = np.dtype([("n", "<u8"), ("lo", "<i8", 3), ("hi", "<i8", 3), ("s1", "<u8", 3), ("s2", "<u8", 6), ("pairs", "<u8", 13),
+                              ("squares", "<u8", 3), ("cubes", "<u8"), ("border", "<u8", 3)])
+_SHAPE_DTYPE = np.dtype([("status", "<i4"), ("pad", "<i4"), ("voxels", "<u8"), ("box_lo", "<i8", 3), ("box_hi", "<i8", 3),
+                         ("border", "<u8", 3), ("centroid", "<f8", 3), ("diameter", "<f8"), ("semi_axes", "<f8", 3), ("axes", "<f8", (3, 3)),
+                         ("faces", "<u8"), ("surface", "<f8"), ("sphericity", "<f8"), ("euler", "<i8")])
+
+
+def label_shape_sums(labels, n_labels=None):
+    """The exact shape sums of every label of a segmentation on the device (include/f3d.h, f3d_label_shape_sums): labels an integer
+    [z, y, x] volume (0 background, 1 .. n_labels the bodies, anything else foreign; n_labels None means labels.max()).  Returns
+    (sums, info): a structured array of n_labels rows (label L at index L - 1) with the fields n, lo, hi, s1, s2, pairs, squares,
+    cubes, border, and a dict of the voxel counts background, foreign, labelled."""
+    fn = _label_shape_entry()
+    bits, n_labels = _labels_as_float_bits(labels, n_labels)
+    if bits.size == 0:
+        raise ValueError("labels must be a non-empty [z, y, x] volume")
+    with _on_device((bits,), "labels must be a [z, y, x] volume") as (box, p, dims):
+        box.set_current()
+        sums, info = (LabelShapeSums * n_labels)(), LabelShapeInfo()
+        check(fn(p[0], n_labels, *dims, sums, C.byref(info)), "f3d_label_shape_sums")
+    assert C.sizeof(LabelShapeSums) == _SHAPE_SUMS_DTYPE.itemsize
+    return np.frombuffer(sums, dtype=_SHAPE_SUMS_DTYPE, count=n_labels).copy(), info.as_dict()
+
+
+class LabelShapes:
+    """The shape of every body of a segmentation (solve_label_shapes): arrays over the labels, label L at index L - 1.  .status (0 ok,
+    1 empty: LABEL_STATUS), .voxels, .box (N, 2, 3: the smallest and the largest x, y, z), .border (N, 3: voxels on the two box faces
+    of each axis), .centroid (N, 3), .diameter (of the ball of the same volume), .semi_axes (N, 3, descending: of the ellipsoid with the
+    same second moments), .axes (N, 3, 3: axes[i, j] is unit axis j of label i), .faces (the staircase area), .surface (the
+    Cauchy-Crofton estimate over 13 directions), .sphericity and .euler (pieces - tunnels + cavities under six-connectivity); .info is
+    the dict of f3d_label_shape_info when the sums came from the device in the same call, else None."""
+
+    def __init__(self, rows, info=None):
+        self.rows, self.info = rows, info
+        self.status, self.voxels = rows["status"].copy(), rows["voxels"].copy()
+        self.box = np.stack([rows["box_lo"], rows["box_hi"]], axis=1) if len(rows) else np.zeros((0, 2, 3), np.int64)
+        self.border, self.centroid, self.diameter = rows["border"].copy(), rows["centroid"].copy(), rows["diameter"].copy()
+        self.semi_axes, self.axes = rows["semi_axes"].copy(), rows["axes"].copy()
+        self.faces, self.surface, self.sphericity, self.euler = (rows[k].copy() for k in ("faces", "surface", "sphericity", "euler"))
+
+    def __len__(self):
+        return len(self.status)
+
+    @property
+    def touches_border(self):
+        """per label: whether a voxel of it lies on a face of the box (the body may be cut by the edge of the scan)"""
+        return self.border.sum(axis=1) > 0
+
+    def as_table(self):
+        """one dict per label: label, status (a word of LABEL_STATUS), voxels, box, border, touches_border, centroid, diameter, semi_axes,
+        axes, faces, surface, sphericity, euler"""
+        touches = self.touches_border
+        return [{"label": i + 1, "status": LABEL_STATUS[self.status[i]], "voxels": int(self.voxels[i]), "box": self.box[i].tolist(),
+                 "border": self.border[i].tolist(), "touches_border": bool(touches[i]), "centroid": self.centroid[i].tolist(),
+                 "diameter": float(self.diameter[i]), "semi_axes": self.semi_axes[i].tolist(), "axes": self.axes[i].tolist(),
+                 "faces": int(self.faces[i]), "surface": float(self.surface[i]), "sphericity": float(self.sphericity[i]),
+                 "euler": int(self.euler[i])} for i in range(len(self))]
+
+
+def _shape_rows(out, n):
+    assert C.sizeof(LabelShape) == _SHAPE_DTYPE.itemsize
+    return np.frombuffer(out, dtype=_SHAPE_DTYPE, count=n).copy() if n else np.zeros(0, _SHAPE_DTYPE)
+
+
+def solve_label_shapes(sums):
+    """f3d_label_shape_solve (include/f3d_host.h; host code, no device): the LabelShapes of the structured array `sums` of
+    label_shape_sums."""
+    sums = np.ascontiguousarray(sums, dtype=_SHAPE_SUMS_DTYPE)
+    if sums.ndim != 1:
+        raise ValueError("sums must be a one-dimensional array of shape sums, one row per label")
+    n = len(sums)
+    out = (LabelShape * max(n, 1))()
+    _host_check(host().f3d_label_shape_solve(sums.ctypes.data_as(C.POINTER(LabelShapeSums)), n, out), "f3d_label_shape_solve")
+    return LabelShapes(_shape_rows(out, n))
+
+
+def label_shapes(labels, n_labels=None):
+    """The shape table of a segmentation from anywhere: label_shape_sums on the device, solve_label_shapes on the host.  Returns a
+    LabelShapes whose .info holds the voxel counts."""
+    sums, info = label_shape_sums(labels, n_labels)
+    shapes = solve_label_shapes(sums)
+    shapes.info = info
+    return shapes
 
 
 class Components:
@@ -2343,7 +2455,32 @@ class OpticalFlow:
         own = np.array(sizes[:count.value], np.uint64)         # the driver owns its list: a copy outlives the next call
         labels = np.empty((d, h, w), np.int32)
         _host_check(host().f3d_flow_labels_download(self._h, labels.ctypes.data_as(C.POINTER(C.c_int))), "f3d_flow_labels_download")
+        self._segmented_labels = int(info.n_labels)            # what label_shapes() takes for n_labels when it is not given
         return Components(labels, own, info.as_dict())
+
+    def label_shapes(self, labels=None, n_labels=None):
+        """The shape table of a segmentation on the grid of the driver: a LabelShapes (see there) with .info.  labels: an integer
+        [z, y, x] volume, or None for the labels segment(), label_motion() or contacts() left on the device; n_labels None then
+        means the number of bodies of the last segment().  No displacement is needed: this runs before any solve."""
+        w, h, d = self.dims
+        if labels is None:
+            if n_labels is None:
+                n_labels = getattr(self, "_segmented_labels", None)
+            if n_labels is None:
+                raise ValueError("n_labels is required when the labels on the device were not made by segment()")
+            ptr = None
+        else:
+            bits, n_labels = _labels_as_float_bits(labels, n_labels)
+            if bits.shape != (d, h, w):
+                raise ValueError(f"labels must be a [z, y, x] volume of shape {(d, h, w)}")
+            lab = bits.view(np.int32)
+            ptr = lab.ctypes.data_as(C.POINTER(C.c_int))
+        n = int(n_labels)
+        if not 1 <= n <= MAX_LABELS:
+            raise ValueError(f"n_labels must be 1 .. {MAX_LABELS}, not {n}")
+        out, info = (LabelShape * n)(), LabelShapeInfo()
+        _host_check(host().f3d_flow_label_shapes_compute(self._h, ptr, n, out, C.byref(info)), "f3d_flow_label_shapes_compute")
+        return LabelShapes(_shape_rows(out, n), info.as_dict())
 
     def segment_end(self):
         """free the driver's list of sizes (the labels stay on the device until label_motion_end() or destroy())"""

@@ -7,6 +7,7 @@
 
 #include "f3d_host.h"
 #include "contact_kinematics.h"
+#include "label_shape.h"
 #include "hip_utils.h"
 #include "motion_fit.h"
 #include "operations.h"
@@ -462,6 +463,24 @@ int f3d_flow_contacts_end(f3d_flow flow)
   g_host_error.clear();
   if (!flow) return HostFail("f3d_flow_contacts_end: null driver");
   std::vector<f3d_contact>().swap(flow->contacts);
+  return 0;
+}
+
+int f3d_label_shape_solve(const struct f3d_label_shape_sums* sums, size_t n_labels, f3d_label_shape* out)
+{
+  g_host_error.clear();
+  if (n_labels && (!sums || !out)) return HostFail("f3d_label_shape_solve: null argument");
+  SolveLabelShapes(sums, n_labels, out);
+  return 0;
+}
+
+int f3d_flow_label_shapes_compute(f3d_flow flow, const int* labels, size_t n_labels, f3d_label_shape* shapes, f3d_label_shape_info* info)
+{
+  g_host_error.clear();
+  if (!flow || !shapes) return HostFail("f3d_flow_label_shapes_compute: null argument");
+  OpticalFlowE& d = flow->driver;
+  if (labels && !d.UploadLabels(labels)) return HostFail(d.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  if (!d.ComputeLabelShapes(n_labels, shapes, info)) return HostFail(d.DerivedError(OpticalFlowE::kLabelMotion).c_str());
   return 0;
 }
 

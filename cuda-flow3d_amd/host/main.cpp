@@ -99,6 +99,11 @@
 // 4096, default 256) and --segment-range A:B (default: the finite minimum and maximum of frame 0) lay the bins; one line says what was
 // chosen and the run goes on exactly as if the numbers had been given.  --histogram, alone or with --segment, writes
 // <tag>_histogram.csv (bin, lower edge with %.9g, count) and prints one line.
+// (--labels FILE | --segment ...) --label-shape writes the shape table of the bodies (f3d_label_shape_sums on the device,
+// f3d_label_shape_solve on the host), once, right after the labels are on the device: <tag>_shapes.csv (tag of the first pair) has one
+// row per label -- label, status, voxels, the bounding box, the voxels on the two box faces of each axis, centroid, diameter of the ball
+// of the same volume, the three semi-axes and their directions, staircase faces, the Cauchy-Crofton surface, sphericity and the Euler
+// number -- and one line sums it up.  It needs no displacement; every other output is the same with and without it.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -132,6 +137,7 @@ static void Usage()
               "               [--validate-min-neighbours K] [--validate-fill N] [--validate-min-zncc Z] [--use-validated]]\n"
               "              [--labels FILE --label-motion translation|rigid|affine [--label-min-voxels K]]\n"
               "              [--labels FILE --contacts [--contact-min-faces K]]\n"
+              "              [(--labels FILE | --segment ...) --label-shape]\n"
               "              [--segment LO:HI [--segment-min-voxels K]]\n"
               "              [--segment-split R | --segment-split-d2 N]\n"
               "              [--segment with otsu, or otsu1 / otsu2, in place of LO or HI] [--segment-bins B] [--segment-range A:B]\n"
@@ -173,6 +179,7 @@ int main(int argc, char** argv)
   unsigned long long label_min_voxels = 27;
   bool label_min_given = false;
   bool contacts = false;          // --contacts
+  bool label_shape = false;       // --label-shape
   unsigned long long contact_min_faces = 4;
   bool contact_min_given = false;
   bool segment = false;           // --segment LO:HI
@@ -443,6 +450,7 @@ int main(int argc, char** argv)
       label_min_given = true;
     }
     else if (a == "--contacts") contacts = true;
+    else if (a == "--label-shape") label_shape = true;
     else if (a == "--segment") {
       need(1);
       // LO:HI, either side empty for an open bound; anything else, a NaN or LO > HI is malformed
@@ -691,7 +699,18 @@ int main(int argc, char** argv)
     Usage();
     return 64;
   }
-  if ((!contacts && !segment && labels_file.empty() != (label_model < 0)) || (label_min_given && label_model < 0)) {
+  if (label_shape && labels_file.empty() && !segment) {
+    std::printf("--label-shape needs --labels FILE or --segment\n");
+    Usage();
+    return 64;
+  }
+  if (label_shape && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--label-shape needs the resident driver, which holds the labels: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if ((!contacts && !segment && !label_shape && labels_file.empty() != (label_model < 0)) || (label_min_given && label_model < 0)) {
     std::printf("--labels and --label-motion need each other, and --label-min-voxels needs both\n");
     Usage();
     return 64;
@@ -711,7 +730,7 @@ int main(int argc, char** argv)
   // the segmentation is read before any device is touched: a file of another size or without a body is an argument error
   std::vector<int> label_volume;
   size_t n_labels = 0, n_bodies = 0;  // the largest label, and how many of 1 .. n_labels occur
-  if ((label_model >= 0 || contacts) && !segment) {
+  if ((label_model >= 0 || contacts || label_shape) && !segment) {
     const size_t count = width * height * depth;
     std::FILE* f = std::fopen(labels_file.c_str(), "rb");
     bool good = f != nullptr;
@@ -876,12 +895,68 @@ int main(int argc, char** argv)
   }
   if (!optical_flow_e.AllocateResidentFrames()) return 3;
   std::printf("Mode: Full GPU mode \n");
-  if ((label_model >= 0 || contacts) && !segment) {
+  if ((label_model >= 0 || contacts || label_shape) && !segment) {
     if (!optical_flow_e.UploadLabels(label_volume.data())) return 3;
     std::vector<int>().swap(label_volume);
   }
   optical_flow_e.silent = silent_mode;
   optical_flow_e.collect_level_statistics = print_stats;
+
+  // --label-shape: the shape table of the `bodies` labels on the device into <tag>_shapes.csv and one line; 0 or the exit status
+  auto write_shapes = [&](size_t bodies) -> int {
+    if (bodies > (static_cast<size_t>(1) << 22)) {
+      std::printf("Error: --label-shape takes at most %d bodies, not %zu: raise --segment-min-voxels so that the small ones get no label\n",
+                  1 << 22, bodies);
+      return 3;
+    }
+    std::vector<f3d_label_shape> shapes(bodies);
+    if (bodies && !optical_flow_e.ComputeLabelShapes(bodies, shapes.data(), nullptr)) {
+      std::printf("Error: %s\n", optical_flow_e.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+      return 3;
+    }
+    const std::string tag = pairs > 1 ? prefix + "_0" : prefix;
+    std::FILE* csv = std::fopen((tag + "_shapes.csv").c_str(), "w");
+    size_t empty = 0, touching = 0, holed = 0;
+    std::vector<double> diameters, sphericities;
+    if (csv) {
+      std::fprintf(csv, "label,status,voxels,x_lo,y_lo,z_lo,x_hi,y_hi,z_hi,border_x,border_y,border_z,centroid_x,centroid_y,centroid_z,"
+                        "diameter,semi_axis_1,semi_axis_2,semi_axis_3,axis_1_x,axis_1_y,axis_1_z,axis_2_x,axis_2_y,axis_2_z,axis_3_x,"
+                        "axis_3_y,axis_3_z,faces,surface,sphericity,euler\n");
+      for (size_t l = 0; l < bodies; ++l) {
+        const f3d_label_shape& s = shapes[l];
+        std::fprintf(csv, "%zu,%d,%llu,%lld,%lld,%lld,%lld,%lld,%lld,%llu,%llu,%llu", l + 1, s.status, s.voxels, s.box_lo[0], s.box_lo[1],
+                     s.box_lo[2], s.box_hi[0], s.box_hi[1], s.box_hi[2], s.border[0], s.border[1], s.border[2]);
+        std::fprintf(csv, ",%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g", s.centroid[0], s.centroid[1], s.centroid[2], s.diameter, s.semi_axes[0],
+                     s.semi_axes[1], s.semi_axes[2]);
+        for (int i = 0; i < 9; ++i) std::fprintf(csv, ",%.9g", s.axes[i]);
+        std::fprintf(csv, ",%llu,%.9g,%.9g,%lld\n", s.faces, s.surface, s.sphericity, s.euler);
+        if (s.status != F3D_LABEL_OK) {
+          ++empty;
+          continue;
+        }
+        if (s.border[0] + s.border[1] + s.border[2]) ++touching;
+        if (s.euler != 1) ++holed;
+        diameters.push_back(s.diameter);
+        sphericities.push_back(s.sphericity);
+      }
+    }
+    const bool csv_error = csv && std::ferror(csv) != 0;
+    if (!csv || std::fclose(csv) != 0 || csv_error) {
+      std::printf("Error: cannot write %s_shapes.csv\n", tag.c_str());
+      return 2;
+    }
+    // the upper median of the bodies that have a voxel; nan without one
+    auto median = [](std::vector<double>& v) {
+      if (v.empty()) return std::nan("");
+      std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
+      return v[v.size() / 2];
+    };
+    std::printf("shapes frame 0: %zu bodies, %zu empty, %zu touch the border, median diameter %.6g, median sphericity %.6g, %zu with Euler "
+                "number != 1\n", bodies, empty, touching, median(diameters), median(sphericities), holed);
+    return 0;
+  };
+  if (label_shape && !segment)
+    if (const int status = write_shapes(n_labels)) return status;
 
   auto report = [&]() {
     Stat3 stat = {0.f, 0.f, 0.f};
@@ -1345,6 +1420,8 @@ int main(int argc, char** argv)
       std::printf("Error: cannot write %s_bodies.csv\n", tag.c_str());
       return 2;
     }
+    if (label_shape)
+      if (const int status = write_shapes(static_cast<size_t>(info.n_labels))) return status;
     if (label_model >= 0 || contacts) {
       if (info.n_labels == 0 || info.n_labels > (1ull << 22)) {
         std::printf(info.n_labels ? "Error: --segment found %llu bodies and --label-motion and --contacts take at most %d: raise "

@@ -12,6 +12,7 @@
 #include "common_utils.h"
 #include "operator_calls.h"
 #include "hip_utils.h"
+#include "label_shape.h"
 #include "motion_fit.h"
 
 // Declared weak: the host library keeps loading against a device library that lacks the entry (the address is then null and the
@@ -54,6 +55,8 @@ extern "C" int f3d_remove_label_motion(f3d_devptr u, f3d_devptr v, f3d_devptr w,
     __attribute__((weak));
 extern "C" int f3d_label_contacts(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr labels, size_t n_labels, size_t width, size_t height,
                                   size_t depth, size_t capacity, struct f3d_contact* out, f3d_contact_info* info) __attribute__((weak));
+extern "C" int f3d_label_shape_sums(f3d_devptr labels, size_t n_labels, size_t width, size_t height, size_t depth,
+                                    struct f3d_label_shape_sums* out, f3d_label_shape_info* info) __attribute__((weak));
 extern "C" int f3d_label_components(f3d_devptr src, float lo, float hi, unsigned long long min_voxels, f3d_devptr labels_out, size_t width,
                                     size_t height, size_t depth, unsigned long long* sizes, size_t capacity, f3d_component_info* info)
     __attribute__((weak));
@@ -1018,6 +1021,25 @@ bool OpticalFlowE::ComputeContacts(const Displacement& of, size_t n_labels, std:
   }
   contacts->clear();
   return set.Fail("the labels have more than 2^24 distinct contacts");
+}
+
+bool OpticalFlowE::ComputeLabelShapes(size_t n_labels, f3d_label_shape* shapes, f3d_label_shape_info* info)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!f3d_label_shape_sums) return set.Fail("the device library has no f3d_label_shape_sums (shapes of labelled bodies)");
+  if (!shapes) return set.Fail("no shapes to write to");
+  if (n_labels == 0 || n_labels > (static_cast<size_t>(1) << 22)) return set.Fail("n_labels must be 1 .. 2^22");
+  const DevicePtr labels = set.ptr[3];
+  if (!labels) return set.Fail("no labels on the device (UploadLabels or ComputeLabels first)");
+  const f3d_size4 c = Container();
+  std::vector<struct f3d_label_shape_sums> sums(n_labels);
+  if (!set.Check(CheckDeviceError(f3d_set_container(&c))) ||
+      !set.Check(CheckDeviceError(f3d_label_shape_sums(labels, n_labels, c.width, c.height, c.depth, sums.data(), info))))
+    return false;
+  SolveLabelShapes(sums.data(), n_labels, shapes);
+  return true;
 }
 
 bool OpticalFlowE::ComputeValidated(const Displacement& of, DevicePtr weight, float weight_min, unsigned step, float eps,

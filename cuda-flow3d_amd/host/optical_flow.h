@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "data_types.h"
+#include "f3d_host.h"
 #include "operations.h"
 
 // One level of the coarse-to-fine pyramid: size and grid spacing in original-voxel units.
@@ -214,6 +215,10 @@ class OpticalFlowE : public OpticalFlowBase {
   bool ComputeSplitLabels(DevicePtr frame, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
                           std::vector<unsigned long long>* sizes, f3d_split_info* info);
   bool DownloadLabels(int* labels);
+  // The shapes of the labels on the device (f3d_label_shape_sums of include/f3d.h, then f3d_label_shape_solve of include/f3d_host.h):
+  // shapes has n_labels entries (required), info is nullable.  It needs the label container alone, however it was filled, so it runs
+  // before any solve.  Waits for the stream.  Errors are reported through DerivedError(kLabelMotion), whose labels these are.
+  bool ComputeLabelShapes(size_t n_labels, f3d_label_shape* shapes, f3d_label_shape_info* info);
   // The histogram of the frame ComputeLabels thresholds (f3d_histogram of include/f3d.h; frame 0 means the resident frame 0).  range:
   // {lo, hi}, or null for the frame's finite minimum and maximum (f3d_value_range); a constant frame and one without a finite voxel
   // then fail with a message that says which.  counts has bins entries, info is required, *lo_used and *hi_used (nullable) receive the

@@ -1103,6 +1103,49 @@ int f3d_value_range(f3d_devptr src, f3d_devptr mask /* 0: none */, size_t width,
 int f3d_histogram(f3d_devptr src, f3d_devptr mask /* 0: none */, float lo, float hi, size_t bins, size_t width, size_t height, size_t depth,
                   unsigned long long* counts /* bins entries, host */, f3d_histogram_info* info);
 
+/* Shape sums of labelled bodies (no reference counterpart: what the shape table of a granular or fibrous study is made of -- size,
+ * bounding box, axes, surface, whether a body is cut by the edge of the scan and whether it has a hole or a cavity).  The entry needs
+ * the labels alone.  The box is width x height x depth (W x H x D = N_0 x N_1 x N_2) in the corner of the current container; labels is
+ * a container read as int32 under the rules of f3d_label_motion_sums: 0 is background, 1 .. n_labels are bodies, every other value is
+ * foreign.  Voxels outside the box do not exist: container padding is never read, as a voxel or as a neighbour, whatever it holds.
+ *
+ * out[L-1] receives 36 exact 64-bit integers of label L, over the voxels p = (x_0, x_1, x_2) of the box with label(p) == L, in plain
+ * integer voxel coordinates:
+ *   n            their number
+ *   lo[3], hi[3] the smallest and the largest x_i among them; for a label without a voxel lo[i] = 0 and hi[i] = -1
+ *   s1[3]        sum x_i
+ *   s2[6]        sum x_i x_k in the order xx yy zz xy xz yz
+ *   pairs[13]    for the direction d_k, the number of p with p and p + d_k in the box and label(p) == label(p + d_k) == L; d_k in this
+ *                order: (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,-1,0) (1,0,1) (1,0,-1) (0,1,1) (0,1,-1) (1,1,1) (1,1,-1) (1,-1,1) (1,-1,-1):
+ *                one of each of the 13 pairs of opposite directions to the 26 neighbours
+ *   squares[3]   the unit squares {p, p + e_i, p + e_k, p + e_i + e_k} in the planes xy, xz, yz with all four voxels in the box and of L
+ *   cubes        the blocks p + {0,1}^3 with all eight voxels in the box and of L
+ *   border[3]    per axis i, the sum of [x_i == 0] + [x_i == N_i - 1]: a voxel of a box one voxel thick along i counts twice
+ * info (nullable) counts every voxel of the box exactly once: background (label 0), foreign (outside 0 .. n_labels) or labelled.
+ * Determinism.  Everything is an integer function of the input, added with integer atomics: two calls give the same bytes, whatever
+ * the schedule.
+ * Limits: f3d_label_components'.  At most 32768 voxels along an axis and 2^31 - 1 in the box.  Widths: a term of s2 is below 2^30, so
+ * s2 < 2^61; s1 < 2^46; every count is at most 2 * (2^31 - 1): single words suffice.  The device accumulates a lane's run over the 32
+ * planes of a tile in 32-bit registers, a 64 x 4 x 32 tile (2^13 voxels) in LDS (s2 < 2^43 in 64-bit words, every other sum below
+ * 2^28 in 32-bit words), the extents as maxima of x_i and of N_i - 1 - x_i so that cleared memory is their identity.
+ * n_labels is 1 .. 2^22: the accumulator is 288 B per label in a grow-only buffer of the library's, cleared on the stream before the
+ * kernel and copied down after it.
+ * Refused (status 1, a message, nothing written): a null labels or out; n_labels outside 1 .. 2^22; an empty box, or a box beyond the
+ * limits; a box larger than the current container.  Library stream; the call waits for the stream.
+ * The solve from the sums to centroid, axes, surface, sphericity and Euler number is host code: f3d_label_shape_solve of
+ * include/f3d_host.h. */
+struct f3d_label_shape_sums {
+  unsigned long long n;
+  long long lo[3], hi[3];
+  unsigned long long s1[3], s2[6];
+  unsigned long long pairs[13], squares[3], cubes, border[3];
+};
+typedef struct f3d_label_shape_info {
+  unsigned long long background, foreign, labelled;
+} f3d_label_shape_info;
+int f3d_label_shape_sums(f3d_devptr labels, size_t n_labels, size_t width, size_t height, size_t depth,
+                         struct f3d_label_shape_sums* out /* n_labels entries, host */, f3d_label_shape_info* info /* nullable */);
+
 /* Validation of a displacement (no reference counterpart: the normalised median test of PIV and volume-correlation post-processing,
  * Westerweel & Scarano 2005, which a workflow applies between the displacement and the strain).  A vector is compared with the median
  * of its neighbours, scaled by the median residual of those neighbours; a rejected vector becomes NaN (which f3d_flow_strain and

@@ -270,6 +270,53 @@ int f3d_flow_contacts_compute(f3d_flow flow, int source, const int* labels /* nu
                               const struct f3d_contact** contacts, size_t* count, f3d_contact_info* info);
 int f3d_flow_contacts_end(f3d_flow flow);
 
+/* The solve from the shape sums of f3d_label_shape_sums (include/f3d.h) to the shape table of the bodies.  Host code, no device
+ * needed.  sums and out have n_labels entries; label L is entry L-1.  Coordinates are voxel indices, a voxel is a unit cube about its
+ * index.  Binary64, every operation rounded on its own, in exactly this order (n, s1, s2, pairs, squares, cubes of the sums; N = (double)n):
+ *   status        F3D_LABEL_EMPTY when n == 0: voxels 0, box_lo 0, box_hi -1, border, faces and euler 0, every double NaN.
+ *                 F3D_LABEL_OK otherwise
+ *   voxels, box_lo, box_hi, border   n, lo, hi, border as they are
+ *   centroid_i    (double)s1_i / N
+ *   diameter      cbrt(6.0 * N / pi): of the ball of the same volume
+ *   C_ik          m_ik = n s2_ik - s1_i s1_k exactly in a 128-bit integer (below 2^93), (double)m_ik / (N * N), and + 1.0 / 12.0 on the
+ *                 diagonal for the voxel's own extent: the covariance of the body as a union of unit cubes, without cancellation in
+ *                 floating point
+ *   l_1 >= l_2 >= l_3, axes   the eigenvalues and unit eigenvectors of C by cyclic Jacobi: 12 sweeps over the pairs (0,1) (0,2)
+ *                 (1,2); for a pair (p, q) with C_pq != 0, theta = (C_qq - C_pp) / (2.0 * C_pq), t = sign(theta) / (|theta| +
+ *                 sqrt(theta * theta + 1.0)) (sign(0) = +1), c = 1.0 / sqrt(t * t + 1.0), s = t * c, columns then rows p and q
+ *                 of C become c * p - s * q and s * p + c * q, C_pq = C_qp = 0, and the columns of the accumulated rotation
+ *                 likewise.  Sorted descending, equal values in column order.  axes[3 * i + a] is component a of axis i, divided
+ *                 by its norm, its sign chosen so that its component of largest magnitude is positive (the first such on ties)
+ *   semi_axes_i   sqrt(5.0 * l_i): the solid ellipsoid with the same second moments
+ *   faces         sum over k = 0, 1, 2 of 2 (n - pairs[k]), an integer: the staircase area, the box border closing the body
+ *   surface       2.0 * sum over k = 0 .. 12, in this order from 0.0, of w_k * (double)(2 (n - pairs[k])) / |d_k|: the Cauchy-Crofton
+ *                 estimate over the 13 directions of f3d_label_shape_sums, |d_k| = 1.0, sqrt(2.0), sqrt(3.0), and w_k = 0.0915557824
+ *                 (3 axes), 0.0739612557 (6 face diagonals), 0.0703912796 (4 body diagonals): the share of the unit sphere nearest
+ *                 to +-d_k among the 26 directions
+ *   sphericity    cbrt(pi * ((6.0 * N) * (6.0 * N))) / surface: 1 for a ball
+ *   euler         n - (pairs[0] + pairs[1] + pairs[2]) + (squares[0] + squares[1] + squares[2]) - cubes: the Euler number of the body
+ *                 under the six-connectivity of f3d_label_components: pieces - tunnels + cavities
+ * Returns non-zero (f3d_host_last_error() set, nothing written) only for a null pointer. */
+typedef struct f3d_label_shape {
+  int status;
+  unsigned long long voxels;
+  long long box_lo[3], box_hi[3];
+  unsigned long long border[3];
+  double centroid[3], diameter, semi_axes[3], axes[9];
+  unsigned long long faces;
+  double surface, sphericity;
+  long long euler;
+} f3d_label_shape;
+int f3d_label_shape_solve(const struct f3d_label_shape_sums* sums, size_t n_labels, f3d_label_shape* out);
+
+/* The shapes of the labels the driver keeps on the device: f3d_label_shape_sums and f3d_label_shape_solve.  labels as in
+ * f3d_flow_label_motion_compute: uploaded when given, and a null labels reuses the ones an earlier call uploaded or
+ * f3d_flow_labels_compute / f3d_flow_labels_split made.  No displacement is needed, so this also runs before any solve.  shapes has
+ * n_labels entries (required); info is nullable.  A device library without f3d_label_shape_sums still loads; then the call fails with
+ * a message naming it. */
+int f3d_flow_label_shapes_compute(f3d_flow flow, const int* labels /* nullable */, size_t n_labels, f3d_label_shape* shapes,
+                                  f3d_label_shape_info* info /* nullable */);
+
 /* The labels made on the device instead of uploaded: f3d_label_components (include/f3d.h has the definition of foreground, component,
  * root, the numbering and every counter) of a frame into the label container of the driver, the one f3d_flow_label_motion_compute and
  * f3d_flow_contacts_compute fill from their `labels` argument and reuse when that is null -- so a null labels and n_labels =
