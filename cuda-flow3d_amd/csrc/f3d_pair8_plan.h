@@ -114,6 +114,38 @@ __host__ __device__ inline bool pair8_decode(int wg, const Pair8Cut& c, int ntx,
   return true;
 }
 
+// ---- the x neighbours of a row wave's lanes, read from the ring (weights-first launch, tile with one band) ----
+// A ring slot holds one plane: `ns` arrays of `nj` rows of 64 floats, behind them the 16-byte x-halo pieces [array][side][row] (side 0:
+// columns x0-4 .. x0-1, side 1: x0+64 .. x0+67), rounded up to whole DMA instructions of 64 pieces.
+__host__ __device__ constexpr int pair8_slot_halo_off(int ns, int nj) { return ns * nj * kPair8Lanes; }
+__host__ __device__ constexpr int pair8_slot_floats(int ns, int nj)
+{
+  return pair8_slot_halo_off(ns, nj) + (ns * 2 * nj + kPair8Lanes - 1) / kPair8Lanes * 4 * kPair8Lanes;
+}
+// Lane -> the row elements that hold its left and its right neighbour; -1 is the last float of the left halo piece, 64 the first of
+// the right one.  The reference's mirror rule (index -1 -> 1, W -> W-2) is part of the rule: at x = 0 the left neighbour IS the right
+// one, at x = W-1 the right one is the left one -- in this order, so a volume one column wide names element 1 twice, as the selects
+// that this replaces did.  Lanes beyond the volume (x >= W) name their geometric neighbours: nobody looks at what they read.
+struct Pair8XNeighbours {
+  int left, right;
+};
+__host__ __device__ inline Pair8XNeighbours pair8_x_neighbours(int lane, int x0, int width)
+{
+  const int x = x0 + lane;
+  Pair8XNeighbours n = {lane - 1, lane + 1};
+  if (x == 0) n.left = n.right;
+  if (x == width - 1) n.right = n.left;
+  return n;
+}
+// float offset inside a slot of element `elem` (-1 .. 64, as above) of ring row `row` of array `array`
+__host__ __device__ inline int pair8_x_neighbour_offset(int elem, int array, int row, int ns, int nj)
+{
+  const int halo = pair8_slot_halo_off(ns, nj) + (array * 2 * nj + row) * 4;
+  if (elem < 0) return halo + 3;
+  if (elem >= kPair8Lanes) return halo + nj * 4;
+  return (array * nj + row) * kPair8Lanes + elem;
+}
+
 // One workgroup per CU at a time: the round model of k_sweep7 -- a chunk costs its planes plus ~7 steps of prologue and repeated
 // stage-1 planes, `per_round` workgroups (256: one per CU) run per round.  `cost` is in plane steps of ONE workgroup; a step of a
 // 16-wave workgroup (TY = 12) takes ~1.28 x a step of a 12-wave one (TY = 8) -- measured at 128^3 ... 512^3 (tools/kbench.py with

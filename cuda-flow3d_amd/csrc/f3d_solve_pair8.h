@@ -384,8 +384,15 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
   // FD: ring index of a stencilled input (u .. phi are inputs 2 .. 8) and centre-ring index of fx, fy, ksi, fz, ft (inputs 0, 1, 9, 10, 11)
   constexpr int SB = FD ? 2 : 0;   // ring array = input - SB
   constexpr int NI = PS ? 4 : 3;   // PS: S = U + dU and phi
-  __shared__ float img1[2][NI][NR][kLanes];  // stage-1 results of the row waves: S = U + dU' (SS) or dU' (SP)
-  __shared__ float hc1[2][NI][2][32];        // the same for the two halo columns: [component][side][core row]
+  // PS keeps its stage-1 image in imgx (a kernel is given only the image it uses): a row has a pad column on either side, [0] and
+  // [kLanes + 1], into which the column wave writes the halo columns' results, so that a row wave of a tile with one band reads the x
+  // neighbours of its lanes from its own image row (see step_ps).  A component is rounded up to a multiple of 64 floats: the accesses to
+  // two components of one (row, column) stay pairs (ds_read2st64_b32 / ds_write2st64_b32), as with rows of 64.
+  constexpr int IW = kLanes + 2;
+  constexpr int IS = (NR * IW + 63) / 64 * 64;
+  __shared__ float imgx[2][PS ? NI : 1][PS ? IS : 1];
+  __shared__ float img1[2][NI][PS ? 1 : NR][kLanes];  // stage-1 results of the row waves: S = U + dU' (SS) or dU' (SP)
+  __shared__ float hc1[2][NI][2][32];        // the same for the two halo columns: [component][side][core row] (PS: folded tiles only)
   __shared__ float img3[(ABL & 64) ? 3 : 1][(ABL & 64) ? NR : 1][(ABL & 64) ? kLanes : 1];  // lab: stage-2 results for a third stage
 
   // the workgroup's tile and planes (f3d_pair8_plan.h: the function the host API decodes with); FOLDS: the numbering described there
@@ -950,7 +957,8 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
   // u + du in plane_finish, as everywhere; `ksi` is NOT a weight here but the raw du kept beside it (phi needs u and du of the plane
   // neighbours apart, and ksi is no input); `phi` is unused -- the computed weights travel in phi_q / phC / phM / ksC.  What stage 2 --
   // the whole sweep of plane q-1 -- reads of its neighbours is finished S = U + dU and phi: published to the images by every stage-1
-  // wave (S without arithmetic), handed over between lanes by DPP and between planes in registers (hM / phM: plane q-2, M / phC: q-1).
+  // wave (S without arithmetic), handed over between lanes through the wave's own image row (a folded tile: by DPP) and between planes in
+  // registers (hM / phM: plane q-2, M / phC: q-1).
   auto row_raw_ps = [&](PlaneRegs& p, const float* slot, int j, bool centre, const float* cs) __attribute__((always_inline)) {
     const float* d = slot + j * kLanes + lane;
     constexpr int st = NJP * kLanes;
@@ -971,12 +979,16 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     p.ksi = p.su;
   };
   S3 nXd = {0.f, 0.f, 0.f}, nInd = {0.f, 0.f, 0.f};   // raw du, dv, dw of the halo column / of the tile's edge column (column wave)
-  // Row waves of a tile with one band: the two halo columns in registers of their own (nXr / nXd: the LEFT one in every lane, nXrR / nXdR:
-  // the RIGHT one).  A lane shift takes its edge value as the `old` operand, which the instruction overwrites: one register that holds
-  // the left value in lanes 0-31 and the right one in lanes 32-63 serves the two shifts of a quantity only through a copy -- six
-  // v_mov_b32 per step here and four in stage 2 -- where a second (broadcast) LDS read costs the vector unit nothing.  A folded tile has
-  // two LEFT halos and no right one: it keeps the register selected by `side`.
-  S3 nXrR = {0.f, 0.f, 0.f}, nXdR = {0.f, 0.f, 0.f};
+  // (nXr / nXd, row waves: folded tiles only -- two LEFT halos, the register selected by `side`)
+  // Row waves of a tile with one band shift no lanes at all for stage 1: the ring holds the raw row when fetch_ps runs, so every lane
+  // reads its left and its right neighbour itself -- its own ring row, one element to the left or right, lanes 0 and 63 the halo piece, and at
+  // an x face of the volume the mirrored element (pair8_x_neighbours in f3d_pair8_plan.h, the function tests/test_pair8_x_neighbours_cpu.py
+  // walks) -- with the twelve LDS reads that used to fetch the two halo columns for the shifts' edge operand, and forms the three x
+  // numerators right there (nDx, beside nDy).  The row area and the halo area of a slot have different array strides, so an address register
+  // per array and side (byte offsets inside a slot, loop-invariant, pinned in march(); the slot is an immediate).  A folded tile has two left
+  // halos and a seam at lane 32: it keeps the shifts, the carried halo values and hc1.
+  unsigned xaL[6] = {}, xaR[6] = {};
+  S3 nDx = {0.f, 0.f, 0.f};
   float phM = 0.f, phC = 0.f, ksC = 0.f;             // phi of planes q-2 and q-1, ksi of plane q-1
   // raw neighbours of the next step's plane: the y numerators ((U[y+1] - U[y-1]) + dU[y+1]) - dU[y-1] complete, the x halo raw
   auto fetch_ps = [&](auto colw_c, const float* S) __attribute__((always_inline)) {
@@ -998,16 +1010,21 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
       if constexpr (FOLD) {
         halo_raw_ps(T2, S, side, jr, e_near);
       } else {
-        PlaneRegs T3;
-        halo_raw_ps(T2, S, 0, jr, 3);
-        halo_raw_ps(T3, S, 1, jr, 0);
-        nXrR = {T3.u, T3.v, T3.w};
-        nXdR = {T3.su, T3.dv, T3.dw};
+        // the wave's own ring row, one element to the left and one to the right of every lane: u, v, w, du, dv, dw
+        float xl[6], xr[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          xl[i] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(S) + xaL[i]);
+          xr[i] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(S) + xaR[i]);
+        }
+        nDx = {((xr[0] - xl[0]) + xr[3]) - xl[3], ((xr[1] - xl[1]) + xr[4]) - xl[4], ((xr[2] - xl[2]) + xr[5]) - xl[5]};
       }
     }
     nDy = {((T1.u - T0.u) + T1.su) - T0.su, ((T1.v - T0.v) + T1.dv) - T0.dv, ((T1.w - T0.w) + T1.dw) - T0.dw};
-    nXr = {T2.u, T2.v, T2.w};
-    nXd = {T2.su, T2.dv, T2.dw};
+    if constexpr (CW || FOLD) {
+      nXr = {T2.u, T2.v, T2.w};
+      nXd = {T2.su, T2.dv, T2.dw};
+    }
   };
   auto step_ps = [&](auto colw_c, auto slot_c, PlaneRegs& M, PlaneRegs& C, PlaneRegs& P, int q) __attribute__((always_inline)) {
     constexpr bool CW = decltype(colw_c)::value;
@@ -1019,6 +1036,7 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     const float* Cp = &cring[(q + 1 - qs) & 1][0];
     const bool do1 = q <= qe;
     const int b = q & 1;
+    auto ix = [&](int buf, int comp, int row, int col) __attribute__((always_inline)) -> float& { return imgx[buf][comp][row * IW + col]; };
     if constexpr (CW) halo_raw_ps(P, Sp, side, jc, e_near);
     else row_raw_ps(P, Sp, jr, core, Cp);
     plane_finish(P);
@@ -1037,12 +1055,12 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
         rxp = rxm;
         dxp = dxm;
       }
-    } else {
-      const S3 eR = FOLD ? nXr : nXrR, edR = FOLD ? nXd : nXdR;   // (a folded tile's shift to the right never looks at its edge value)
+    } else if constexpr (FOLD) {
+      // (a folded tile's shift to the right never looks at its edge value)
       rxm = {left_or(C.u, nXr.u), left_or(C.v, nXr.v), left_or(C.w, nXr.w)};
-      rxp = {lane_right_or(C.u, eR.u), lane_right_or(C.v, eR.v), lane_right_or(C.w, eR.w)};
+      rxp = {lane_right_or(C.u, nXr.u), lane_right_or(C.v, nXr.v), lane_right_or(C.w, nXr.w)};
       dxm = {left_or(C.ksi, nXd.u), left_or(C.dv, nXd.v), left_or(C.dw, nXd.w)};
-      dxp = {lane_right_or(C.ksi, edR.u), lane_right_or(C.dv, edR.v), lane_right_or(C.dw, edR.w)};
+      dxp = {lane_right_or(C.ksi, nXd.u), lane_right_or(C.dv, nXd.v), lane_right_or(C.dw, nXd.w)};
       vx = x;
       vy = band ? y + TY : y;
       if (tile_at_x_face) {   // mirror rule at the x faces of the volume
@@ -1055,29 +1073,52 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
           dxp = dxm;
         }
       }
+    } else {   // one band: the x numerators arrive complete, mirror rule included (fetch_ps)
+      vx = x;
+      vy = y;
     }
-    float nq[9] = {((rxp.u - rxm.u) + dxp.u) - dxm.u, nDy.u, ((P.u - M.u) + P.ksi) - M.ksi,
-                   ((rxp.v - rxm.v) + dxp.v) - dxm.v, nDy.v, ((P.v - M.v) + P.dv) - M.dv,
-                   ((rxp.w - rxm.w) + dxp.w) - dxm.w, nDy.w, ((P.w - M.w) + P.dw) - M.dw};
+    float nq[9] = {0.f, nDy.u, ((P.u - M.u) + P.ksi) - M.ksi, 0.f, nDy.v, ((P.v - M.v) + P.dv) - M.dv,
+                   0.f, nDy.w, ((P.w - M.w) + P.dw) - M.dw};
+    if constexpr (CW || FOLD) {
+      nq[0] = ((rxp.u - rxm.u) + dxp.u) - dxm.u;
+      nq[3] = ((rxp.v - rxm.v) + dxp.v) - dxm.v;
+      nq[6] = ((rxp.w - rxm.w) + dxp.w) - dxm.w;
+    } else {
+      nq[0] = nDx.u;
+      nq[3] = nDx.v;
+      nq[6] = nDx.w;
+    }
     // a lane counts where a stage 2 can look at its weights: inside the volume (padding must not send the wave down the slow roads), and
     // not in the extra step of the top chunk (q = MDIM: stage 1 runs on whatever the ring holds and nobody looks at its results)
     const bool counts = do1 && vx >= 0 && vx < g.W && vy >= 0 && vy < RDIM && (!CW || cactive);
     float phi_q = 0.f, ksi_q = 0.f;
     weights_first_stage1(nq, !CW && core, C.f0, C.f1, C.fz, C.ft, C.ksi, C.dv, C.dw, sdivs, a.eps_s2, a.eps_d2, phi_q, ksi_q, counts,
                          a.plain_division == 0);
+    // One band: a row wave's lane writes image column lane + 1, the column wave the pad columns 0 and kLanes + 1 of the core rows' image
+    // rows (row wave RH + crow), so that stage 2 finds the x neighbours of lane L at [L] and [L + 2] of its own row.  A folded tile keeps
+    // hc1 and image column `lane`.
+    constexpr int IX = FOLD ? 0 : 1;
     if (do1) {
       if constexpr (CW) {
         if (cactive) {
-          hc1[b][0][side][crow] = C.su;
-          hc1[b][1][side][crow] = C.sv;
-          hc1[b][2][side][crow] = C.sw;
-          hc1[b][3][side][crow] = phi_q;
+          if constexpr (FOLD) {
+            hc1[b][0][side][crow] = C.su;
+            hc1[b][1][side][crow] = C.sv;
+            hc1[b][2][side][crow] = C.sw;
+            hc1[b][3][side][crow] = phi_q;
+          } else {
+            const int pad = side ? kLanes + 1 : 0;
+            ix(b, 0, RH + crow, pad) = C.su;
+            ix(b, 1, RH + crow, pad) = C.sv;
+            ix(b, 2, RH + crow, pad) = C.sw;
+            ix(b, 3, RH + crow, pad) = phi_q;
+          }
         }
       } else {
-        img1[b][0][r][lane] = C.su;
-        img1[b][1][r][lane] = C.sv;
-        img1[b][2][r][lane] = C.sw;
-        img1[b][3][r][lane] = phi_q;
+        ix(b, 0, r, lane + IX) = C.su;
+        ix(b, 1, r, lane + IX) = C.sv;
+        ix(b, 2, r, lane + IX) = C.sw;
+        ix(b, 3, r, lane + IX) = phi_q;
       }
     }
     if (!CW && do1 && owner && q >= z0 && q < z1) {   // the weights of the planes this chunk owns
@@ -1095,16 +1136,22 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
       const int pb = t & 1;
       const int im = band ? r_ymb : r_ym, ip = band ? r_ypb : r_yp;
       Face6 ym = {}, yp = {}, xm = {}, xp = {}, zm = {}, zp = {}, cf = {};
-      ym.v[LSU] = img1[pb][0][im][lane]; ym.v[LSV] = img1[pb][1][im][lane]; ym.v[LSW] = img1[pb][2][im][lane]; ym.v[LPHI] = img1[pb][3][im][lane];
-      yp.v[LSU] = img1[pb][0][ip][lane]; yp.v[LSV] = img1[pb][1][ip][lane]; yp.v[LSW] = img1[pb][2][ip][lane]; yp.v[LPHI] = img1[pb][3][ip][lane];
-      // the halo columns' stage-1 results: left and right in registers of their own, as the raw ones above (FOLD: both are `side`'s)
-      const int sl = FOLD ? side : 0, sr = FOLD ? side : 1;
-      const float eu = hc1[pb][0][sl][r - RH], ev = hc1[pb][1][sl][r - RH], ew = hc1[pb][2][sl][r - RH], ep = hc1[pb][3][sl][r - RH];
-      const float fu = hc1[pb][0][sr][r - RH], fv = hc1[pb][1][sr][r - RH], fw = hc1[pb][2][sr][r - RH], fp = hc1[pb][3][sr][r - RH];
+      const int li = lane + IX;
+      ym.v[LSU] = ix(pb, 0, im, li); ym.v[LSV] = ix(pb, 1, im, li); ym.v[LSW] = ix(pb, 2, im, li); ym.v[LPHI] = ix(pb, 3, im, li);
+      yp.v[LSU] = ix(pb, 0, ip, li); yp.v[LSV] = ix(pb, 1, ip, li); yp.v[LSW] = ix(pb, 2, ip, li); yp.v[LPHI] = ix(pb, 3, ip, li);
       cf.v[LSU] = M.su; cf.v[LSV] = M.sv; cf.v[LSW] = M.sw; cf.v[LPHI] = phC;
-      xm.v[LSU] = left_or(M.su, eu); xm.v[LSV] = left_or(M.sv, ev); xm.v[LSW] = left_or(M.sw, ew); xm.v[LPHI] = left_or(phC, ep);
-      xp.v[LSU] = lane_right_or(M.su, fu); xp.v[LSV] = lane_right_or(M.sv, fv); xp.v[LSW] = lane_right_or(M.sw, fw);
-      xp.v[LPHI] = lane_right_or(phC, fp);
+      if constexpr (FOLD) {
+        // the halo columns' stage-1 results (both are `side`'s) as the edge operands of lane shifts
+        const float eu = hc1[pb][0][side][r - RH], ev = hc1[pb][1][side][r - RH], ew = hc1[pb][2][side][r - RH], ep = hc1[pb][3][side][r - RH];
+        xm.v[LSU] = left_or(M.su, eu); xm.v[LSV] = left_or(M.sv, ev); xm.v[LSW] = left_or(M.sw, ew); xm.v[LPHI] = left_or(phC, ep);
+        xp.v[LSU] = lane_right_or(M.su, eu); xp.v[LSV] = lane_right_or(M.sv, ev); xp.v[LSW] = lane_right_or(M.sw, ew);
+        xp.v[LPHI] = lane_right_or(phC, ep);
+      } else {
+        // one band: the wave's own image row, written one step ago, one column to the left and one to the right
+        xm.v[LSU] = ix(pb, 0, r, lane); xm.v[LSV] = ix(pb, 1, r, lane); xm.v[LSW] = ix(pb, 2, r, lane); xm.v[LPHI] = ix(pb, 3, r, lane);
+        xp.v[LSU] = ix(pb, 0, r, lane + 2); xp.v[LSV] = ix(pb, 1, r, lane + 2); xp.v[LSW] = ix(pb, 2, r, lane + 2);
+        xp.v[LPHI] = ix(pb, 3, r, lane + 2);
+      }
       zm.v[LSU] = hM.u; zm.v[LSV] = hM.v; zm.v[LSW] = hM.w; zm.v[LPHI] = phM;
       zp.v[LSU] = C.su; zp.v[LSV] = C.sv; zp.v[LSW] = C.sw; zp.v[LPHI] = phi_q;
       // mirror rule at the faces of the volume: the missing neighbour is the opposite one
@@ -1161,6 +1208,20 @@ __device__ __forceinline__ void pair8_body(const PairArgs& a, const F3dGeo& g, c
     plane_finish(B);
     int q = qs;
     if constexpr (PS) {
+      if constexpr (!CW && !FOLD) {
+        // where this lane's x neighbours lie in a slot (see xaL): formed once, and pinned -- left to itself the compiler makes the
+        // selects of lanes 0 and 63 and of the mirror lanes again in every step
+        static_assert(pair8_slot_halo_off(L::NS, NJ) == L::kHaloOff && pair8_slot_floats(L::NS, NJ) == L::kSlotFloats && L::NS == 6 && NJP == NJ,
+                      "pair8_x_neighbour_offset describes this slot");
+        const Pair8XNeighbours xn = pair8_x_neighbours(lane, x0, g.W);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          xaL[i] = 4u * static_cast<unsigned>(pair8_x_neighbour_offset(xn.left, i, jr, L::NS, NJ));
+          xaR[i] = 4u * static_cast<unsigned>(pair8_x_neighbour_offset(xn.right, i, jr, L::NS, NJ));
+          asm volatile("" : "+v"(xaL[i]));
+          asm volatile("" : "+v"(xaR[i]));
+        }
+      }
       fetch_ps(colw_c, S0);
       for (; q + 2 <= q_end; q += 3) {
         step_ps(colw_c, Slot2{}, A, B, Cc, q);
