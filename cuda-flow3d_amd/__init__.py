@@ -162,6 +162,36 @@ class LabelShape(C.Structure):  # f3d_label_shape
                 ("euler", C.c_longlong)]
 
 
+class Overlap(C.Structure):  # struct f3d_overlap: the exact sums of one pair (label of A, label of B)
+    _fields_ = [("a", C.c_int), ("b", C.c_int), ("n", C.c_ulonglong), ("ca2", C.c_longlong * 3), ("cb2", C.c_longlong * 3)]
+
+
+class OverlapInfo(C.Structure):  # f3d_overlap_info: every voxel of the volume in exactly one of the first six counters
+    _fields_ = [(name, C.c_ulonglong) for name in ("foreign_a", "lost_background", "lost_body", "foreign_b", "background", "overlap",
+                                                   "table_lost", "n_pairs")] + [("complete", C.c_int)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TrackA(C.Structure):  # f3d_track_a
+    _fields_ = [("n", C.c_ulonglong), ("n_lost", C.c_ulonglong), ("n_background", C.c_ulonglong), ("n_best", C.c_ulonglong),
+                ("best_b", C.c_int), ("n_targets", C.c_int), ("fraction", C.c_double), ("shift", C.c_double * 3), ("iou", C.c_double),
+                ("status", C.c_uint)]
+
+
+class TrackB(C.Structure):  # f3d_track_b
+    _fields_ = [("m", C.c_ulonglong), ("n_unreached", C.c_ulonglong), ("n_best", C.c_ulonglong), ("best_a", C.c_int),
+                ("n_sources", C.c_int), ("status", C.c_uint)]
+
+
+class TrackSummary(C.Structure):  # f3d_track_summary
+    _fields_ = [(name, C.c_ulonglong) for name in ("matched", "split", "merged", "vanished", "appeared", "left", "n_ids")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class ComponentInfo(C.Structure):  # f3d_component_info: every voxel of the box in exactly one of foreground and background
     _fields_ = [(name, C.c_ulonglong) for name in ("foreground", "background", "nan", "n_components", "n_labels", "dropped_components",
                                                    "dropped_voxels", "largest")]
@@ -422,6 +452,15 @@ def host():
         "f3d_flow_labels_split": [C.c_void_p, _dp, C.c_float, C.c_float, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.POINTER(C.c_ulonglong)),
                                   C.POINTER(_sz), C.POINTER(SplitInfo)],
         "f3d_flow_labels_end": [C.c_void_p], "f3d_flow_labels_download": [C.c_void_p, C.POINTER(C.c_int)],
+        "f3d_overlap_solve": [C.POINTER(Overlap), _sz, _sz, _sz, C.c_double, C.POINTER(TrackA), C.POINTER(TrackB), C.POINTER(C.c_int),
+                              C.POINTER(TrackSummary)],
+        "f3d_flow_labels_b_upload": [C.c_void_p, C.POINTER(C.c_int)],
+        "f3d_flow_labels_b_segment": [C.c_void_p, _dp, C.c_float, C.c_float, C.c_ulonglong, C.c_ulonglong,
+                                      C.POINTER(C.POINTER(C.c_ulonglong)), C.POINTER(_sz), C.POINTER(SplitInfo)],
+        "f3d_flow_overlap_compute": [C.c_void_p, C.c_int, _sz, _sz, C.POINTER(C.POINTER(Overlap)), C.POINTER(_sz), C.POINTER(OverlapInfo)],
+        "f3d_flow_overlap_end": [C.c_void_p],
+        "f3d_flow_labels_b_relabel": [C.c_void_p, C.POINTER(C.c_int), _sz],
+        "f3d_flow_labels_b_download": [C.c_void_p, C.POINTER(C.c_int)],
         "f3d_histogram_edge": [C.c_float, C.c_float, _sz, _sz, _fp],
         "f3d_otsu": [C.POINTER(C.c_ulonglong), _sz, C.c_int, C.POINTER(C.c_uint), C.POINTER(OtsuInfo)],
         "f3d_histogram_rank": [C.POINTER(C.c_ulonglong), _sz, C.c_ulonglong, C.POINTER(C.c_uint)],
@@ -642,6 +681,16 @@ def _contacts_entry():
 def _label_shape_entry():
     return _entry("f3d_label_shape_sums", [_dp] + [_sz] * 4 + [C.POINTER(LabelShapeSums), C.POINTER(LabelShapeInfo)],
                   "sum the shapes of the labels of a segmentation")
+
+
+def _overlap_entry():
+    return _entry("f3d_label_overlap", [_dp, _sz, _dp, _sz] + [_dp] * 3 + [_sz] * 4 + [C.POINTER(Overlap), C.POINTER(OverlapInfo)],
+                  "find the overlap of two label volumes")
+
+
+def _relabel_entry():
+    return _entry("f3d_relabel_labels", [_dp, _sz, C.POINTER(C.c_int), _dp] + [_sz] * 3 + [C.POINTER(C.c_ulonglong)],
+                  "give the bodies of a label volume new numbers")
 
 
 def _components_entry():
@@ -1350,6 +1399,165 @@ def label_shapes(labels, n_labels=None):
     shapes = solve_label_shapes(sums)
     shapes.info = info
     return shapes
+
+
+MAX_OVERLAPS = 1 << 24
+# the bits of the status of a body after solve_overlaps (F3D_TRACK_*)
+TRACK_STATUS = {"empty": 1, "matched": 2, "split": 4, "vanished": 8, "left": 16, "merged": 32, "appeared": 64}
+_OVERLAP_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("n", "<u8"), ("ca2", "<i8", 3), ("cb2", "<i8", 3)])
+_TRACK_A_DTYPE = np.dtype([("n", "<u8"), ("n_lost", "<u8"), ("n_background", "<u8"), ("n_best", "<u8"), ("best_b", "<i4"),
+                           ("n_targets", "<i4"), ("fraction", "<f8"), ("shift", "<f8", 3), ("iou", "<f8"), ("status", "<u4"), ("pad", "<u4")])
+_TRACK_B_DTYPE = np.dtype([("m", "<u8"), ("n_unreached", "<u8"), ("n_best", "<u8"), ("best_a", "<i4"), ("n_sources", "<i4"),
+                           ("status", "<u4"), ("pad", "<u4")])
+
+
+class Overlaps:
+    """The overlap of two label volumes through a displacement (label_overlap): arrays over the pairs, sorted by (a, b).  .a, .b (the
+    labels; b == -1 is the part of body a that left the volume, b == 0 the part that landed on background, a == 0 the part of body b
+    nothing reached), .n (voxels), .ca2, .cb2 (N, 3: the sums of the doubled source and target coordinates about the volume centre),
+    all exact integers, and .info, the dict of f3d_overlap_info.  .rows is the C array f3d_overlap_solve takes."""
+
+    def __init__(self, rows, count, info):
+        self.rows, self.info = rows, info
+        table = np.frombuffer(rows, dtype=_OVERLAP_DTYPE, count=count) if count else np.zeros(0, _OVERLAP_DTYPE)
+        self.a, self.b, self.n = table["a"].copy(), table["b"].copy(), table["n"].copy()
+        self.ca2, self.cb2 = table["ca2"].copy(), table["cb2"].copy()
+
+    def __len__(self):
+        return len(self.a)
+
+    def matrix(self, n_a=None, n_b=None):
+        """the voxel counts as a mapping: {(a, b): n} without n_a and n_b, else a dense (n_a + 1, n_b + 2) uint64 array whose row is a
+        and whose column is b + 1 (column 0 is what left the volume), for small numbers of bodies"""
+        if n_a is None or n_b is None:
+            return {(int(a), int(b)): int(n) for a, b, n in zip(self.a, self.b, self.n)}
+        dense = np.zeros((int(n_a) + 1, int(n_b) + 2), np.uint64)
+        dense[self.a, self.b + 1] = self.n
+        return dense
+
+    def as_table(self):
+        """one dict per pair: a, b, n, ca2, cb2 (Python integers) and shift, (cb2 - ca2) / (2 n), None for b == -1"""
+        return [{"a": int(self.a[i]), "b": int(self.b[i]), "n": int(self.n[i]), "ca2": self.ca2[i].tolist(), "cb2": self.cb2[i].tolist(),
+                 "shift": None if self.b[i] < 0 else [(int(q) - int(p)) / (2 * int(self.n[i])) for p, q in zip(self.ca2[i], self.cb2[i])]}
+                for i in range(len(self))]
+
+
+def _overlap_capacity(capacity, n_a, n_b):
+    """(the first capacity, whether to retry with twice the room): capacity None starts at 8 * (n_a + n_b), at most 2^20"""
+    if capacity is None:
+        return min(8 * (n_a + n_b), 1 << 20), True
+    capacity = int(capacity)
+    if not 1 <= capacity <= MAX_OVERLAPS:
+        raise ValueError(f"capacity must be 1 .. {MAX_OVERLAPS}, not {capacity}")
+    return capacity, False
+
+
+def label_overlap(labels_a, labels_b, u=None, v=None, w=None, n_a=None, n_b=None, capacity=None):
+    """The overlap of two label volumes on the device (include/f3d.h, f3d_label_overlap): labels_a an integer [z, y, x] volume on the
+    grid of the displacement u, v, w (numpy [z, y, x] float32, or all three None for the identity), labels_b one of the same shape on
+    the grid the displacement leads to; 0 background, 1 .. n_a / n_b the bodies, anything else foreign; n_a / n_b None means the
+    volume's maximum.  capacity is the room for distinct pairs: None starts at 8 * (n_a + n_b) (at most 2^20) and doubles until the
+    table is complete; a given capacity is tried once, and an Overlaps with no rows and info["complete"] == 0 comes back when it does
+    not suffice.  Returns an Overlaps."""
+    fn = _overlap_entry()
+    given = [x is not None for x in (u, v, w)]
+    if any(given) and not all(given):
+        raise ValueError("u, v and w must be given all three or not at all")
+    bits_a, n_a = _labels_as_float_bits(labels_a, n_a)
+    bits_b, n_b = _labels_as_float_bits(labels_b, n_b)
+    capacity, retry = _overlap_capacity(capacity, n_a, n_b)
+    vols = (bits_a, bits_b, u, v, w) if all(given) else (bits_a, bits_b)
+    with _on_device(vols, "labels_a, labels_b and u, v, w must be [z, y, x] volumes of one shape") as (box, p, dims):
+        box.set_current()
+        d = p[2:] if all(given) else [0, 0, 0]
+        while True:
+            rows, info = (Overlap * capacity)(), OverlapInfo()
+            check(fn(p[0], n_a, p[1], n_b, *d, *dims, capacity, rows, C.byref(info)), "f3d_label_overlap")
+            if info.complete or not retry or capacity >= MAX_OVERLAPS:
+                break
+            capacity = min(2 * capacity, MAX_OVERLAPS)
+    assert C.sizeof(Overlap) == _OVERLAP_DTYPE.itemsize
+    return Overlaps(rows, int(info.n_pairs) if info.complete else 0, info.as_dict())
+
+
+class Tracks:
+    """The tracks of the bodies of two label volumes (solve_overlaps): .a, a structured array over the bodies of A (body a at index
+    a - 1: n, n_lost, n_background, n_best, best_b, n_targets, fraction, shift, iou, status), .b, one over the bodies of B (m,
+    n_unreached, n_best, best_a, n_sources, status), status being bits of TRACK_STATUS; .map_b (int32: the number every body of B
+    takes so that a matched body carries the number of its body of A, new bodies n_a + 1 .., 0 for a body nothing landed in);
+    .summary (dict: matched, split, merged, vanished, appeared, left, n_ids); .info, the dict of f3d_overlap_info when the overlaps
+    came from the device in the same call, else None; .relabelled, B under the new numbers when the call made it, else None."""
+
+    def __init__(self, a, b, map_b, summary, info=None):
+        self.a, self.b, self.map_b, self.summary, self.info = a, b, map_b, summary, info
+        self.relabelled = None
+
+    @staticmethod
+    def _words(status):
+        return [name for name, bit in TRACK_STATUS.items() if status & bit]
+
+    def as_table(self):
+        """one dict per body, those of A first: side ("a" / "b"), label, status (a list of the words of TRACK_STATUS), then the fields"""
+        rows = []
+        for side, table in (("a", self.a), ("b", self.b)):
+            for i in range(len(table)):
+                row = {"side": side, "label": i + 1, "status": self._words(int(table["status"][i]))}
+                row.update({name: table[name][i].tolist() for name in table.dtype.names if name not in ("status", "pad")})
+                if side == "b":
+                    row["new_label"] = int(self.map_b[i])
+                rows.append(row)
+        return rows
+
+
+def solve_overlaps(overlaps, n_a, n_b, min_fraction=0.1):
+    """f3d_overlap_solve (include/f3d_host.h; host code, no device): the Tracks of an Overlaps of volumes with n_a and n_b bodies.  A
+    partner counts as a target (source) when it holds at least min_fraction, in (0, 1], of the body's voxels."""
+    n_a, n_b, min_fraction = int(n_a), int(n_b), float(min_fraction)
+    if not (1 <= n_a <= MAX_LABELS and 1 <= n_b <= MAX_LABELS):
+        raise ValueError(f"n_a and n_b must be 1 .. {MAX_LABELS}, not {n_a} and {n_b}")
+    if not 0.0 < min_fraction <= 1.0:
+        raise ValueError(f"min_fraction must be in (0, 1], not {min_fraction}")
+    a, b, map_b, summary = (TrackA * n_a)(), (TrackB * n_b)(), np.zeros(n_b, np.int32), TrackSummary()
+    _host_check(host().f3d_overlap_solve(overlaps.rows, len(overlaps), n_a, n_b, min_fraction, a, b, map_b.ctypes.data_as(C.POINTER(C.c_int)),
+                                         C.byref(summary)), "f3d_overlap_solve")
+    assert C.sizeof(TrackA) == _TRACK_A_DTYPE.itemsize and C.sizeof(TrackB) == _TRACK_B_DTYPE.itemsize
+    return Tracks(np.frombuffer(a, _TRACK_A_DTYPE, n_a).copy(), np.frombuffer(b, _TRACK_B_DTYPE, n_b).copy(), map_b, summary.as_dict())
+
+
+def relabel_labels(labels, mapping, count_foreign=False):
+    """New numbers for the bodies of a label volume on the device (include/f3d.h, f3d_relabel_labels): an int32 [z, y, x] volume with
+    mapping[l - 1] where labels == l in 1 .. len(mapping) and 0 elsewhere.  No entry of mapping may be negative; two labels may share a
+    number.  With count_foreign, (volume, the number of voxels outside 0 .. len(mapping))."""
+    fn = _relabel_entry()
+    mapping = np.ascontiguousarray(mapping)
+    if mapping.ndim != 1 or not np.issubdtype(mapping.dtype, np.integer):
+        raise ValueError("mapping must be a one-dimensional array of integers, the new number of label l at index l - 1")
+    if mapping.size and (int(mapping.min()) < 0 or int(mapping.max()) > 2 ** 31 - 1):
+        raise ValueError("the entries of mapping must be 0 .. 2^31 - 1")
+    bits, n = _labels_as_float_bits(labels, len(mapping))
+    mapping = mapping.astype(np.int32)
+    with _on_device((bits,), "labels must be a [z, y, x] volume") as (box, p, dims):
+        box.set_current()
+        foreign = C.c_ulonglong()
+        check(fn(p[0], n, mapping.ctypes.data_as(C.POINTER(C.c_int)), p[0], *dims, C.byref(foreign)), "f3d_relabel_labels")
+        out = box.download(p[0], dims).view(np.int32)
+    return (out, int(foreign.value)) if count_foreign else out
+
+
+def track_labels(labels_a, labels_b, u=None, v=None, w=None, min_fraction=0.1, n_a=None, n_b=None):
+    """Which body of B is which body of A, from anywhere: label_overlap on the device, solve_overlaps on the host, relabel_labels of B
+    on the device.  Returns a Tracks with .info and .relabelled (B under the numbers of A: a matched body carries the number of its body
+    of A, every other body a new one)."""
+    overlaps = label_overlap(labels_a, labels_b, u, v, w, n_a, n_b)
+    if not overlaps.info["complete"]:
+        raise F3dError(f"label_overlap: the two label volumes have more than {MAX_OVERLAPS} distinct pairs")
+    n_a = int(np.max(labels_a)) if n_a is None else int(n_a)
+    n_b = int(np.max(labels_b)) if n_b is None else int(n_b)
+    tracks = solve_overlaps(overlaps, n_a, n_b, min_fraction)
+    tracks.info = overlaps.info
+    tracks.overlaps = overlaps
+    tracks.relabelled = relabel_labels(labels_b, tracks.map_b)
+    return tracks
 
 
 class Components:
@@ -2456,7 +2664,85 @@ class OpticalFlow:
         labels = np.empty((d, h, w), np.int32)
         _host_check(host().f3d_flow_labels_download(self._h, labels.ctypes.data_as(C.POINTER(C.c_int))), "f3d_flow_labels_download")
         self._segmented_labels = int(info.n_labels)            # what label_shapes() takes for n_labels when it is not given
+        self._segment_settled = (lo, hi, min_voxels, split)    # what segment_next() repeats on the later frame: the cuts as numbers
         return Components(labels, own, info.as_dict())
+
+    def segment_next(self, lo=None, hi=None, min_voxels=None, split=None):
+        """The bodies of the resident LATER frame (the raw frame 1 of the last upload()), labelled on the device into a second label
+        volume, "B", beside the one segment() fills: a Components, after which track() finds which body of it is which body of frame
+        0.  lo, hi, min_voxels and split as in segment(), numbers only; with all four None, what the last segment() settled (an Otsu
+        cut of frame 0 is kept as the number it came to and not taken again on this frame)."""
+        if lo is None and hi is None and min_voxels is None and split is None:
+            settled = getattr(self, "_segment_settled", None)
+            if settled is None:
+                raise ValueError("segment_next() without arguments repeats the last segment(), and there was none")
+            lo, hi, min_voxels, split = settled
+        else:
+            lo = -np.inf if lo is None else lo
+            hi = np.inf if hi is None else hi
+            if isinstance(lo, str) or isinstance(hi, str):
+                raise ValueError("segment_next() takes numbers for lo and hi: an Otsu cut is not taken again on the later frame")
+            lo, hi, min_voxels = _component_range(lo, hi, 27 if min_voxels is None else min_voxels)
+        w, h, d = self.dims
+        sizes, count, info = C.POINTER(C.c_ulonglong)(), _sz(0), SplitInfo()
+        core_d2 = 0 if split is None else _core_d2(None, split)
+        _host_check(host().f3d_flow_labels_b_segment(self._h, 0, lo, hi, core_d2, min_voxels, C.byref(sizes), C.byref(count), C.byref(info)),
+                    "f3d_flow_labels_b_segment")
+        own = np.array(sizes[:count.value], np.uint64)         # the driver owns its list: a copy outlives the next call
+        labels = np.empty((d, h, w), np.int32)
+        _host_check(host().f3d_flow_labels_b_download(self._h, labels.ctypes.data_as(C.POINTER(C.c_int))), "f3d_flow_labels_b_download")
+        self._segmented_labels_b = int(info.n_labels)
+        found = info.as_dict()
+        if split is None:                                      # the counters of f3d_component_info alone
+            found = {name: found[name] for name, _ in ComponentInfo._fields_}
+        return Components(labels, own, found)
+
+    def track(self, labels_b=None, source="flow", n_a=None, n_b=None, min_fraction=0.1, relabel=True):
+        """Which body of the second label volume is which body of the labels on frame 0's grid, through the flow the driver holds
+        (source="flow") or the trajectory (source="trajectory"): f3d_label_overlap on the device, f3d_overlap_solve on the host and,
+        with relabel, f3d_relabel_labels of the second volume on the device.  labels_b: an integer [z, y, x] volume on the grid the
+        displacement leads to, or None for the bodies segment_next() left on the device.  n_a / n_b None mean the number of bodies of
+        the last segment() / segment_next() (labels_b.max() when labels_b is given).  Returns a Tracks with .info, .overlaps and, with
+        relabel, .relabelled: the second volume under frame 0's numbers, which also replaces it on the device."""
+        w, h, d = self.dims
+        if labels_b is not None:
+            bits, n_b = _labels_as_float_bits(labels_b, n_b)
+            if bits.shape != (d, h, w):
+                raise ValueError(f"labels_b must be a [z, y, x] volume of shape {(d, h, w)}")
+            lab = bits.view(np.int32)
+            _host_check(host().f3d_flow_labels_b_upload(self._h, lab.ctypes.data_as(C.POINTER(C.c_int))), "f3d_flow_labels_b_upload")
+        elif n_b is None:
+            n_b = getattr(self, "_segmented_labels_b", None)
+        if n_a is None:
+            n_a = getattr(self, "_segmented_labels", None)
+        if n_a is None or n_b is None:
+            raise ValueError("n_a and n_b are required when the labels on the device were not made by segment() and segment_next()")
+        n_a, n_b = int(n_a), int(n_b)
+        if not (1 <= n_a <= MAX_LABELS and 1 <= n_b <= MAX_LABELS):
+            raise ValueError(f"n_a and n_b must be 1 .. {MAX_LABELS}, not {n_a} and {n_b}")
+        if not 0.0 < float(min_fraction) <= 1.0:
+            raise ValueError(f"min_fraction must be in (0, 1], not {min_fraction}")
+        rows, count, info = C.POINTER(Overlap)(), _sz(0), OverlapInfo()
+        _host_check(host().f3d_flow_overlap_compute(self._h, _source(source), n_a, n_b, C.byref(rows), C.byref(count), C.byref(info)),
+                    "f3d_flow_overlap_compute")
+        own = (Overlap * max(count.value, 1))()                # the driver owns its list: a copy outlives the next call
+        if count.value:
+            C.memmove(own, rows, count.value * C.sizeof(Overlap))
+        overlaps = Overlaps(own, count.value, info.as_dict())
+        tracks = solve_overlaps(overlaps, n_a, n_b, min_fraction)
+        tracks.info, tracks.overlaps = overlaps.info, overlaps
+        if relabel:
+            _host_check(host().f3d_flow_labels_b_relabel(self._h, tracks.map_b.ctypes.data_as(C.POINTER(C.c_int)), n_b),
+                        "f3d_flow_labels_b_relabel")
+            tracks.relabelled = np.empty((d, h, w), np.int32)
+            _host_check(host().f3d_flow_labels_b_download(self._h, tracks.relabelled.ctypes.data_as(C.POINTER(C.c_int))),
+                        "f3d_flow_labels_b_download")
+            self._segmented_labels_b = max(int(tracks.summary["n_ids"]), 1)   # the second volume now carries these numbers
+        return tracks
+
+    def track_end(self):
+        """free the driver's list of overlaps (both label volumes stay on the device until label_motion_end() or destroy())"""
+        _host_check(host().f3d_flow_overlap_end(self._h), "f3d_flow_overlap_end")
 
     def label_shapes(self, labels=None, n_labels=None):
         """The shape table of a segmentation on the grid of the driver: a LabelShapes (see there) with .info.  labels: an integer

@@ -8,6 +8,7 @@
 #include "f3d_host.h"
 #include "contact_kinematics.h"
 #include "label_shape.h"
+#include "label_track.h"
 #include "hip_utils.h"
 #include "motion_fit.h"
 #include "operations.h"
@@ -26,6 +27,8 @@ struct f3d_flow_s {
   bool zncc_of_held_flow = false;  // the match container holds the zncc of the flow the driver holds (f3d_flow_motion_compute's mask)
   std::vector<f3d_contact> contacts;  // what f3d_flow_contacts_compute hands out
   std::vector<unsigned long long> label_sizes;  // what f3d_flow_labels_compute hands out
+  std::vector<unsigned long long> label_b_sizes;  // what f3d_flow_labels_b_segment hands out
+  std::vector<f3d_overlap> overlaps;  // what f3d_flow_overlap_compute hands out
 };
 
 struct f3d_slabflow_s {
@@ -515,6 +518,7 @@ int f3d_flow_labels_end(f3d_flow flow)
   g_host_error.clear();
   if (!flow) return HostFail("f3d_flow_labels_end: null driver");
   std::vector<unsigned long long>().swap(flow->label_sizes);
+  std::vector<unsigned long long>().swap(flow->label_b_sizes);
   return 0;
 }
 
@@ -523,6 +527,73 @@ int f3d_flow_labels_download(f3d_flow flow, int* labels)
   g_host_error.clear();
   if (!flow || !labels) return HostFail("f3d_flow_labels_download: null argument");
   if (!flow->driver.DownloadLabels(labels)) return HostFail(flow->driver.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  return 0;
+}
+
+int f3d_overlap_solve(const struct f3d_overlap* rows, size_t count, size_t n_a, size_t n_b, double min_fraction, f3d_track_a* a,
+                      f3d_track_b* b, int* map_b, f3d_track_summary* summary)
+{
+  g_host_error.clear();
+  if ((count && !rows) || !a || !b || !map_b) return HostFail("f3d_overlap_solve: null argument");
+  if (n_a == 0 || n_b == 0) return HostFail("f3d_overlap_solve: n_a and n_b must be at least 1");
+  std::string why;
+  return SolveOverlaps(rows, count, n_a, n_b, min_fraction, a, b, map_b, summary, &why) ? 0 : HostFail(why.c_str());
+}
+
+int f3d_flow_labels_b_upload(f3d_flow flow, const int* labels)
+{
+  g_host_error.clear();
+  if (!flow || !labels) return HostFail("f3d_flow_labels_b_upload: null argument");
+  if (!flow->driver.UploadLabelsB(labels)) return HostFail(flow->driver.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  return 0;
+}
+
+int f3d_flow_labels_b_segment(f3d_flow flow, f3d_devptr frame, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
+                              const unsigned long long** sizes, size_t* count, f3d_split_info* info)
+{
+  g_host_error.clear();
+  if (!flow || !sizes || !count || !info) return HostFail("f3d_flow_labels_b_segment: null argument");
+  OpticalFlowE& d = flow->driver;
+  if (!d.ComputeLabelsB(frame, lo, hi, core_d2, min_voxels, &flow->label_b_sizes, info))
+    return HostFail(d.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  *sizes = flow->label_b_sizes.data();
+  *count = flow->label_b_sizes.size();
+  return 0;
+}
+
+int f3d_flow_overlap_compute(f3d_flow flow, int source, size_t n_a, size_t n_b, const struct f3d_overlap** rows, size_t* count,
+                             f3d_overlap_info* info)
+{
+  OpticalFlowE::Displacement of;
+  if (!DerivedSource(flow, source, rows && count && info, "f3d_flow_overlap_compute", &of)) return 1;
+  OpticalFlowE& d = flow->driver;
+  if (!d.ComputeOverlap(of, n_a, n_b, &flow->overlaps, info)) return HostFail(d.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  *rows = flow->overlaps.data();
+  *count = flow->overlaps.size();
+  return 0;
+}
+
+int f3d_flow_overlap_end(f3d_flow flow)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_overlap_end: null driver");
+  std::vector<f3d_overlap>().swap(flow->overlaps);
+  return 0;
+}
+
+int f3d_flow_labels_b_relabel(f3d_flow flow, const int* map, size_t n_b)
+{
+  g_host_error.clear();
+  if (!flow || !map) return HostFail("f3d_flow_labels_b_relabel: null argument");
+  if (!flow->driver.RelabelB(map, n_b)) return HostFail(flow->driver.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  return 0;
+}
+
+int f3d_flow_labels_b_download(f3d_flow flow, int* labels)
+{
+  g_host_error.clear();
+  if (!flow || !labels) return HostFail("f3d_flow_labels_b_download: null argument");
+  if (!flow->driver.DownloadLabelsB(labels)) return HostFail(flow->driver.DerivedError(OpticalFlowE::kLabelMotion).c_str());
   return 0;
 }
 

@@ -104,6 +104,14 @@
 // row per label -- label, status, voxels, the bounding box, the voxels on the two box faces of each axis, centroid, diameter of the ball
 // of the same volume, the three semi-axes and their directions, staircase faces, the Cauchy-Crofton surface, sphericity and the Euler
 // number -- and one line sums it up.  It needs no displacement; every other output is the same with and without it.
+// --segment ... --track [--track-min-fraction F] follows the bodies from frame to frame.  While pair k is resident the RAW frame k+1 is
+// segmented into a second label volume with what --segment settled for frame 0 -- the thresholds as numbers, --segment-min-voxels and the
+// split; an Otsu cut is the number it came to on frame 0 and is not taken again per frame.  The overlap of frame 0's bodies with these
+// through the pair's flow or, with --cumulative, the displacement from frame 0 (the validated one under --use-validated) is counted on
+// the device (f3d_label_overlap), solved on the host (f3d_overlap_solve: a share of at least F, default 0.1, counts) and the later
+// frame's bodies are renumbered on the device (f3d_relabel_labels).  <tag>_tracks.csv has a row per body of frame 0 (side a) and then
+// per body of frame k+1 (side b); <tag>_tracked-labels.raw is frame k+1's bodies under frame 0's numbers, new bodies after them; one
+// line sums it up.  With more than two frames it needs --cumulative; every other output is the same with and without it.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -141,7 +149,9 @@ static void Usage()
               "              [--segment LO:HI [--segment-min-voxels K]]\n"
               "              [--segment-split R | --segment-split-d2 N]\n"
               "              [--segment with otsu, or otsu1 / otsu2, in place of LO or HI] [--segment-bins B] [--segment-range A:B]\n"
-              "              [--histogram]\n");
+              "              [--histogram]\n"
+              "              [--segment ... --track [--track-min-fraction F]]  (frame k+1 is cut at the numbers --segment settled\n"
+              "               for frame 0; an Otsu cut is not taken again per frame)\n");
 }
 
 int main(int argc, char** argv)
@@ -192,6 +202,9 @@ int main(int argc, char** argv)
   float segment_range[2] = {0.f, 0.f};  // --segment-range A:B
   bool segment_range_given = false;
   bool histogram = false;          // --histogram
+  bool track = false;              // --track
+  double track_min_fraction = 0.1; // --track-min-fraction F
+  bool track_min_given = false;
   int segment_split_given = 0;            // --segment-split R and --segment-split-d2 N, counted
   unsigned long long segment_core_d2 = 0;  // 0: no split
   const unsigned inverse_iterations = 32;
@@ -451,6 +464,18 @@ int main(int argc, char** argv)
     }
     else if (a == "--contacts") contacts = true;
     else if (a == "--label-shape") label_shape = true;
+    else if (a == "--track") track = true;
+    else if (a == "--track-min-fraction") {
+      need(1);
+      char* rest = nullptr;
+      track_min_fraction = std::strtod(argv[++i], &rest);
+      if (rest == argv[i] || *rest || !(track_min_fraction > 0.0 && track_min_fraction <= 1.0)) {
+        std::printf("--track-min-fraction %s: F must be in (0, 1]\n", argv[i]);
+        Usage();
+        return 64;
+      }
+      track_min_given = true;
+    }
     else if (a == "--segment") {
       need(1);
       // LO:HI, either side empty for an open bound; anything else, a NaN or LO > HI is malformed
@@ -667,6 +692,23 @@ int main(int argc, char** argv)
   }
   if ((segment_bins_given || segment_range_given) && !segment_token[0] && !segment_token[1] && !histogram) {
     std::printf("--segment-bins and --segment-range lay the bins of a histogram: they need otsu, otsu1 or otsu2 in --segment, or --histogram\n");
+    Usage();
+    return 64;
+  }
+  if ((track && !segment) || (track_min_given && !track)) {
+    std::printf("--track follows the bodies --segment makes: it needs --segment, and --track-min-fraction needs --track\n");
+    Usage();
+    return 64;
+  }
+  if (track && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--track needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if (track && !synthetic && files.size() > 2 && !cumulative) {
+    std::printf("--track of more than two frames needs --cumulative: the labels live on frame 0's grid, and only the displacement from "
+                "frame 0 lives there too\n");
     Usage();
     return 64;
   }
@@ -1303,6 +1345,73 @@ int main(int argc, char** argv)
     f.print(k);
   };
 
+  // --track: no field of voxels either.  Pair k is resident, so its raw later frame is: the bodies of frame k+1 with the numbers
+  // --segment settled, their overlap with frame 0's bodies through `of`, the solve, the new numbers, and the two files, all before
+  // the next solve is enqueued (every call waits for the stream).  0: fine; otherwise the exit status.
+  size_t track_n_a = 0;  // the bodies of frame 0 (segment_frame_0)
+  auto track_pair = [&](size_t k, const OpticalFlowE::Displacement& of) {
+    const auto failed = [&]() {
+      std::printf("Error: %s\n", optical_flow_e.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+      return 3;
+    };
+    f3d_split_info later = {};
+    if (!optical_flow_e.ComputeLabelsB(0, segment_lo, segment_hi, segment_core_d2, segment_min_voxels, nullptr, &later)) return failed();
+    if (later.n_labels > (1ull << 22)) {
+      std::printf("Error: --track found %llu bodies in frame %zu and takes at most %d: raise --segment-min-voxels (now %llu)\n",
+                  later.n_labels, k + 1, 1 << 22, segment_min_voxels);
+      return 3;
+    }
+    // a frame without a body still has an answer: every body of frame 0 vanished.  Body 1 then has no voxel and comes out empty.
+    const size_t n_b = std::max<size_t>(1, static_cast<size_t>(later.n_labels));
+    std::vector<f3d_overlap> rows;
+    f3d_overlap_info counted = {};
+    if (!optical_flow_e.ComputeOverlap(validated_or(of), track_n_a, n_b, &rows, &counted)) return failed();
+    std::vector<f3d_track_a> a(track_n_a);
+    std::vector<f3d_track_b> b(n_b);
+    std::vector<int> map_b(n_b);
+    f3d_track_summary sum = {};
+    if (f3d_overlap_solve(rows.data(), rows.size(), track_n_a, n_b, track_min_fraction, a.data(), b.data(), map_b.data(), &sum)) {
+      std::printf("Error: %s\n", f3d_host_last_error());
+      return 3;
+    }
+    std::vector<int> volume(width * height * depth);
+    if (!optical_flow_e.RelabelB(map_b.data(), n_b) || !optical_flow_e.DownloadLabelsB(volume.data())) return failed();
+    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
+    std::FILE* raw = std::fopen((tag + "_tracked-labels.raw").c_str(), "wb");
+    const bool raw_good = raw && std::fwrite(volume.data(), sizeof(int), volume.size(), raw) == volume.size();
+    if ((raw && std::fclose(raw) != 0) || !raw_good) {
+      std::printf("Error: cannot write %s_tracked-labels.raw\n", tag.c_str());
+      return 2;
+    }
+    std::FILE* csv = std::fopen((tag + "_tracks.csv").c_str(), "w");
+    double iou_sum = 0.0;
+    if (csv) {
+      std::fprintf(csv, "side,label,status,voxels,lost,background,unreached,best,n_best,partners,fraction,shift_x,shift_y,shift_z,iou,new_label\n");
+      for (size_t i = 0; i < a.size(); ++i) {
+        const f3d_track_a& t = a[i];
+        std::fprintf(csv, "a,%zu,%u,%llu,%llu,%llu,0,%d,%llu,%d,%.9g,%.9g,%.9g,%.9g,%.9g,%zu\n", i + 1, t.status, t.n, t.n_lost, t.n_background,
+                     t.best_b, t.n_best, t.n_targets, t.fraction, t.shift[0], t.shift[1], t.shift[2], t.iou, i + 1);
+      }
+      for (size_t i = 0; i < b.size(); ++i) {
+        const f3d_track_b& t = b[i];
+        std::fprintf(csv, "b,%zu,%u,%llu,0,0,%llu,%d,%llu,%d,nan,nan,nan,nan,nan,%d\n", i + 1, t.status, t.m, t.n_unreached, t.best_a, t.n_best,
+                     t.n_sources, map_b[i]);
+      }
+    }
+    const bool csv_error = csv && std::ferror(csv) != 0;
+    if (!csv || std::fclose(csv) != 0 || csv_error) {
+      std::printf("Error: cannot write %s_tracks.csv\n", tag.c_str());
+      return 2;
+    }
+    for (const f3d_track_a& t : a)
+      if (t.status & F3D_TRACK_MATCHED) iou_sum += t.iou;
+    std::printf("track frame %zu -> frame %zu: %llu of %zu bodies matched, %llu split, %llu merged, %llu vanished, %llu appeared, %llu left; "
+                "mean IoU %.6g; lost %llu, foreign %llu\n", cumulative ? size_t(0) : k, k + 1, sum.matched, track_n_a, sum.split, sum.merged,
+                sum.vanished, sum.appeared, sum.left, sum.matched ? iou_sum / static_cast<double>(sum.matched) : std::nan(""),
+                counted.lost_body + counted.lost_background, counted.foreign_a + counted.foreign_b);
+    return 0;
+  };
+
   // --segment: the labels of frame 0, made while the first pair is resident and before anything reads labels.  0: fine; otherwise
   // the exit status.
   auto segment_frame_0 = [&]() {
@@ -1422,6 +1531,14 @@ int main(int argc, char** argv)
     }
     if (label_shape)
       if (const int status = write_shapes(static_cast<size_t>(info.n_labels))) return status;
+    if (track) {
+      if (info.n_labels == 0 || info.n_labels > (1ull << 22)) {
+        std::printf("Error: --segment found %llu bodies and --track takes 1 .. %d; --segment-min-voxels is %llu\n", info.n_labels, 1 << 22,
+                    segment_min_voxels);
+        return 3;
+      }
+      track_n_a = static_cast<size_t>(info.n_labels);
+    }
     if (label_model >= 0 || contacts) {
       if (info.n_labels == 0 || info.n_labels > (1ull << 22)) {
         std::printf(info.n_labels ? "Error: --segment found %llu bodies and --label-motion and --contacts take at most %d: raise "
@@ -1465,6 +1582,8 @@ int main(int argc, char** argv)
       if (!compute_contacts(cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::HeldFlow())) return 3;
       write_contacts(0);
     }
+    if (track)
+      if (const int status = track_pair(0, cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::HeldFlow())) return status;
   } else {
     // Sequence: pair k solves on the device while the host reads frame k+2 and uploads it on one copy queue, and downloads and
     // writes the flow of pair k-1 on another -- from and to page-locked buffers (the reference's ALLOCATE_PINNED_MEMORY switch,
@@ -1583,6 +1702,8 @@ int main(int argc, char** argv)
         CheckDeviceError(f3d_event_record_on(f.down, down));
       }
       if (contacts && !compute_contacts(cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return 3;
+      if (track)  // frame k+1 stays in its container until the upload of frame k+4, two solves from here
+        if (const int status = track_pair(k, cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return status;
       pending_output = true;
     }
     CheckDeviceError(f3d_queue_sync(down));

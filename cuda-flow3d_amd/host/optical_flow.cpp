@@ -57,6 +57,11 @@ extern "C" int f3d_label_contacts(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_
                                   size_t depth, size_t capacity, struct f3d_contact* out, f3d_contact_info* info) __attribute__((weak));
 extern "C" int f3d_label_shape_sums(f3d_devptr labels, size_t n_labels, size_t width, size_t height, size_t depth,
                                     struct f3d_label_shape_sums* out, f3d_label_shape_info* info) __attribute__((weak));
+extern "C" int f3d_label_overlap(f3d_devptr labels_a, size_t n_a, f3d_devptr labels_b, size_t n_b, f3d_devptr u, f3d_devptr v, f3d_devptr w,
+                                 size_t width, size_t height, size_t depth, size_t capacity, struct f3d_overlap* out, f3d_overlap_info* info)
+    __attribute__((weak));
+extern "C" int f3d_relabel_labels(f3d_devptr labels, size_t n, const int* map, f3d_devptr out, size_t width, size_t height, size_t depth,
+                                  unsigned long long* foreign) __attribute__((weak));
 extern "C" int f3d_label_components(f3d_devptr src, float lo, float hi, unsigned long long min_voxels, f3d_devptr labels_out, size_t width,
                                     size_t height, size_t depth, unsigned long long* sizes, size_t capacity, f3d_component_info* info)
     __attribute__((weak));
@@ -1021,6 +1026,138 @@ bool OpticalFlowE::ComputeContacts(const Displacement& of, size_t n_labels, std:
   }
   contacts->clear();
   return set.Fail("the labels have more than 2^24 distinct contacts");
+}
+
+// The second label volume lives in the slot behind the set's four fields: no mask selects it, so Allocate, Download and the loops over
+// the fields never see it, and Release (which walks every slot) frees it with the rest.
+bool OpticalFlowE::AllocateLabelsB()
+{
+  FieldSet& set = derived_[kLabelMotion];
+  DevicePtr& b = set.ptr[kLabelsBSlot];
+  if (b) return true;
+  const DataSize4& c = dev_container_size_;
+  size_t pitch = 0;
+  if (f3d_alloc_pitched(&b, &pitch, c.width * sizeof(float), c.height * c.depth) != 0) b = 0;
+  if (b && pitch != c.pitch) {
+    CheckDeviceError(f3d_free(b));
+    b = 0;
+  }
+  return b ? true : set.Fail("the container of the second label volume does not fit beside the driver's on the device");
+}
+
+bool OpticalFlowE::UploadLabelsB(const int* labels)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!labels) return set.Fail("no labels to upload");
+  if (!AllocateLabelsB()) return false;
+  const DataSize4& c = dev_container_size_;
+  // the copy moves bytes: the int32 labels arrive as they are
+  return set.Check(CheckDeviceError(f3d_copy3d_h2d(set.ptr[kLabelsBSlot], c.pitch, c.height, 0, reinterpret_cast<const float*>(labels),
+                                                   c.width, c.height, c.depth)));
+}
+
+bool OpticalFlowE::DownloadLabelsB(int* labels)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!labels) return set.Fail("no labels to download to");
+  if (!set.ptr[kLabelsBSlot]) return set.Fail("no second label volume on the device (UploadLabelsB or ComputeLabelsB first)");
+  const DataSize4& c = dev_container_size_;
+  return set.Check(CheckDeviceError(f3d_copy3d_d2h(reinterpret_cast<float*>(labels), c.width, c.height, c.depth, set.ptr[kLabelsBSlot],
+                                                   c.pitch, c.height, 0)));
+}
+
+bool OpticalFlowE::ComputeLabelsB(DevicePtr frame, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
+                                  std::vector<unsigned long long>* sizes, f3d_split_info* info)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (core_d2 == 0 && !f3d_label_components)
+    return set.Fail("the device library has no f3d_label_components (connected bodies of a thresholded volume)");
+  if (core_d2 != 0 && !f3d_split_components)
+    return set.Fail("the device library has no f3d_split_components (bodies of a thresholded volume, touching bodies apart)");
+  if (!info) return set.Fail("no info to write to");
+  if (!frame) frame = resident_frame_[1];
+  if (!frame) return set.Fail("no later frame on the device (AllocateResidentFrames and UploadResidentFrames first)");
+  if (!AllocateLabelsB()) return false;
+  const DevicePtr b = set.ptr[kLabelsBSlot];
+  const f3d_size4 c = Container();
+  if (!set.Check(CheckDeviceError(f3d_set_container(&c)))) return false;
+  *info = f3d_split_info{};
+  // one call of either entry: its first eight counters are f3d_component_info's, field for field
+  auto run = [&](unsigned long long* room, size_t capacity) {
+    if (core_d2 != 0)
+      return set.Check(CheckDeviceError(f3d_split_components(frame, lo, hi, core_d2, min_voxels, b, c.width, c.height, c.depth, room, capacity, info)));
+    f3d_component_info plain = {};
+    if (!set.Check(CheckDeviceError(f3d_label_components(frame, lo, hi, min_voxels, b, c.width, c.height, c.depth, room, capacity, &plain))))
+      return false;
+    info->foreground = plain.foreground;
+    info->background = plain.background;
+    info->nan = plain.nan;
+    info->n_components = plain.n_components;
+    info->n_labels = plain.n_labels;
+    info->dropped_components = plain.dropped_components;
+    info->dropped_voxels = plain.dropped_voxels;
+    info->largest = plain.largest;
+    return true;
+  };
+  // as in ComputeLabels: the number of bodies is known only afterwards, and the labels are the same bytes both times
+  if (sizes) sizes->clear();
+  if (!run(nullptr, 0)) return false;
+  if (!sizes || info->n_labels == 0) return true;
+  sizes->resize(static_cast<size_t>(info->n_labels));
+  return run(sizes->data(), sizes->size());
+}
+
+bool OpticalFlowE::ComputeOverlap(const Displacement& of, size_t n_a, size_t n_b, std::vector<f3d_overlap>* rows, f3d_overlap_info* info)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  DevicePtr d[3];
+  set.error.clear();
+  if (!f3d_label_overlap) return set.Fail("the device library has no f3d_label_overlap (overlap of two label volumes)");
+  if (!ResolveDisplacement(set, of, true, d)) return false;
+  if (!rows || !info) return set.Fail("no rows or info to write to");
+  const size_t most_labels = static_cast<size_t>(1) << 22;
+  if (n_a == 0 || n_a > most_labels || n_b == 0 || n_b > most_labels) return set.Fail("n_a and n_b must be 1 .. 2^22");
+  const DevicePtr labels_a = set.ptr[3], labels_b = set.ptr[kLabelsBSlot];
+  if (!labels_a) return set.Fail("no labels on the device (UploadLabels or ComputeLabels first)");
+  if (!labels_b) return set.Fail("no second label volume on the device (UploadLabelsB or ComputeLabelsB first)");
+  const f3d_size4 c = Container();
+  if (!set.Check(CheckDeviceError(f3d_set_container(&c)))) return false;
+  // as in ComputeContacts: the room is left uninitialised, and the first capacity is capped
+  const size_t most = static_cast<size_t>(1) << 24, first = static_cast<size_t>(1) << 20;
+  rows->clear();
+  for (size_t capacity = std::min(8 * (n_a + n_b), first);; capacity = std::min(2 * capacity, most)) {
+    std::unique_ptr<f3d_overlap[]> room(new f3d_overlap[capacity]);
+    if (!set.Check(CheckDeviceError(f3d_label_overlap(labels_a, n_a, labels_b, n_b, d[0], d[1], d[2], c.width, c.height, c.depth, capacity,
+                                                      room.get(), info))))
+      return false;
+    if (info->complete) {
+      rows->assign(room.get(), room.get() + static_cast<size_t>(info->n_pairs));
+      return true;
+    }
+    if (capacity == most) break;
+  }
+  rows->clear();
+  return set.Fail("the two label volumes have more than 2^24 distinct pairs");
+}
+
+bool OpticalFlowE::RelabelB(const int* map, size_t n_b)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!f3d_relabel_labels) return set.Fail("the device library has no f3d_relabel_labels (new numbers for labelled bodies)");
+  if (!map) return set.Fail("no map to relabel with");
+  const DevicePtr b = set.ptr[kLabelsBSlot];
+  if (!b) return set.Fail("no second label volume on the device (UploadLabelsB or ComputeLabelsB first)");
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         set.Check(CheckDeviceError(f3d_relabel_labels(b, n_b, map, b, c.width, c.height, c.depth, nullptr)));
 }
 
 bool OpticalFlowE::ComputeLabelShapes(size_t n_labels, f3d_label_shape* shapes, f3d_label_shape_info* info)

@@ -135,7 +135,8 @@ class OpticalFlowE : public OpticalFlowBase {
   //               selected by F3D_VALIDATE_R (r) and F3D_VALIDATE_D (u, v, w); the fill passes keep a second u, v, w beside them.
   //   kLabelMotion f3d_label_motion_sums, the host solve per label (motion_fit.h) and f3d_remove_label_motion: the displacement with the
   //               fit of each voxel's label taken out.  Three outputs, the residual u, v, w, always all of them, and a fourth container
-  //               that holds the labels (UploadLabels; never downloaded).
+  //               that holds the labels (UploadLabels; never downloaded).  A second label volume (UploadLabelsB, ComputeLabelsB) lives
+  //               in a slot behind these four that no mask selects, and is freed with them.
   //   kWindowStrain f3d_window_strain: the strain fields of kStrain from the least-squares gradient over a (2 radius + 1)^3 window, and
   //               that gradient.  Seventeen outputs in the order vol, exx, eyy, ezz, exy, exz, eyz, eq, G00 .. G22, selected by
   //               F3D_STRAIN_VOL / _E / _EQ and F3D_WSTRAIN_G.
@@ -219,6 +220,20 @@ class OpticalFlowE : public OpticalFlowBase {
   // shapes has n_labels entries (required), info is nullable.  It needs the label container alone, however it was filled, so it runs
   // before any solve.  Waits for the stream.  Errors are reported through DerivedError(kLabelMotion), whose labels these are.
   bool ComputeLabelShapes(size_t n_labels, f3d_label_shape* shapes, f3d_label_shape_info* info);
+  // A second label volume, "B", beside the one UploadLabels fills ("A"): the bodies of a later frame, on the grid a displacement
+  // leads to, in a container of its own that goes with ReleaseDerived(kLabelMotion) or Destroy().  UploadLabelsB / DownloadLabelsB as
+  // their namesakes.  ComputeLabelsB: f3d_label_components (core_d2 == 0; only the first eight counters of info, those of
+  // f3d_component_info, are then written, the rest are 0) or f3d_split_components (core_d2 >= 1) of `frame` into B; frame 0 means the
+  // resident frame 1, the RAW later frame of the pair; sizes is nullable, info required.  ComputeOverlap: f3d_label_overlap of A and B
+  // through `of` (include/f3d.h), the capacity starting at 8 * (n_a + n_b) (at most 2^20) and doubling until the table is complete;
+  // rows receives them sorted by (a, b), info (required) the counters of the call that sufficed.  RelabelB: f3d_relabel_labels of B
+  // in place (map has n_b entries).  All wait for the stream but RelabelB; errors are reported through DerivedError(kLabelMotion).
+  bool UploadLabelsB(const int* labels);
+  bool ComputeLabelsB(DevicePtr frame, float lo, float hi, unsigned long long core_d2, unsigned long long min_voxels,
+                      std::vector<unsigned long long>* sizes, f3d_split_info* info);
+  bool ComputeOverlap(const Displacement& of, size_t n_a, size_t n_b, std::vector<f3d_overlap>* rows, f3d_overlap_info* info);
+  bool RelabelB(const int* map, size_t n_b);
+  bool DownloadLabelsB(int* labels);
   // The histogram of the frame ComputeLabels thresholds (f3d_histogram of include/f3d.h; frame 0 means the resident frame 0).  range:
   // {lo, hi}, or null for the frame's finite minimum and maximum (f3d_value_range); a constant frame and one without a finite voxel
   // then fail with a message that says which.  counts has bins entries, info is required, *lo_used and *hi_used (nullable) receive the
@@ -277,6 +292,9 @@ class OpticalFlowE : public OpticalFlowBase {
   // the window pass of both: checks, the nine containers on first use, f3d_window_strain with F3D_WSTRAIN_G alone into them
   bool ComputeWindowGradient(FieldSet& set, const Displacement& of, bool have_entry, unsigned radius, unsigned min_count);
   void ReleaseWindowGradient();
+  // the slot of derived_[kLabelMotion] that holds the second label volume, behind the set's four fields
+  static constexpr int kLabelsBSlot = 4;
+  bool AllocateLabelsB();
   // clears set's error and gives the three containers of `of`, or fails with the text that says what is missing
   bool ResolveDisplacement(FieldSet& set, const Displacement& of, bool have_entry, DevicePtr (&disp)[3]);
   f3d_size4 Container() const;

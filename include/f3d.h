@@ -1146,6 +1146,72 @@ typedef struct f3d_label_shape_info {
 int f3d_label_shape_sums(f3d_devptr labels, size_t n_labels, size_t width, size_t height, size_t depth,
                          struct f3d_label_shape_sums* out /* n_labels entries, host */, f3d_label_shape_info* info /* nullable */);
 
+/* Overlap of two labelled volumes through a displacement (no reference counterpart: which body of a later frame is which body of the
+ * first one, which grain broke, which two sintered, which left the field of view -- and a check of the displacement that the grey values
+ * do not see).  The volume is width x height x depth (W x H x D = N_0 x N_1 x N_2).  labels_a is a container read as int32 on the grid
+ * of the displacement under the rules of f3d_label_motion_sums: 0 is background, 1 .. n_a are bodies, every other value is foreign.
+ * labels_b is the same with n_b, on the grid the displacement leads to.  u, v, w are given all three or none (0): none is the identity.
+ *
+ * Classes.  Every voxel x = (x_0, x_1, x_2) of the volume falls into exactly one class, decided in this order:
+ *   foreign_a        a = labels_a(x) is outside 0 .. n_a
+ *   lost_background  p = x + d(x), one float32 add per axis ((float)x_0 + u(x), ...; with no u, v, w p = x), is NaN in a component or
+ *   lost_body        outside [0, W-1] x [0, H-1] x [0, D-1] (the test of f3d_invert_displacement and f3d_carry_field): lost_background
+ *                    when a == 0, lost_body otherwise
+ *   foreign_b        y_c = min(N_c - 1, (int)floorf(p_c + 0.5f)) per axis, float32 add included (the rule of F3D_CARRY_NEAREST);
+ *                    b = labels_b(y) is outside 0 .. n_b
+ *   background       a == 0 and b == 0
+ *   overlap          everything else
+ * Keys.  An overlap voxel has the key (a, b): (a, 0) is the part of a body of A that landed on background, (0, b) the part of a body of
+ * B that nothing of A reached.  A lost_body voxel has the key (a, -1), so that a body that partly left the volume shows it.  No other
+ * voxel has a key.
+ * Sums of a key, all exact 64-bit integers:
+ *   n        its voxels
+ *   ca2[j]   the sum of 2 x_j - (N_j - 1): the doubled source coordinates about the volume centre, as in f3d_label_contacts
+ *   cb2[j]   the sum of 2 y_j - (N_j - 1); 0 for b == -1
+ * so that (cb2 - ca2) / (2 n) is the exact mean displacement of the part, in whole voxels of B's grid, without any quantisation.
+ * Widths: with at most 32768 voxels along an axis and 2^33 in all, a term is below 2^16 and every sum below 2^49.
+ *
+ * f3d_overlap_info counts every voxel exactly once in its first six fields, and besides
+ *   table_lost   keyed voxels that found no slot in the table (see below)
+ *   n_pairs      occupied slots of the table: the number of distinct keys when table_lost == 0, a lower bound otherwise
+ *   complete     1 when table_lost == 0 and n_pairs <= capacity, else 0
+ * The sum of n over the rows is lost_body + overlap.
+ *
+ * The table is f3d_label_contacts': an open-addressed table in a grow-only buffer of the library's, the smallest power of two of at
+ * least 2 * capacity slots of 64 B (the key and the seven sums), cleared on the stream, a slot claimed by a 64-bit compare-and-swap
+ * within at most 256 linear probes, the sums added with integer atomics.  Any schedule gives the same sums.  When complete, out
+ * receives n_pairs entries sorted by (a, b) ascending as signed ints, so (a, -1) leads the rows of a: the same bytes on every call.
+ * When not -- more distinct keys than capacity, or a voxel lost to the table -- NOTHING is written to out, the six class counters are
+ * still exact, the call returns 0 and the caller retries with more room.
+ * Refused (status 1, a message, nothing written): a null labels_a, labels_b, out or info; only some of u, v, w given; n_a or n_b
+ * outside 1 .. 2^22; capacity outside 1 .. 2^24; an empty volume or one above 32768 along an axis or 2^33 voxels; labels_a and
+ * labels_b being one container; a label container among u, v, w.  Container padding is never read.
+ * Geometry from the current container, whole volume, library stream; the call waits for the stream.
+ * The solve from the rows to matches, splits, merges and new numbers is host code: f3d_overlap_solve of include/f3d_host.h. */
+struct f3d_overlap {
+  int a, b;
+  unsigned long long n;
+  long long ca2[3], cb2[3];
+};
+typedef struct f3d_overlap_info {
+  unsigned long long foreign_a, lost_background, lost_body, foreign_b, background, overlap;
+  unsigned long long table_lost, n_pairs;
+  int complete;
+} f3d_overlap_info;
+int f3d_label_overlap(f3d_devptr labels_a, size_t n_a, f3d_devptr labels_b, size_t n_b, f3d_devptr u, f3d_devptr v,
+                      f3d_devptr w /* all three or none (0) */, size_t width, size_t height, size_t depth, size_t capacity,
+                      struct f3d_overlap* out /* capacity entries, host */, f3d_overlap_info* info);
+
+/* New numbers for the bodies of a label volume: out(x) = map[l - 1] for l = labels(x) in 1 .. n, 0 for l == 0 and 0 for a foreign l
+ * (outside 0 .. n); the foreign voxels are counted in foreign (nullable; asking waits for the stream).  map is a host array of n ints,
+ * none negative, uploaded per call into a grow-only buffer of the library's (the call waits for that copy); two labels may share a
+ * number.  out may be labels itself: each voxel reads and writes its own word.  One streaming pass; container padding is neither read
+ * nor written.  Refused (status 1, a message, nothing written): a null labels, map or out; n outside 1 .. 2^22; a negative map entry;
+ * a volume above 32768 along an axis or one that does not fit the current container.  Geometry from the current container, whole
+ * volume, library stream. */
+int f3d_relabel_labels(f3d_devptr labels, size_t n, const int* map /* n entries, host */, f3d_devptr out, size_t width, size_t height,
+                       size_t depth, unsigned long long* foreign /* nullable; non-null waits */);
+
 /* Validation of a displacement (no reference counterpart: the normalised median test of PIV and volume-correlation post-processing,
  * Westerweel & Scarano 2005, which a workflow applies between the displacement and the strain).  A vector is compared with the median
  * of its neighbours, scaled by the median residual of those neighbours; a rejected vector becomes NaN (which f3d_flow_strain and

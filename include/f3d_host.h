@@ -335,6 +335,86 @@ int f3d_flow_labels_split(f3d_flow flow, f3d_devptr frame /* 0: the resident fra
 int f3d_flow_labels_end(f3d_flow flow);
 int f3d_flow_labels_download(f3d_flow flow, int* labels);
 
+/* The solve from the overlap rows of f3d_label_overlap (include/f3d.h) to the tracks of the bodies: which body of B is which body of
+ * A, which broke, which merged, which came and went.  Host code, no device needed.  rows are count rows with distinct keys (the sorted
+ * list of f3d_label_overlap; the result does not depend on their order), n_ab is the n of the row (a, b).  a has n_a entries (body a at
+ * index a - 1), b and map_b have n_b entries, summary is nullable.  min_fraction is in (0, 1]; "the share of p in q counts" means
+ * (double)p >= min_fraction * (double)q in binary64 with that one multiplication.  Integers are exact; every double is formed as
+ * written, every operation rounded on its own.  In exactly this order:
+ *   1. per body a >= 1 of A, over its rows (a, b), b = -1, 0, 1 .. n_b:
+ *        n = sum n_ab;  n_lost = n_(a,-1);  n_background = n_(a,0)
+ *        best_b = the b >= 1 of largest n_ab > 0, ties to the smallest b, 0 when there is none;  n_best = that n_ab, else 0
+ *        shift_j = (double)(cb2_j - ca2_j) / (2.0 * (double)n_best) of the row (a, best_b): the exact mean displacement of the part of
+ *                  a that landed in best_b, rounded once.  NaN without a best_b
+ *      per body b >= 1 of B, over its rows (a, b), a = 0 .. n_a:
+ *        m = sum n_ab: the voxels of A's GRID that land in b -- not the voxel count of b in its own volume, which the rows do not hold
+ *        n_unreached = n_(0,b);  best_a = the a >= 1 of largest n_ab > 0, ties to the smallest a, 0 when there is none;  n_best likewise
+ *   2. n_targets of a = the number of b >= 1 whose n_ab's share of n counts;  n_sources of b = the number of a >= 1 whose n_ab's share
+ *      of m counts
+ *   3. a with n == 0: status F3D_TRACK_EMPTY alone, fraction, shift and iou NaN.  Otherwise
+ *        fraction = (double)n_best / (double)n
+ *        iou = (double)n_best / (double)(n + m_(best_b) - n_best), 0.0 without a best_b
+ *        F3D_TRACK_MATCHED   best_b >= 1 and best_a of best_b is a (mutual best)
+ *        F3D_TRACK_SPLIT     n_targets >= 2
+ *        F3D_TRACK_VANISHED  n_targets == 0
+ *        F3D_TRACK_LEFT      n_lost's share of n counts
+ *      b with m == 0: status F3D_TRACK_EMPTY alone.  Otherwise F3D_TRACK_MATCHED (best_a >= 1 and best_b of best_a is b),
+ *        F3D_TRACK_MERGED (n_sources >= 2), F3D_TRACK_APPEARED (n_sources == 0)
+ *   4. map_b[b - 1]: a MATCHED b gets the number of its a; every other b that is not EMPTY gets n_a + 1, n_a + 2, ... in ascending b;
+ *      an EMPTY b gets 0.  So the largest fragment of a broken body keeps the body's number and the others are new.
+ * summary counts the bodies of A that are matched, split, vanished, left, those of B that are merged, appeared, and n_ids, the largest
+ * number map_b hands out (n_a when none is new).
+ * Returns non-zero (f3d_host_last_error() set, nothing written) for a null rows (with count > 0), a, b or map_b (with bodies to
+ * write), n_a or n_b of 0, a min_fraction outside (0, 1] or NaN, and a row whose key is outside 0 .. n_a x -1 .. n_b or is (0, 0) or
+ * (0, -1). */
+#define F3D_TRACK_EMPTY 1u
+#define F3D_TRACK_MATCHED 2u
+#define F3D_TRACK_SPLIT 4u
+#define F3D_TRACK_VANISHED 8u
+#define F3D_TRACK_LEFT 16u
+#define F3D_TRACK_MERGED 32u
+#define F3D_TRACK_APPEARED 64u
+typedef struct f3d_track_a {
+  unsigned long long n, n_lost, n_background, n_best;
+  int best_b, n_targets;
+  double fraction, shift[3], iou;
+  unsigned status;
+} f3d_track_a;
+typedef struct f3d_track_b {
+  unsigned long long m, n_unreached, n_best;
+  int best_a, n_sources;
+  unsigned status;
+} f3d_track_b;
+typedef struct f3d_track_summary {
+  unsigned long long matched, split, merged, vanished, appeared, left, n_ids;
+} f3d_track_summary;
+int f3d_overlap_solve(const struct f3d_overlap* rows, size_t count, size_t n_a, size_t n_b, double min_fraction, f3d_track_a* a,
+                      f3d_track_b* b, int* map_b, f3d_track_summary* summary /* nullable */);
+
+/* A second label volume, "B", beside the labels of the driver ("A", on frame 0's grid): the bodies of a later frame, on the grid a
+ * displacement leads to.  It lives in a container of its own that goes with f3d_flow_label_motion_end or f3d_flow_destroy.
+ *   f3d_flow_labels_b_upload    width * height * depth int32, 0 background, 1 .. n_b the bodies
+ *   f3d_flow_labels_b_segment   f3d_label_components (core_d2 == 0) or f3d_split_components (core_d2 >= 1) of `frame` into B; frame 0
+ *                               means the resident frame 1, the RAW later frame of the pair the driver holds.  *sizes receives a list of
+ *                               *count = info->n_labels sizes that the driver owns until the next call of this entry,
+ *                               f3d_flow_labels_end or f3d_flow_destroy.  info (required) is f3d_split_info; without a split only its first
+ *                               eight fields, those of f3d_component_info, are written and the rest are 0
+ *   f3d_flow_overlap_compute    f3d_label_overlap of A and B through the held flow or the trajectory (source F3D_STRAIN_OF_FLOW /
+ *                               F3D_STRAIN_OF_TRAJECTORY), with a capacity that starts at 8 * (n_a + n_b) (at most 2^20) and doubles
+ *                               until the table is complete.  *rows receives *count rows sorted by (a, b) that the driver owns until
+ *                               the next call of this entry, f3d_flow_overlap_end or f3d_flow_destroy.  info is required
+ *   f3d_flow_labels_b_relabel   f3d_relabel_labels of B in place with map (n_b entries), e.g. f3d_overlap_solve's map_b
+ *   f3d_flow_labels_b_download  B to width * height * depth int32
+ * A device library without the entry a call needs still loads; then the call fails with a message naming the entry. */
+int f3d_flow_labels_b_upload(f3d_flow flow, const int* labels);
+int f3d_flow_labels_b_segment(f3d_flow flow, f3d_devptr frame /* 0: the resident frame 1 */, float lo, float hi, unsigned long long core_d2,
+                              unsigned long long min_voxels, const unsigned long long** sizes, size_t* count, f3d_split_info* info);
+int f3d_flow_overlap_compute(f3d_flow flow, int source, size_t n_a, size_t n_b, const struct f3d_overlap** rows, size_t* count,
+                             f3d_overlap_info* info);
+int f3d_flow_overlap_end(f3d_flow flow);
+int f3d_flow_labels_b_relabel(f3d_flow flow, const int* map, size_t n_b);
+int f3d_flow_labels_b_download(f3d_flow flow, int* labels);
+
 /* Exact selection on a histogram of f3d_histogram (include/f3d.h has the bin rule).  Host code, no device needed.  Each returns
  * non-zero (f3d_host_last_error() set, nothing written) when it refuses its arguments.
  *
