@@ -162,6 +162,28 @@ class LabelShape(C.Structure):  # f3d_label_shape
                 ("euler", C.c_longlong)]
 
 
+class LabelFieldSumsRow(C.Structure):  # struct f3d_label_field_sums: the eight exact words of one label
+    _fields_ = [("n", C.c_ulonglong), ("min_key", C.c_ulonglong), ("max_key", C.c_ulonglong), ("iq", C.c_longlong),
+                ("iqq_lo", C.c_ulonglong), ("iqq_hi", C.c_ulonglong), ("below", C.c_ulonglong), ("above", C.c_ulonglong)]
+
+
+class LabelFieldInfo(C.Structure):  # f3d_label_field_info: every voxel of the box in exactly one counter, tried in this order
+    _fields_ = [(k, C.c_ulonglong) for k in ("background", "foreign", "nan", "out_of_range", "used")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class LabelFieldStat(C.Structure):  # f3d_label_field_stat
+    _fields_ = [("status", C.c_int), ("q05_bin", C.c_int), ("median_bin", C.c_int), ("q95_bin", C.c_int), ("n", C.c_ulonglong),
+                ("below", C.c_ulonglong), ("above", C.c_ulonglong)] + \
+               [(k, C.c_double) for k in ("min", "max", "mean", "variance", "std", "q05", "median", "q95")]
+
+
+class LabelFieldSummary(C.Structure):  # f3d_label_field_summary
+    _fields_ = [("ok", C.c_ulonglong), ("empty", C.c_ulonglong), ("small", C.c_ulonglong), ("mean", C.c_double)]
+
+
 class Overlap(C.Structure):  # struct f3d_overlap: the exact sums of one pair (label of A, label of B)
     _fields_ = [("a", C.c_int), ("b", C.c_int), ("n", C.c_ulonglong), ("ca2", C.c_longlong * 3), ("cb2", C.c_longlong * 3)]
 
@@ -461,6 +483,14 @@ def host():
         "f3d_flow_overlap_end": [C.c_void_p],
         "f3d_flow_labels_b_relabel": [C.c_void_p, C.POINTER(C.c_int), _sz],
         "f3d_flow_labels_b_download": [C.c_void_p, C.POINTER(C.c_int)],
+        "f3d_label_field_solve": [C.POINTER(LabelFieldSumsRow), C.POINTER(C.c_uint), _sz, C.c_int, C.c_float, C.c_float, _sz, C.c_ulonglong,
+                                  C.POINTER(LabelFieldStat), C.POINTER(LabelFieldSummary)],
+        "f3d_label_field_shift": [C.c_float, C.c_float, C.c_ulonglong],
+        "f3d_flow_label_field_compute": [C.c_void_p, _dp, _sz, C.c_int, _fp, _sz, C.c_ulonglong, C.POINTER(LabelFieldStat),
+                                         C.POINTER(C.c_uint), C.POINTER(LabelFieldInfo), C.POINTER(LabelFieldSummary)],
+        "f3d_flow_label_field_range": [C.c_void_p, _dp, _fp, _fp, C.POINTER(RangeInfo)],
+        "f3d_flow_field_container": [C.c_void_p, C.c_char_p, C.POINTER(_dp)],
+        "f3d_flow_labels_paint": [C.c_void_p, _fp, _sz, _fp],
         "f3d_histogram_edge": [C.c_float, C.c_float, _sz, _sz, _fp],
         "f3d_otsu": [C.POINTER(C.c_ulonglong), _sz, C.c_int, C.POINTER(C.c_uint), C.POINTER(OtsuInfo)],
         "f3d_histogram_rank": [C.POINTER(C.c_ulonglong), _sz, C.c_ulonglong, C.POINTER(C.c_uint)],
@@ -681,6 +711,16 @@ def _contacts_entry():
 def _label_shape_entry():
     return _entry("f3d_label_shape_sums", [_dp] + [_sz] * 4 + [C.POINTER(LabelShapeSums), C.POINTER(LabelShapeInfo)],
                   "sum the shapes of the labels of a segmentation")
+
+
+def _label_field_entry():
+    return _entry("f3d_label_field_sums", [_dp, _dp, _sz, C.c_int, C.c_float, C.c_float] + [_sz] * 4 +
+                  [C.POINTER(LabelFieldSumsRow), C.POINTER(C.c_uint), C.POINTER(LabelFieldInfo)],
+                  "sum a field over the labels of a segmentation")
+
+
+def _paint_entry():
+    return _entry("f3d_paint_labels", [_dp, _sz, _fp, _dp] + [_sz] * 3, "paint a value per label into a volume")
 
 
 def _overlap_entry():
@@ -1399,6 +1439,197 @@ def label_shapes(labels, n_labels=None):
     shapes = solve_label_shapes(sums)
     shapes.info = info
     return shapes
+
+
+MAX_LABEL_FIELD_BINS = 256
+MAX_LABEL_FIELD_COUNTS = 1 << 26
+_FIELD_SUMS_DTYPE = np.dtype([("n", "<u8"), ("min_key", "<u8"), ("max_key", "<u8"), ("iq", "<i8"), ("iqq_lo", "<u8"), ("iqq_hi", "<u8"),
+                              ("below", "<u8"), ("above", "<u8")])
+_FIELD_STAT_DTYPE = np.dtype([("status", "<i4"), ("q05_bin", "<i4"), ("median_bin", "<i4"), ("q95_bin", "<i4"), ("n", "<u8"),
+                              ("below", "<u8"), ("above", "<u8"), ("min", "<f8"), ("max", "<f8"), ("mean", "<f8"), ("variance", "<f8"),
+                              ("std", "<f8"), ("q05", "<f8"), ("median", "<f8"), ("q95", "<f8")])
+
+
+def _field_bins(bins):
+    if int(bins) != bins or not 0 <= int(bins) <= MAX_LABEL_FIELD_BINS:
+        raise ValueError(f"bins must be an integer in 0 .. {MAX_LABEL_FIELD_BINS}, not {bins}")
+    return int(bins)
+
+
+def _field_shift(shift):
+    if shift is None:
+        return None
+    if int(shift) != shift or not -100 <= int(shift) <= 100:
+        raise ValueError(f"shift must be an integer in -100 .. 100, not {shift}")
+    return int(shift)
+
+
+def label_field_shift(lo, hi, finite=1):
+    """f3d_label_field_shift (include/f3d_host.h; host code): the shift for a field whose finite values lie in [lo, hi]: with
+    max(|lo|, |hi|) = f * 2^e (frexp) it is 24 - e clamped to -100 .. 100, and 0 when that is 0 or nothing is finite."""
+    return int(host().f3d_label_field_shift(float(np.float32(lo)), float(np.float32(hi)), int(finite)))
+
+
+def _bin_scale_is_finite(lo, hi, bins):
+    """whether f3d_histogram's scale (float)bins / (hi - lo) is finite and positive in float32"""
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        width = np.float32(hi) - np.float32(lo)
+        scale = np.float32(bins) / width
+    return bool(np.isfinite(width) and width > 0 and np.isfinite(scale) and scale > 0)
+
+
+def _field_settings(shift, bins, bounds, lo, hi, finite):
+    """(shift, bins, bounds, note) with what the caller left open taken from the field's finite range [lo, hi] under the labels"""
+    note = None
+    if shift is None:
+        shift = label_field_shift(lo, hi, finite)
+    if bins and bounds is None:
+        if finite == 0:
+            bins, note = 0, "no bins: the field has no finite voxel under the labels, so there is no range to lay them over"
+        elif not lo < hi:
+            bins, note = 0, f"no bins: the field is constant ({lo}) under the labels, so there is no range to lay them over"
+        elif not _bin_scale_is_finite(lo, hi, bins):
+            bins, note = 0, f"no bins: the width of the field's range [{lo}, {hi}] or the scale of {bins} bins over it is not finite in float32"
+        else:
+            bounds = (float(lo), float(hi))
+    return shift, bins, bounds, note
+
+
+class LabelFieldSums:
+    """What f3d_label_field_sums gave (label_field_sums): .rows (a structured array over the labels, label L at index L - 1, with the
+    fields n, min_key, max_key, iq, iqq_lo, iqq_hi, below, above), .counts (uint32 [n_labels, bins], None without bins), .shift, .bins,
+    .lo and .hi (the float32 bounds of the bins, None without), and .info: the dict of f3d_label_field_info, with a "note" when bins
+    were asked for and the field had no range to lay them over."""
+
+    def __init__(self, rows, counts, shift, lo, hi, info):
+        self.rows, self.counts, self.shift, self.lo, self.hi, self.info = rows, counts, int(shift), lo, hi, info
+        self.bins = 0 if counts is None else counts.shape[1]
+
+    def __len__(self):
+        return len(self.rows)
+
+
+def _field_sums_result(rows, n_labels, counts, shift, bounds, info, note):
+    assert C.sizeof(LabelFieldSumsRow) == _FIELD_SUMS_DTYPE.itemsize
+    found = info.as_dict()
+    if note:
+        found["note"] = note
+    return LabelFieldSums(np.frombuffer(rows, dtype=_FIELD_SUMS_DTYPE, count=n_labels).copy(), counts, shift,
+                          None if counts is None else bounds[0], None if counts is None else bounds[1], found)
+
+
+def label_field_sums(field, labels, n_labels=None, shift=None, bins=0, range=None):
+    """The exact sums of a scalar field over every label of a segmentation on the device (include/f3d.h, f3d_label_field_sums): field a
+    [z, y, x] volume (taken as float32), labels an integer volume of its shape (0 background, 1 .. n_labels the bodies, anything else
+    foreign; n_labels None means labels.max()).  shift: the quantisation q = rint(s * 2^shift), -100 .. 100; None picks
+    label_field_shift of value_range(field, mask=labels), with which nothing finite is out of range.  bins 0 .. 256 over range =
+    (lo, hi); range None takes that finite range, and a field that has none (constant, or nothing finite) gets bins = 0 and a note in
+    .info.  Returns a LabelFieldSums."""
+    fn, bins, shift = _label_field_entry(), _field_bins(bins), _field_shift(shift)
+    bounds = None if range is None else _bin_range(range)
+    field = np.asarray(field)
+    if field.ndim != 3 or field.size == 0:
+        raise ValueError("field must be a non-empty [z, y, x] volume")
+    bits, n_labels = _labels_as_float_bits(labels, n_labels)
+    if bits.shape != field.shape:
+        raise ValueError(f"labels must have the shape of the field, {field.shape}")
+    if n_labels * bins > MAX_LABEL_FIELD_COUNTS:
+        raise ValueError(f"n_labels * bins must be at most 2^26, not {n_labels} * {bins}")
+    open_ = shift is None or (bins and bounds is None)
+    find = _value_range_entry() if open_ else None
+    note = None
+    with _on_device((field, bits), "field and labels must be [z, y, x] volumes of one shape") as (box, p, dims):
+        box.set_current()
+        if open_:
+            lo, hi, found = C.c_float(), C.c_float(), RangeInfo()
+            check(find(p[0], p[1], *dims, C.byref(lo), C.byref(hi), C.byref(found)), "f3d_value_range")
+            shift, bins, bounds, note = _field_settings(shift, bins, bounds, lo.value, hi.value, found.finite)
+        rows, info = (LabelFieldSumsRow * n_labels)(), LabelFieldInfo()
+        counts = np.zeros((n_labels, bins), np.uint32) if bins else None
+        lo_hi = bounds if bins else (0.0, 0.0)
+        check(fn(p[0], p[1], n_labels, shift, lo_hi[0], lo_hi[1], bins, *dims, rows,
+                 counts.ctypes.data_as(C.POINTER(C.c_uint)) if bins else None, C.byref(info)), "f3d_label_field_sums")
+    return _field_sums_result(rows, n_labels, counts, shift, bounds, info, note)
+
+
+class LabelFieldStats:
+    """The statistics of a scalar field per body (solve_label_field): arrays over the labels, label L at index L - 1.  .status (0 ok,
+    1 empty, 2 small: LABEL_STATUS), .n (the voxels that took part), .min, .max, .mean, .variance, .std (population), .q05, .median,
+    .q95 (the midpoint of the bin that holds the rank; NaN without bins) and their bins .q05_bin, .median_bin, .q95_bin (-1 without),
+    .below and .above (voxels outside the range of the bins), .counts (uint32 [n_labels, bins] or None), .shift, .lo, .hi, .bins, .info
+    (the dict of f3d_label_field_info, with a "note" when bins were dropped) and .summary: ok, empty, small and mean, the n-weighted
+    mean over the ok labels."""
+
+    def __init__(self, rows, summary, sums):
+        self.rows, self.summary = rows, summary
+        for name in _FIELD_STAT_DTYPE.names:
+            setattr(self, name, rows[name].copy())
+        self.counts, self.info, self.shift, self.lo, self.hi, self.bins = sums.counts, sums.info, sums.shift, sums.lo, sums.hi, sums.bins
+
+    def __len__(self):
+        return len(self.status)
+
+    def as_table(self):
+        """one dict per label: label, status (a word of LABEL_STATUS), n, min, max, mean, std, q05, median, q95, below, above"""
+        return [{"label": i + 1, "status": LABEL_STATUS[self.status[i]], "n": int(self.n[i]), "min": float(self.min[i]),
+                 "max": float(self.max[i]), "mean": float(self.mean[i]), "std": float(self.std[i]), "q05": float(self.q05[i]),
+                 "median": float(self.median[i]), "q95": float(self.q95[i]), "below": int(self.below[i]), "above": int(self.above[i])}
+                for i in range(len(self))]
+
+
+def _field_stats_result(out, n, summary, sums):
+    assert C.sizeof(LabelFieldStat) == _FIELD_STAT_DTYPE.itemsize
+    rows = np.frombuffer(out, dtype=_FIELD_STAT_DTYPE, count=n).copy() if n else np.zeros(0, _FIELD_STAT_DTYPE)
+    return LabelFieldStats(rows, {"ok": int(summary.ok), "empty": int(summary.empty), "small": int(summary.small),
+                                  "mean": float(summary.mean)}, sums)
+
+
+def solve_label_field(sums, min_voxels=1):
+    """f3d_label_field_solve (include/f3d_host.h; host code, no device): the LabelFieldStats of the LabelFieldSums `sums`; a label
+    with fewer than min_voxels voxels is "small" (and still filled)."""
+    if not isinstance(sums, LabelFieldSums):
+        raise ValueError("sums must be the LabelFieldSums of label_field_sums")
+    if int(min_voxels) != min_voxels or not 0 <= int(min_voxels) < 2 ** 64:
+        raise ValueError(f"min_voxels must be a non-negative integer, not {min_voxels}")
+    rows = np.ascontiguousarray(sums.rows, dtype=_FIELD_SUMS_DTYPE)
+    n = len(rows)
+    counts = None
+    if sums.bins:
+        counts = np.ascontiguousarray(sums.counts, dtype=np.uint32)
+        if counts.shape != (n, sums.bins):
+            raise ValueError(f"counts must be [n_labels, bins] = {(n, sums.bins)}, not {counts.shape}")
+    out, summary = (LabelFieldStat * max(n, 1))(), LabelFieldSummary()
+    _host_check(host().f3d_label_field_solve(rows.ctypes.data_as(C.POINTER(LabelFieldSumsRow)),
+                                             counts.ctypes.data_as(C.POINTER(C.c_uint)) if sums.bins else None, n, sums.shift,
+                                             sums.lo if sums.bins else 0.0, sums.hi if sums.bins else 0.0, sums.bins, int(min_voxels), out,
+                                             C.byref(summary)), "f3d_label_field_solve")
+    return _field_stats_result(out, n, summary, sums)
+
+
+def label_field_stats(field, labels, n_labels=None, shift=None, bins=0, range=None, min_voxels=1):
+    """The statistics of a scalar field per body from anywhere: label_field_sums on the device, solve_label_field on the host.
+    Returns a LabelFieldStats."""
+    return solve_label_field(label_field_sums(field, labels, n_labels, shift, bins, range), min_voxels)
+
+
+def _paint_values(values):
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    if values.ndim != 1 or not 1 <= values.size <= MAX_LABELS:
+        raise ValueError(f"values must be a one-dimensional array of 1 .. {MAX_LABELS} numbers, the value of label l at index l - 1")
+    return values
+
+
+def paint_labels(values, labels):
+    """A value per label painted into a volume on the device (include/f3d.h, f3d_paint_labels): a float32 [z, y, x] volume with
+    values[l - 1] where labels == l in 1 .. len(values) (the bytes are copied: a NaN keeps its payload) and NaN elsewhere."""
+    fn, values = _paint_entry(), _paint_values(values)
+    bits, n = _labels_as_float_bits(labels, len(values))
+    if bits.size == 0:
+        raise ValueError("labels must be a non-empty [z, y, x] volume")
+    with _on_device((bits,), "labels must be a [z, y, x] volume") as (box, p, dims):
+        box.set_current()
+        check(fn(p[0], n, values.ctypes.data_as(_fp), p[0], *dims), "f3d_paint_labels")   # in place: each voxel its own word
+        return box.download(p[0], dims)
 
 
 MAX_OVERLAPS = 1 << 24
@@ -2767,6 +2998,65 @@ class OpticalFlow:
         out, info = (LabelShape * n)(), LabelShapeInfo()
         _host_check(host().f3d_flow_label_shapes_compute(self._h, ptr, n, out, C.byref(info)), "f3d_flow_label_shapes_compute")
         return LabelShapes(_shape_rows(out, n), info.as_dict())
+
+    def _device_labels(self, n_labels):
+        if n_labels is None:
+            n_labels = getattr(self, "_segmented_labels", None)
+        if n_labels is None:
+            raise ValueError("n_labels is required when the labels on the device were not made by segment()")
+        n = int(n_labels)
+        if not 1 <= n <= MAX_LABELS:
+            raise ValueError(f"n_labels must be 1 .. {MAX_LABELS}, not {n}")
+        return n
+
+    def label_field(self, field="eq", n_labels=None, shift=None, bins=0, range=None, min_voxels=1):
+        """The statistics of a field per body of the labels segment(), label_motion(), contacts() or label_shapes() left on the device: a
+        LabelFieldStats (see there).  field: the name of a field the driver holds -- "grey" (the raw frame 0 of the last upload()),
+        "vol", "eq" (after strain()), "gmax" (principal()), "angle" (rotation()), "zncc", "rmsd" (match()), "wvol", "weq"
+        (window_strain()) -- which stays on the device, or a [z, y, x] array on the driver's grid, which is taken through
+        label_field_stats with the downloaded labels.  n_labels None means the number of bodies of the last segment(); shift, bins,
+        range and min_voxels as in label_field_sums and solve_label_field."""
+        n = self._device_labels(n_labels)
+        bins, shift = _field_bins(bins), _field_shift(shift)
+        bounds = None if range is None else _bin_range(range)
+        w, h, d = self.dims
+        if not isinstance(field, str):
+            field = np.asarray(field)
+            if field.shape != (d, h, w):
+                raise ValueError(f"field must be a name or a [z, y, x] volume of shape {(d, h, w)}")
+            labels = np.empty((d, h, w), np.int32)
+            _host_check(host().f3d_flow_labels_download(self._h, labels.ctypes.data_as(C.POINTER(C.c_int))), "f3d_flow_labels_download")
+            return label_field_stats(field, labels, n, shift, bins, range, min_voxels)
+        if n * bins > MAX_LABEL_FIELD_COUNTS:
+            raise ValueError(f"n_labels * bins must be at most 2^26, not {n} * {bins}")
+        ptr = _dp(0)
+        _host_check(host().f3d_flow_field_container(self._h, field.encode(), C.byref(ptr)), "f3d_flow_field_container")
+        note = None
+        if shift is None or (bins and bounds is None):
+            lo, hi, found = C.c_float(), C.c_float(), RangeInfo()
+            _host_check(host().f3d_flow_label_field_range(self._h, ptr, C.byref(lo), C.byref(hi), C.byref(found)),
+                        "f3d_flow_label_field_range")
+            shift, bins, bounds, note = _field_settings(shift, bins, bounds, lo.value, hi.value, found.finite)
+        out, info, summary = (LabelFieldStat * n)(), LabelFieldInfo(), LabelFieldSummary()
+        counts = np.zeros((n, bins), np.uint32) if bins else None
+        _host_check(host().f3d_flow_label_field_compute(self._h, ptr, n, shift, (C.c_float * 2)(*bounds) if bins else None, bins,
+                                                        int(min_voxels), out, counts.ctypes.data_as(C.POINTER(C.c_uint)) if bins else None,
+                                                        C.byref(info), C.byref(summary)), "f3d_flow_label_field_compute")
+        found = info.as_dict()
+        if note:
+            found["note"] = note
+        sums = LabelFieldSums(np.zeros(0, _FIELD_SUMS_DTYPE), counts, shift, bounds[0] if bins else None, bounds[1] if bins else None, found)
+        return _field_stats_result(out, n, summary, sums)
+
+    def paint_labels(self, values):
+        """values[l - 1] painted into the voxels of label l of the labels on the device, NaN elsewhere (f3d_paint_labels): a float32
+        [z, y, x] volume, e.g. paint_labels(label_field("eq").mean)."""
+        values = _paint_values(values)
+        w, h, d = self.dims
+        out = np.empty((d, h, w), np.float32)
+        _host_check(host().f3d_flow_labels_paint(self._h, values.ctypes.data_as(_fp), len(values), out.ctypes.data_as(_fp)),
+                    "f3d_flow_labels_paint")
+        return out
 
     def segment_end(self):
         """free the driver's list of sizes (the labels stay on the device until label_motion_end() or destroy())"""

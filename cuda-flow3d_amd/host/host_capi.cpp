@@ -7,6 +7,7 @@
 
 #include "f3d_host.h"
 #include "contact_kinematics.h"
+#include "label_field.h"
 #include "label_shape.h"
 #include "label_track.h"
 #include "hip_utils.h"
@@ -594,6 +595,56 @@ int f3d_flow_labels_b_download(f3d_flow flow, int* labels)
   g_host_error.clear();
   if (!flow || !labels) return HostFail("f3d_flow_labels_b_download: null argument");
   if (!flow->driver.DownloadLabelsB(labels)) return HostFail(flow->driver.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  return 0;
+}
+
+int f3d_label_field_solve(const struct f3d_label_field_sums* sums, const unsigned* counts, size_t n_labels, int shift, float lo, float hi,
+                          size_t bins, unsigned long long min_voxels, f3d_label_field_stat* stats, f3d_label_field_summary* summary)
+{
+  g_host_error.clear();
+  std::string why;
+  return SolveLabelField(sums, counts, n_labels, shift, lo, hi, bins, min_voxels, stats, summary, &why)
+             ? 0
+             : HostFail(("f3d_label_field_solve: " + why).c_str());
+}
+
+int f3d_flow_label_field_compute(f3d_flow flow, f3d_devptr field, size_t n_labels, int shift, const float* range, size_t bins,
+                                 unsigned long long min_voxels, f3d_label_field_stat* stats, unsigned* counts, f3d_label_field_info* info,
+                                 f3d_label_field_summary* summary)
+{
+  g_host_error.clear();
+  if (!flow || !stats) return HostFail("f3d_flow_label_field_compute: null argument");
+  OpticalFlowE& d = flow->driver;
+  if (!d.ComputeLabelField(field, n_labels, shift, range, bins, min_voxels, stats, counts, info, summary))
+    return HostFail(d.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  return 0;
+}
+
+int f3d_label_field_shift(float min, float max, unsigned long long finite) { return LabelFieldShift(min, max, finite); }
+
+int f3d_flow_label_field_range(f3d_flow flow, f3d_devptr field, float* min, float* max, f3d_range_info* info)
+{
+  g_host_error.clear();
+  if (!flow || !min || !max || !info) return HostFail("f3d_flow_label_field_range: null argument");
+  if (!flow->driver.LabelFieldRange(field, min, max, info)) return HostFail(flow->driver.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+  return 0;
+}
+
+int f3d_flow_field_container(f3d_flow flow, const char* name, f3d_devptr* container)
+{
+  g_host_error.clear();
+  if (!flow || !name || !container) return HostFail("f3d_flow_field_container: null argument");
+  const f3d_devptr found = flow->driver.NamedField(name);
+  if (!found) return HostFail((std::string("f3d_flow_field_container: no field '") + name + "' on the device (not a name, or not computed)").c_str());
+  *container = found;
+  return 0;
+}
+
+int f3d_flow_labels_paint(f3d_flow flow, const float* values, size_t n_labels, float* out)
+{
+  g_host_error.clear();
+  if (!flow || !values || !out) return HostFail("f3d_flow_labels_paint: null argument");
+  if (!flow->driver.PaintLabels(values, n_labels, out)) return HostFail(flow->driver.DerivedError(OpticalFlowE::kLabelMotion).c_str());
   return 0;
 }
 

@@ -104,6 +104,15 @@
 // row per label -- label, status, voxels, the bounding box, the voxels on the two box faces of each axis, centroid, diameter of the ball
 // of the same volume, the three semi-axes and their directions, staircase faces, the Cauchy-Crofton surface, sphericity and the Euler
 // number -- and one line sums it up.  It needs no displacement; every other output is the same with and without it.
+// (--labels FILE | --segment ...) --label-stats LIST [--label-stats-bins B] [--label-stats-paint] gives the statistics of fields per
+// body (f3d_label_field_sums on the device, f3d_label_field_solve on the host).  LIST is a comma-separated subset of grey (the raw
+// frame 0 of the first pair; done once, when the labels and that frame are on the device), vol, eq (--strain must select the name), gmax
+// (--principal shear), angle (--rotation angle), zncc, rmsd (--match), wvol, weq (--window-strain); a field of a pair is read in its
+// container right after it was computed, under the conditions and from the source of --label-motion.  The shift of the quantisation and,
+// with B bins (0 .. 256, default 64), their range are taken from the field's finite range under the labels.  <tag>_labelstats.csv has
+// one row per (field, label): field, label, status, n, min, max, mean, std, q05, median, q95, below, above; one line is printed per
+// field and pair; with --label-stats-paint <tag>_labelmean-<name>-W-H-D.raw is the mean of each ok label painted into its voxels
+// (f3d_paint_labels), NaN elsewhere.  Every other output is the same with and without it.
 // --segment ... --track [--track-min-fraction F] follows the bodies from frame to frame.  While pair k is resident the RAW frame k+1 is
 // segmented into a second label volume with what --segment settled for frame 0 -- the thresholds as numbers, --segment-min-voxels and the
 // split; an Otsu cut is the number it came to on frame 0 and is not taken again per frame.  The overlap of frame 0's bodies with these
@@ -146,6 +155,9 @@ static void Usage()
               "              [--labels FILE --label-motion translation|rigid|affine [--label-min-voxels K]]\n"
               "              [--labels FILE --contacts [--contact-min-faces K]]\n"
               "              [(--labels FILE | --segment ...) --label-shape]\n"
+              "              [(--labels FILE | --segment ...) --label-stats grey,vol,eq,gmax,angle,zncc,rmsd,wvol,weq\n"
+              "               [--label-stats-bins B] [--label-stats-paint]]  (a name needs the option that computes it: --strain vol / eq,\n"
+              "               --principal shear, --rotation angle, --match zncc / rmsd, --window-strain vol / eq)\n"
               "              [--segment LO:HI [--segment-min-voxels K]]\n"
               "              [--segment-split R | --segment-split-d2 N]\n"
               "              [--segment with otsu, or otsu1 / otsu2, in place of LO or HI] [--segment-bins B] [--segment-range A:B]\n"
@@ -190,6 +202,9 @@ int main(int argc, char** argv)
   bool label_min_given = false;
   bool contacts = false;          // --contacts
   bool label_shape = false;       // --label-shape
+  std::vector<std::string> label_stats;  // --label-stats: the names in the order given
+  size_t label_stats_bins = 64;   // --label-stats-bins
+  bool label_stats_bins_given = false, label_stats_paint = false;
   unsigned long long contact_min_faces = 4;
   bool contact_min_given = false;
   bool segment = false;           // --segment LO:HI
@@ -464,6 +479,38 @@ int main(int argc, char** argv)
     }
     else if (a == "--contacts") contacts = true;
     else if (a == "--label-shape") label_shape = true;
+    else if (a == "--label-stats") {
+      need(1);
+      std::string list = argv[++i];
+      size_t pos = 0;
+      while (pos <= list.size()) {
+        const size_t comma = std::min(list.find(',', pos), list.size());
+        const std::string item = list.substr(pos, comma - pos);
+        static const char* const known[9] = {"grey", "vol", "eq", "gmax", "angle", "zncc", "rmsd", "wvol", "weq"};
+        const bool is_known = std::find_if(known, known + 9, [&](const char* n) { return item == n; }) != known + 9;
+        if (!is_known || std::find(label_stats.begin(), label_stats.end(), item) != label_stats.end()) {
+          std::printf("--label-stats %s: '%s' is not one of grey, vol, eq, gmax, angle, zncc, rmsd, wvol, weq, or is given twice\n",
+                      list.c_str(), item.c_str());
+          Usage();
+          return 64;
+        }
+        label_stats.push_back(item);
+        pos = comma + 1;
+      }
+    }
+    else if (a == "--label-stats-bins") {
+      need(1);
+      char* rest = nullptr;
+      const unsigned long long b = std::strtoull(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest || argv[i][0] == '-' || b > 256) {
+        std::printf("--label-stats-bins %s: B must be 0 .. 256\n", argv[i]);
+        Usage();
+        return 64;
+      }
+      label_stats_bins = static_cast<size_t>(b);
+      label_stats_bins_given = true;
+    }
+    else if (a == "--label-stats-paint") label_stats_paint = true;
     else if (a == "--track") track = true;
     else if (a == "--track-min-fraction") {
       need(1);
@@ -752,7 +799,52 @@ int main(int argc, char** argv)
     Usage();
     return 64;
   }
-  if ((!contacts && !segment && !label_shape && labels_file.empty() != (label_model < 0)) || (label_min_given && label_model < 0)) {
+  if ((label_stats_bins_given || label_stats_paint) && label_stats.empty()) {
+    std::printf("--label-stats-bins and --label-stats-paint need --label-stats\n");
+    Usage();
+    return 64;
+  }
+  if (!label_stats.empty() && labels_file.empty() && !segment) {
+    std::printf("--label-stats needs --labels FILE or --segment\n");
+    Usage();
+    return 64;
+  }
+  if (!label_stats.empty() && (use_partial_gpu || concurrent > 1)) {
+    std::printf("--label-stats needs the resident driver, which holds the labels and the fields: it cannot be combined with %s\n",
+                use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  bool label_stats_of_pair = false;  // a name besides grey
+  for (const std::string& name : label_stats) {
+    const char* option = nullptr;
+    if (name == "vol" && !(strain_fields & F3D_STRAIN_VOL)) option = "--strain vol";
+    if (name == "eq" && !(strain_fields & F3D_STRAIN_EQ)) option = "--strain eq";
+    if (name == "gmax" && !(principal_fields & F3D_PRINCIPAL_SHEAR)) option = "--principal shear";
+    if (name == "angle" && !(polar_fields & F3D_POLAR_ANGLE)) option = "--rotation angle";
+    if (name == "zncc" && !(match_fields & OpticalFlowE::kMatchZncc)) option = "--match zncc";
+    if (name == "rmsd" && !(match_fields & OpticalFlowE::kMatchRmsd)) option = "--match rmsd";
+    if (name == "wvol" && !(wstrain_fields & F3D_STRAIN_VOL)) option = "--window-strain vol";
+    if (name == "weq" && !(wstrain_fields & F3D_STRAIN_EQ)) option = "--window-strain eq";
+    if (option) {
+      std::printf("--label-stats %s needs %s, which computes the field\n", name.c_str(), option);
+      Usage();
+      return 64;
+    }
+    if ((name == "zncc" || name == "rmsd") && cumulative) {
+      std::printf("--label-stats %s cannot be combined with --cumulative: the fields of --match live on the pair's grid\n", name.c_str());
+      Usage();
+      return 64;
+    }
+    if (name != "grey") label_stats_of_pair = true;
+  }
+  if (label_stats_of_pair && !synthetic && files.size() > 2 && !cumulative) {
+    std::printf("--label-stats of a field of more than two frames needs --cumulative: the labels live on frame 0's grid, and only the "
+                "displacement from frame 0 lives there too\n");
+    Usage();
+    return 64;
+  }
+  if ((!contacts && !segment && !label_shape && label_stats.empty() && labels_file.empty() != (label_model < 0)) || (label_min_given && label_model < 0)) {
     std::printf("--labels and --label-motion need each other, and --label-min-voxels needs both\n");
     Usage();
     return 64;
@@ -772,7 +864,7 @@ int main(int argc, char** argv)
   // the segmentation is read before any device is touched: a file of another size or without a body is an argument error
   std::vector<int> label_volume;
   size_t n_labels = 0, n_bodies = 0;  // the largest label, and how many of 1 .. n_labels occur
-  if ((label_model >= 0 || contacts || label_shape) && !segment) {
+  if ((label_model >= 0 || contacts || label_shape || !label_stats.empty()) && !segment) {
     const size_t count = width * height * depth;
     std::FILE* f = std::fopen(labels_file.c_str(), "rb");
     bool good = f != nullptr;
@@ -937,7 +1029,7 @@ int main(int argc, char** argv)
   }
   if (!optical_flow_e.AllocateResidentFrames()) return 3;
   std::printf("Mode: Full GPU mode \n");
-  if ((label_model >= 0 || contacts || label_shape) && !segment) {
+  if ((label_model >= 0 || contacts || label_shape || !label_stats.empty()) && !segment) {
     if (!optical_flow_e.UploadLabels(label_volume.data())) return 3;
     std::vector<int>().swap(label_volume);
   }
@@ -999,6 +1091,99 @@ int main(int argc, char** argv)
   };
   if (label_shape && !segment)
     if (const int status = write_shapes(n_labels)) return status;
+
+  // --label-stats: the statistics of one named field over the `stats_labels` labels on the device, as rows of the pair's table
+  // (`stats_rows`, written by flush_stats), one line, and with --label-stats-paint the painted means; 0 or the exit status
+  size_t stats_labels = n_labels;  // the bodies of --segment once it has run
+  std::string stats_rows;
+  auto stats_of = [&](const std::string& name, size_t k, bool whole_line) -> int {
+    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
+    const auto failed = [&]() {
+      std::printf("Error: %s\n", optical_flow_e.DerivedError(OpticalFlowE::kLabelMotion).c_str());
+      return 3;
+    };
+    if (stats_labels == 0 || stats_labels > (static_cast<size_t>(1) << 22)) {
+      std::printf("Error: --label-stats takes 1 .. %d bodies, not %zu; --segment-min-voxels decides which get a label\n", 1 << 22, stats_labels);
+      return 3;
+    }
+    const DevicePtr field = optical_flow_e.NamedField(name.c_str());
+    if (!field) {
+      std::printf("Error: --label-stats %s: the field is not on the device\n", name.c_str());
+      return 3;
+    }
+    float range[2] = {0.f, 0.f};
+    f3d_range_info found = {};
+    if (!optical_flow_e.LabelFieldRange(field, &range[0], &range[1], &found)) return failed();
+    const int shift = f3d_label_field_shift(range[0], range[1], found.finite);
+    // a constant field has no range for bins, and neither has one whose width or scale overflows float32 (f3d_histogram's rule)
+    const float span = range[1] - range[0];
+    const bool has_range = found.finite != 0 && range[0] < range[1] && std::isfinite(span) && label_stats_bins != 0 &&
+                           std::isfinite(static_cast<float>(label_stats_bins) / span);
+    const size_t bins = has_range ? label_stats_bins : 0;
+    std::vector<f3d_label_field_stat> stats(stats_labels);
+    std::vector<unsigned> counts(stats_labels * bins);
+    f3d_label_field_info info = {};
+    f3d_label_field_summary sum = {};
+    if (!optical_flow_e.ComputeLabelField(field, stats_labels, shift, bins ? range : nullptr, bins, 1, stats.data(),
+                                          bins ? counts.data() : nullptr, &info, &sum))
+      return failed();
+    char row[512];
+    for (size_t l = 0; l < stats_labels; ++l) {
+      const f3d_label_field_stat& s = stats[l];
+      std::snprintf(row, sizeof(row), "%s,%zu,%s,%llu,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%llu,%llu\n", name.c_str(), l + 1,
+                    s.status == F3D_LABEL_OK ? "ok" : s.status == F3D_LABEL_EMPTY ? "empty" : "small", s.n, s.min, s.max, s.mean, s.std,
+                    s.q05, s.median, s.q95, s.below, s.above);
+      stats_rows += row;
+    }
+    if (whole_line)
+      std::printf("label stats %s frame %zu -> frame %zu: ", name.c_str(), cumulative ? size_t(0) : k, k + 1);
+    else
+      std::printf("label stats %s frame 0: ", name.c_str());
+    std::printf("%llu ok, %llu empty, %llu small of %zu labels, mean %.9g; shift %d, %zu bins over [%.9g, %.9g]; %llu voxels used, %llu "
+                "nan, %llu out of range, %llu foreign\n", sum.ok, sum.empty, sum.small, stats_labels, sum.mean, shift, bins,
+                static_cast<double>(range[0]), static_cast<double>(range[1]), info.used, info.nan, info.out_of_range, info.foreign);
+    if (label_stats_paint) {
+      std::vector<float> means(stats_labels);
+      for (size_t l = 0; l < stats_labels; ++l)
+        means[l] = stats[l].status == F3D_LABEL_OK ? static_cast<float>(stats[l].mean) : std::nanf("");
+      Data3D painted;
+      if (!painted.Allocate(width, height, depth)) return 2;
+      if (!optical_flow_e.PaintLabels(means.data(), stats_labels, &painted)) return failed();
+      painted.WriteRAWToFileF32((tag + "_labelmean-" + name + suffix).c_str());
+    }
+    return 0;
+  };
+  auto flush_stats = [&](size_t k) -> int {
+    if (stats_rows.empty()) return 0;
+    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
+    std::FILE* csv = std::fopen((tag + "_labelstats.csv").c_str(), "w");
+    if (csv) {
+      std::fprintf(csv, "field,label,status,n,min,max,mean,std,q05,median,q95,below,above\n");
+      std::fwrite(stats_rows.data(), 1, stats_rows.size(), csv);
+    }
+    stats_rows.clear();
+    const bool csv_error = csv && std::ferror(csv) != 0;
+    if (!csv || std::fclose(csv) != 0 || csv_error) {
+      std::printf("Error: cannot write %s_labelstats.csv\n", tag.c_str());
+      return 2;
+    }
+    return 0;
+  };
+  const bool stats_grey = std::find(label_stats.begin(), label_stats.end(), "grey") != label_stats.end();
+  // grey: once, when the labels and the raw frame 0 of the first pair are both on the device; its rows lead the first pair's table
+  auto stats_of_frame_0 = [&]() -> int {
+    if (!stats_grey) return 0;
+    if (const int status = stats_of("grey", 0, false)) return status;
+    return label_stats_of_pair ? 0 : flush_stats(0);
+  };
+  // the fields of pair k, right after they were computed
+  auto stats_of_pair = [&](size_t k) -> int {
+    if (!label_stats_of_pair) return 0;
+    for (const std::string& name : label_stats)
+      if (name != "grey")
+        if (const int status = stats_of(name, k, true)) return status;
+    return flush_stats(k);
+  };
 
   auto report = [&]() {
     Stat3 stat = {0.f, 0.f, 0.f};
@@ -1531,6 +1716,7 @@ int main(int argc, char** argv)
     }
     if (label_shape)
       if (const int status = write_shapes(static_cast<size_t>(info.n_labels))) return status;
+    stats_labels = static_cast<size_t>(info.n_labels);
     if (track) {
       if (info.n_labels == 0 || info.n_labels > (1ull << 22)) {
         std::printf("Error: --segment found %llu bodies and --track takes 1 .. %d; --segment-min-voxels is %llu\n", info.n_labels, 1 << 22,
@@ -1562,6 +1748,7 @@ int main(int argc, char** argv)
     if (print_stats) report();
     if (segment || histogram)
       if (const int status = segment_frame_0()) return status;
+    if (const int status = stats_of_frame_0()) return status;
     optical_flow_e.DownloadFlow(flow_u, flow_v, flow_w);
     write_pair(0, flow_u, flow_v, flow_w);
     if (cumulative) {
@@ -1578,6 +1765,7 @@ int main(int argc, char** argv)
         return 3;
       write_derived(f, 0);
     }
+    if (const int status = stats_of_pair(0)) return status;
     if (contacts) {
       if (!compute_contacts(cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::HeldFlow())) return 3;
       write_contacts(0);
@@ -1672,6 +1860,8 @@ int main(int argc, char** argv)
       optical_flow_e.EndComputeFlowResident();
       if ((segment || histogram) && k == 0)  // frame 0 is still in its container: frame 3 overwrites it only beside the solve of pair 1
         if (const int status = segment_frame_0()) return status;
+      if (k == 0)
+        if (const int status = stats_of_frame_0()) return status;
       if (print_stats) report();
       std::printf("pair %zu of %zu: %.3f s on the device\n", k + 1, pairs, optical_flow_e.LastDeviceSeconds());
       if (!optical_flow_e.TakeResult(taken)) return 3;
@@ -1701,6 +1891,7 @@ int main(int argc, char** argv)
                                                     optical_flow_e.DerivedContainer(f.which, i), c.pitch, c.height, 0));
         CheckDeviceError(f3d_event_record_on(f.down, down));
       }
+      if (const int status = stats_of_pair(k)) return status;  // waits for the fields of pair k, which stay until pair k+1 rewrites them
       if (contacts && !compute_contacts(cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return 3;
       if (track)  // frame k+1 stays in its container until the upload of frame k+4, two solves from here
         if (const int status = track_pair(k, cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return status;

@@ -7,11 +7,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <memory>
 
 #include "common_utils.h"
 #include "operator_calls.h"
 #include "hip_utils.h"
+#include "label_field.h"
 #include "label_shape.h"
 #include "motion_fit.h"
 
@@ -62,6 +64,11 @@ extern "C" int f3d_label_overlap(f3d_devptr labels_a, size_t n_a, f3d_devptr lab
     __attribute__((weak));
 extern "C" int f3d_relabel_labels(f3d_devptr labels, size_t n, const int* map, f3d_devptr out, size_t width, size_t height, size_t depth,
                                   unsigned long long* foreign) __attribute__((weak));
+extern "C" int f3d_label_field_sums(f3d_devptr field, f3d_devptr labels, size_t n_labels, int shift, float lo, float hi, size_t bins,
+                                    size_t width, size_t height, size_t depth, struct f3d_label_field_sums* out, unsigned* counts,
+                                    f3d_label_field_info* info) __attribute__((weak));
+extern "C" int f3d_paint_labels(f3d_devptr labels, size_t n_labels, const float* values, f3d_devptr out, size_t width, size_t height,
+                                size_t depth) __attribute__((weak));
 extern "C" int f3d_label_components(f3d_devptr src, float lo, float hi, unsigned long long min_voxels, f3d_devptr labels_out, size_t width,
                                     size_t height, size_t depth, unsigned long long* sizes, size_t capacity, f3d_component_info* info)
     __attribute__((weak));
@@ -1177,6 +1184,84 @@ bool OpticalFlowE::ComputeLabelShapes(size_t n_labels, f3d_label_shape* shapes, 
     return false;
   SolveLabelShapes(sums.data(), n_labels, shapes);
   return true;
+}
+
+bool OpticalFlowE::ComputeLabelField(DevicePtr field, size_t n_labels, int shift, const float* range, size_t bins,
+                                     unsigned long long min_voxels, f3d_label_field_stat* stats, unsigned* counts,
+                                     f3d_label_field_info* info, f3d_label_field_summary* summary)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!f3d_label_field_sums) return set.Fail("the device library has no f3d_label_field_sums (statistics of a field per labelled body)");
+  if (!stats) return set.Fail("no stats to write to");
+  if (n_labels == 0 || n_labels > (static_cast<size_t>(1) << 22)) return set.Fail("n_labels must be 1 .. 2^22");
+  if ((bins != 0) != (range != nullptr)) return set.Fail("a range goes with bins, and bins with a range");
+  if ((bins != 0) != (counts != nullptr)) return set.Fail("counts go with bins, and bins with counts");
+  const DevicePtr labels = set.ptr[3];
+  if (!labels) return set.Fail("no labels on the device (UploadLabels or ComputeLabels first)");
+  if (!field) field = resident_frame_[0];
+  if (!field) return set.Fail("no frame on the device (AllocateResidentFrames and UploadResidentFrames first)");
+  const f3d_size4 c = Container();
+  const float lo = range ? range[0] : 0.f, hi = range ? range[1] : 0.f;
+  std::vector<struct f3d_label_field_sums> sums(n_labels);
+  if (!set.Check(CheckDeviceError(f3d_set_container(&c))) ||
+      !set.Check(CheckDeviceError(f3d_label_field_sums(field, labels, n_labels, shift, lo, hi, bins, c.width, c.height, c.depth, sums.data(),
+                                                       counts, info))))
+    return false;
+  std::string why;
+  if (!SolveLabelField(sums.data(), counts, n_labels, shift, lo, hi, bins, min_voxels, stats, summary, &why)) return set.Fail(why.c_str());
+  return true;
+}
+
+bool OpticalFlowE::LabelFieldRange(DevicePtr field, float* lo, float* hi, f3d_range_info* info)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!f3d_value_range) return set.Fail("the device library has no f3d_value_range (finite minimum and maximum of a frame)");
+  if (!lo || !hi || !info) return set.Fail("no range or info to write to");
+  const DevicePtr labels = set.ptr[3];
+  if (!labels) return set.Fail("no labels on the device (UploadLabels or ComputeLabels first)");
+  if (!field) field = resident_frame_[0];
+  if (!field) return set.Fail("no frame on the device (AllocateResidentFrames and UploadResidentFrames first)");
+  const f3d_size4 c = Container();
+  return set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+         set.Check(CheckDeviceError(f3d_value_range(field, labels, c.width, c.height, c.depth, lo, hi, info)));
+}
+
+bool OpticalFlowE::PaintLabels(const float* values, size_t n_labels, float* out)
+{
+  FieldSet& set = derived_[kLabelMotion];
+  set.error.clear();
+  if (!initialized_) return set.Fail("the driver was not initialized");
+  if (!f3d_paint_labels) return set.Fail("the device library has no f3d_paint_labels (a value per label painted into a volume)");
+  if (!values || !out) return set.Fail("no values to paint or no volume to paint into");
+  const DevicePtr labels = set.ptr[3];
+  if (!labels) return set.Fail("no labels on the device (UploadLabels or ComputeLabels first)");
+  const f3d_size4 c = Container();
+  const DevicePtr painted = Borrow();
+  if (!painted) return set.Fail("no container to paint into");
+  const bool ok = set.Check(CheckDeviceError(f3d_set_container(&c))) &&
+                  set.Check(CheckDeviceError(f3d_paint_labels(labels, n_labels, values, painted, c.width, c.height, c.depth))) &&
+                  set.Check(CheckDeviceError(f3d_copy3d_d2h(out, c.width, c.height, c.depth, painted, c.pitch, c.height, 0)));
+  GiveBack(painted);
+  return ok;
+}
+
+DevicePtr OpticalFlowE::NamedField(const char* name) const
+{
+  static const struct {
+    const char* name;
+    Derived which;
+    int field;
+  } kNamed[] = {{"vol", kStrain, 0},  {"eq", kStrain, 7}, {"gmax", kPrincipal, 3},     {"angle", kPolar, 0},
+                {"zncc", kMatch, 1}, {"rmsd", kMatch, 2}, {"wvol", kWindowStrain, 0}, {"weq", kWindowStrain, 7}};
+  if (!name) return 0;
+  if (std::strcmp(name, "grey") == 0) return resident_frame_[0];
+  for (const auto& f : kNamed)
+    if (std::strcmp(name, f.name) == 0) return derived_[f.which].ptr[f.field];
+  return 0;
 }
 
 bool OpticalFlowE::ComputeValidated(const Displacement& of, DevicePtr weight, float weight_min, unsigned step, float eps,

@@ -220,6 +220,23 @@ class OpticalFlowE : public OpticalFlowBase {
   // shapes has n_labels entries (required), info is nullable.  It needs the label container alone, however it was filled, so it runs
   // before any solve.  Waits for the stream.  Errors are reported through DerivedError(kLabelMotion), whose labels these are.
   bool ComputeLabelShapes(size_t n_labels, f3d_label_shape* shapes, f3d_label_shape_info* info);
+  // Statistics of a scalar field over the labels on the device (f3d_label_field_sums of include/f3d.h, then f3d_label_field_solve of
+  // include/f3d_host.h).  field: a container of the driver's geometry -- DerivedContainer() or NamedField() of a computed field -- or 0
+  // for the resident frame 0.  range: {lo, hi}, null iff bins == 0; counts: n_labels * bins entries, null iff bins == 0; stats has
+  // n_labels entries (required); info and summary are nullable.  PaintLabels: values[l - 1] into the voxels of label l and NaN elsewhere
+  // (f3d_paint_labels) in a pooled container, and down to out (width * height * depth floats).  Both wait for the stream; errors are
+  // reported through DerivedError(kLabelMotion), whose labels these are.  NamedField: the container of grey (the resident frame 0),
+  // vol, eq (kStrain), gmax (kPrincipal), angle (kPolar), zncc, rmsd (kMatch), wvol, weq (kWindowStrain); 0 for another name and
+  // until the field is computed.
+  bool ComputeLabelField(DevicePtr field, size_t n_labels, int shift, const float* range, size_t bins, unsigned long long min_voxels,
+                         f3d_label_field_stat* stats, unsigned* counts, f3d_label_field_info* info,
+                         f3d_label_field_summary* summary = nullptr);
+  // the finite minimum and maximum of `field` (0: the resident frame 0) over the voxels whose label is not 0 (f3d_value_range masked by
+  // the labels): what the shift and the range of ComputeLabelField are chosen from when the caller gives none
+  bool LabelFieldRange(DevicePtr field, float* lo, float* hi, f3d_range_info* info);
+  bool PaintLabels(const float* values, size_t n_labels, float* out);
+  bool PaintLabels(const float* values, size_t n_labels, Data3D* out) { return PaintLabels(values, n_labels, out ? out->DataPtr() : nullptr); }
+  DevicePtr NamedField(const char* name) const;
   // A second label volume, "B", beside the one UploadLabels fills ("A"): the bodies of a later frame, on the grid a displacement
   // leads to, in a container of its own that goes with ReleaseDerived(kLabelMotion) or Destroy().  UploadLabelsB / DownloadLabelsB as
   // their namesakes.  ComputeLabelsB: f3d_label_components (core_d2 == 0; only the first eight counters of info, those of

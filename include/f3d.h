@@ -1212,6 +1212,70 @@ int f3d_label_overlap(f3d_devptr labels_a, size_t n_a, f3d_devptr labels_b, size
 int f3d_relabel_labels(f3d_devptr labels, size_t n, const int* map /* n entries, host */, f3d_devptr out, size_t width, size_t height,
                        size_t depth, unsigned long long* foreign /* nullable; non-null waits */);
 
+/* Statistics of a scalar field per labelled body (no reference counterpart: what the equivalent strain, the volume change, the match
+ * quality or the grey value say about every grain of a segmented sample, as exact sums that do not depend on the order).  The box is
+ * width x height x depth in the corner of the current container; field is a container of floats; labels is a container read as int32
+ * under the rules of f3d_label_motion_sums: 0 is background, 1 .. n_labels are bodies, every other value is foreign.  Container
+ * padding is never read.
+ *
+ * Classes.  f3d_label_field_info (nullable) counts every voxel of the box exactly once, tried in this order, with s the field's value:
+ *   background    the label is 0
+ *   foreign       the label is outside 0 .. n_labels
+ *   nan           s is a NaN
+ *   out_of_range  t = s * scale, ONE float32 product with scale = ldexpf(1.0f, shift), has fabsf(t) > 16777216.0f: an infinity lands
+ *                 here.  The product is exact unless it underflows, and then it is the float32 result of that product
+ *   used          the voxel takes part:  sum of n over the rows == used
+ * Quantisation.  A voxel that takes part has q = (int)rintf(t), to nearest, ties to even, so |q| <= 2^24 and every sum below is an
+ * exact integer.  shift is -100 .. 100.
+ * out[L-1] receives eight 64-bit words of label L, over the voxels of L that take part:
+ *   n                  their number
+ *   min_key, max_key   the smallest and the largest raw s among them as f3d_value_range's totally ordered integer key of the bits
+ *                      (csrc/f3d_histogram_bin.h, key_of_bits): -0.0f is below +0.0f and a denormal keeps its value.  The key of a finite
+ *                      float is never 0 or 0xffffffff; a label without a voxel gets min_key 0xffffffff and max_key 0
+ *   iq                 sum q, signed; |iq| < 2^55
+ *   iqq_lo, iqq_hi     sum q^2 (q^2 <= 2^48 and n < 2^31: below 2^79) in two limbs, the sum being hi * 2^32 + lo as a 128-bit integer.
+ *                      On the device each addend v (a lane's run of at most 32 voxels, or the 2^13 voxels of a tile from the
+ *                      workgroup's table: v < 2^61) adds v & 0xffffffff to lo and v >> 32 to hi, as f3d_label_motion_sums does;
+ *                      neither limb overflows.  How the voxels fall into addends depends on the schedule, so the entry carries the
+ *                      limbs before it writes out: iqq_lo is below 2^32 and iqq_hi is the rest, a function of the input alone
+ *   below, above       with bins: the voxels with s < lo and with s > hi; 0 without
+ * Bins.  bins is 0 .. 256.  With bins == 0, lo and hi are ignored, below = above = 0 and counts must be null.  With bins, lo < hi are
+ * both finite, scale_b = (float)bins / (hi - lo) is formed as f3d_histogram forms it, and the bin rule of csrc/f3d_histogram_bin.h is
+ * applied, unchanged, to the raw s of every voxel that takes part: s < lo adds to below, s > hi to above, every other voxel adds one to
+ * counts[(L-1) * bins + min((int)((s - lo) * scale_b), bins - 1)].  So below + above + sum(counts row) == n for every label.
+ * Determinism.  Everything is an integer function of the input, added with integer atomics, the extremes maxima over integer keys (the
+ * device accumulates max(key) and max(0xffffffff - key), so that cleared memory is the identity): two calls give the same bytes.
+ * Limits: f3d_label_shape_sums'.  At most 32768 voxels along an axis and 2^31 - 1 in the box; n_labels is 1 .. 2^22 and
+ * n_labels * bins at most 2^26; counts are 32-bit.  The accumulators (64 B per label, the five counters, 4 B per count) live in a
+ * grow-only buffer of the library's, cleared on the stream before the kernel and copied down after it.
+ * Refused (status 1, a message, nothing written): a null field, labels or out; field and labels being one container; shift outside
+ * -100 .. 100; bins above 256; counts given with bins == 0 or missing with bins > 0; what f3d_histogram refuses of lo, hi, bins;
+ * n_labels outside 1 .. 2^22; n_labels * bins above 2^26; an empty box, a box beyond the limits or larger than the current
+ * container.  Geometry from the current container, library stream; the call waits for the stream.
+ * The solve from the rows to mean, deviation and quantiles is host code: f3d_label_field_solve of include/f3d_host.h. */
+struct f3d_label_field_sums {
+  unsigned long long n, min_key, max_key;
+  long long iq;
+  unsigned long long iqq_lo, iqq_hi, below, above;
+};
+typedef struct f3d_label_field_info {
+  unsigned long long background, foreign, nan, out_of_range, used;
+} f3d_label_field_info;
+int f3d_label_field_sums(f3d_devptr field, f3d_devptr labels, size_t n_labels, int shift, float lo, float hi, size_t bins, size_t width,
+                         size_t height, size_t depth, struct f3d_label_field_sums* out /* n_labels entries, host */,
+                         unsigned* counts /* n_labels * bins entries, host; null iff bins == 0 */,
+                         f3d_label_field_info* info /* nullable */);
+
+/* A value per label painted into a volume: out(x) = values[l - 1] for l = labels(x) in 1 .. n_labels -- the bytes are copied, a NaN
+ * keeps its payload -- and the quiet NaN 0x7fc00000 for background (0) and foreign (outside 0 .. n_labels) voxels.  values is a host
+ * array of n_labels floats, uploaded per call into a grow-only buffer of the library's (the call waits for that copy, not for the
+ * kernel).  out may be labels itself: each voxel reads and writes its own word, and the caller then reads the container as floats.  One
+ * streaming pass; container padding is neither read nor written.  Refused (status 1, a message, nothing written): a null labels,
+ * values or out; n_labels outside 1 .. 2^22; an empty box, one above 32768 along an axis or 2^31 - 1 voxels, or one that does not fit
+ * the current container.  Geometry from the current container, library stream. */
+int f3d_paint_labels(f3d_devptr labels, size_t n_labels, const float* values /* n_labels entries, host */, f3d_devptr out, size_t width,
+                     size_t height, size_t depth);
+
 /* Validation of a displacement (no reference counterpart: the normalised median test of PIV and volume-correlation post-processing,
  * Westerweel & Scarano 2005, which a workflow applies between the displacement and the strain).  A vector is compared with the median
  * of its neighbours, scaled by the median residual of those neighbours; a rejected vector becomes NaN (which f3d_flow_strain and

@@ -415,6 +415,70 @@ int f3d_flow_overlap_end(f3d_flow flow);
 int f3d_flow_labels_b_relabel(f3d_flow flow, const int* map, size_t n_b);
 int f3d_flow_labels_b_download(f3d_flow flow, int* labels);
 
+/* The solve from the rows and counts of f3d_label_field_sums (include/f3d.h) to the statistics of a scalar field per body.  Host code,
+ * no device needed; shift, lo, hi and bins are those of the device call, counts is null iff bins == 0.  stats[L-1] of label L:
+ *   status        F3D_LABEL_EMPTY when n == 0, else F3D_LABEL_SMALL when n < min_voxels, else F3D_LABEL_OK.  A SMALL label is filled
+ *                 like an OK one
+ *   n, below, above   copied from the row
+ *   min, max      the floats of min_key and max_key as binary64; NaN for an EMPTY label, as is every double below
+ *   mean          ldexp((double)iq / (double)n, -shift)
+ *   variance      V = n * iqq - iq^2 (iqq = iqq_hi * 2^32 + iqq_lo) formed exactly in unsigned __int128 -- below 2^111, never
+ *                 negative -- rounded once to binary64, divided by (double)n and again by (double)n: vq, the population variance of
+ *                 q; variance = ldexp(vq, -2 * shift)
+ *   std           ldexp(sqrt(vq), -shift)
+ *   q05, median, q95   with bins and m = sum(counts row) > 0: the ranks (m - 1) / 20, (m - 1) / 2 and (m - 1) - (m - 1) / 20 in integer
+ *                 arithmetic, f3d_histogram_rank of each gives a bin k (q05_bin, median_bin, q95_bin), and the value is the binary64
+ *                 midpoint (e_k + e_(k+1)) / 2.0 of that bin's float32 edges e_k = f3d_histogram_edge(lo, hi, bins, k), with hi for
+ *                 e_bins: a quantile is known to a bin, no finer.  Without bins, or with m == 0, the values are NaN and the bins -1
+ * summary (nullable): the numbers of OK, EMPTY and SMALL labels and mean = sum(n * mean) / sum(n) over the OK labels, both sums in
+ * binary64 in label order, every operation rounded on its own; NaN without an OK label.
+ * Returns non-zero (f3d_host_last_error() set) for a null sums or stats, counts given with bins == 0 or missing with bins > 0, shift
+ * outside -100 .. 100, bins above 256, what f3d_histogram refuses of lo, hi, bins, or a row of counts that adds up to more than
+ * 2^33. */
+typedef struct f3d_label_field_stat {
+  int status;
+  int q05_bin, median_bin, q95_bin;
+  unsigned long long n, below, above;
+  double min, max, mean, variance, std, q05, median, q95;
+} f3d_label_field_stat;
+typedef struct f3d_label_field_summary {
+  unsigned long long ok, empty, small;
+  double mean;
+} f3d_label_field_summary;
+int f3d_label_field_solve(const struct f3d_label_field_sums* sums, const unsigned* counts /* n_labels * bins; null iff bins == 0 */,
+                          size_t n_labels, int shift, float lo, float hi, size_t bins, unsigned long long min_voxels,
+                          f3d_label_field_stat* stats /* n_labels entries */, f3d_label_field_summary* summary /* nullable */);
+
+/* The shift of f3d_label_field_sums for a field whose finite values lie in [min, max], `finite` of them (f3d_value_range's results): with
+ * m = max(|min|, |max|) = f * 2^e, f in [0.5, 1) (frexp), the shift is 24 - e clamped to -100 .. 100, and 0 when m == 0, nothing is
+ * finite or a bound is not.  Unless the clamp acts (m at or above 2^124), m * 2^shift < 2^24: no finite voxel is out of range, the
+ * quantum is 2^-24 of the largest magnitude, and an integer field below 2^24 in magnitude, a uint16 grey value say, is kept exactly.
+ * Returns the shift; nothing can fail. */
+int f3d_label_field_shift(float min, float max, unsigned long long finite);
+
+/* Statistics of a field over the labels the driver keeps on the device (f3d_label_field_sums, then f3d_label_field_solve), and a value
+ * per label painted into a volume (f3d_paint_labels).  The labels are those an earlier call uploaded or f3d_flow_labels_compute /
+ * f3d_flow_labels_split made.
+ *   f3d_flow_label_field_compute  field is a device container of the driver's geometry -- a derived field's container, say -- or 0 for
+ *                                 the resident frame 0.  range is {lo, hi}, null iff bins == 0.  stats has n_labels entries (required);
+ *                                 counts has n_labels * bins entries (null iff bins == 0); info and summary are nullable
+ *   f3d_flow_labels_paint         values[l - 1] into the voxels of label l, NaN elsewhere, into a container of the driver's pool, and
+ *                                 down into out (width * height * depth floats)
+ * A device library without the entry a call needs still loads; then the call fails with a message naming the entry. */
+int f3d_flow_label_field_compute(f3d_flow flow, f3d_devptr field /* 0: the resident frame 0 */, size_t n_labels, int shift,
+                                 const float* range /* {lo, hi}; null iff bins == 0 */, size_t bins, unsigned long long min_voxels,
+                                 f3d_label_field_stat* stats, unsigned* counts, f3d_label_field_info* info,
+                                 f3d_label_field_summary* summary);
+int f3d_flow_labels_paint(f3d_flow flow, const float* values, size_t n_labels, float* out);
+/* f3d_value_range of `field` (0: the resident frame 0) masked by the driver's labels: the finite minimum and maximum over the voxels whose
+ * label is not 0, from which a caller takes f3d_label_field_shift and, with bins, the range when it has none of its own. */
+int f3d_flow_label_field_range(f3d_flow flow, f3d_devptr field /* 0: the resident frame 0 */, float* min, float* max, f3d_range_info* info);
+/* The container of a field the driver holds, for f3d_flow_label_field_compute: "grey" (the resident frame 0), "vol", "eq"
+ * (f3d_flow_strain_compute), "gmax" (the maximum shear of f3d_flow_principal_compute), "angle" (f3d_flow_polar_compute), "zncc", "rmsd"
+ * (f3d_flow_match_compute), "wvol", "weq" (f3d_flow_window_strain_compute).  Fails for another name and until the field is computed;
+ * the container is the driver's and lives as long as that field does. */
+int f3d_flow_field_container(f3d_flow flow, const char* name, f3d_devptr* container);
+
 /* Exact selection on a histogram of f3d_histogram (include/f3d.h has the bin rule).  Host code, no device needed.  Each returns
  * non-zero (f3d_host_last_error() set, nothing written) when it refuses its arguments.
  *
