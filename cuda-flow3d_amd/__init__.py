@@ -531,6 +531,7 @@ def host():
         "f3d_plan_sweeps": [C.c_int] * 4 + [C.POINTER(C.c_int)] * 2 + [C.c_int],
         "f3d_plan_sweeps_weights_first": [C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.c_int],
         "f3d_pair8_plan": [C.c_int] * 7 + [C.POINTER(C.c_longlong)],
+        "f3d_solver_chunk_limit": [C.c_ulonglong, C.c_int],
         "f3d_pair8_decode": [C.c_int] * 4 + [C.POINTER(C.c_longlong)] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2,
         "f3d_pair8_plan_wide": [C.c_int] * 7 + [C.POINTER(C.c_longlong)],
         "f3d_pair8_decode_wide": [C.c_int] * 4 + [C.POINTER(C.c_longlong)] + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2,
@@ -2433,6 +2434,13 @@ def pair8_plan(width, rows, planes, ty, zc_limit=None, per_round=0, fold=False):
     out = (C.c_longlong * 8)()
     check(host().f3d_pair8_plan(width, rows, planes, ty, planes if zc_limit is None else zc_limit, per_round, int(bool(fold)), out))
     return Pair8Plan(*[int(v) for v in out])
+
+
+def solver_chunk_limit(plane_bytes, reach):
+    """The planes a z-chunk of a solver launch may hold at most in a container whose planes are `plane_bytes` (container height x
+    pitch in bytes), for a launch that reads `reach` halo planes on either side of a chunk (1: phi/ksi or one sweep, 2: the
+    two-stage launches, 3: the three-stage ones); 0 where not even one plane fits the 32-bit offsets and the launch is refused."""
+    return int(host().f3d_solver_chunk_limit(int(plane_bytes), int(reach)))
 
 
 def pair8_decode(width, rows, ty, fold, plan, xcd_remap, z_lo, z_hi):

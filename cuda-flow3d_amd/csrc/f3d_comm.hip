@@ -600,14 +600,15 @@ int f3d_copy_plane_segments(const f3d_devptr* dst, const int* dst_plane0, const 
   if (n_segments < 0 || (n_segments > 0 && (!dst || !dst_plane0 || !src || !src_plane0 || !count)))
     return f3d::fail("f3d_copy_plane_segments: bad argument");
   const f3d_size4& c = f3d::container();
+  for (int i = 0; i < n_segments; ++i)   // every triple first: a refusal launches nothing, not the triples in front of it either
+    if (check_planes(dst_plane0[i], count[i], width, height, "f3d_copy_plane_segments") ||
+        check_planes(src_plane0[i], count[i], width, height, "f3d_copy_plane_segments"))
+      return 1;
   for (int i = 0; i < n_segments; i += kMaxSeg) {
     const int n = std::min(kMaxSeg, n_segments - i);
     CopyTable t = {};
     int max_count = 0;
     for (int k = 0; k < n; ++k) {
-      if (check_planes(dst_plane0[i + k], count[i + k], width, height, "f3d_copy_plane_segments") ||
-          check_planes(src_plane0[i + k], count[i + k], width, height, "f3d_copy_plane_segments"))
-        return 1;
       t.dst[k] = f3d_ptr<float>(dst[i + k]);
       t.src[k] = f3d_ptr<const float>(src[i + k]);
       t.dst_plane0[k] = dst_plane0[i + k];

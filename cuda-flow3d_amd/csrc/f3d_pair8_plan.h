@@ -24,6 +24,19 @@ constexpr int kPair8Lanes = 64;   // columns of a tile
 #define PAIR8_UNIFORM(x) (x)
 #endif
 
+// The solver kernels address a z-chunk with unsigned 32-bit byte offsets from the lowest plane the chunk touches: its own planes and
+// `reach` halo planes on either side (1 for one sweep or the weights, 2 for the two-stage launches, 3 for the three-stage ones) must
+// span at most 2^32 bytes of one array.  Returns the planes a chunk may hold at most -- eight planes of slack below 2^32 wherever
+// that leaves a plane; where it does not (planes above 2^32 / 9 bytes), 1 as long as one plane with its halo still fits -- or 0:
+// no chunk fits, the launch must be refused.  The entries and their planners ask with the reach of the launch.
+inline int solver_chunk_limit(unsigned long long plane_bytes, int reach)
+{
+  if (plane_bytes == 0 || plane_bytes > 0x100000000ull || reach < 0) return 0;
+  const long long planes = static_cast<long long>(0xffffffffull / plane_bytes) - 8;
+  if (planes >= 1) return planes > 0x3fffffff ? 0x3fffffff : static_cast<int>(planes);
+  return (1ull + 2ull * static_cast<unsigned long long>(reach)) * plane_bytes <= 0x100000000ull ? 1 : 0;
+}
+
 // Tiles of a level, numbered x first.  With a folded last column (`fold`) a pair of tile rows (ty, ty + 1), ty even, is numbered: the
 // ntx - 1 regular tiles of row ty, the folded tile, the regular tiles of row ty + 1 -- so the folded tile marches in step with its y
 // neighbours; with nty odd the last row is alone with its folded tile (whose band B is empty).

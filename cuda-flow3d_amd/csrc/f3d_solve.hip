@@ -1029,13 +1029,25 @@ const Tuning& tuning()
 // The kernels address a z-chunk with 32-bit byte offsets from the chunk's first plane: a chunk, with the halo planes it
 // reads on either side, must stay below 4 GiB of one array.  Planes of a container larger than 1024 x 1024 floats leave room
 // for fewer than 1024 of them.
-inline int max_planes_per_chunk(const F3dGeo& g)
+inline int max_planes_per_chunk(const F3dGeo& g, int reach)
 {
   static const bool off = std::getenv("F3D_CHUNK_LIMIT") && std::atoi(std::getenv("F3D_CHUNK_LIMIT")) == 0;
   if (off) return 0x3fffffff;  // only to show that tests/test_gpu_big.py catches the overflow
   const unsigned long long plane_bytes = static_cast<unsigned long long>(g.Hc) * static_cast<unsigned long long>(g.pitch) * 4ull;
-  const long long planes = static_cast<long long>(0xffffffffull / plane_bytes) - 8;  // 3-4 halo planes each way and slack
-  return planes < 1 ? 1 : (planes > 0x3fffffff ? 0x3fffffff : static_cast<int>(planes));
+  const int planes = solver_chunk_limit(plane_bytes, reach);  // (f3d_pair8_plan.h)
+  return planes < 1 ? 1 : planes;  // (0: chunk_limit_ok has refused the launch; a planner still priced never divides by it)
+}
+
+// Every entry that cuts its launch with max_planes_per_chunk asks this first, with the same reach: planes so large that ONE plane and the `reach` halo
+// planes its launch reads on either side pass 2^32 bytes would be addressed with wrapped offsets, so the launch is refused.
+bool chunk_limit_ok(const F3dGeo& g, int reach, const char* who)
+{
+  const unsigned long long plane_bytes = static_cast<unsigned long long>(g.Hc) * static_cast<unsigned long long>(g.pitch) * 4ull;
+  if (solver_chunk_limit(plane_bytes, reach) >= 1) return true;
+  f3d::fail("%s: a container plane of %llu bytes is too large: one plane and %d halo planes on either side pass the 4 GiB that a "
+            "z-chunk's 32-bit byte offsets span",
+            who, plane_bytes, reach);
+  return false;
 }
 
 // Frame derivatives of a level, once: fx, fy, fz as A.3 / A.4 form them (the numerator left to right, one IEEE division by 4h)
@@ -1099,7 +1111,7 @@ void launch_solver(const SolveArgs& args, const F3dGeo& g)
     zchunk = static_cast<int>((planes + chunks - 1) / chunks);
   }
   if (t.zchunk > 0) zchunk = t.zchunk;
-  zchunk = std::min(zchunk, max_planes_per_chunk(g));
+  zchunk = std::min(zchunk, max_planes_per_chunk(g, 1));
   SolveArgs a = args;
   int nz = (planes + zchunk - 1) / zchunk;
   if (!SWEEP && a.z2_hi > a.z2_lo) {  // the chunks of the second window follow those of the first
@@ -1138,7 +1150,7 @@ void launch_sweep2_ty(const SolveArgs& a, const F3dGeo& g, long want_wg, int for
   // chunks of at least two planes: a coarse level is latency-bound and prefers many short marches (64^3: 2-plane chunks in
   // one round, 28 -> 16 us per launch), a fine one never gets near the limit
   const int max_chunks = planes / 2 > 0 ? planes / 2 : 1;
-  const int zc_limit = max_planes_per_chunk(g);
+  const int zc_limit = max_planes_per_chunk(g, 2);
   int zchunk = std::min(planes, zc_limit);
   if (want_wg > 0) {  // experiments: aim at a workgroup count
     long nzc = (want_wg + tiles - 1) / tiles;
@@ -1264,8 +1276,8 @@ int tri_rows(const F3dGeo& g)
   if (forced == 4 || forced == 7) return forced;
   static const long step4 = std::getenv("F3D_TRI_STEP4") ? std::atol(std::getenv("F3D_TRI_STEP4")) : 80;
   const int planes = g.z_hi - g.z_lo;
-  const long c4 = tri_plan_dims(g.W, g.H, planes, 4, max_planes_per_chunk(g)).cost * step4;
-  const long c7 = tri_plan_dims(g.W, g.H, planes, 7, max_planes_per_chunk(g)).cost * 100;
+  const long c4 = tri_plan_dims(g.W, g.H, planes, 4, max_planes_per_chunk(g, 3)).cost * step4;
+  const long c7 = tri_plan_dims(g.W, g.H, planes, 7, max_planes_per_chunk(g, 3)).cost * 100;
   return c4 < c7 ? 4 : 7;
 }
 
@@ -1283,7 +1295,7 @@ int tri_launch(const char* who, bool with_weights, const f3d_devptr (&in)[10], s
     for (int k = 0; k < 10; ++k)
       if (out[i] == in[k]) return f3d::fail("%s: an output buffer is also an input (other tiles still read it)", who);
   if (g.z_lo == g.z_hi) return 0;
-  if (!slab_reach_ok(g, 3, who)) return 1;
+  if (!slab_reach_ok(g, 3, who) || !chunk_limit_ok(g, 3, who)) return 1;
   PairArgs a = {};
   static const int plain_division = std::getenv("F3D_UDIV") && std::atoi(std::getenv("F3D_UDIV")) == 0;
   a.plain_division = plain_division;
@@ -1323,7 +1335,7 @@ int sweep_launch(const char* who, const f3d_devptr (&in)[10], size_t width, size
         if (out[i] == in[k]) return f3d::fail("%s: an output buffer is also an input (other tiles still read it)", who);
   }
   if (g.z_lo == g.z_hi) return 0;
-  if (!slab_reach_ok(g, 1, who)) return 1;
+  if (!slab_reach_ok(g, 1, who) || !chunk_limit_ok(g, 1, who)) return 1;
   SolveArgs a;
   static const int plain_division = std::getenv("F3D_UDIV") && std::atoi(std::getenv("F3D_UDIV")) == 0;
   a.plain_division = plain_division;
@@ -1355,7 +1367,7 @@ int f3d_phi_ksi(f3d_devptr frame_0, f3d_devptr frame_1, f3d_devptr flow_u, f3d_d
   if (!f3d::make_geo(&g, width, height, depth, slab, "f3d_phi_ksi")) return 1;
   if (g.W < 2 || g.H < 2 || g.D < 2) return f3d::fail("f3d_phi_ksi: every dimension must be at least 2");
   if (g.z_lo == g.z_hi) return 0;
-  if (!slab_reach_ok(g, 1, "f3d_phi_ksi")) return 1;
+  if (!slab_reach_ok(g, 1, "f3d_phi_ksi") || !chunk_limit_ok(g, 1, "f3d_phi_ksi")) return 1;
   SolveArgs a;
   static const int plain_division = std::getenv("F3D_UDIV") && std::atoi(std::getenv("F3D_UDIV")) == 0;
   a.plain_division = plain_division;
@@ -1392,6 +1404,7 @@ int f3d_phi_ksi_zones(f3d_devptr frame_0, f3d_devptr frame_1, f3d_devptr flow_u,
                        equation_smoothness, equation_data, phi, ksi, g.z_lo == g.z_hi ? zone_b : zone_a);
   if (!(g.z_hi <= g2.z_lo || g2.z_hi <= g.z_lo)) return f3d::fail("f3d_phi_ksi_zones: the windows overlap");
   if (!slab_reach_ok(g, 1, "f3d_phi_ksi_zones") || !slab_reach_ok(g2, 1, "f3d_phi_ksi_zones")) return 1;
+  if (!chunk_limit_ok(g, 1, "f3d_phi_ksi_zones")) return 1;
   SolveArgs a;
   static const int plain_division = std::getenv("F3D_UDIV") && std::atoi(std::getenv("F3D_UDIV")) == 0;
   a.plain_division = plain_division;
@@ -1446,6 +1459,9 @@ int f3d_solve_sweep2(f3d_devptr frame_0, f3d_devptr frame_1, f3d_devptr flow_u, 
     return f3d::fail("f3d_solve_sweep2: alpha / h^2 must be finite and not negative (alpha %g, h %g %g %g)", equation_alpha, hx, hy, hz);
   if (g.z_lo == g.z_hi) return 0;
   if (!slab_reach_ok(g, 2, "f3d_solve_sweep2")) return 1;
+  // (a level that marches along y is never cut in z: pair8_ymarch_rows keeps a guard of its own)
+  const bool y_march = pair8_enabled() && g.pitch % kLanes == 0 && pair8_ymarch_rows(g) != 0;
+  if (!y_march && !chunk_limit_ok(g, 2, "f3d_solve_sweep2")) return 1;
   SolveArgs a;
   static const int plain_division = std::getenv("F3D_UDIV") && std::atoi(std::getenv("F3D_UDIV")) == 0;
   a.plain_division = plain_division;
@@ -1483,6 +1499,8 @@ int f3d_solve_sweep_phi_ksi_edges(f3d_devptr frame_0, f3d_devptr frame_1, f3d_de
     return f3d::fail("f3d_solve_sweep_phi_ksi: the container pitch must be a multiple of 256 bytes (f3d_alloc_pitched gives that)");
   if (g.z_lo == g.z_hi) return 0;
   if (!slab_reach_ok(g, 2, "f3d_solve_sweep_phi_ksi")) return 1;
+  const bool y_march = !keep_below && !keep_above && pair8_ymarch_rows(g) != 0;  // (never cut in z: a guard of its own)
+  if (!y_march && !chunk_limit_ok(g, 2, "f3d_solve_sweep_phi_ksi")) return 1;
   PairArgs a = {};
   a.keep_below = keep_below != 0;
   a.keep_above = keep_above != 0;
@@ -1602,7 +1620,7 @@ int pair8_fd(const char* who, bool with_weights, const f3d_devptr (&in)[12], siz
   if (with_weights && (out[3] == in[8] || out[4] == in[9] || out[3] == in[9] || out[4] == in[8]))
     return f3d::fail("%s: phi_next / ksi_next must not alias phi / ksi (other tiles still read them)", who);
   if (g.z_lo == g.z_hi) return 0;
-  if (!slab_reach_ok(g, 2, who)) return 1;
+  if (!slab_reach_ok(g, 2, who) || !chunk_limit_ok(g, 2, who)) return 1;
   PairArgs a = {};
   a.keep_below = with_weights && keep_below != 0;
   a.keep_above = with_weights && keep_above != 0;
@@ -1687,6 +1705,7 @@ int wpair8_fd(const char* who, bool weights_first, const f3d_devptr (&in)[12], s
   if (!pair_weights_finite(hx, hy, hz, alpha)) return f3d::fail("%s: alpha / h^2 must be finite and not negative (alpha %g, h %g %g %g)", who, alpha, hx, hy, hz);
   if (g.pitch % 256 != 0) return f3d::fail("%s: the container pitch must be a multiple of 256 floats", who);
   if (!pair8_enabled() || pair8_ymarch_rows(g) != 0) return f3d::fail("%s: the fused launches march along y on this level", who);
+  if (!chunk_limit_ok(g, 2, who)) return 1;
   for (int i = 0; i < 5; ++i)
     for (int k = 0; k < 12; ++k)
       if (out[i] && out[i] == in[k]) return f3d::fail("%s: an output buffer is also an input (other tiles still read it)", who);

@@ -1302,7 +1302,7 @@ inline Pair8Plan pair8_plan_launch_kept(int width, int rows, int planes, int ty,
 // the plan of a level window (f3d_pair8_plan.h); F3D_PAIR8_ROUND replaces the 256 workgroups of a round
 inline Pair8Plan pair8_plan(const F3dGeo& g, int ty, long per_round = 256)
 {
-  return pair8_plan_launch_kept(g.W, g.H, g.z_hi - g.z_lo, ty, max_planes_per_chunk(g), pair8_per_round(per_round),
+  return pair8_plan_launch_kept(g.W, g.H, g.z_hi - g.z_lo, ty, max_planes_per_chunk(g, 2), pair8_per_round(per_round),
                                 pair8_folds(g.W, g.H, ty));
 }
 
@@ -1340,7 +1340,7 @@ void launch_pair8(const PairArgs& args, const F3dGeo& g, int force_zchunk, int x
   const int planes = YM ? g.H : g.z_hi - g.z_lo;
   const int ntx = (g.W + kLanes - 1) / kLanes;
   const int nty = (rows + TY - 1) / TY;
-  const int zc_limit = YM ? planes : max_planes_per_chunk(g);
+  const int zc_limit = YM ? planes : max_planes_per_chunk(g, 2);
 #ifdef F3D_LAB
   static const int abl = std::getenv("F3D_ABLATE8") ? std::atoi(std::getenv("F3D_ABLATE8")) : 0;
 #else

@@ -468,7 +468,7 @@ void launch_tri(const PairArgs& args, const F3dGeo& g, int force_zchunk, int xcd
   const int planes = g.z_hi - g.z_lo;
   const int ntx = tri_tile_columns(g.W);
   const int nty = (g.H + TY - 1) / TY;
-  const int zc_limit = max_planes_per_chunk(g);
+  const int zc_limit = max_planes_per_chunk(g, 3);
   int zchunk = tri_plan_dims(g.W, g.H, planes, TY, zc_limit).zchunk;
   if (force_zchunk > 0) zchunk = force_zchunk;
   zchunk = std::min(zchunk, zc_limit);

@@ -967,6 +967,8 @@ int f3d_pair8_plan(int width, int rows, int planes, int ty, int zc_limit, int pe
   return 0;
 }
 
+int f3d_solver_chunk_limit(unsigned long long plane_bytes, int reach) { return solver_chunk_limit(plane_bytes, reach); }
+
 int f3d_pair8_decode(int width, int rows, int ty, int fold, const long long* plan, int xcd_remap, int z_lo, int z_hi, int first,
                      int count, int* out, int* grid)
 {

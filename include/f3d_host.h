@@ -590,6 +590,12 @@ int f3d_plan_sweeps_weights_first(int inner, int* first, int* sweeps, int* weigh
  * per_round: workgroups that run at a time (<= 0: 256, or F3D_PAIR8_ROUND); fold: the last tile column holds two row bands per tile.
  * plan[8] = A, a, b, zc_a, zc_b, workgroups, cost in plane steps, tiles.  F3D_PAIR8_PLAN=0 gives the uniform plan. */
 int f3d_pair8_plan(int width, int rows, int planes, int ty, int zc_limit, int per_round, int fold, long long* plan);
+/* the `zc_limit` of the solver launches (the launchers' own function, csrc/f3d_pair8_plan.h): the planes a z-chunk may hold at most
+ * in a container whose planes are plane_bytes = container height x pitch bytes, for a launch that reads `reach` halo planes on either
+ * side of a chunk (1: f3d_phi_ksi[_zones], f3d_solve_sweep[_add]; 2: the two-stage launches; 3: f3d_solve_sweep3,
+ * f3d_solve_sweep2_phi_ksi) -- a chunk and its halo span at most 2^32 bytes, which is what the kernels' 32-bit byte offsets cover.
+ * 0: not even one plane fits, and every such launch refuses the container (a level that marches along y is not cut in z). */
+int f3d_solver_chunk_limit(unsigned long long plane_bytes, int reach);
 /* the kernel's decode of workgroup numbers first .. first + count - 1 under plan[0 .. 4] (the same function, compiled for the host):
  * out[6 i ..] = tile, tile column, tile row, folded, z0, z1 (planes [z0, z1) of [z_lo, z_hi)), or six times -1 for a padding number.
  * *grid (if given) = workgroup numbers of the launch.  Returns 0, or 1 for arguments that make no plan. */

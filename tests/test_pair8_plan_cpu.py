@@ -174,3 +174,59 @@ def test_levels_that_one_round_covers_keep_their_chunks(monkeypatch):
             monkeypatch.setenv("F3D_PAIR8_PLAN", "0")
             assert plan == f3d.pair8_plan(size, size, size, ty, size, 256, fold)
             assert plan.A == 0 and plan.zc_b == uniform_plan(tiles, size, size, 256)[0], (size, ty)
+
+
+# ---- the chunk limit of the solver launches (solver_chunk_limit in csrc/f3d_pair8_plan.h, through f3d_solver_chunk_limit) ----
+# A chunk of c planes of a launch that reads `reach` halo planes on either side touches planes z0 - reach .. z1 - 1 + reach, and the
+# kernels form (plane - lowest plane) * plane_bytes + an offset inside the plane in 32 unsigned bits: (c + 2 reach) * plane_bytes must
+# not pass 2^32.  The reach of each mode, read from the kernels: k_sweep6 / k_phiksi6 one plane each way, k_pair8 / k_wpair8 / k_sweep7
+# z0 - 2 .. z1 + 1, k_tri z0 - 3 .. z1 + 2.
+REACHES = (1, 2, 3)
+
+
+def plane_sizes():
+    """4 KiB .. 2 GiB: every power of two, its neighbours that a pitch of 256 bytes allows, and the sizes around each threshold
+    2^32 / n (n = 3 .. 17: where the clamp to one plane starts, and where one plane with a halo of 1, 2, 3 stops fitting)"""
+    sizes = set()
+    for e in range(12, 32):
+        sizes.update((1 << e, (1 << e) + 256, (1 << e) - 256, 3 << (e - 1)))
+    for n in range(3, 18):
+        q = (1 << 32) // n
+        sizes.update((q // 256 * 256 - 256, q // 256 * 256, q // 256 * 256 + 256, q, q + 1))
+    sizes.update((8192 * 32768, 16384 * 32768, 1664 * 262144, 1665 * 262144))   # planes of 256 and 512 MiB, 416 MiB and one row more
+    return sorted(s for s in sizes if 4096 <= s <= 1 << 31)
+
+
+@pytest.mark.parametrize("reach", REACHES)
+def test_a_chunk_and_its_halo_never_pass_4_gib_or_the_launch_is_refused(reach):
+    refused = fitted = 0
+    for pb in plane_sizes():
+        limit = f3d.solver_chunk_limit(pb, reach)
+        one_fits = (1 + 2 * reach) * pb <= 1 << 32
+        if limit == 0:
+            assert not one_fits, (pb, reach)         # refused only where not even one plane fits
+            refused += 1
+            continue
+        fitted += 1
+        assert limit >= 1 and one_fits, (pb, reach, limit)
+        assert (limit + 2 * reach) * pb <= 1 << 32, (pb, reach, limit)
+        # as it always was where eight planes of slack leave a plane: every plan of every earlier container stays what it was
+        if (0xffffffff // pb) - 8 >= 1:
+            assert limit == min((0xffffffff // pb) - 8, 0x3fffffff), (pb, reach, limit)
+        else:
+            assert limit == 1, (pb, reach, limit)
+    assert refused and fitted, "both sides of the threshold are among the sizes"
+
+
+def test_where_the_chunk_limit_starts_to_refuse():
+    gib = 1 << 30
+    assert f3d.solver_chunk_limit(8192 * 32768, 2) == 7              # planes of 256 MiB: 15 - 8
+    assert [f3d.solver_chunk_limit(gib // 2, r) for r in REACHES] == [1, 1, 1]   # 512 MiB: 7 planes are 3.5 GiB
+    assert [f3d.solver_chunk_limit(gib, r) for r in REACHES] == [1, 0, 0]        # 1 GiB: 3 planes fit, 5 and 7 do not
+    assert [f3d.solver_chunk_limit(2 * gib, r) for r in REACHES] == [0, 0, 0]
+    for r in REACHES:   # the last plane size that fits and the first that does not, in steps of the 256-byte pitch unit
+        edge = (1 << 32) // (1 + 2 * r) // 256 * 256
+        assert f3d.solver_chunk_limit(edge, r) == 1 and f3d.solver_chunk_limit(edge + 256, r) == 0
+    assert f3d.solver_chunk_limit(0, 1) == 0 and f3d.solver_chunk_limit(4096, -1) == 0
+    assert f3d.solver_chunk_limit((1 << 32) + 256, 0) == 0
+    assert f3d.solver_chunk_limit(4096, 3) == 0xffffffff // 4096 - 8
