@@ -269,6 +269,13 @@ class ValidateStats(C.Structure):  # f3d_validate_stats
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class InitialInfo(C.Structure):  # f3d_initial_info: what f3d_initial_flow found in a displacement a solve is to start from
+    _fields_ = [("voxels", C.c_ulonglong), ("replaced", C.c_ulonglong), ("leaving", C.c_ulonglong), ("max_abs", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FlowParams(C.Structure):  # f3d_flow_params
     _fields_ = [
         ("warp_levels_count", C.c_size_t), ("warp_scale_factor", C.c_float),
@@ -435,6 +442,11 @@ def host():
         "f3d_flow_trajectory_begin": [C.c_void_p], "f3d_flow_trajectory_append": [C.c_void_p],
         "f3d_flow_trajectory_download": [C.c_void_p, _fp, _fp, _fp, C.POINTER(C.c_ulonglong)],
         "f3d_flow_trajectory_end": [C.c_void_p],
+        "f3d_flow_initial_upload": [C.c_void_p, _fp, _fp, _fp, C.POINTER(InitialInfo)],
+        "f3d_flow_initial_take": [C.c_void_p, C.c_int, C.POINTER(InitialInfo)],
+        "f3d_flow_initial_download": [C.c_void_p, _fp, _fp, _fp], "f3d_flow_initial_end": [C.c_void_p],
+        "f3d_flow_compute_resident_from_initial": [C.c_void_p, pp, C.c_int, _fp],
+        "f3d_flow_compute_from_initial": [C.c_void_p, _fp, _fp, pp, C.c_int, _fp, _fp, _fp],
         "f3d_flow_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(StrainStats)],
         "f3d_flow_strain_end": [C.c_void_p],
         "f3d_flow_window_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(_fp),
@@ -635,6 +647,10 @@ def _compose_entry():
     return _entry("f3d_compose_flow", [_dp] * 6 + [_sz] * 3 + [C.POINTER(C.c_ulonglong)], "compose flows into a trajectory")
 
 
+def _initial_entry():
+    return _entry("f3d_initial_flow", [_dp] * 6 + [_sz] * 3 + [C.POINTER(InitialInfo)], "prepare a displacement to start a solve from")
+
+
 def _strain_entry():
     return _entry("f3d_flow_strain", [_dp] * 3 + [_dpp, C.c_uint] + [_sz] * 3 + [C.POINTER(StrainStats)], "compute strain fields")
 
@@ -822,6 +838,20 @@ def compose_flow(acc, inc):
         lost = C.c_ulonglong()
         check(fn(*p, *dims, C.byref(lost)), "f3d_compose_flow")
         return tuple(box.download(a, dims) for a in p[:3]) + (int(lost.value),)
+
+
+def initial_flow(u, v, w):
+    """A displacement made fit to start a solve from (include/f3d.h, f3d_initial_flow) for volumes from anywhere (numpy [z, y, x]
+    float32, voxel units).  Returns ((u, v, w), info): the three components where all three are finite and +0 in all three where
+    one is not, and an InitialInfo with the voxels, the replaced voxels, the finite voxels whose end point leaves the volume, and
+    the largest |component| over the finite voxels.  The inputs are not modified."""
+    fn = _initial_entry()
+    mismatch = "u, v and w must be three [z, y, x] volumes of one shape"
+    with _on_device([u, v, w], mismatch) as (box, p, dims):
+        box.set_current()
+        info = InitialInfo()
+        check(fn(*p, *p, *dims, C.byref(info)), "f3d_initial_flow")
+        return tuple(box.download(a, dims) for a in p), info
 
 
 # the eight outputs of f3d_flow_strain in ABI order, and the F3D_STRAIN_* group of each
@@ -2590,9 +2620,10 @@ class OpticalFlow:
         self.dims = (width, height, depth)
         return True
 
-    def compute(self, frame_0, frame_1, silent=True, out=None, **kw):
+    def compute(self, frame_0, frame_1, silent=True, out=None, initial=None, **kw):
         """OpticalFlowE::ComputeFlow: upload, solve, download.  `out` = three preallocated C-contiguous float32 [z,y,x] arrays
-        to receive u, v, w (the reference's caller owns its flow volumes too, page-locked or not); fresh ones otherwise."""
+        to receive u, v, w (the reference's caller owns its flow volumes too, page-locked or not); fresh ones otherwise.
+        `initial` (see set_initial): the displacement the pyramid starts from instead of zero; None is the call as it always was."""
         f0, p0 = _f32(frame_0)
         f1, p1 = _f32(frame_1)
         w, h, d = self.dims
@@ -2606,6 +2637,12 @@ class OpticalFlow:
                 if a.dtype != np.float32 or a.shape != (d, h, w) or not a.flags["C_CONTIGUOUS"]:
                     raise ValueError(f"out arrays must be C-contiguous float32 [z,y,x] = {(d, h, w)}")
         prm = make_params(**kw)
+        if initial is not None:
+            self.set_initial(initial)
+            _host_check(host().f3d_flow_compute_from_initial(self._h, p0, p1, C.byref(prm), int(silent), u.ctypes.data_as(_fp),
+                                                             v.ctypes.data_as(_fp), ww.ctypes.data_as(_fp)),
+                        "f3d_flow_compute_from_initial")
+            return u, v, ww
         check(host().f3d_flow_compute(self._h, p0, p1, C.byref(prm), int(silent), u.ctypes.data_as(_fp),
                                       v.ctypes.data_as(_fp), ww.ctypes.data_as(_fp)), "f3d_flow_compute")
         return u, v, ww
@@ -2615,9 +2652,15 @@ class OpticalFlow:
         f1, p1 = _f32(frame_1)
         check(host().f3d_flow_upload(self._h, p0, p1), "f3d_flow_upload")
 
-    def compute_resident(self, silent=True, **kw):
+    def compute_resident(self, silent=True, initial=None, **kw):
+        """solve the uploaded pair; `initial` (see set_initial) starts the pyramid from a displacement instead of zero"""
         prm = make_params(**kw)
         secs = C.c_float()
+        if initial is not None:
+            self.set_initial(initial)
+            _host_check(host().f3d_flow_compute_resident_from_initial(self._h, C.byref(prm), int(silent), C.byref(secs)),
+                        "f3d_flow_compute_resident_from_initial")
+            return secs.value
         check(host().f3d_flow_compute_resident(self._h, C.byref(prm), int(silent), C.byref(secs)),
               "f3d_flow_compute_resident")
         return secs.value
@@ -2627,6 +2670,38 @@ class OpticalFlow:
         u, v, ww = (np.empty((d, h, w), np.float32) for _ in range(3))
         check(host().f3d_flow_download(self._h, u.ctypes.data_as(_fp), v.ctypes.data_as(_fp), ww.ctypes.data_as(_fp)))
         return u, v, ww
+
+    # ---- the displacement a solve starts from (include/f3d_host.h, f3d_flow_initial_*) ----
+    def set_initial(self, initial):
+        """Hold `initial` as the flow the next compute(initial=...) calls start their pyramid from: a tuple of three [z, y, x]
+        arrays (a guess from outside), "flow" (a copy of what compute_resident() left on the device) or "trajectory" (a copy of the
+        cumulative displacement).  A voxel with a component that is not finite starts from zero.  Returns the InitialInfo.  The
+        flow is kept, unchanged by any solve, until it is set again, initial_end() or destroy()."""
+        info = InitialInfo()
+        if isinstance(initial, str):
+            _host_check(host().f3d_flow_initial_take(self._h, _source(initial), C.byref(info)), "f3d_flow_initial_take")
+            return info
+        parts = list(initial)
+        w, h, d = self.dims
+        if len(parts) != 3:
+            raise ValueError("initial must be 'flow', 'trajectory' or three [z, y, x] volumes")
+        held = [_f32(a) for a in parts]
+        if any(a.shape != (d, h, w) for a, _ in held):
+            raise ValueError(f"the components of the initial flow must be [z,y,x] = {(d, h, w)}")
+        _host_check(host().f3d_flow_initial_upload(self._h, held[0][1], held[1][1], held[2][1], C.byref(info)), "f3d_flow_initial_upload")
+        return info
+
+    def initial_download(self):
+        """(u, v, w): the prepared initial flow as the solve will read it"""
+        w, h, d = self.dims
+        u, v, ww = (np.empty((d, h, w), np.float32) for _ in range(3))
+        _host_check(host().f3d_flow_initial_download(self._h, u.ctypes.data_as(_fp), v.ctypes.data_as(_fp), ww.ctypes.data_as(_fp)),
+                    "f3d_flow_initial_download")
+        return u, v, ww
+
+    def initial_end(self):
+        """free the containers of the initial flow (destroy() does too)"""
+        _host_check(host().f3d_flow_initial_end(self._h), "f3d_flow_initial_end")
 
     def set_level_stats(self, enable=True):
         """record, per pyramid level of every later compute, the residual before the solve and the flow statistics after it"""
@@ -3124,19 +3199,28 @@ class OpticalFlow:
         """free the containers of the validated displacement (destroy() does too)"""
         _host_check(host().f3d_flow_validate_end(self._h), "f3d_flow_validate_end")
 
-    def compute_sequence(self, frames, cumulative=False, silent=True, **kw):
-        """Generator over the consecutive pairs of `frames` (an iterable of [z, y, x] volumes): yields (k, (u, v, w), disp) for
-        pair k (frame k -> k+1), where disp is None, or with cumulative=True the trajectory_download() tuple (u, v, w, lost) of
-        the displacement frame 0 -> frame k+1.  Each pair is uploaded and solved with compute_resident()."""
-        previous = None
+    def compute_sequence(self, frames, cumulative=False, silent=True, total=False, warm_start=False, initial=None, **kw):
+        """Generator over the pairs of `frames` (an iterable of [z, y, x] volumes): yields (k, (u, v, w), disp) for pair k, where disp
+        is None, or with cumulative=True the trajectory_download() tuple (u, v, w, lost) of the displacement frame 0 -> frame k+1.
+        Each pair is uploaded and solved with compute_resident().  Pair k is frame k -> k+1, unless total=True: then it is
+        frame 0 -> frame k+1, solved directly and started from the result of the pair before (set_initial("flow")), and the flow
+        yielded is that total displacement on frame 0's grid (exclusive with cumulative, which composes it from the pairs).
+        warm_start=True keeps the consecutive pairs and starts pair k from pair k-1's flow as it stands (steady motion).
+        `initial` (see set_initial) starts pair 0."""
+        if total and cumulative:
+            raise ValueError("total=True solves frame 0 -> frame k+1 directly; cumulative=True composes it from the pairs: choose one")
+        if total and warm_start:
+            raise ValueError("total=True starts every pair from the one before already; warm_start belongs to consecutive pairs")
+        first = previous = None
         k = 0
         if cumulative:
             self.trajectory_begin()
         try:
             for frame in frames:
                 if previous is not None:
-                    self.upload(previous, frame)
-                    self.compute_resident(silent=silent, **kw)
+                    self.upload(first if total else previous, frame)
+                    start = initial if k == 0 else ("flow" if (total or warm_start) else None)
+                    self.compute_resident(silent=silent, initial=start, **kw)
                     flow = self.download()
                     disp = None
                     if cumulative:
@@ -3144,6 +3228,8 @@ class OpticalFlow:
                         disp = self.trajectory_download()
                     yield k, flow, disp
                     k += 1
+                else:
+                    first = frame
                 previous = frame
         finally:
             if cumulative and self._h:

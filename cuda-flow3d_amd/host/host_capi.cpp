@@ -247,6 +247,85 @@ int f3d_flow_trajectory_end(f3d_flow flow)
   return 0;
 }
 
+int f3d_flow_initial_upload(f3d_flow flow, const float* u, const float* v, const float* w, f3d_initial_info* info)
+{
+  g_host_error.clear();
+  if (!flow || !u || !v || !w) return HostFail("f3d_flow_initial_upload: null argument");
+  const DataSize4& c = flow->driver.ContainerSize();
+  Data3D fu(const_cast<float*>(u), c.width, c.height, c.depth), fv(const_cast<float*>(v), c.width, c.height, c.depth),
+      fw(const_cast<float*>(w), c.width, c.height, c.depth);
+  if (!flow->driver.SetInitialFlow(fu, fv, fw, info)) return HostFail(flow->driver.InitialFlowError().c_str());
+  return 0;
+}
+
+int f3d_flow_initial_take(f3d_flow flow, int source, f3d_initial_info* info)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_initial_take: null driver");
+  if (source != F3D_STRAIN_OF_FLOW && source != F3D_STRAIN_OF_TRAJECTORY)
+    return HostFail("f3d_flow_initial_take: source must be F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY");
+  if (source == F3D_STRAIN_OF_TRAJECTORY && !flow->trajectory_started)
+    return HostFail("f3d_flow_initial_take: no trajectory is active (f3d_flow_trajectory_begin first)");
+  const OpticalFlowE::Displacement of = source == F3D_STRAIN_OF_FLOW ? OpticalFlowE::HeldFlow() : OpticalFlowE::Trajectory();
+  if (!flow->driver.SetInitialFlow(of, info)) return HostFail(flow->driver.InitialFlowError().c_str());
+  return 0;
+}
+
+int f3d_flow_initial_download(f3d_flow flow, float* u, float* v, float* w)
+{
+  g_host_error.clear();
+  if (!flow || !u || !v || !w) return HostFail("f3d_flow_initial_download: null argument");
+  const DataSize4& c = flow->driver.ContainerSize();
+  Data3D fu(u, c.width, c.height, c.depth), fv(v, c.width, c.height, c.depth), fw(w, c.width, c.height, c.depth);
+  if (!flow->driver.DownloadInitialFlow(fu, fv, fw)) return HostFail(flow->driver.InitialFlowError().c_str());
+  return 0;
+}
+
+int f3d_flow_initial_end(f3d_flow flow)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_initial_end: null driver");
+  flow->driver.ReleaseInitialFlow();
+  return 0;
+}
+
+int f3d_flow_compute_resident_from_initial(f3d_flow flow, const f3d_flow_params* params, int silent, float* device_seconds)
+{
+  g_host_error.clear();
+  if (!flow || !params) return HostFail("f3d_flow_compute_resident_from_initial: null argument");
+  flow->zncc_of_held_flow = false;
+  f3d_flow_params p = *params;
+  OperationParameters bag;
+  FillBag(bag, p);
+  flow->driver.silent = silent != 0;
+  if (!flow->driver.ComputeFlowResident(bag, true)) {
+    const std::string& why = flow->driver.InitialFlowError();
+    return HostFail(why.empty() ? "f3d_flow_compute_resident_from_initial: the solve could not run (f3d_flow_upload first)" : why.c_str());
+  }
+  if (device_seconds) *device_seconds = flow->driver.LastDeviceSeconds();
+  return 0;
+}
+
+int f3d_flow_compute_from_initial(f3d_flow flow, const float* frame_0, const float* frame_1, const f3d_flow_params* params, int silent,
+                                  float* u, float* v, float* w)
+{
+  g_host_error.clear();
+  if (!flow || !frame_0 || !frame_1 || !params || !u || !v || !w) return HostFail("f3d_flow_compute_from_initial: null argument");
+  const DataSize4& c = flow->driver.ContainerSize();
+  Data3D f0(const_cast<float*>(frame_0), c.width, c.height, c.depth);
+  Data3D f1(const_cast<float*>(frame_1), c.width, c.height, c.depth);
+  Data3D fu(u, c.width, c.height, c.depth), fv(v, c.width, c.height, c.depth), fw(w, c.width, c.height, c.depth);
+  f3d_flow_params p = *params;
+  OperationParameters bag;
+  FillBag(bag, p);
+  flow->driver.silent = silent != 0;
+  if (!flow->driver.ComputeFlow(f0, f1, fu, fv, fw, bag, true)) {
+    const std::string& why = flow->driver.InitialFlowError();
+    return HostFail(why.empty() ? "f3d_flow_compute_from_initial: the solve could not run" : why.c_str());
+  }
+  return 0;
+}
+
 namespace {
 
 // the checks every f3d_flow_*_compute makes of its driver, its source and the trajectory; `who` is the entry point's name

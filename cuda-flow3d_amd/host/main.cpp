@@ -5,6 +5,7 @@
 // flags:  flow3d --dims W H D --frames f0.raw f1.raw [f2.raw ...] [--f32] [--out prefix] [--levels N] [--scale s]
 //                [--outer N] [--inner N] [--alpha a] [--eps-smooth e] [--eps-data e] [--median r] [--sigma s]
 //                [--synthetic] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]] [--concurrent N] [--cumulative]
+//                [--initial-flow U V W] [--warm-start | --total]
 //                [--strain vol,e,eq] [--principal val,shear,dir1,dir3] [--rotation angle,vector,stretch] [--inverse]
 //                [--window-strain vol,e,eq,grad [--window-radius R] [--window-min-count K]]
 //                [--window-principal val,shear,dir1,dir3] [--window-rotation angle,vector,stretch]
@@ -29,6 +30,16 @@
 // --cumulative (resident driver, pairs in order) also composes every pair's flow into the displacement of each voxel of frame 0 on
 // the device (f3d_compose_flow) and writes <prefix>_<k>_disp-{u,v,w}-W-H-D.raw: frame 0 -> frame k+1 on frame 0's grid, NaN where
 // the point has left the volume.
+// --initial-flow U V W (resident driver, pairs in order) starts the pyramid of pair 0 from a displacement instead of zero: three float32
+// raw files of W x H x D in the layout the flows are written in (a coarse DVC, an FE prediction, a rigid pre-registration).  A voxel
+// with a component that is not finite starts from zero (f3d_initial_flow); one line per pair that starts from a displacement says how
+// many such voxels there were, how many end points leave the volume and the largest component.
+// --warm-start starts pair k >= 1 from the flow of pair k-1 as it stands (steady motion); the pairs stay the consecutive ones.
+// --total makes pair k frame 0 -> frame k+1, solved directly and started from the result of pair k-1: the other route to the
+// displacement from frame 0, which --cumulative composes from the consecutive pairs with one interpolation per step.  The flow of a
+// pair is then a displacement on frame 0's grid, so whatever needs --cumulative with more than two frames takes --total as well; the
+// outputs carry the pair's tags.  With two frames both do nothing.  Not with each other, and --total not with --cumulative.
+// With --levels N a started pyramid can be shallow: its depth has to cover the error of the guess, not the displacement.
 // --strain LIST (resident driver, pairs in order; LIST a comma-separated subset of vol,e,eq) also differentiates every pair's flow --
 // with --cumulative the displacement frame 0 -> frame k+1 instead -- on the device (f3d_flow_strain) and writes the selected fields
 // as <tag>_strain-{vol | exx,eyy,ezz,exy,exz,eyz | eq}-W-H-D.raw with the flow's (or the displacement's) tag, and one line of
@@ -75,7 +86,7 @@
 // --labels FILE --label-motion MODEL (same conditions and the same source as --detrend, --use-validated included) fits MODEL to the
 // voxels of every body of a segmentation on the device (f3d_label_motion_sums, f3d_motion_solve_labels) and takes each body's fit out of
 // its voxels (f3d_remove_label_motion).  FILE is raw little-endian int32 of W x H x D on frame 0's grid: 0 background, 1 .. max the
-// bodies; it is uploaded once.  With more than two frames it needs --cumulative: only the displacement from frame 0 lives on that grid.
+// bodies; it is uploaded once.  With more than two frames it needs --cumulative or --total: only the displacement from frame 0 lives on that grid.
 // A body with fewer than --label-min-voxels voxels (default 27) is not fitted.  <tag>_labelres-{u,v,w}-W-H-D.raw is what remains (NaN
 // where there is no fit), <tag>_labelmotion.csv has one row per label, and one line per pair sums it up.
 // --labels FILE --contacts (same conditions and the same source as --label-motion, with or without it) finds the contacts between the
@@ -145,7 +156,8 @@ static void Usage()
   std::printf("usage: flow3d --dims W H D (--frames f0.raw f1.raw [f2.raw ...] [--f32] | --synthetic) [--out prefix]\n"
               "              [--levels N] [--scale s] [--outer N] [--inner N] [--alpha a] [--eps-smooth e]\n"
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
-              "              [--concurrent N] [--cumulative] [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
+              "              [--concurrent N] [--cumulative] [--initial-flow U V W] [--warm-start | --total]\n"
+              "              [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
               "              [--rotation angle,vector,stretch] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
               "              [--window-strain vol,e,eq,grad [--window-radius R] [--window-min-count K]]\n"
               "              [--window-principal val,shear,dir1,dir3] [--window-rotation angle,vector,stretch]\n"
@@ -173,6 +185,8 @@ int main(int argc, char** argv)
   std::string prefix = "flow3d";
   bool f32_input = false, synthetic = false, write_vtk = false, silent_mode = false, print_stats = false;
   bool use_partial_gpu = false, partial_full = false, cumulative = false;
+  bool total = false, warm_start = false, initial_given = false;  // --total, --warm-start, --initial-flow U V W
+  std::vector<std::string> initial_files;
   size_t concurrent = 1;
   unsigned strain_fields = 0;     // --strain: F3D_STRAIN_* groups
   unsigned wstrain_fields = 0;    // --window-strain: F3D_STRAIN_* groups and F3D_WSTRAIN_G
@@ -269,6 +283,12 @@ int main(int argc, char** argv)
     else if (a == "--budget-mb") { need(1); setenv("F3D_P_BUDGET_MB", argv[++i], 1); }
     else if (a == "--concurrent") { need(1); concurrent = std::strtoull(argv[++i], nullptr, 10); }
     else if (a == "--cumulative") cumulative = true;
+    else if (a == "--total") total = true;
+    else if (a == "--warm-start") warm_start = true;
+    else if (a == "--initial-flow") {
+      initial_given = true;
+      while (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) initial_files.push_back(argv[++i]);
+    }
     else if (a == "--inverse") inverse = true;
     else if (a == "--strain") {
       need(1);
@@ -632,6 +652,38 @@ int main(int argc, char** argv)
                 use_partial_gpu ? "--partial" : "--concurrent N > 1");
     return 64;
   }
+  // the solves that start from a displacement: all refusals before any device is touched
+  if (total && (cumulative || warm_start)) {
+    std::printf(cumulative ? "--total solves frame 0 -> frame k+1 directly and --cumulative composes it from the pairs: choose one\n"
+                           : "--total starts every pair from the one before already; --warm-start belongs to consecutive pairs\n");
+    Usage();
+    return 64;
+  }
+  if ((total || warm_start || initial_given) && (use_partial_gpu || concurrent > 1)) {
+    std::printf("%s needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
+                total ? "--total" : (warm_start ? "--warm-start" : "--initial-flow"), use_partial_gpu ? "--partial" : "--concurrent N > 1");
+    Usage();
+    return 64;
+  }
+  if (initial_given) {
+    if (initial_files.size() != 3) {
+      std::printf("--initial-flow takes three files, the u, v and w of the displacement pair 0 starts from\n");
+      Usage();
+      return 64;
+    }
+    for (const std::string& path : initial_files) {
+      std::FILE* f = std::fopen(path.c_str(), "rb");
+      const bool good = f && std::fseek(f, 0, SEEK_END) == 0 && static_cast<size_t>(std::ftell(f)) == width * height * depth * sizeof(float);
+      if (f) std::fclose(f);
+      if (!good) {
+        std::printf("--initial-flow %s: not a file of %zu x %zu x %zu float32 values (%zu bytes)\n", path.c_str(), width, height, depth,
+                    width * height * depth * sizeof(float));
+        Usage();
+        return 64;
+      }
+    }
+  }
+  const bool from_frame_0 = cumulative || total;  // the displacement the derived fields are computed of starts at frame 0
   if (strain_fields && (use_partial_gpu || concurrent > 1)) {
     std::printf("--strain needs the resident driver solving the pairs in order: it cannot be combined with %s\n",
                 use_partial_gpu ? "--partial" : "--concurrent N > 1");
@@ -753,8 +805,8 @@ int main(int argc, char** argv)
     Usage();
     return 64;
   }
-  if (track && !synthetic && files.size() > 2 && !cumulative) {
-    std::printf("--track of more than two frames needs --cumulative: the labels live on frame 0's grid, and only the displacement from "
+  if (track && !synthetic && files.size() > 2 && !from_frame_0) {
+    std::printf("--track of more than two frames needs --cumulative or --total: the labels live on frame 0's grid, and only the displacement from "
                 "frame 0 lives there too\n");
     Usage();
     return 64;
@@ -782,8 +834,8 @@ int main(int argc, char** argv)
     Usage();
     return 64;
   }
-  if (contacts && !synthetic && files.size() > 2 && !cumulative) {
-    std::printf("--contacts of more than two frames needs --cumulative: the labels live on frame 0's grid, and only the displacement "
+  if (contacts && !synthetic && files.size() > 2 && !from_frame_0) {
+    std::printf("--contacts of more than two frames needs --cumulative or --total: the labels live on frame 0's grid, and only the displacement "
                 "from frame 0 lives there too\n");
     Usage();
     return 64;
@@ -838,8 +890,8 @@ int main(int argc, char** argv)
     }
     if (name != "grey") label_stats_of_pair = true;
   }
-  if (label_stats_of_pair && !synthetic && files.size() > 2 && !cumulative) {
-    std::printf("--label-stats of a field of more than two frames needs --cumulative: the labels live on frame 0's grid, and only the "
+  if (label_stats_of_pair && !synthetic && files.size() > 2 && !from_frame_0) {
+    std::printf("--label-stats of a field of more than two frames needs --cumulative or --total: the labels live on frame 0's grid, and only the "
                 "displacement from frame 0 lives there too\n");
     Usage();
     return 64;
@@ -855,8 +907,8 @@ int main(int argc, char** argv)
     Usage();
     return 64;
   }
-  if (label_model >= 0 && !synthetic && files.size() > 2 && !cumulative) {
-    std::printf("--label-motion of more than two frames needs --cumulative: the labels live on frame 0's grid, and only the displacement "
+  if (label_model >= 0 && !synthetic && files.size() > 2 && !from_frame_0) {
+    std::printf("--label-motion of more than two frames needs --cumulative or --total: the labels live on frame 0's grid, and only the displacement "
                 "from frame 0 lives there too\n");
     Usage();
     return 64;
@@ -1136,7 +1188,7 @@ int main(int argc, char** argv)
       stats_rows += row;
     }
     if (whole_line)
-      std::printf("label stats %s frame %zu -> frame %zu: ", name.c_str(), cumulative ? size_t(0) : k, k + 1);
+      std::printf("label stats %s frame %zu -> frame %zu: ", name.c_str(), from_frame_0 ? size_t(0) : k, k + 1);
     else
       std::printf("label stats %s frame 0: ", name.c_str());
     std::printf("%llu ok, %llu empty, %llu small of %zu labels, mean %.9g; shift %d, %zu bins over [%.9g, %.9g]; %llu voxels used, %llu "
@@ -1285,7 +1337,7 @@ int main(int argc, char** argv)
          const f3d_strain_stats& st = strain_stats;
          const double mean = st.defined ? st.vol_sum / static_cast<double>(st.defined) : std::nan("");
          std::printf("strain frame %zu -> frame %zu: vol min/mean/max %.6g/%.6g/%.6g, eq max %.6g, %llu folded, %llu undefined of %zu "
-                     "voxels\n", cumulative ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max, st.eq_max, st.folded,
+                     "voxels\n", from_frame_0 ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max, st.eq_max, st.folded,
                      static_cast<unsigned long long>(voxels) - st.defined, voxels);
        }},
       {"principal", OpticalFlowE::kPrincipal, principal_fields, principal_names, false,
@@ -1293,7 +1345,7 @@ int main(int argc, char** argv)
        [&](size_t k) {
          const f3d_principal_stats& st = principal_stats;
          std::printf("principal frame %zu -> frame %zu: e1 max %.6g, e3 min %.6g, shear max %.6g, %llu undefined of %zu voxels\n",
-                     cumulative ? size_t(0) : k, k + 1, st.e1_max, st.e3_min, st.shear_max,
+                     from_frame_0 ? size_t(0) : k, k + 1, st.e1_max, st.e3_min, st.shear_max,
                      static_cast<unsigned long long>(voxels) - st.defined, voxels);
        }},
       {"inverse", OpticalFlowE::kInverse, inverse ? 1u : 0u, inverse_names, false,
@@ -1304,7 +1356,7 @@ int main(int argc, char** argv)
          const f3d_inverse_stats& st = inverse_stats;
          const double mean = st.defined ? static_cast<double>(st.steps_sum) / static_cast<double>(st.defined) : std::nan("");
          std::printf("inverse frame %zu -> frame %zu: err max %.6g, mean steps %.6g, %llu unconverged, %llu lost of %zu voxels\n", k + 1,
-                     cumulative ? size_t(0) : k, st.err_max, mean, st.unconverged, static_cast<unsigned long long>(voxels) - st.defined,
+                     from_frame_0 ? size_t(0) : k, st.err_max, mean, st.unconverged, static_cast<unsigned long long>(voxels) - st.defined,
                      voxels);
        }},
       // the frames of the pair are the resident pair: in a sequence SelectResidentPair(k, k+1) holds until the next solve begins
@@ -1328,7 +1380,7 @@ int main(int argc, char** argv)
        [&](size_t k) {
          const f3d_motion_fit& f = motion_fit;
          const f3d_motion_residual& r = motion_residual;
-         std::printf("motion frame %zu -> frame %zu (%s): t (%.6g, %.6g, %.6g), ", cumulative ? size_t(0) : k, k + 1,
+         std::printf("motion frame %zu -> frame %zu (%s): t (%.6g, %.6g, %.6g), ", from_frame_0 ? size_t(0) : k, k + 1,
                      motion_models[detrend_model], f.t[0], f.t[1], f.t[2]);
          if (detrend_model == F3D_MOTION_RIGID) {
            // degrees appear in this line only: the fit itself carries the cosine and the axial vector
@@ -1354,7 +1406,7 @@ int main(int argc, char** argv)
        [&](size_t k) {
          const f3d_validate_stats& st = validate_stats;
          std::printf("validate frame %zu -> frame %zu (%s, step %u): %llu tested, %llu outliers, %llu replaced, %llu undefined, r max %.6g "
-                     "of %zu voxels\n", cumulative ? size_t(0) : k, k + 1, validate_mode == F3D_VALIDATE_MARK ? "mark" : "replace",
+                     "of %zu voxels\n", from_frame_0 ? size_t(0) : k, k + 1, validate_mode == F3D_VALIDATE_MARK ? "mark" : "replace",
                      validate_step, st.tested, st.outliers, st.replaced, st.undefined, st.r_max, voxels);
        }},
       // listed last so that the indices above stay; it runs after the principal strains (`order` below)
@@ -1364,7 +1416,7 @@ int main(int argc, char** argv)
          const f3d_polar_stats& st = polar_stats;
          const double mean = st.defined ? st.theta_sum / static_cast<double>(st.defined) : std::nan("");
          std::printf("rotation frame %zu -> frame %zu: angle max %.6g rad, mean %.6g rad, stretch max %.6g, min %.6g, %llu folded, %llu "
-                     "undefined of %zu voxels\n", cumulative ? size_t(0) : k, k + 1, st.theta_max, mean, st.l1_max, st.l3_min, st.folded,
+                     "undefined of %zu voxels\n", from_frame_0 ? size_t(0) : k, k + 1, st.theta_max, mean, st.l1_max, st.l3_min, st.folded,
                      static_cast<unsigned long long>(voxels) - st.defined - st.folded, voxels);
        }},
       // the same source as --detrend; the table of the labels is written with the line
@@ -1421,7 +1473,7 @@ int main(int argc, char** argv)
            median = length.size() % 2 ? length[length.size() / 2] : 0.5 * (length[length.size() / 2 - 1] + length[length.size() / 2]);
          }
          std::printf("label motion frame %zu -> frame %zu (%s): %zu labels fitted, %zu empty, %zu small, %zu degenerate; median |t| %.6g, ",
-                     cumulative ? size_t(0) : k, k + 1, motion_models[label_model], count[0], count[1], count[2], count[3], median);
+                     from_frame_0 ? size_t(0) : k, k + 1, motion_models[label_model], count[0], count[1], count[2], count[3], median);
          if (label_model == F3D_MOTION_RIGID) std::printf("max angle %.6g deg, ", max_angle);
          std::printf("%llu foreign, %llu out of range voxels\n", label_info.foreign, label_info.out_of_range);
        }},
@@ -1434,7 +1486,7 @@ int main(int argc, char** argv)
          const f3d_window_strain_stats& st = wstrain_stats;
          const double mean = st.defined ? st.vol_sum / static_cast<double>(st.defined) : std::nan("");
          std::printf("window strain (r=%u) frame %zu -> frame %zu: vol min/mean/max %.6g/%.6g/%.6g, eq max %.6g, %llu folded, %llu thin, "
-                     "%llu lost of %zu voxels\n", window_radius, cumulative ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max,
+                     "%llu lost of %zu voxels\n", window_radius, from_frame_0 ? size_t(0) : k, k + 1, st.vol_min, mean, st.vol_max,
                      st.eq_max, st.folded, st.thin, st.lost, voxels);
        }},
       // the principal strains and the rotation of the window's gradient: after the window strain, the lines of --principal / --rotation
@@ -1446,7 +1498,7 @@ int main(int argc, char** argv)
        [&](size_t k) {
          const f3d_principal_stats& st = wprincipal_stats;
          std::printf("window principal (r=%u) frame %zu -> frame %zu: e1 max %.6g, e3 min %.6g, shear max %.6g, %llu undefined of %zu "
-                     "voxels\n", window_radius, cumulative ? size_t(0) : k, k + 1, st.e1_max, st.e3_min, st.shear_max,
+                     "voxels\n", window_radius, from_frame_0 ? size_t(0) : k, k + 1, st.e1_max, st.e3_min, st.shear_max,
                      static_cast<unsigned long long>(voxels) - st.defined, voxels);
        }},
       {"wrotation", OpticalFlowE::kWindowPolar, wpolar_fields, polar_names, false,
@@ -1457,7 +1509,7 @@ int main(int argc, char** argv)
          const f3d_polar_stats& st = wpolar_stats;
          const double mean = st.defined ? st.theta_sum / static_cast<double>(st.defined) : std::nan("");
          std::printf("window rotation (r=%u) frame %zu -> frame %zu: angle max %.6g rad, mean %.6g rad, stretch max %.6g, min %.6g, %llu "
-                     "folded, %llu undefined of %zu voxels\n", window_radius, cumulative ? size_t(0) : k, k + 1, st.theta_max, mean,
+                     "folded, %llu undefined of %zu voxels\n", window_radius, from_frame_0 ? size_t(0) : k, k + 1, st.theta_max, mean,
                      st.l1_max, st.l3_min, st.folded, static_cast<unsigned long long>(voxels) - st.defined - st.folded, voxels);
        }}};
   // --contacts: no field of voxels, so no DerivedField: the table of pair k is computed after the derived fields of pair k (the fits of
@@ -1503,7 +1555,7 @@ int main(int argc, char** argv)
       label_table_failed = true;
     }
     std::printf("contacts frame %zu -> frame %zu: %zu contacts between %zu bodies, mean coordination %.6g, %zu opening, %zu closing "
-                "beyond 2^-14, largest slip %.6g; %llu contact faces, %llu without a jump, %llu foreign\n", cumulative ? size_t(0) : k,
+                "beyond 2^-14, largest slip %.6g; %llu contact faces, %llu without a jump, %llu foreign\n", from_frame_0 ? size_t(0) : k,
                 k + 1, contact_list.size(), n_bodies, n_bodies ? 2.0 * static_cast<double>(contact_list.size()) / static_cast<double>(n_bodies) : 0.0,
                 opening, closing, largest_slip, contact_info.contact, contact_info.jump_absent, contact_info.foreign);
   };
@@ -1591,7 +1643,7 @@ int main(int argc, char** argv)
     for (const f3d_track_a& t : a)
       if (t.status & F3D_TRACK_MATCHED) iou_sum += t.iou;
     std::printf("track frame %zu -> frame %zu: %llu of %zu bodies matched, %llu split, %llu merged, %llu vanished, %llu appeared, %llu left; "
-                "mean IoU %.6g; lost %llu, foreign %llu\n", cumulative ? size_t(0) : k, k + 1, sum.matched, track_n_a, sum.split, sum.merged,
+                "mean IoU %.6g; lost %llu, foreign %llu\n", from_frame_0 ? size_t(0) : k, k + 1, sum.matched, track_n_a, sum.split, sum.merged,
                 sum.vanished, sum.appeared, sum.left, sum.matched ? iou_sum / static_cast<double>(sum.matched) : std::nan(""),
                 counted.lost_body + counted.lost_background, counted.foreign_a + counted.foreign_b);
     return 0;
@@ -1741,10 +1793,30 @@ int main(int argc, char** argv)
     return 0;
   };
 
+  // --initial-flow, --warm-start, --total: what a pair starts from, and the line that says what was found in it
+  auto say_initial = [&](const f3d_initial_info& found) {
+    std::printf("initial flow: %llu replaced, %llu leaving, max |.| %.6g\n", found.replaced, found.leaving, static_cast<double>(found.max_abs));
+  };
+  auto initial_from_files = [&]() {
+    Data3D guess[3];
+    for (int i = 0; i < 3; ++i)
+      if (!guess[i].ReadRAWFromFileF32(initial_files[i].c_str(), width, height, depth)) return 2;
+    f3d_initial_info found = {};
+    if (!optical_flow_e.SetInitialFlow(guess[0], guess[1], guess[2], &found)) {
+      std::printf("Error: %s\n", optical_flow_e.InitialFlowError().c_str());
+      return 3;
+    }
+    say_initial(found);
+    return 0;
+  };
+
   if (pairs == 1) {
     if (!synthetic && !load(frame_1, files[1])) return 2;
     optical_flow_e.UploadResidentFrames(frame_0, frame_1);
-    optical_flow_e.ComputeFlowResident(params);
+    if (initial_given)
+      if (const int status = initial_from_files()) return status;
+    // (a plain solve that cannot run goes on as it always did; one that was to start from the displacement says why and ends)
+    if (!optical_flow_e.ComputeFlowResident(params, initial_given) && initial_given) return 3;
     if (print_stats) report();
     if (segment || histogram)
       if (const int status = segment_frame_0()) return status;
@@ -1805,8 +1877,13 @@ int main(int argc, char** argv)
     if (CheckDeviceError(f3d_queue_create(&up)) || CheckDeviceError(f3d_queue_create(&down))) return 3;
     for (f3d_event& e : uploaded)
       if (CheckDeviceError(f3d_event_create(&e))) return 3;
-    auto upload = [&](size_t frame_index) {  // file -> page-locked buffer -> device container, slot = frame index mod 3
-      const int slot = static_cast<int>(frame_index % 3);
+    // The slot of a frame.  Consecutive pairs: frame index mod 3.  --total: frame 0 keeps slot 0 for the whole sequence and frame
+    // i >= 1 takes slot 1 + (i - 1) % 2, so that the upload of frame k+2 beside solve k (frames 0 and k+1) goes into the slot of frame k.
+    auto slot_of = [&](size_t frame_index) {
+      return static_cast<int>(total ? (frame_index == 0 ? 0 : 1 + (frame_index - 1) % 2) : frame_index % 3);
+    };
+    auto upload = [&](size_t frame_index) {  // file -> page-locked buffer -> device container
+      const int slot = slot_of(frame_index);
       if (!load(host_frame[slot], files[frame_index])) return false;
       CheckDeviceError(f3d_copy_planes_h2d_on(up, optical_flow_e.SequenceFrame(slot), c.pitch, c.height, 0, host_frame[slot].DataPtr(),
                                               width, height, width, height, depth));
@@ -1826,7 +1903,7 @@ int main(int argc, char** argv)
     // stream right after compose k (or after TakeResult); its statistics wait for that kernel only.  The fields go down on `down` beside
     // solve k+1 once the kernel is done (`done`), and the kernel of pair k+1, which rewrites the same containers, waits for that
     // download (`down`).
-    // --match is the one reader of the frame containers after the solve: match k reads frames k and k+1, and the upload of frame k+3
+    // --match is the one reader of the frame containers after the solve: match k reads the frames of pair k, and the upload of frame k+3
     // on `up`, issued right after solve k+1 is enqueued, overwrites frame k's slot.  The host wait of EndComputeFlowResident and of
     // the statistics happens to order the two; the order is made explicit all the same: `up` waits for match k (`done`) before it
     // reuses the slot.
@@ -1837,15 +1914,38 @@ int main(int argc, char** argv)
     DevicePtr taken[3] = {0, 0, 0};
     bool pending_output = false;
     const bool serial_sequence = std::getenv("F3D_SEQ_SERIAL") && std::atoi(std::getenv("F3D_SEQ_SERIAL")) != 0;
+    // --total: everything pair k-1 enqueued on the library stream that may read frame k in its slot (the match, the second label volume
+    // of --track) is behind `pair_read`; `up` waits for it before frame k+2 goes into that slot.  (The host waits of the statistics and
+    // of the overlap happen to order the two already; the order is made explicit all the same, as for --match.)
+    f3d_event pair_read = nullptr;
+    if (total && CheckDeviceError(f3d_event_create(&pair_read))) return 3;
     for (size_t k = 0; k < pairs; ++k) {
-      // the solve of pair k waits (on the device) for the uploads of frames k and k+1
-      CheckDeviceError(f3d_queue_wait_event(nullptr, uploaded[k % 3]));
-      CheckDeviceError(f3d_queue_wait_event(nullptr, uploaded[(k + 1) % 3]));
-      optical_flow_e.SelectResidentPair(static_cast<int>(k % 3), static_cast<int>((k + 1) % 3));
-      optical_flow_e.BeginComputeFlowResident(params);
+      // pair k is frame k -> frame k+1, or with --total frame 0 -> frame k+1
+      const size_t first = total ? 0 : k;
+      // the solve of pair k waits (on the device) for the uploads of its two frames
+      CheckDeviceError(f3d_queue_wait_event(nullptr, uploaded[slot_of(first)]));
+      CheckDeviceError(f3d_queue_wait_event(nullptr, uploaded[slot_of(k + 1)]));
+      optical_flow_e.SelectResidentPair(slot_of(first), slot_of(k + 1));
+      // what the pair starts from: the files for pair 0; the flow of pair k-1 for a later pair of --warm-start (as it stands) and of
+      // --total (frame 0 -> frame k).  `taken` still holds that flow: it goes back to the pool further down, beside this solve.
+      bool from_initial = false;
+      if (k == 0 && initial_given) {
+        if (const int status = initial_from_files()) return status;
+        from_initial = true;
+      } else if (k > 0 && (total || warm_start)) {
+        f3d_initial_info found = {};
+        if (!optical_flow_e.SetInitialFlow(OpticalFlowE::Containers(taken), &found)) {
+          std::printf("Error: %s\n", optical_flow_e.InitialFlowError().c_str());
+          return 3;
+        }
+        say_initial(found);
+        from_initial = true;
+      }
+      if (!optical_flow_e.BeginComputeFlowResident(params, from_initial) && from_initial) return 3;  // the plain path goes on as before
       if (serial_sequence) optical_flow_e.EndComputeFlowResident();  // A/B timing: nothing runs beside the solve
       // beside it: frame k+2 into the container pair k-1 has released, and the previous pair's flow out to its files
       if (match.fields && k > 0) CheckDeviceError(f3d_queue_wait_event(up, match.done));  // match k-1 read the slot of frame k+2
+      if (total && k > 0) CheckDeviceError(f3d_queue_wait_event(up, pair_read));          // so did whatever else pair k-1 ran on frame k
       if (k + 2 <= pairs && !upload(k + 2)) return 2;
       if (pending_output) {
         CheckDeviceError(f3d_queue_sync(down));
@@ -1858,7 +1958,8 @@ int main(int argc, char** argv)
         pending_output = false;
       }
       optical_flow_e.EndComputeFlowResident();
-      if ((segment || histogram) && k == 0)  // frame 0 is still in its container: frame 3 overwrites it only beside the solve of pair 1
+      // frame 0 is still in its container: frame 3 overwrites it only beside the solve of pair 1, and with --total nothing ever does
+      if ((segment || histogram) && k == 0)
         if (const int status = segment_frame_0()) return status;
       if (k == 0)
         if (const int status = stats_of_frame_0()) return status;
@@ -1893,10 +1994,14 @@ int main(int argc, char** argv)
       }
       if (const int status = stats_of_pair(k)) return status;  // waits for the fields of pair k, which stay until pair k+1 rewrites them
       if (contacts && !compute_contacts(cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return 3;
-      if (track)  // frame k+1 stays in its container until the upload of frame k+4, two solves from here
+      // frame k+1 stays in its container until the upload of frame k+4, two solves from here; with --total until the upload of frame
+      // k+3 beside the next solve, which waits for `pair_read`
+      if (track)
         if (const int status = track_pair(k, cumulative ? OpticalFlowE::Trajectory() : OpticalFlowE::Containers(taken))) return status;
+      if (total) CheckDeviceError(f3d_event_record(pair_read));
       pending_output = true;
     }
+    if (pair_read) f3d_event_destroy(pair_read);
     CheckDeviceError(f3d_queue_sync(down));
     optical_flow_e.GiveResultBack(taken);
     write_pair(pairs - 1, host_flow[(pairs - 1) & 1][0], host_flow[(pairs - 1) & 1][1], host_flow[(pairs - 1) & 1][2]);

@@ -22,6 +22,8 @@
 extern "C" int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr acc_w, f3d_devptr inc_u, f3d_devptr inc_v,
                                 f3d_devptr inc_w, size_t width, size_t height, size_t depth, unsigned long long* lost)
     __attribute__((weak));
+extern "C" int f3d_initial_flow(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr out_u, f3d_devptr out_v, f3d_devptr out_w,
+                                size_t width, size_t height, size_t depth, f3d_initial_info* info) __attribute__((weak));
 extern "C" int f3d_flow_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[8], unsigned fields, size_t width,
                                size_t height, size_t depth, f3d_strain_stats* stats) __attribute__((weak));
 extern "C" int f3d_window_strain(f3d_devptr u, f3d_devptr v, f3d_devptr w, const f3d_devptr out[17], unsigned fields, unsigned radius,
@@ -175,6 +177,10 @@ OpticalFlowE::OpticalFlowE()
       trajectory_{this, 3, nullptr, "the three trajectory containers do not fit beside the driver's on the device",
                   kTrajectoryNotStarted, "no host volume for a trajectory component",
                   "the device library has no f3d_compose_flow (trajectory composition)", "no flow to compose"},
+      initial_{this, 3, nullptr, "the three containers of the initial flow do not fit beside the driver's on the device",
+               "no initial flow is held (SetInitialFlow first)", "no host volume for a component of the initial flow",
+               "the device library has no f3d_initial_flow (a solve started from a given displacement)",
+               "no displacement to start from"},
       derived_{{this, kDerivedFields[kStrain], kStrainGroups, "the strain containers do not fit beside the driver's on the device",
                 "a requested strain field has not been computed", "no host volume for a requested strain field",
                 "the device library has no f3d_flow_strain (strain fields)", "no displacement to differentiate"},
@@ -349,12 +355,27 @@ void OpticalFlowE::UploadResidentFrames(Data3D& frame_0, Data3D& frame_1)
 void OpticalFlowE::ComputeFlow(Data3D& frame_0, Data3D& frame_1, Data3D& flow_u, Data3D& flow_v, Data3D& flow_w,
                                OperationParameters& params)
 {
-  if (!IsInitialized()) return;
+  ComputeFlow(frame_0, frame_1, flow_u, flow_v, flow_w, params, false);
+}
+
+bool OpticalFlowE::CheckInitial(bool use_initial)
+{
+  initial_.error.clear();
+  if (use_initial && !HasInitialFlow()) return initial_.Fail(initial_.not_computed);
+  return true;
+}
+
+bool OpticalFlowE::ComputeFlow(Data3D& frame_0, Data3D& frame_1, Data3D& flow_u, Data3D& flow_v, Data3D& flow_w,
+                               OperationParameters& params, bool use_initial)
+{
+  if (!IsInitialized()) return false;
+  if (!CheckInitial(use_initial)) return false;
+  const DevicePtr initial[3] = {initial_.ptr[0], initial_.ptr[1], initial_.ptr[2]};
   if (frame_0.Width() != dev_container_size_.width || frame_0.Height() != dev_container_size_.height ||
       frame_0.Depth() != dev_container_size_.depth || frame_1.Width() != frame_0.Width() ||
       frame_1.Height() != frame_0.Height() || frame_1.Depth() != frame_0.Depth()) {
     std::printf("Error: '%s'. Frame dimensions differ from the initialised container.\n", GetName());
-    return;
+    return false;
   }
   ReleaseResult();
 
@@ -368,7 +389,8 @@ void OpticalFlowE::ComputeFlow(Data3D& frame_0, Data3D& frame_1, Data3D& flow_u,
   CopyData3DtoDevice(frame_0, raw_0, dev_container_size_.height, dev_container_size_.pitch);
   CopyData3DtoDevice(frame_1, raw_1, dev_container_size_.height, dev_container_size_.pitch);
 
-  if (RunPyramid(params, raw_0, raw_1, true)) {
+  const bool ok = RunPyramid(params, raw_0, raw_1, true, use_initial ? &initial : nullptr);
+  if (ok) {
     DownloadFlow(flow_u, flow_v, flow_w);
     float elapsed_ms = 0.f;
     CheckDeviceError(f3d_event_record(ev_stop));
@@ -382,21 +404,27 @@ void OpticalFlowE::ComputeFlow(Data3D& frame_0, Data3D& frame_1, Data3D& flow_u,
   ReleaseResult();
   f3d_event_destroy(ev_start);
   f3d_event_destroy(ev_stop);
+  return ok;
 }
 
-void OpticalFlowE::ComputeFlowResident(OperationParameters& params)
+void OpticalFlowE::ComputeFlowResident(OperationParameters& params) { ComputeFlowResident(params, false); }
+
+bool OpticalFlowE::ComputeFlowResident(OperationParameters& params, bool use_initial)
 {
-  if (!IsInitialized()) return;
+  if (!IsInitialized()) return false;
+  if (!CheckInitial(use_initial)) return false;
+  const DevicePtr initial[3] = {initial_.ptr[0], initial_.ptr[1], initial_.ptr[2]};
   if (!resident_frame_[0]) {
     std::printf("Error: '%s'. Resident frames were not allocated.\n", GetName());
-    return;
+    return false;
   }
   ReleaseResult();
   f3d_event ev_start = nullptr, ev_stop = nullptr;
   CheckDeviceError(f3d_event_create(&ev_start));
   CheckDeviceError(f3d_event_create(&ev_stop));
   CheckDeviceError(f3d_event_record(ev_start));
-  if (RunPyramid(params, resident_frame_[0], resident_frame_[1], false)) {
+  const bool ok = RunPyramid(params, resident_frame_[0], resident_frame_[1], false, use_initial ? &initial : nullptr);
+  if (ok) {
     float elapsed_ms = 0.f;
     CheckDeviceError(f3d_event_record(ev_stop));
     CheckDeviceError(f3d_event_sync(ev_stop));
@@ -405,6 +433,7 @@ void OpticalFlowE::ComputeFlowResident(OperationParameters& params)
   }
   f3d_event_destroy(ev_start);
   f3d_event_destroy(ev_stop);
+  return ok;
 }
 
 bool OpticalFlowE::AllocateSequenceFrames()
@@ -430,15 +459,21 @@ void OpticalFlowE::SelectResidentPair(int slot_0, int slot_1)
   resident_frame_[1] = sequence_frame_[slot_1 % 3];
 }
 
-void OpticalFlowE::BeginComputeFlowResident(OperationParameters& params)
+void OpticalFlowE::BeginComputeFlowResident(OperationParameters& params) { BeginComputeFlowResident(params, false); }
+
+bool OpticalFlowE::BeginComputeFlowResident(OperationParameters& params, bool use_initial)
 {
-  if (!IsInitialized() || !resident_frame_[0] || ev_begin_) return;
+  if (!IsInitialized() || !resident_frame_[0] || ev_begin_) return false;
+  if (!CheckInitial(use_initial)) return false;
+  const DevicePtr initial[3] = {initial_.ptr[0], initial_.ptr[1], initial_.ptr[2]};
   ReleaseResult();
   CheckDeviceError(f3d_event_create(&ev_begin_));
   CheckDeviceError(f3d_event_create(&ev_end_));
   CheckDeviceError(f3d_event_record(ev_begin_));
-  RunPyramid(params, resident_frame_[0], resident_frame_[1], false);  // enqueues; nothing in it waits for the device when silent
+  // enqueues; nothing in it waits for the device when silent
+  const bool ok = RunPyramid(params, resident_frame_[0], resident_frame_[1], false, use_initial ? &initial : nullptr);
   CheckDeviceError(f3d_event_record(ev_end_));
+  return ok;
 }
 
 void OpticalFlowE::EndComputeFlowResident()
@@ -645,6 +680,57 @@ bool OpticalFlowE::DownloadTrajectory(Data3D& u, Data3D& v, Data3D& w, unsigned 
     *lost = count;
   }
   return true;
+}
+
+// ---- the flow a solve starts from ----------------------------------------------------------------------------------------------
+
+bool OpticalFlowE::SetInitialFlow(Data3D& u, Data3D& v, Data3D& w, f3d_initial_info* info)
+{
+  initial_.error.clear();
+  if (!f3d_initial_flow) return initial_.Fail(initial_.no_entry);
+  if (!initialized_) return initial_.Fail("the driver was not initialized");
+  Data3D* const in[3] = {&u, &v, &w};
+  for (Data3D* a : in)
+    if (a->Width() != dev_container_size_.width || a->Height() != dev_container_size_.height || a->Depth() != dev_container_size_.depth)
+      return initial_.Fail("the components of the initial flow must have the dimensions the driver was initialized with");
+  initial_set_ = false;
+  if (!initial_.Allocate(0)) return false;
+  for (int i = 0; i < 3; ++i) CopyData3DtoDevice(*in[i], initial_.ptr[i], dev_container_size_.height, dev_container_size_.pitch);
+  const f3d_size4 c = Container();
+  initial_set_ = initial_.Check(CheckDeviceError(f3d_set_container(&c))) &&
+                 initial_.Check(CheckDeviceError(f3d_initial_flow(initial_.ptr[0], initial_.ptr[1], initial_.ptr[2], initial_.ptr[0],
+                                                                  initial_.ptr[1], initial_.ptr[2], c.width, c.height, c.depth, info)));
+  return initial_set_;
+}
+
+bool OpticalFlowE::SetInitialFlow(const Displacement& of, f3d_initial_info* info)
+{
+  DevicePtr d[3];
+  if (!ResolveDisplacement(initial_, of, f3d_initial_flow != nullptr, d)) return false;
+  for (DevicePtr p : d)
+    for (int i = 0; i < 3; ++i)
+      if (p == initial_.ptr[i]) return initial_.Fail("the initial flow cannot be set from its own containers");
+  initial_set_ = false;
+  if (!initial_.Allocate(0)) return false;
+  const f3d_size4 c = Container();
+  initial_set_ = initial_.Check(CheckDeviceError(f3d_set_container(&c))) &&
+                 initial_.Check(CheckDeviceError(f3d_initial_flow(d[0], d[1], d[2], initial_.ptr[0], initial_.ptr[1], initial_.ptr[2],
+                                                                  c.width, c.height, c.depth, info)));
+  return initial_set_;
+}
+
+bool OpticalFlowE::DownloadInitialFlow(Data3D& u, Data3D& v, Data3D& w)
+{
+  initial_.error.clear();
+  if (!HasInitialFlow()) return initial_.Fail(initial_.not_computed);
+  Data3D* const out[3] = {&u, &v, &w};
+  return initial_.Download(out, 0);
+}
+
+void OpticalFlowE::ReleaseInitialFlow()
+{
+  initial_.Release();
+  initial_set_ = false;
 }
 
 // ---- derived fields of a displacement: strain, principal strain, inverse, match quality -------------------------------------------
@@ -1306,7 +1392,8 @@ bool OpticalFlowE::ComputeValidated(const Displacement& of, DevicePtr weight, fl
 //   blurred[2]   the two full-size frames the pyramid reads (pre-blurred copies, or the raw frames when sigma <= 0)
 //   level[2]     the two frames at the current level; level[1] is replaced by its registered version
 //   flow[3]      u, v, w so far        step[3]   the level's increments du, dv, dw (and, between levels, ping-pong room)
-bool OpticalFlowE::RunPyramid(OperationParameters& params, DevicePtr raw_0, DevicePtr raw_1, bool raw_is_pooled)
+bool OpticalFlowE::RunPyramid(OperationParameters& params, DevicePtr raw_0, DevicePtr raw_1, bool raw_is_pooled,
+                              const DevicePtr (*initial)[3])
 {
   size_t warp_levels_count, outer_iterations_count, inner_iterations_count, median_radius;
   float warp_scale_factor, equation_alpha, equation_smoothness, equation_data, gaussian_sigma;
@@ -1359,9 +1446,18 @@ bool OpticalFlowE::RunPyramid(OperationParameters& params, DevicePtr raw_0, Devi
   DevicePtr step[3] = {Borrow(), Borrow(), Borrow()};
   const calls::Flow flow_roles = {&flow[0], &flow[1], &flow[2]}, step_roles = {&step[0], &step[1], &step[2]};
 
+  // the initial flow as it is (whole containers: the box is the whole volume)
+  auto copy_initial = [&]() {
+    for (int c = 0; c < 3; ++c) CheckDeviceError(f3d_copy_d2d(flow[c], (*initial)[c], dev_container_size_.pitch * container_rows));
+  };
+
   level_stats_.clear();
-  if (first_level < 0)  // no level requested: the flow is identically zero
-    for (DevicePtr p : flow) zero_container(p);
+  if (first_level < 0) {  // no level requested: the flow is identically zero, or the initial flow
+    if (initial)
+      copy_initial();
+    else
+      for (DevicePtr p : flow) zero_container(p);
+  }
 
   // `count` (<= 3) volumes of one box through the three resampling passes together: three launches, a scratch container each
   auto resample_together = [&](DevicePtr* in, DevicePtr* out, size_t count, DataSize4& from, DataSize4& to) {
@@ -1391,10 +1487,19 @@ bool OpticalFlowE::RunPyramid(OperationParameters& params, DevicePtr raw_0, Devi
     else
       resample_together(blurred, level_frame, 2, whole, box);
 
-    // 2. the flow so far at this size (zero before the first level): resampled into the increments' containers, roles swapped;
+    // 2. the flow so far at this size (zero, or the initial flow, before the first level): resampled into the increments' containers, roles swapped;
     //    the values are not rescaled -- the flow is kept in original-voxel units
-    if (coarser.width == 0) {
+    if (coarser.width == 0 && !initial) {
       for (DevicePtr p : flow) zero_container(p);
+    } else if (coarser.width == 0) {
+      // a given start: at the original size as it is, at any other level through the resampling the frames take (also when the
+      // box happens to have the whole's dimensions)
+      if (level == 0) {
+        copy_initial();
+      } else {
+        DevicePtr from[3] = {(*initial)[0], (*initial)[1], (*initial)[2]};
+        resample_together(from, flow, 3, whole, box);
+      }
     } else {
       resample_together(flow, step, 3, coarser, box);
       for (int c = 0; c < 3; ++c) std::swap(flow[c], step[c]);
@@ -1473,6 +1578,7 @@ void OpticalFlowE::Destroy()
   for (CudaOperationBase* cuop : cuda_operations_) cuop->Destroy();
   ReleaseResult();
   trajectory_.Release();
+  ReleaseInitialFlow();
   for (FieldSet& set : derived_) set.Release();
   ReleaseWindowGradient();
   size_t freed = 0;

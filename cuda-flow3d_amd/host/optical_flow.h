@@ -160,6 +160,28 @@ class OpticalFlowE : public OpticalFlowBase {
   static Displacement HeldFlow() { return {Displacement::kHeldFlow, {0, 0, 0}}; }      // what ComputeFlowResident() left on the device
   static Displacement Trajectory() { return {Displacement::kTrajectory, {0, 0, 0}}; }  // ResetTrajectory first
   static Displacement Containers(const DevicePtr (&d)[3]) { return {Displacement::kContainers, {d[0], d[1], d[2]}}; }  // TakeResult's
+  // Initial flow: a displacement a solve starts its pyramid from instead of zero (a guess from outside, the flow of the pair before,
+  // the displacement frame 0 -> frame k-1 for a direct solve frame 0 -> frame k).  It is data in three containers of the driver's
+  // own, allocated on first use and kept until it is set again, ReleaseInitialFlow() or Destroy() -- no solve consumes it, and only
+  // the calls that are told to (use_initial) read it.  Each setter fills the containers through f3d_initial_flow (include/f3d.h:
+  // a voxel with a component that is not finite becomes zero) and, when info is given, waits for the stream and reports what was
+  // found.  The second setter copies on the library stream at once, so the containers of `of` may go back to the pool afterwards.
+  // Every call returns false with InitialFlowError() set when it cannot run -- among other reasons when the device library lacks
+  // f3d_initial_flow.  The pyramid resamples the three components from the original size to its first level (they are copied when
+  // that level is the original size, level 0); values are not rescaled: a flow is in original-voxel units at every level.
+  bool SetInitialFlow(Data3D& u, Data3D& v, Data3D& w, f3d_initial_info* info);
+  bool SetInitialFlow(const Displacement& of, f3d_initial_info* info);
+  bool HasInitialFlow() const { return initial_.ptr[0] != 0 && initial_set_; }
+  bool DownloadInitialFlow(Data3D& u, Data3D& v, Data3D& w);
+  void ReleaseInitialFlow();
+  const std::string& InitialFlowError() const { return initial_.error; }
+  // The three compute calls started from the initial flow that is held (use_initial) or, with use_initial false, exactly as their
+  // namesakes above; false with InitialFlowError() set when use_initial is asked for and none is held.
+  bool ComputeFlow(Data3D& frame_0, Data3D& frame_1, Data3D& flow_u, Data3D& flow_v, Data3D& flow_w, OperationParameters& params,
+                   bool use_initial);
+  bool ComputeFlowResident(OperationParameters& params, bool use_initial);
+  bool BeginComputeFlowResident(OperationParameters& params, bool use_initial);
+
   bool ComputeStrain(const Displacement& of, unsigned fields, f3d_strain_stats* stats);
   bool ComputePrincipal(const Displacement& of, unsigned fields, f3d_principal_stats* stats);
   // radius 1 .. 3; a voxel with fewer than min_count (1 .. (2 radius + 1)^3) present points in its window is undefined
@@ -271,7 +293,10 @@ class OpticalFlowE : public OpticalFlowBase {
   bool InitCudaOperations();
   DevicePtr Borrow();
   void GiveBack(DevicePtr p);
-  bool RunPyramid(OperationParameters& params, DevicePtr raw_0, DevicePtr raw_1, bool raw_is_pooled);
+  // initial (nullable): the three full-size components the first level starts from instead of zero
+  bool RunPyramid(OperationParameters& params, DevicePtr raw_0, DevicePtr raw_1, bool raw_is_pooled,
+                  const DevicePtr (*initial)[3] = nullptr);
+  bool CheckInitial(bool use_initial);  // false with the error set when use_initial is asked for and no initial flow is held
   void ReleaseResult();
 
   DataSize4 dev_container_size_ = {0, 0, 0, 0};
@@ -303,6 +328,8 @@ class OpticalFlowE : public OpticalFlowBase {
     void Release();
   };
   FieldSet trajectory_;
+  FieldSet initial_;
+  bool initial_set_ = false;  // the three containers hold a prepared flow (they can exist without one after a failed upload)
   FieldSet derived_[kDerivedCount];
   // the gradient of kWindowPrincipal and kWindowPolar (G00 .. G22), never downloaded
   DevicePtr window_gradient_[9] = {};

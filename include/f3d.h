@@ -472,6 +472,28 @@ int f3d_residual_stats(f3d_devptr frame_0, f3d_devptr frame_1_warped, size_t wid
 int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr acc_w, f3d_devptr inc_u, f3d_devptr inc_v,
                      f3d_devptr inc_w, size_t width, size_t height, size_t depth, unsigned long long* lost);
 
+/* A displacement made fit to start a solve from (no reference counterpart: the reference starts every pyramid from a flow of zero,
+ * src/optical_flow/optical_flow_e.cpp:303-345).  (u, v, w) is a guess of the flow of a pair on frame 0's grid, voxel units: a coarse
+ * DVC, an FE prediction, a rigid pre-registration, the flow of the pair before.  For every voxel (x, y, z) of the box:
+ *   u, v and w all finite:  out = (u, v, w), the same bits (a -0 stays -0)
+ *   else:                   out = (+0, +0, +0), and the voxel counts in `replaced`
+ * info (nullable):
+ *   voxels    width * height * depth
+ *   replaced  as above
+ *   leaving   the finite voxels whose end point (x + u, y + v, z + w) (one float add per axis, as in f3d_compose_flow) lies outside
+ *             [0, width-1] x [0, height-1] x [0, depth-1]
+ *   max_abs   the largest |component| over the finite voxels, 0 when there is none
+ * All four are exact whatever the schedule (integer counts, a maximum).  out_u, out_v, out_w may be u, v, w themselves (component
+ * for component); any other sharing between the six containers is refused.  Padding outside the box is neither read nor written.
+ * Geometry from the current container (f3d_set_container), whole volume, library stream.  Asking for info waits for the stream,
+ * passing NULL only enqueues.  Refused: a null container, a zero dimension, a box larger than the container. */
+typedef struct f3d_initial_info {
+  unsigned long long voxels, replaced, leaving;
+  float max_abs;
+} f3d_initial_info;
+int f3d_initial_flow(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr out_u, f3d_devptr out_v, f3d_devptr out_w, size_t width,
+                     size_t height, size_t depth, f3d_initial_info* info);
+
 /* Strain fields of a displacement (no reference counterpart: the deformation analysis a motion study does with the flows of
  * src/main.cpp:132-185).  d = (u, v, w) is a pair's flow or a cumulative displacement, voxel units.  G[r][c] = d d_r / d x_c
  * (row r = component 0 u, 1 v, 2 w; column c = axis 0 x, 1 y, 2 z), F = I + G.

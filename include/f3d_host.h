@@ -100,6 +100,31 @@ int f3d_flow_trajectory_end(f3d_flow flow);
 int f3d_flow_strain_compute(f3d_flow flow, int source, unsigned fields, float* const out[8], f3d_strain_stats* stats);
 int f3d_flow_strain_end(f3d_flow flow);
 
+/* A solve started from a given displacement instead of zero (f3d_initial_flow of include/f3d.h prepares it: a voxel with a component
+ * that is not finite becomes zero; info, nullable, says what was found).  The initial flow is data in three containers of the driver's
+ * own, like the trajectory: it stays as it is until it is set again, f3d_flow_initial_end or f3d_flow_destroy, and only the two
+ * *_from_initial calls read it -- f3d_flow_compute and f3d_flow_compute_resident never do.
+ *   upload    from three host volumes of width * height * depth floats (a guess from outside: a coarse DVC, an FE prediction, a
+ *             rigid pre-registration)
+ *   take      a copy of the flow the driver holds (source F3D_STRAIN_OF_FLOW, after f3d_flow_compute_resident: the pair before
+ *             under steady motion, or frame 0 -> frame k-1 for a direct solve frame 0 -> frame k) or of the trajectory
+ *             (F3D_STRAIN_OF_TRAJECTORY, after f3d_flow_trajectory_begin)
+ *   download  the prepared flow (for tests)
+ *   end       frees the three containers
+ *   f3d_flow_compute_resident_from_initial / f3d_flow_compute_from_initial: their namesakes with the pyramid's first level started
+ *             from the initial flow resampled to that level's size (copied when that level is the original size; values are not
+ *             rescaled, a flow is in original voxels at every level); with no level at all the result is the prepared initial flow.
+ *             The depth (warp_levels_count) has to cover the error of the guess, not the displacement.
+ * A device library without f3d_initial_flow still loads; then upload and take fail with a message naming it, and the compute calls
+ * fail because no initial flow is held.  Failures are described by f3d_host_last_error(). */
+int f3d_flow_initial_upload(f3d_flow flow, const float* u, const float* v, const float* w, f3d_initial_info* info);
+int f3d_flow_initial_take(f3d_flow flow, int source, f3d_initial_info* info);
+int f3d_flow_initial_download(f3d_flow flow, float* u, float* v, float* w);
+int f3d_flow_initial_end(f3d_flow flow);
+int f3d_flow_compute_resident_from_initial(f3d_flow flow, const f3d_flow_params* params, int silent, float* device_seconds);
+int f3d_flow_compute_from_initial(f3d_flow flow, const float* frame_0, const float* frame_1, const f3d_flow_params* params, int silent,
+                                  float* u, float* v, float* w);
+
 /* Strain fields over a strain window (f3d_window_strain of include/f3d.h has the definition) of the same two sources,
  * F3D_STRAIN_OF_FLOW or F3D_STRAIN_OF_TRAJECTORY.  fields selects groups of the seventeen outputs vol, exx, eyy, ezz, exy, exz, eyz, eq,
  * G00 .. G22 (F3D_STRAIN_VOL / _E / _EQ, F3D_WSTRAIN_G); radius 1 .. 3; min_count 1 .. (2 radius + 1)^3.  Everything else as for
