@@ -25,30 +25,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SWITCHES = ("F3D_PAIR8_TY", "F3D_PAIR8_ROUND", "F3D_PAIR8_PLAN", "F3D_PAIR8_FOLD", "F3D_PAIR8_YMARCH", "F3D_PAIR8_TIGHT", "F3D_TRI_TY")
 
 
-class Rigs:
-    """one allocation at a time: the 256 MiB geometry (5 GiB), then the y march's (3.8 GiB)"""
-
-    def __init__(self, f3d):
-        self.f3d, self.kind, self.rig = f3d, None, None
-
-    def get(self, hc, dc):
-        if self.kind != (hc, dc):
-            self.close()
-            self.rig, self.kind = wc.Wide(self.f3d, hc, dc), (hc, dc)
-        return self.rig
-
-    def close(self):
-        if self.rig is not None:
-            self.rig.close()
-        self.rig = self.kind = None
-
-
 @pytest.fixture(scope="module")
 def rigs(f3d):
     free, _ = f3d.mem_info()
     if free < 8 << 30:
         pytest.skip("less than 8 GiB of device memory free (%.1f GiB)" % (free / 2.0 ** 30))
-    r = Rigs(f3d)
+    r = wc.Rigs(f3d)
     yield r
     r.close()
 
@@ -293,7 +275,8 @@ def test_add_clear_and_memset_past_4_gib(f3d, oracle, rigs, window):
 
 @pytest.mark.parametrize("window", WINDOWS, ids=WINDOW_IDS)
 def test_reductions_past_4_gib(f3d, rigs, window):
-    """against numpy in binary64 under the bounds of tests/test_gpu_reductions.py: extremes exact, sums within 1e-12 of the exact sum"""
+    """f3d_abs_max, f3d_flow_stats and f3d_residual_stats through the callers of tests/test_gpu_reductions.py, against numpy in binary64
+    under that module's bounds: extremes exact, sums within 1e-12 of the exact sum"""
     import exact_ref as X
     import test_gpu_reductions as red
     W, H, D = BOX
@@ -332,7 +315,7 @@ def test_resampling_passes_past_4_gib(f3d, oracle, rigs, axis, n, m, rest, windo
     src_dims = tuple(n if r is None else r for r in rest)
     dst_dims = tuple(m if r is None else r for r in rest)
     ow, oh, od = dst_dims
-    name = "f3d_resample_" + "xyz"[axis]
+    name = ("f3d_resample_x", "f3d_resample_y", "f3d_resample_z")[axis]      # and f3d_resample_x_n, f3d_resample_y_n, f3d_resample_z_n
     rng = np.random.default_rng(600 + 10 * n + m)
     srcs = [uniform(rng, src_dims, -5, 5) for _ in range(3)]
     exps = []

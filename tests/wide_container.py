@@ -1,5 +1,5 @@
 """A container whose planes are hundreds of MiB, for tests/test_gpu_wide_container_offsets.py (and its child interpreter,
-tests/wide_container_worker.py).
+tests/wide_container_worker.py) and tests/test_gpu_wide_container_analysis.py.
 
 An address depends on the container's geometry (height, pitch), not on the box: a 70 x 20 x 19 box in the corner of a container whose
 planes are 256 MiB forms the byte offsets a huge volume forms.  ONE device allocation of 8192 x 8192 x 20 floats (pitch 32 768 bytes,
@@ -108,6 +108,25 @@ class Wide:
     def unchanged(self, ptr, vol, plane0=0):
         d, h, w = vol.shape
         return bit_same(self.download(ptr, w, h, (plane0, plane0 + d)), vol)
+
+
+class Rigs:
+    """one allocation at a time, shared by the tests of a module: rigs.get(8192, 20) is the 256 MiB geometry (5 GiB), get(4096, 40) the
+    same 5 GiB as planes of 128 MiB, get(13654, 9) the y march's (3.8 GiB)"""
+
+    def __init__(self, f3d):
+        self.f3d, self.kind, self.rig = f3d, None, None
+
+    def get(self, hc, dc):
+        if self.kind != (hc, dc):
+            self.close()
+            self.rig, self.kind = Wide(self.f3d, hc, dc), (hc, dc)
+        return self.rig
+
+    def close(self):
+        if self.rig is not None:
+            self.rig.close()
+        self.rig = self.kind = None
 
 
 # ---- the solver family ------------------------------------------------------------------------------------------------------------
