@@ -276,6 +276,35 @@ class InitialInfo(C.Structure):  # f3d_initial_info: what f3d_initial_flow found
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BlockMatchGrid(C.Structure):  # f3d_block_match_grid (include/f3d_block_match.h)
+    _fields_ = [("ox", C.c_int), ("oy", C.c_int), ("oz", C.c_int), ("step", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("window", C.c_int), ("rx", C.c_int), ("ry", C.c_int), ("rz", C.c_int)]
+
+
+class BlockMatchInfo(C.Structure):  # f3d_block_match_info
+    _fields_ = [("nodes", C.c_ulonglong), ("ok", C.c_ulonglong), ("flat_nodes", C.c_ulonglong), ("none_nodes", C.c_ulonglong),
+                ("evaluated", C.c_ulonglong), ("outside", C.c_ulonglong), ("flat", C.c_ulonglong), ("nan", C.c_ulonglong)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BlockMatchSummary(C.Structure):  # f3d_block_match_summary
+    _fields_ = [("nodes", C.c_ulonglong), ("ok", C.c_ulonglong), ("flat", C.c_ulonglong), ("none", C.c_ulonglong),
+                ("low", C.c_ulonglong), ("edge", C.c_ulonglong)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# f3d_block_match_record as 32 int32 per node, and f3d_block_match_node as a numpy record
+BLOCK_MATCH_RECORD_WORDS = 32
+BLOCK_MATCH_NODE = np.dtype([("position", np.int32, 3), ("shift", np.int32, 3), ("status", np.int32), ("evaluated", np.int32),
+                             ("outside", np.int32), ("flat", np.int32), ("zncc", np.float64), ("offset", np.float64, 3),
+                             ("u", np.float32), ("v", np.float32), ("w", np.float32), ("reserved", np.int32)])
+BLOCK_NODE_STATUS = ("ok", "flat", "none", "low", "edge")
+
+
 class FlowParams(C.Structure):  # f3d_flow_params
     _fields_ = [
         ("warp_levels_count", C.c_size_t), ("warp_scale_factor", C.c_float),
@@ -447,6 +476,13 @@ def host():
         "f3d_flow_initial_download": [C.c_void_p, _fp, _fp, _fp], "f3d_flow_initial_end": [C.c_void_p],
         "f3d_flow_compute_resident_from_initial": [C.c_void_p, pp, C.c_int, _fp],
         "f3d_flow_compute_from_initial": [C.c_void_p, _fp, _fp, pp, C.c_int, _fp, _fp, _fp],
+        "f3d_block_match_layout": [_sz, _sz, _sz] + [C.c_int] * 5 + [C.POINTER(BlockMatchGrid)],
+        "f3d_flow_block_match": [C.c_void_p] + [C.c_int] * 5 + [_sz, _fp, C.c_void_p, C.c_double, C.POINTER(BlockMatchGrid),
+                                 C.POINTER(BlockMatchInfo), C.POINTER(BlockMatchSummary)],
+        "f3d_flow_block_match_rows": [C.c_void_p, _sz, C.c_void_p, C.c_void_p],
+        "f3d_flow_initial_from_nodes": [C.c_void_p, C.POINTER(ValidateStats), C.POINTER(InitialInfo)],
+        "f3d_block_match_solve": [C.c_void_p, C.POINTER(BlockMatchGrid), C.c_void_p, C.c_double, C.c_void_p,
+                                  C.POINTER(BlockMatchSummary)],
         "f3d_flow_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(StrainStats)],
         "f3d_flow_strain_end": [C.c_void_p],
         "f3d_flow_window_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(_fp),
@@ -852,6 +888,152 @@ def initial_flow(u, v, w):
         info = InitialInfo()
         check(fn(*p, *p, *dims, C.byref(info)), "f3d_initial_flow")
         return tuple(box.download(a, dims) for a in p), info
+
+
+def _block_match_entry():
+    return _entry("f3d_block_match", [_dp, _dp, C.c_float, C.c_float, _sz, _sz, _sz, _sz, C.POINTER(BlockMatchGrid), C.c_void_p, C.c_void_p,
+                                      C.POINTER(BlockMatchInfo)], "match blocks of two frames")
+
+
+def _expand_nodes_entry():
+    return _entry("f3d_expand_nodes", [_fp, _fp, _fp] + [C.c_int] * 7 + [_dp] * 3 + [_sz] * 3, "expand node vectors to a dense field")
+
+
+def block_match_grid(dims, step=16, window=8, search=8, origin=None, counts=None):
+    """The node grid of block_match over a (w, h, d) volume as a BlockMatchGrid: nodes `step` apart whose (2 window + 1)^3 windows lie
+    inside the volume, as many as fit and centred, unless origin = (ox, oy, oz) and / or counts = (nx, ny, nz) say otherwise.
+    search: one radius or (rx, ry, rz).  ValueError when a window leaves the volume."""
+    radii = (int(search),) * 3 if np.isscalar(search) else tuple(int(r) for r in search)
+    step, window = int(step), int(window)
+    if len(radii) != 3 or step < 1 or window < 1:
+        raise ValueError("search must be one radius or three, step and window at least 1")
+    first, count = [], []
+    for axis, n in enumerate(dims):
+        room = int(n) - 1 - 2 * window
+        if room < 0:
+            raise ValueError(f"a window of radius {window} leaves the volume along {'xyz'[axis]} ({n} voxels)")
+        o = window + (room % step) // 2 if origin is None else int(origin[axis])
+        c = (int(n) - 1 - window - o) // step + 1 if counts is None else int(counts[axis])
+        if o < window or c < 1 or o + (c - 1) * step + window > int(n) - 1:
+            raise ValueError(f"a window of radius {window} leaves the volume along {'xyz'[axis]}: origin {o}, {c} nodes, step {step}")
+        first.append(o)
+        count.append(c)
+    return BlockMatchGrid(*first, step, *count, window, *radii)
+
+
+class BlockMatchNodes:
+    """The node table of block_match: `rows`, one BLOCK_MATCH_NODE record per node (x fastest); `records`, the [nodes, 32] int32 records
+    of f3d_block_match they were solved from; `info` and `summary`, the dicts of f3d_block_match_info and f3d_block_match_summary;
+    `grid` (BlockMatchGrid), `centre`.  origin, step, counts and u, v, w as [nz, ny, nx] arrays feed expand_nodes."""
+
+    def __init__(self, rows, records, info, summary, grid, centre):
+        self.rows, self.records, self.info, self.summary, self.grid, self.centre = rows, records, info, summary, grid, centre
+        self.origin, self.step, self.counts = (grid.ox, grid.oy, grid.oz), grid.step, (grid.nx, grid.ny, grid.nz)
+
+    def __len__(self):
+        return len(self.rows)
+
+    def _component(self, name):
+        return np.ascontiguousarray(self.rows[name].reshape(self.counts[::-1]))
+
+    u = property(lambda self: self._component("u"))
+    v = property(lambda self: self._component("v"))
+    w = property(lambda self: self._component("w"))
+
+    def as_table(self):
+        return [dict(x=int(r["position"][0]), y=int(r["position"][1]), z=int(r["position"][2]), shift=tuple(int(s) for s in r["shift"]),
+                     offset=tuple(float(o) for o in r["offset"]), zncc=float(r["zncc"]), status=BLOCK_NODE_STATUS[int(r["status"])],
+                     evaluated=int(r["evaluated"]), outside=int(r["outside"]), flat=int(r["flat"])) for r in self.rows]
+
+
+def _centre_array(centre, nodes):
+    if centre is None:
+        return None
+    centre = np.ascontiguousarray(centre, dtype=np.int32)
+    if centre.size != 3 * nodes:
+        raise ValueError(f"centre must hold one (x, y, z) triple per node, {nodes} of them")
+    return centre.reshape(nodes, 3)
+
+
+def solve_block_match(records, grid, centre=None, min_zncc=0.5):
+    """f3d_block_match_solve (include/f3d_host.h) of [nodes, 32] int32 records: -> (rows as BLOCK_MATCH_NODE records, summary dict).
+    Host code, no device needed."""
+    nodes = grid.nx * grid.ny * grid.nz
+    records = np.ascontiguousarray(records, dtype=np.int32)
+    if records.shape != (nodes, BLOCK_MATCH_RECORD_WORDS):
+        raise ValueError(f"records must be [{nodes}, {BLOCK_MATCH_RECORD_WORDS}] int32")
+    centre = _centre_array(centre, nodes)
+    rows, summary = np.zeros(nodes, BLOCK_MATCH_NODE), BlockMatchSummary()
+    _host_check(host().f3d_block_match_solve(records.ctypes.data, C.byref(grid), None if centre is None else centre.ctypes.data,
+                                             float(min_zncc), rows.ctypes.data, C.byref(summary)), "f3d_block_match_solve")
+    return rows, summary.as_dict()
+
+
+def block_match(a, b, step=16, window=8, search=8, bins=256, range=None, centre=None, min_zncc=0.5, origin=None, counts=None):
+    """Coarse block matching on the device (include/f3d_block_match.h, f3d_block_match, then f3d_block_match_solve): on a grid of nodes
+    `step` voxels apart, the integer shift within `search` (one radius or (rx, ry, rz)) of `centre` (one int triple per node, default
+    zero) that maximises the zero-normalised cross-correlation of the (2 window + 1)^3 window of `a` against `b`, refined to a sub-voxel
+    peak.  Grey values are quantised to `bins` codes over range = (lo, hi), the finite minimum and maximum of `a` when None.  a, b:
+    numpy [z, y, x] float32 of one shape.  Returns a BlockMatchNodes; nodes whose ZNCC is below min_zncc, or that found nothing, have
+    NaN vectors (validate_displacement on the node grid repairs them, expand_nodes makes the field dense)."""
+    fn = _block_match_entry()
+    find = _value_range_entry() if range is None else None
+    bounds = None if range is None else _bin_range(range)
+    with _on_device([a, b], "a and b must be two [z, y, x] volumes of one shape") as (box, p, dims):
+        grid = block_match_grid(dims, step, window, search, origin, counts)
+        nodes = grid.nx * grid.ny * grid.nz
+        centre = _centre_array(centre, nodes)
+        box.set_current()
+        if bounds is None:
+            lo, hi, found = C.c_float(), C.c_float(), RangeInfo()
+            check(find(p[0], 0, *dims, C.byref(lo), C.byref(hi), C.byref(found)), "f3d_value_range")
+            if found.finite == 0 or not lo.value < hi.value:
+                raise ValueError("frame 0 has no two finite values: there is no range to lay the codes over")
+            bounds = (lo.value, hi.value)
+        records, info = np.zeros((nodes, BLOCK_MATCH_RECORD_WORDS), np.int32), BlockMatchInfo()
+        check(fn(p[0], p[1], bounds[0], bounds[1], int(bins), *dims, C.byref(grid), None if centre is None else centre.ctypes.data,
+                 records.ctypes.data, C.byref(info)), "f3d_block_match")
+    rows, summary = solve_block_match(records, grid, centre, min_zncc)
+    return BlockMatchNodes(rows, records, info.as_dict(), summary, grid, centre)
+
+
+def expand_nodes(u, v, w, origin, step, dims):
+    """Node vectors to a dense field on the device (include/f3d_block_match.h, f3d_expand_nodes): u, v, w numpy [nz, ny, nx] float32,
+    node (i, j, k) at origin + step * (i, j, k); dims = (w, h, d) of the field.  Trilinear between the nodes, held constant outside
+    their hull, NaN wherever a NaN node takes part.  Returns three [d, h, w] float32 volumes."""
+    fn = _expand_nodes_entry()
+    held = [_f32(c) for c in (u, v, w)]
+    if any(a.ndim != 3 or a.shape != held[0][0].shape for a, _ in held):
+        raise ValueError("u, v and w must be three [nz, ny, nx] arrays of one shape")
+    nz, ny, nx = held[0][0].shape
+    w_, h_, d_ = (int(n) for n in dims)
+    previous = Size4()
+    check(hip().f3d_get_container(C.byref(previous)), "f3d_get_container")
+    box = Containers(w_, h_, d_)
+    try:
+        outs = [box.alloc() for _ in range(3)]
+        box.set_current()
+        check(fn(held[0][1], held[1][1], held[2][1], int(origin[0]), int(origin[1]), int(origin[2]), int(step), nx, ny, nz, *outs,
+                 w_, h_, d_), "f3d_expand_nodes")
+        return tuple(box.download(o, (w_, h_, d_)) for o in outs)
+    finally:
+        if previous.pitch:
+            hip().f3d_set_container(C.byref(previous))
+        box.free()
+
+
+def block_match_initial(a, b, validate=True, **kw):
+    """The dense guess of a pair for compute(initial=...): block_match(a, b, **kw), the node vectors through validate_displacement in
+    replace mode with its defaults (the node grid is a small volume: outliers and the NaN nodes get their neighbours' median), then
+    expand_nodes over the volume.  Returns ((u, v, w), nodes).  Voxels a NaN node still reaches are NaN; set_initial starts them from
+    zero and counts them."""
+    nodes = block_match(a, b, **kw)
+    u, v, w = nodes.u, nodes.v, nodes.w
+    if validate:
+        d = validate_displacement(u, v, w, mode="replace", fields=("d",))
+        u, v, w = d["u"], d["v"], d["w"]
+    shape = np.asarray(a).shape
+    return expand_nodes(u, v, w, nodes.origin, nodes.step, shape[::-1]), nodes
 
 
 # the eight outputs of f3d_flow_strain in ABI order, and the F3D_STRAIN_* group of each
@@ -2638,6 +2820,9 @@ class OpticalFlow:
                     raise ValueError(f"out arrays must be C-contiguous float32 [z,y,x] = {(d, h, w)}")
         prm = make_params(**kw)
         if initial is not None:
+            if isinstance(initial, str) and initial in ("block-match", "held"):
+                raise ValueError(f"initial={initial!r} reads the pair that is resident, and compute() uploads its own afterwards: "
+                                 "upload() the pair and use compute_resident(initial=...)")
             self.set_initial(initial)
             _host_check(host().f3d_flow_compute_from_initial(self._h, p0, p1, C.byref(prm), int(silent), u.ctypes.data_as(_fp),
                                                              v.ctypes.data_as(_fp), ww.ctypes.data_as(_fp)),
@@ -2676,8 +2861,15 @@ class OpticalFlow:
         """Hold `initial` as the flow the next compute(initial=...) calls start their pyramid from: a tuple of three [z, y, x]
         arrays (a guess from outside), "flow" (a copy of what compute_resident() left on the device) or "trajectory" (a copy of the
         cumulative displacement).  A voxel with a component that is not finite starts from zero.  Returns the InitialInfo.  The
-        flow is kept, unchanged by any solve, until it is set again, initial_end() or destroy()."""
+        flow is kept, unchanged by any solve, until it is set again, initial_end() or destroy().  "block-match": the guess of
+        block_match() with its defaults on the uploaded pair, through set_initial_from_nodes().  "held": whatever is held already
+        (set_initial or set_initial_from_nodes before), nothing is set and None is returned."""
         info = InitialInfo()
+        if isinstance(initial, str) and initial == "held":
+            return None
+        if isinstance(initial, str) and initial == "block-match":
+            self.block_match()
+            return self.set_initial_from_nodes()[1]
         if isinstance(initial, str):
             _host_check(host().f3d_flow_initial_take(self._h, _source(initial), C.byref(info)), "f3d_flow_initial_take")
             return info
@@ -2702,6 +2894,35 @@ class OpticalFlow:
     def initial_end(self):
         """free the containers of the initial flow (destroy() does too)"""
         _host_check(host().f3d_flow_initial_end(self._h), "f3d_flow_initial_end")
+
+    # ---- the guess from the frames themselves (include/f3d_host.h, f3d_flow_block_match, f3d_flow_initial_from_nodes) ----
+    def block_match(self, step=16, window=8, search=8, bins=256, range=None, centre=None, min_zncc=0.5):
+        """block_match() of the module on the pair the driver holds (upload first), on the library stream; the grid is the one
+        block_match_grid lays over the volume.  Returns a BlockMatchNodes; the table also stays with the driver for
+        set_initial_from_nodes()."""
+        radii = (int(search),) * 3 if np.isscalar(search) else tuple(int(r) for r in search)
+        if len(radii) != 3:
+            raise ValueError("search must be one radius or three")
+        grid = BlockMatchGrid()
+        _host_check(host().f3d_block_match_layout(*self.dims, int(step), int(window), *radii, C.byref(grid)), "f3d_block_match_layout")
+        nodes = grid.nx * grid.ny * grid.nz
+        centre = _centre_array(centre, nodes)
+        bounds = None if range is None else (C.c_float * 2)(*_bin_range(range))
+        info, summary = BlockMatchInfo(), BlockMatchSummary()
+        _host_check(host().f3d_flow_block_match(self._h, int(step), int(window), *radii, int(bins), bounds,
+                                                None if centre is None else centre.ctypes.data, float(min_zncc), C.byref(grid),
+                                                C.byref(info), C.byref(summary)), "f3d_flow_block_match")
+        records, rows = np.zeros((nodes, BLOCK_MATCH_RECORD_WORDS), np.int32), np.zeros(nodes, BLOCK_MATCH_NODE)
+        _host_check(host().f3d_flow_block_match_rows(self._h, nodes, records.ctypes.data, rows.ctypes.data), "f3d_flow_block_match_rows")
+        return BlockMatchNodes(rows, records, info.as_dict(), summary.as_dict(), grid, centre)
+
+    def set_initial_from_nodes(self):
+        """Hold the guess of the last block_match() as the flow compute_resident(initial=True) starts from: the node vectors through
+        the median test on the node grid (validate_displacement, replace mode, its defaults), expanded over the volume (expand_nodes)
+        and prepared as set_initial prepares a flow.  Returns (the dict of the median test's statistics, InitialInfo)."""
+        validated, info = ValidateStats(), InitialInfo()
+        _host_check(host().f3d_flow_initial_from_nodes(self._h, C.byref(validated), C.byref(info)), "f3d_flow_initial_from_nodes")
+        return validated.as_dict(), info
 
     def set_level_stats(self, enable=True):
         """record, per pyramid level of every later compute, the residual before the solve and the flow statistics after it"""

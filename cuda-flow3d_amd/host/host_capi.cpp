@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "f3d_host.h"
+#include "block_match.h"
 #include "contact_kinematics.h"
 #include "label_field.h"
 #include "label_shape.h"
@@ -618,6 +619,61 @@ int f3d_overlap_solve(const struct f3d_overlap* rows, size_t count, size_t n_a, 
   if (n_a == 0 || n_b == 0) return HostFail("f3d_overlap_solve: n_a and n_b must be at least 1");
   std::string why;
   return SolveOverlaps(rows, count, n_a, n_b, min_fraction, a, b, map_b, summary, &why) ? 0 : HostFail(why.c_str());
+}
+
+int f3d_block_match_solve(const f3d_block_match_record* records, const f3d_block_match_grid* grid, const int* centre, double min_zncc,
+                          f3d_block_match_node* nodes, f3d_block_match_summary* summary)
+{
+  g_host_error.clear();
+  if (!records || !grid || !nodes) return HostFail("f3d_block_match_solve: null argument");
+  std::string why;
+  return SolveBlockMatch(records, grid, centre, min_zncc, nodes, summary, &why) ? 0 : HostFail(why.c_str());
+}
+
+int f3d_block_match_layout(size_t width, size_t height, size_t depth, int step, int window, int rx, int ry, int rz,
+                           f3d_block_match_grid* grid)
+{
+  g_host_error.clear();
+  if (!grid) return HostFail("f3d_block_match_layout: null argument");
+  std::string why;
+  return LayoutBlockMatch(width, height, depth, step, window, rx, ry, rz, grid, &why) ? 0 : HostFail(why.c_str());
+}
+
+int f3d_flow_block_match(f3d_flow flow, int step, int window, int rx, int ry, int rz, size_t bins, const float* range, const int* centre,
+                         double min_zncc, f3d_block_match_grid* grid, f3d_block_match_info* info, f3d_block_match_summary* summary)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_block_match: null driver");
+  OpticalFlowE::BlockMatchParams p;
+  p.step = step;
+  p.window = window;
+  p.radius[0] = rx, p.radius[1] = ry, p.radius[2] = rz;
+  p.bins = bins;
+  p.range = range;
+  p.min_zncc = min_zncc;
+  if (!flow->driver.BlockMatch(p, centre, info, summary)) return HostFail(flow->driver.InitialFlowError().c_str());
+  if (grid) *grid = flow->driver.BlockMatchGrid();
+  return 0;
+}
+
+int f3d_flow_block_match_rows(f3d_flow flow, size_t capacity, f3d_block_match_record* records, f3d_block_match_node* nodes)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_block_match_rows: null driver");
+  const std::vector<f3d_block_match_node>& rows = flow->driver.BlockMatchNodes();
+  if (rows.empty()) return HostFail("f3d_flow_block_match_rows: no node table is held (f3d_flow_block_match first)");
+  if (rows.size() > capacity) return HostFail("f3d_flow_block_match_rows: the table has more nodes than there is room for");
+  if (records) std::memcpy(records, flow->driver.BlockMatchRecords().data(), rows.size() * sizeof(f3d_block_match_record));
+  if (nodes) std::memcpy(static_cast<void*>(nodes), rows.data(), rows.size() * sizeof(f3d_block_match_node));
+  return 0;
+}
+
+int f3d_flow_initial_from_nodes(f3d_flow flow, f3d_validate_stats* validated, f3d_initial_info* info)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_initial_from_nodes: null driver");
+  if (!flow->driver.SetInitialFromNodes(validated, info)) return HostFail(flow->driver.InitialFlowError().c_str());
+  return 0;
 }
 
 int f3d_flow_labels_b_upload(f3d_flow flow, const int* labels)

@@ -34,6 +34,13 @@
 // raw files of W x H x D in the layout the flows are written in (a coarse DVC, an FE prediction, a rigid pre-registration).  A voxel
 // with a component that is not finite starts from zero (f3d_initial_flow); one line per pair that starts from a displacement says how
 // many such voxels there were, how many end points leave the volume and the largest component.
+// --block-match (resident driver, pairs in order) makes that guess from the frames themselves: on a grid of nodes
+// --block-match-step apart (default 16) the integer shift within --block-match-search R or RX:RY:RZ (default 8) that maximises the
+// ZNCC of a window of radius --block-match-window (default 8) of the pair's first frame against its second, refined to a sub-voxel
+// peak; nodes below --block-match-min-zncc (default 0.5) have no vector.  Per pair: <tag>_blockmatch.csv (per node the position, the
+// shift, the offset, the ZNCC, the status and the counts of candidates), one line (nodes ok / low / flat / edge / none, the median and
+// the largest |shift|), then the node vectors go through the median test on the node grid, are expanded over the volume and start
+// the pair's solve; the initial flow: line follows.  --block-match-only (one pair) stops after the table.
 // --warm-start starts pair k >= 1 from the flow of pair k-1 as it stands (steady motion); the pairs stay the consecutive ones.
 // --total makes pair k frame 0 -> frame k+1, solved directly and started from the result of pair k-1: the other route to the
 // displacement from frame 0, which --cumulative composes from the consecutive pairs with one interpolation per step.  The flow of a
@@ -157,6 +164,8 @@ static void Usage()
               "              [--levels N] [--scale s] [--outer N] [--inner N] [--alpha a] [--eps-smooth e]\n"
               "              [--eps-data e] [--median r] [--sigma s] [--vtk] [--stats] [--silent] [--partial [--full] [--budget-mb N]]\n"
               "              [--concurrent N] [--cumulative] [--initial-flow U V W] [--warm-start | --total]\n"
+              "              [--block-match [--block-match-step S] [--block-match-window W] [--block-match-search R | RX:RY:RZ]\n"
+              "               [--block-match-min-zncc T] [--block-match-only]]\n"
               "              [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
               "              [--rotation angle,vector,stretch] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
               "              [--window-strain vol,e,eq,grad [--window-radius R] [--window-min-count K]]\n"
@@ -187,6 +196,8 @@ int main(int argc, char** argv)
   bool use_partial_gpu = false, partial_full = false, cumulative = false;
   bool total = false, warm_start = false, initial_given = false;  // --total, --warm-start, --initial-flow U V W
   std::vector<std::string> initial_files;
+  bool block_match = false, block_match_only = false, block_match_sub_given = false;  // --block-match and its options
+  OpticalFlowE::BlockMatchParams block_match_params;
   size_t concurrent = 1;
   unsigned strain_fields = 0;     // --strain: F3D_STRAIN_* groups
   unsigned wstrain_fields = 0;    // --window-strain: F3D_STRAIN_* groups and F3D_WSTRAIN_G
@@ -288,6 +299,44 @@ int main(int argc, char** argv)
     else if (a == "--initial-flow") {
       initial_given = true;
       while (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) initial_files.push_back(argv[++i]);
+    }
+    else if (a == "--block-match") block_match = true;
+    else if (a == "--block-match-only") block_match_only = block_match_sub_given = true;
+    else if (a == "--block-match-step" || a == "--block-match-window") {
+      need(1);
+      char* rest = nullptr;
+      const long n = std::strtol(argv[++i], &rest, 10);
+      if (rest == argv[i] || *rest || n < 1 || n > (a == "--block-match-step" ? 1 << 20 : F3D_BLOCK_MATCH_MAX_WINDOW)) { Usage(); return 64; }
+      (a == "--block-match-step" ? block_match_params.step : block_match_params.window) = static_cast<int>(n);
+      block_match_sub_given = true;
+    }
+    else if (a == "--block-match-search") {
+      need(1);
+      // R or RX:RY:RZ
+      const std::string list = argv[++i];
+      int count = 0;
+      size_t at = 0;
+      while (count < 3) {
+        const size_t end = list.find(':', at);
+        const std::string item = list.substr(at, end == std::string::npos ? std::string::npos : end - at);
+        char* rest = nullptr;
+        const long n = std::strtol(item.c_str(), &rest, 10);
+        if (item.empty() || *rest || n < 0 || n > F3D_BLOCK_MATCH_MAX_REACH) { Usage(); return 64; }
+        block_match_params.radius[count++] = static_cast<int>(n);
+        if (end == std::string::npos) break;
+        at = end + 1;
+        if (count == 3) { Usage(); return 64; }
+      }
+      if (count == 1) block_match_params.radius[1] = block_match_params.radius[2] = block_match_params.radius[0];
+      else if (count != 3) { Usage(); return 64; }
+      block_match_sub_given = true;
+    }
+    else if (a == "--block-match-min-zncc") {
+      need(1);
+      char* rest = nullptr;
+      block_match_params.min_zncc = std::strtod(argv[++i], &rest);
+      if (rest == argv[i] || *rest || std::isnan(block_match_params.min_zncc)) { Usage(); return 64; }
+      block_match_sub_given = true;
     }
     else if (a == "--inverse") inverse = true;
     else if (a == "--strain") {
@@ -681,6 +730,32 @@ int main(int argc, char** argv)
         Usage();
         return 64;
       }
+    }
+  }
+  // --block-match: the guess comes from the frames themselves; all refusals before any device is touched
+  if (block_match_sub_given && !block_match) {
+    std::printf("--block-match-step, -window, -search, -min-zncc and -only need --block-match\n");
+    Usage();
+    return 64;
+  }
+  if (block_match) {
+    const size_t pairs_given = synthetic ? 1 : (files.empty() ? 0 : files.size() - 1);
+    const char* why = nullptr;
+    if (initial_given) why = "--block-match makes the guess --initial-flow would read: choose one";
+    else if (use_partial_gpu || concurrent > 1) why = "--block-match needs the resident driver solving the pairs in order: it cannot be combined with --partial or --concurrent N > 1";
+    else if ((total || warm_start) && pairs_given > 1) why = "--block-match on the pairs after the first is not available under --warm-start or --total, which start them from the pair before";
+    else if (block_match_only && pairs_given > 1) why = "--block-match-only takes one pair";
+    std::string layout_error;
+    f3d_block_match_grid laid;
+    if (!why && f3d_block_match_layout(width, height, depth, block_match_params.step, block_match_params.window, block_match_params.radius[0],
+                                       block_match_params.radius[1], block_match_params.radius[2], &laid)) {
+      layout_error = std::string("--block-match: ") + f3d_host_last_error();
+      why = layout_error.c_str();
+    }
+    if (why) {
+      std::printf("%s\n", why);
+      Usage();
+      return 64;
     }
   }
   const bool from_frame_0 = cumulative || total;  // the displacement the derived fields are computed of starts at frame 0
@@ -1810,13 +1885,66 @@ int main(int argc, char** argv)
     return 0;
   };
 
+  // --block-match: the node table of the resident pair into <tag>_blockmatch.csv, one line about it, and (unless only the table is
+  // wanted) the guess of the pair's solve from it
+  auto initial_from_block_match = [&](size_t k) {
+    f3d_block_match_summary sum = {};
+    if (!optical_flow_e.BlockMatch(block_match_params, nullptr, nullptr, &sum)) {
+      std::printf("Error: %s\n", optical_flow_e.InitialFlowError().c_str());
+      return 3;
+    }
+    const std::vector<f3d_block_match_node>& rows = optical_flow_e.BlockMatchNodes();
+    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
+    std::FILE* csv = std::fopen((tag + "_blockmatch.csv").c_str(), "w");
+    if (!csv) {
+      std::printf("Error: cannot write %s_blockmatch.csv\n", tag.c_str());
+      return 2;
+    }
+    static const char* const kStatus[] = {"ok", "flat", "none", "low", "edge"};
+    std::fprintf(csv, "x,y,z,shift_x,shift_y,shift_z,offset_x,offset_y,offset_z,zncc,status,evaluated,outside,flat\n");
+    std::vector<double> lengths;
+    for (const f3d_block_match_node& r : rows) {
+      std::fprintf(csv, "%d,%d,%d,%d,%d,%d,%.17g,%.17g,%.17g,%.17g,%s,%d,%d,%d\n", r.position[0], r.position[1], r.position[2], r.shift[0],
+                   r.shift[1], r.shift[2], r.offset[0], r.offset[1], r.offset[2], r.zncc, kStatus[r.status], r.evaluated, r.outside, r.flat);
+      if (r.status == F3D_BLOCK_NODE_OK || r.status == F3D_BLOCK_NODE_EDGE)
+        lengths.push_back(std::sqrt(static_cast<double>(r.u) * r.u + static_cast<double>(r.v) * r.v + static_cast<double>(r.w) * r.w));
+    }
+    std::fclose(csv);
+    // the upper median and the maximum of |shift + offset| over the nodes that have a vector; nan without one
+    double median = std::nan(""), largest = std::nan("");
+    if (!lengths.empty()) {
+      std::nth_element(lengths.begin(), lengths.begin() + lengths.size() / 2, lengths.end());
+      median = lengths[lengths.size() / 2];
+      largest = *std::max_element(lengths.begin(), lengths.end());
+    }
+    std::printf("block match: %llu nodes, %llu ok, %llu low, %llu flat, %llu edge, %llu none, median shift %.4f, largest %.4f\n", sum.nodes, sum.ok,
+                sum.low, sum.flat, sum.edge, sum.none, median, largest);
+    if (block_match_only) return 0;
+    f3d_initial_info found = {};
+    if (!optical_flow_e.SetInitialFromNodes(nullptr, &found)) {
+      std::printf("Error: %s\n", optical_flow_e.InitialFlowError().c_str());
+      return 3;
+    }
+    say_initial(found);
+    return 0;
+  };
+
   if (pairs == 1) {
     if (!synthetic && !load(frame_1, files[1])) return 2;
     optical_flow_e.UploadResidentFrames(frame_0, frame_1);
     if (initial_given)
       if (const int status = initial_from_files()) return status;
+    if (block_match) {
+      if (const int status = initial_from_block_match(0)) return status;
+      if (block_match_only) {
+        optical_flow_e.Destroy();
+        f3d_host_shutdown();
+        return 0;
+      }
+    }
+    const bool from_guess = initial_given || block_match;
     // (a plain solve that cannot run goes on as it always did; one that was to start from the displacement says why and ends)
-    if (!optical_flow_e.ComputeFlowResident(params, initial_given) && initial_given) return 3;
+    if (!optical_flow_e.ComputeFlowResident(params, from_guess) && from_guess) return 3;
     if (print_stats) report();
     if (segment || histogram)
       if (const int status = segment_frame_0()) return status;
@@ -1931,6 +2059,9 @@ int main(int argc, char** argv)
       bool from_initial = false;
       if (k == 0 && initial_given) {
         if (const int status = initial_from_files()) return status;
+        from_initial = true;
+      } else if (block_match) {
+        if (const int status = initial_from_block_match(k)) return status;
         from_initial = true;
       } else if (k > 0 && (total || warm_start)) {
         f3d_initial_info found = {};

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <memory>
 
+#include "block_match.h"
 #include "common_utils.h"
 #include "operator_calls.h"
 #include "hip_utils.h"
@@ -21,6 +22,12 @@
 // trajectory calls fail with a message instead of the whole library failing to load).
 extern "C" int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr acc_w, f3d_devptr inc_u, f3d_devptr inc_v,
                                 f3d_devptr inc_w, size_t width, size_t height, size_t depth, unsigned long long* lost)
+    __attribute__((weak));
+extern "C" int f3d_block_match(f3d_devptr a, f3d_devptr b, float lo, float hi, size_t bins, size_t width, size_t height, size_t depth,
+                               const f3d_block_match_grid* grid, const int* centre, f3d_block_match_record* records,
+                               f3d_block_match_info* info) __attribute__((weak));
+extern "C" int f3d_expand_nodes(const float* u, const float* v, const float* w, int ox, int oy, int oz, int step, int nx, int ny, int nz,
+                                f3d_devptr out_u, f3d_devptr out_v, f3d_devptr out_w, size_t width, size_t height, size_t depth)
     __attribute__((weak));
 extern "C" int f3d_initial_flow(f3d_devptr u, f3d_devptr v, f3d_devptr w, f3d_devptr out_u, f3d_devptr out_v, f3d_devptr out_w,
                                 size_t width, size_t height, size_t depth, f3d_initial_info* info) __attribute__((weak));
@@ -731,6 +738,99 @@ void OpticalFlowE::ReleaseInitialFlow()
 {
   initial_.Release();
   initial_set_ = false;
+}
+
+// ---- the guess from the frames themselves: block matching on a grid of nodes -------------------------------------
+
+bool OpticalFlowE::BlockMatch(const BlockMatchParams& params, const int* centre, f3d_block_match_info* info,
+                              f3d_block_match_summary* summary)
+{
+  initial_.error.clear();
+  if (!initialized_) return initial_.Fail("the driver was not initialized");
+  if (!f3d_block_match) return initial_.Fail("the device library has no f3d_block_match (coarse block matching of two frames)");
+  if (!params.range && !f3d_value_range)
+    return initial_.Fail("the device library has no f3d_value_range (finite minimum and maximum of a frame)");
+  if (!resident_frame_[0] || !resident_frame_[1])
+    return initial_.Fail("no frames on the device (AllocateResidentFrames and UploadResidentFrames first)");
+  const f3d_size4 c = Container();
+  f3d_block_match_grid grid;
+  std::string why;
+  if (!LayoutBlockMatch(c.width, c.height, c.depth, params.step, params.window, params.radius[0], params.radius[1], params.radius[2],
+                        &grid, &why))
+    return initial_.Fail(why.c_str());
+  if (!initial_.Check(CheckDeviceError(f3d_set_container(&c)))) return false;
+  float lo = 0.f, hi = 0.f;
+  if (params.range) {
+    lo = params.range[0];
+    hi = params.range[1];
+  } else {
+    f3d_range_info found = {};
+    if (!initial_.Check(CheckDeviceError(f3d_value_range(resident_frame_[0], 0, c.width, c.height, c.depth, &lo, &hi, &found))))
+      return false;
+    if (found.finite == 0 || !(lo < hi)) return initial_.Fail("frame 0 has no two finite values: there is no range to lay the codes over");
+  }
+  const size_t nodes = static_cast<size_t>(grid.nx) * grid.ny * grid.nz;
+  std::vector<f3d_block_match_record> records(nodes);
+  std::vector<f3d_block_match_node> rows(nodes);
+  if (!initial_.Check(CheckDeviceError(f3d_block_match(resident_frame_[0], resident_frame_[1], lo, hi, params.bins, c.width, c.height,
+                                                       c.depth, &grid, centre, records.data(), info))))
+    return false;
+  if (!SolveBlockMatch(records.data(), &grid, centre, params.min_zncc, rows.data(), summary, &why)) return initial_.Fail(why.c_str());
+  match_grid_ = grid;
+  match_records_.swap(records);
+  match_nodes_.swap(rows);
+  return true;
+}
+
+bool OpticalFlowE::SetInitialFromNodes(f3d_validate_stats* validated, f3d_initial_info* info)
+{
+  initial_.error.clear();
+  if (!f3d_initial_flow) return initial_.Fail(initial_.no_entry);
+  if (!f3d_expand_nodes) return initial_.Fail("the device library has no f3d_expand_nodes (node vectors to a dense field)");
+  if (!f3d_validate_displacement) return initial_.Fail("the device library has no f3d_validate_displacement (displacement validation)");
+  if (match_nodes_.empty()) return initial_.Fail("no node table is held (BlockMatch first)");
+  const f3d_block_match_grid& g = match_grid_;
+  const size_t nx = g.nx, ny = g.ny, nz = g.nz, nodes = nx * ny * nz;
+  std::vector<float> node[3];
+  for (int i = 0; i < 3; ++i) node[i].resize(nodes);
+  for (size_t at = 0; at < nodes; ++at) {
+    node[0][at] = match_nodes_[at].u;
+    node[1][at] = match_nodes_[at].v;
+    node[2][at] = match_nodes_[at].w;
+  }
+  // the median test on the node grid: six small containers of the grid's own geometry
+  f3d_devptr small[6] = {0, 0, 0, 0, 0, 0};
+  f3d_size4 grid_box = {nx, ny, nz, 0};
+  bool ok = true;
+  for (int i = 0; i < 6 && ok; ++i) {
+    size_t pitch = 0;
+    ok = initial_.Check(CheckDeviceError(f3d_alloc_pitched(&small[i], &pitch, nx * sizeof(float), ny * nz)));
+    if (ok && grid_box.pitch && pitch != grid_box.pitch) ok = initial_.Fail("the node containers came back with different pitches");
+    grid_box.pitch = pitch;
+  }
+  for (int i = 0; i < 3 && ok; ++i)
+    ok = initial_.Check(CheckDeviceError(f3d_copy3d_h2d(small[i], grid_box.pitch, ny, 0, node[i].data(), nx, ny, nz)));
+  const f3d_devptr out[4] = {0, small[3], small[4], small[5]};
+  f3d_validate_stats stats = {};
+  ok = ok && initial_.Check(CheckDeviceError(f3d_set_container(&grid_box))) &&
+       initial_.Check(CheckDeviceError(f3d_validate_displacement(small[0], small[1], small[2], 0, 0.8f, 1, 0.1f, 2.0f, 9, F3D_VALIDATE_REPLACE,
+                                                                 out, F3D_VALIDATE_D, nx, ny, nz, &stats)));
+  for (int i = 0; i < 3 && ok; ++i)
+    ok = initial_.Check(CheckDeviceError(f3d_copy3d_d2h(node[i].data(), nx, ny, nz, small[3 + i], grid_box.pitch, ny, 0)));
+  for (f3d_devptr p : small)
+    if (p) f3d_free(p);
+  const f3d_size4 c = Container();
+  const bool restored = initial_.Check(CheckDeviceError(f3d_set_container(&c)));
+  if (!ok || !restored) return false;
+  if (validated) *validated = stats;
+  initial_set_ = false;
+  if (!initial_.Allocate(0)) return false;
+  initial_set_ = initial_.Check(CheckDeviceError(f3d_expand_nodes(node[0].data(), node[1].data(), node[2].data(), g.ox, g.oy, g.oz, g.step,
+                                                                  g.nx, g.ny, g.nz, initial_.ptr[0], initial_.ptr[1], initial_.ptr[2],
+                                                                  c.width, c.height, c.depth))) &&
+                 initial_.Check(CheckDeviceError(f3d_initial_flow(initial_.ptr[0], initial_.ptr[1], initial_.ptr[2], initial_.ptr[0],
+                                                                  initial_.ptr[1], initial_.ptr[2], c.width, c.height, c.depth, info)));
+  return initial_set_;
 }
 
 // ---- derived fields of a displacement: strain, principal strain, inverse, match quality -------------------------------------------

@@ -175,6 +175,24 @@ class OpticalFlowE : public OpticalFlowBase {
   bool DownloadInitialFlow(Data3D& u, Data3D& v, Data3D& w);
   void ReleaseInitialFlow();
   const std::string& InitialFlowError() const { return initial_.error; }
+  // The guess from the frames themselves (include/f3d_block_match.h).  BlockMatch searches the resident pair on the
+  // grid f3d_block_match_layout lays (f3d_block_match on the library stream, then f3d_block_match_solve); range null: the finite
+  // minimum and maximum of frame 0 (f3d_value_range).  The records, the rows and the grid stay with the driver.
+  // SetInitialFromNodes puts the node vectors of the last BlockMatch through f3d_validate_displacement as an nx x ny x nz volume
+  // (replace mode, step 1, eps 0.1, threshold 2, 9 neighbours: the defaults of --validate), expands the result into the containers of
+  // the initial flow (f3d_expand_nodes) and prepares them (f3d_initial_flow).  False with InitialFlowError() set when they cannot
+  // run, among other reasons when the device library lacks one of the entries.
+  struct BlockMatchParams {
+    int step = 16, window = 8, radius[3] = {8, 8, 8};
+    size_t bins = 256;
+    const float* range = nullptr;  // lo, hi
+    double min_zncc = 0.5;
+  };
+  bool BlockMatch(const BlockMatchParams& params, const int* centre, f3d_block_match_info* info, f3d_block_match_summary* summary);
+  const f3d_block_match_grid& BlockMatchGrid() const { return match_grid_; }
+  const std::vector<f3d_block_match_record>& BlockMatchRecords() const { return match_records_; }
+  const std::vector<f3d_block_match_node>& BlockMatchNodes() const { return match_nodes_; }
+  bool SetInitialFromNodes(f3d_validate_stats* validated, f3d_initial_info* info);
   // The three compute calls started from the initial flow that is held (use_initial) or, with use_initial false, exactly as their
   // namesakes above; false with InitialFlowError() set when use_initial is asked for and none is held.
   bool ComputeFlow(Data3D& frame_0, Data3D& frame_1, Data3D& flow_u, Data3D& flow_v, Data3D& flow_w, OperationParameters& params,
@@ -330,6 +348,9 @@ class OpticalFlowE : public OpticalFlowBase {
   FieldSet trajectory_;
   FieldSet initial_;
   bool initial_set_ = false;  // the three containers hold a prepared flow (they can exist without one after a failed upload)
+  f3d_block_match_grid match_grid_ = {};  // of the last BlockMatch; match_nodes_ empty: none yet
+  std::vector<f3d_block_match_record> match_records_;
+  std::vector<f3d_block_match_node> match_nodes_;
   FieldSet derived_[kDerivedCount];
   // the gradient of kWindowPrincipal and kWindowPolar (G00 .. G22), never downloaded
   DevicePtr window_gradient_[9] = {};

@@ -15,6 +15,7 @@
 #define F3D_HOST_H_
 
 #include "f3d.h"
+#include "f3d_block_match.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -557,6 +558,70 @@ int f3d_flow_histogram(f3d_flow flow, f3d_devptr frame /* 0: the resident frame 
 int f3d_flow_validate_compute(f3d_flow flow, int source, unsigned step, float eps, float threshold, unsigned min_neighbours,
                               unsigned mode, unsigned fill_passes, float min_zncc, float* const out[4], f3d_validate_stats* stats);
 int f3d_flow_validate_end(f3d_flow flow);
+
+/* The solve from the records of f3d_block_match (include/f3d_block_match.h) to one row per node.  Host code, no device needed;
+ * binary64, every operation rounded on its own, in exactly this order.  With n = (2 window + 1)^3 and da = n saa - sa^2 of a record,
+ * the ZNCC of a shift with sums sb, sbb, sab is
+ *   z = (double)(n sab - sa sb) / sqrt((double)da * (double)(n sbb - sb^2))
+ * zncc is z at the best shift, z0.  Per axis, when both face neighbours of the best shift are valid, with z- and z+ theirs:
+ *   curvature = (z- - 2.0 * z0) + z+;  when curvature < 0.0:  offset = (z- - z+) / (2.0 * curvature), clamped to [-0.5, 0.5]
+ * and the offset is 0.0 otherwise (the three-point parabola through the peak).  status, the first that applies:
+ *   F3D_BLOCK_NODE_FLAT  the record says the window of frame 0 is constant
+ *   F3D_BLOCK_NODE_NONE  the record has no candidate
+ *   F3D_BLOCK_NODE_LOW   zncc < min_zncc
+ *   F3D_BLOCK_NODE_EDGE  along an axis with a search radius above 0 the best shift lies radius from the centre: on the face of the
+ *                        search range, the motion is probably beyond reach
+ *   F3D_BLOCK_NODE_OK
+ * u, v, w = (float)((double)shift + offset) when the status is OK or EDGE, NaN otherwise; shift, zncc (NaN) and offset (0) of a FLAT
+ * or NONE node are empty.  position is the node's voxel; evaluated, outside, flat are the record's counts.  centre is the array given
+ * to f3d_block_match (nullable: all zero).  Returns non-zero (f3d_host_last_error() set, nothing written) for a null records, grid
+ * or nodes, a grid f3d_block_match refuses, or a NaN min_zncc. */
+#define F3D_BLOCK_NODE_OK 0
+#define F3D_BLOCK_NODE_FLAT 1
+#define F3D_BLOCK_NODE_NONE 2
+#define F3D_BLOCK_NODE_LOW 3
+#define F3D_BLOCK_NODE_EDGE 4
+typedef struct f3d_block_match_node {
+  int position[3];
+  int shift[3];
+  int status;
+  int evaluated, outside, flat;
+  double zncc;
+  double offset[3];
+  float u, v, w;
+  int reserved; /* 0 */
+} f3d_block_match_node;
+typedef struct f3d_block_match_summary {
+  unsigned long long nodes, ok, flat, none, low, edge; /* nodes is the sum of the others */
+} f3d_block_match_summary;
+/* The grid of nodes block matching lays over a width x height x depth volume: nodes `step` apart whose (2 window + 1)^3 windows lie
+ * inside the volume, as many as fit, centred: per axis of n voxels, with room = n - 1 - 2 window, the first node lies at
+ * window + (room % step) / 2 and there are (n - 1 - window - first) / step + 1 of them (integer arithmetic).  Host code.  Returns
+ * non-zero (f3d_host_last_error() set, nothing written) for a null grid, a step below 1, a window outside 1 .. 8, a negative radius,
+ * window + radius above 16, a window that leaves the volume, or more than 2^22 nodes. */
+int f3d_block_match_layout(size_t width, size_t height, size_t depth, int step, int window, int rx, int ry, int rz,
+                           f3d_block_match_grid* grid);
+int f3d_block_match_solve(const f3d_block_match_record* records, const f3d_block_match_grid* grid, const int* centre, double min_zncc,
+                          f3d_block_match_node* nodes /* nx ny nz entries */, f3d_block_match_summary* summary /* nullable */);
+
+/* Block matching on the pair the driver holds (f3d_flow_upload), and the guess of the solve from it.
+ *   f3d_flow_block_match      f3d_block_match_layout over the driver's volume, f3d_block_match of the resident frames 0 and 1 on the
+ *                             library stream (range null: the finite minimum and maximum of frame 0, f3d_value_range), then
+ *                             f3d_block_match_solve.  centre (nullable) has one int32 triple per node of that layout.  grid, info,
+ *                             summary are nullable.  The records and the rows stay with the driver.
+ *   f3d_flow_block_match_rows copies them out: records and / or nodes (each nullable) with room for `capacity` nodes; fails when
+ *                             there are more, or none yet
+ *   f3d_flow_initial_from_nodes  the node vectors u, v, w of the rows as an nx x ny x nz volume through f3d_validate_displacement
+ *                             (F3D_VALIDATE_REPLACE, no weight, step 1, eps 0.1, threshold 2, 9 neighbours; validated nullable),
+ *                             the result through f3d_expand_nodes into the driver's initial-flow containers, those through
+ *                             f3d_initial_flow (info nullable).  Afterwards f3d_flow_compute_resident_from_initial starts from it.
+ * A device library without f3d_block_match, f3d_expand_nodes, f3d_value_range, f3d_validate_displacement or f3d_initial_flow still
+ * loads; then the call that needs it fails with a message naming it.  Failures are described by f3d_host_last_error(). */
+int f3d_flow_block_match(f3d_flow flow, int step, int window, int rx, int ry, int rz, size_t bins, const float* range /* lo, hi */,
+                         const int* centre, double min_zncc, f3d_block_match_grid* grid, f3d_block_match_info* info,
+                         f3d_block_match_summary* summary);
+int f3d_flow_block_match_rows(f3d_flow flow, size_t capacity, f3d_block_match_record* records, f3d_block_match_node* nodes);
+int f3d_flow_initial_from_nodes(f3d_flow flow, f3d_validate_stats* validated, f3d_initial_info* info);
 /* message of this thread's last call that failed in the host library itself; f3d_last_error() when there is none */
 const char* f3d_host_last_error(void);
 int f3d_flow_destroy(f3d_flow flow);
