@@ -305,6 +305,37 @@ BLOCK_MATCH_NODE = np.dtype([("position", np.int32, 3), ("shift", np.int32, 3), 
 BLOCK_NODE_STATUS = ("ok", "flat", "none", "low", "edge")
 
 
+class SubsetGrid(C.Structure):  # f3d_subset_match_grid (include/f3d_subset_match.h)
+    _fields_ = [("ox", C.c_int), ("oy", C.c_int), ("oz", C.c_int), ("step", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("window", C.c_int)]
+
+
+class SubsetInfo(C.Structure):  # f3d_subset_match_info
+    _fields_ = [("nodes", C.c_ulonglong), ("status", C.c_ulonglong * 9), ("iterations", C.c_ulonglong), ("nan", C.c_ulonglong)]
+
+    def as_dict(self):
+        return dict(nodes=self.nodes, status=list(self.status), iterations=self.iterations, nan=self.nan)
+
+
+class SubsetSummary(C.Structure):  # f3d_subset_match_summary (include/f3d_host.h)
+    _fields_ = [("nodes", C.c_ulonglong), ("status", C.c_ulonglong * 10), ("compared", C.c_ulonglong), ("median_zncc", C.c_double),
+                ("rms", C.c_double), ("median", C.c_double), ("p95", C.c_double)]
+
+    def as_dict(self):
+        return dict(nodes=self.nodes, status=list(self.status), compared=self.compared, median_zncc=self.median_zncc, rms=self.rms,
+                    median=self.median, p95=self.p95)
+
+
+# f3d_subset_match_record and f3d_subset_match_node as numpy records
+SUBSET_RECORD = np.dtype([("p", np.float64, 12), ("zncc", np.float64), ("step", np.float64), ("df", np.float64), ("dg", np.float64),
+                          ("status", np.int32), ("iterations", np.int32), ("nan", np.int32), ("reserved", np.int32)])
+SUBSET_NODE = np.dtype([("position", np.int32, 3), ("status", np.int32), ("iterations", np.int32), ("reserved", np.int32),
+                        ("zncc", np.float64), ("u", np.float32), ("v", np.float32), ("w", np.float32), ("grad", np.float32, 9),
+                        ("diff", np.float32, 3), ("reserved2", np.int32)])
+SUBSET_STATUS = ("ok", "nan", "flat", "flat_target", "singular", "outside", "lost", "not_converged", "no_start", "low")
+SUBSET_MODELS = {"translation": 0, "affine": 1}
+
+
 class FlowParams(C.Structure):  # f3d_flow_params
     _fields_ = [
         ("warp_levels_count", C.c_size_t), ("warp_scale_factor", C.c_float),
@@ -483,6 +514,11 @@ def host():
         "f3d_flow_initial_from_nodes": [C.c_void_p, C.POINTER(ValidateStats), C.POINTER(InitialInfo)],
         "f3d_block_match_solve": [C.c_void_p, C.POINTER(BlockMatchGrid), C.c_void_p, C.c_double, C.c_void_p,
                                   C.POINTER(BlockMatchSummary)],
+        "f3d_subset_match_layout": [_sz, _sz, _sz, C.c_int, C.c_int, C.POINTER(SubsetGrid)],
+        "f3d_flow_subset_match": [C.c_void_p] + [C.c_int] * 5 + [C.c_double] * 3 + [C.POINTER(SubsetGrid), C.POINTER(SubsetInfo),
+                                                                                   C.POINTER(SubsetSummary)],
+        "f3d_flow_subset_match_rows": [C.c_void_p, _sz, C.c_void_p, C.c_void_p],
+        "f3d_subset_match_table": [C.c_void_p, C.POINTER(SubsetGrid), C.c_double, C.POINTER(_fp), C.c_void_p, C.POINTER(SubsetSummary)],
         "f3d_flow_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.POINTER(_fp), C.POINTER(StrainStats)],
         "f3d_flow_strain_end": [C.c_void_p],
         "f3d_flow_window_strain_compute": [C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(_fp),
@@ -1034,6 +1070,127 @@ def block_match_initial(a, b, validate=True, **kw):
         u, v, w = d["u"], d["v"], d["w"]
     shape = np.asarray(a).shape
     return expand_nodes(u, v, w, nodes.origin, nodes.step, shape[::-1]), nodes
+
+
+def _subset_match_entry():
+    return _entry("f3d_subset_match", [_dp, _dp, _sz, _sz, _sz, C.POINTER(SubsetGrid), C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                       C.c_void_p, C.POINTER(SubsetInfo)], "correlate subsets of two frames")
+
+
+def subset_grid(dims, step=16, window=8, origin=None, counts=None):
+    """The node grid of subset_match over a (w, h, d) volume as a SubsetGrid: nodes `step` apart whose (2 window + 1)^3 windows and one
+    voxel round them (the central differences) lie inside the volume, as many as fit and centred (f3d_subset_match_layout lays the
+    same), unless origin = (ox, oy, oz) and / or counts = (nx, ny, nz) say otherwise.  ValueError when a window leaves the volume."""
+    step, window = int(step), int(window)
+    if step < 1 or not 1 <= window <= 8:
+        raise ValueError("step must be at least 1 and window 1 .. 8")
+    reach = window + 1
+    first, count = [], []
+    for axis, n in enumerate(dims):
+        room = int(n) - 1 - 2 * reach
+        if room < 0:
+            raise ValueError(f"a window of radius {window} and a voxel round it leave the volume along {'xyz'[axis]} ({n} voxels)")
+        o = reach + (room % step) // 2 if origin is None else int(origin[axis])
+        c = (int(n) - 1 - reach - o) // step + 1 if counts is None else int(counts[axis])
+        if o < reach or c < 1 or o + (c - 1) * step + reach > int(n) - 1:
+            raise ValueError(f"a window of radius {window} leaves the volume along {'xyz'[axis]}: origin {o}, {c} nodes, step {step}")
+        first.append(o)
+        count.append(c)
+    return SubsetGrid(*first, step, *count, window)
+
+
+class SubsetNodes:
+    """The node table of subset_match: `rows`, one SUBSET_NODE record per node (x fastest); `records`, the SUBSET_RECORD records of
+    f3d_subset_match they were made from; `info` and `summary`, the dicts of f3d_subset_match_info and f3d_subset_match_summary; `grid`
+    (SubsetGrid).  u, v, w, zncc, status, iterations are [nz, ny, nx] arrays; `grad` is the nine gradients (ux, uy, uz, vx, ..., wz) as
+    [nz, ny, nx] float32 arrays, the list principal_from_gradient and polar_from_gradient take; diff the three of compare - subset."""
+
+    def __init__(self, rows, records, info, summary, grid):
+        self.rows, self.records, self.info, self.summary, self.grid = rows, records, info, summary, grid
+        self.origin, self.step, self.counts = (grid.ox, grid.oy, grid.oz), grid.step, (grid.nx, grid.ny, grid.nz)
+
+    def __len__(self):
+        return len(self.rows)
+
+    def _component(self, name):
+        return np.ascontiguousarray(self.rows[name].reshape(self.counts[::-1]))
+
+    u = property(lambda self: self._component("u"))
+    v = property(lambda self: self._component("v"))
+    w = property(lambda self: self._component("w"))
+    zncc = property(lambda self: self._component("zncc"))
+    status = property(lambda self: self._component("status"))
+    iterations = property(lambda self: self._component("iterations"))
+    grad = property(lambda self: [np.ascontiguousarray(self.rows["grad"][:, k].reshape(self.counts[::-1])) for k in range(9)])
+    diff = property(lambda self: [np.ascontiguousarray(self.rows["diff"][:, k].reshape(self.counts[::-1])) for k in range(3)])
+
+    def as_table(self):
+        return [dict(x=int(r["position"][0]), y=int(r["position"][1]), z=int(r["position"][2]), status=SUBSET_STATUS[int(r["status"])],
+                     iterations=int(r["iterations"]), zncc=float(r["zncc"]), u=float(r["u"]), v=float(r["v"]), w=float(r["w"]),
+                     grad=tuple(float(g) for g in r["grad"]), diff=tuple(float(d) for d in r["diff"])) for r in self.rows]
+
+
+def subset_table(records, grid, min_zncc=0.8, compare=None):
+    """f3d_subset_match_table (include/f3d_host.h) of SUBSET_RECORD records: -> (rows as SUBSET_NODE records, summary dict).  compare:
+    three arrays of one float32 per node, a displacement to hold the subsets against.  Host code, no device needed."""
+    nodes = grid.nx * grid.ny * grid.nz
+    records = np.ascontiguousarray(records, dtype=SUBSET_RECORD)
+    if records.shape != (nodes,):
+        raise ValueError(f"records must be {nodes} SUBSET_RECORD records")
+    held = None
+    if compare is not None:
+        held = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in compare]
+        if len(held) != 3 or any(c.size != nodes for c in held):
+            raise ValueError(f"compare must be three arrays of {nodes} node values")
+    pointers = None if held is None else (_fp * 3)(*[c.ctypes.data_as(_fp) for c in held])
+    rows, summary = np.zeros(nodes, SUBSET_NODE), SubsetSummary()
+    _host_check(host().f3d_subset_match_table(records.ctypes.data, C.byref(grid), float(min_zncc), pointers, rows.ctypes.data,
+                                              C.byref(summary)), "f3d_subset_match_table")
+    return rows, summary.as_dict()
+
+
+def _subset_start(start, nodes):
+    """start of subset_match as [nodes, 12] binary64 or None: 12 values per node, or three node arrays (u, v, w: gradients zero)"""
+    if start is None:
+        return None
+    # three node arrays are three entries of `nodes` values each; a [3, 12] list for three nodes has 12 values per entry
+    if isinstance(start, (tuple, list)) and len(start) == 3 and all(np.size(c) == nodes for c in start):
+        full = np.zeros((nodes, 12), np.float64)
+        for k, c in enumerate(start):
+            c = np.asarray(c, dtype=np.float64).reshape(-1)
+            if c.size != nodes:
+                raise ValueError(f"start must hold one value per node, {nodes} of them, in each of u, v, w")
+            full[:, 4 * k] = c
+        return full
+    start = np.ascontiguousarray(start, dtype=np.float64)
+    if start.size != 12 * nodes:
+        raise ValueError(f"start must hold 12 parameters per node, {nodes} nodes, or be three node arrays (u, v, w)")
+    return start.reshape(nodes, 12)
+
+
+def subset_match(a, b, grid=None, start=None, model="affine", max_iterations=20, tolerance=1e-3, reach=None, min_zncc=0.8, compare=None):
+    """Subset correlation (local DVC) on the device (include/f3d_subset_match.h, f3d_subset_match, then f3d_subset_match_table): at
+    every node of `grid` (a SubsetGrid, subset_grid(dims) when None) the displacement and, for model "affine", the displacement
+    gradient that carry the (2 window + 1)^3 subset of `a` onto `b`, by inverse-compositional Gauss-Newton on the zero-normalised sum
+    of squared differences with cubic interpolation of b, in binary64.  start: [nodes, 12] parameters (u, ux, uy, uz, v, ...), or three
+    node arrays (u, v, w), or None for zero; a node with a NaN start is left out.  A node stops when its step is below `tolerance`
+    (ok), after max_iterations, or when it has moved more than `reach` (the window radius when None) from its start.  a, b: numpy
+    [z, y, x] float32 of one shape.  Returns a SubsetNodes: nodes that did not end ok with zncc >= min_zncc have NaN vectors; compare =
+    (u, v, w) node arrays gives the difference to them and its rms, median and 95 % quantile in the summary."""
+    fn = _subset_match_entry()
+    if model not in SUBSET_MODELS:
+        raise ValueError(f"model must be one of {sorted(SUBSET_MODELS)}")
+    with _on_device([a, b], "a and b must be two [z, y, x] volumes of one shape") as (box, p, dims):
+        if grid is None:
+            grid = subset_grid(dims)
+        nodes = grid.nx * grid.ny * grid.nz
+        start = _subset_start(start, nodes)
+        box.set_current()
+        records, info = np.zeros(nodes, SUBSET_RECORD), SubsetInfo()
+        check(fn(p[0], p[1], *dims, C.byref(grid), SUBSET_MODELS[model], None if start is None else start.ctypes.data, int(max_iterations),
+                 float(tolerance), float(grid.window if reach is None else reach), records.ctypes.data, C.byref(info)), "f3d_subset_match")
+    rows, summary = subset_table(records, grid, min_zncc, compare)
+    return SubsetNodes(rows, records, info.as_dict(), summary, grid)
 
 
 # the eight outputs of f3d_flow_strain in ABI order, and the F3D_STRAIN_* group of each
@@ -2923,6 +3080,24 @@ class OpticalFlow:
         validated, info = ValidateStats(), InitialInfo()
         _host_check(host().f3d_flow_initial_from_nodes(self._h, C.byref(validated), C.byref(info)), "f3d_flow_initial_from_nodes")
         return validated.as_dict(), info
+
+    def subset_match(self, start="flow", step=16, window=8, model="affine", max_iterations=20, tolerance=1e-3, reach=None, min_zncc=0.8):
+        """subset_match() of the module on the pair the driver holds (upload first), on the library stream, on the grid
+        subset_grid lays over the volume.  start: "zero"; "block-match", the table of the last block_match() (each node takes the
+        vector of the nearest block-match node, NaN unless that one is ok or edge); "flow", the held flow at the node voxels
+        (compute_resident first).  Whenever a flow is held it is also the comparison: the summary has the rms, median and 95 %
+        quantile of |flow - subset| over the accepted nodes.  Returns a SubsetNodes; the table also stays with the driver."""
+        sources = {"zero": 0, "block-match": 1, "flow": 2}
+        if start not in sources or model not in SUBSET_MODELS:
+            raise ValueError(f"start must be one of {sorted(sources)} and model one of {sorted(SUBSET_MODELS)}")
+        grid, info, summary = SubsetGrid(), SubsetInfo(), SubsetSummary()
+        _host_check(host().f3d_flow_subset_match(self._h, int(step), int(window), SUBSET_MODELS[model], sources[start], int(max_iterations),
+                                                 float(tolerance), 0.0 if reach is None else float(reach), float(min_zncc), C.byref(grid),
+                                                 C.byref(info), C.byref(summary)), "f3d_flow_subset_match")
+        nodes = grid.nx * grid.ny * grid.nz
+        records, rows = np.zeros(nodes, SUBSET_RECORD), np.zeros(nodes, SUBSET_NODE)
+        _host_check(host().f3d_flow_subset_match_rows(self._h, nodes, records.ctypes.data, rows.ctypes.data), "f3d_flow_subset_match_rows")
+        return SubsetNodes(rows, records, info.as_dict(), summary.as_dict(), grid)
 
     def set_level_stats(self, enable=True):
         """record, per pyramid level of every later compute, the residual before the solve and the flow statistics after it"""

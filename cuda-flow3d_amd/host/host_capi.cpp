@@ -7,6 +7,7 @@
 
 #include "f3d_host.h"
 #include "block_match.h"
+#include "subset_match.h"
 #include "contact_kinematics.h"
 #include "label_field.h"
 #include "label_shape.h"
@@ -637,6 +638,54 @@ int f3d_block_match_layout(size_t width, size_t height, size_t depth, int step, 
   if (!grid) return HostFail("f3d_block_match_layout: null argument");
   std::string why;
   return LayoutBlockMatch(width, height, depth, step, window, rx, ry, rz, grid, &why) ? 0 : HostFail(why.c_str());
+}
+
+int f3d_subset_match_table(const f3d_subset_match_record* records, const f3d_subset_match_grid* grid, double min_zncc,
+                           const float* const* compare, f3d_subset_match_node* nodes, f3d_subset_match_summary* summary)
+{
+  g_host_error.clear();
+  if (!records || !grid || !nodes) return HostFail("f3d_subset_match_table: null argument");
+  std::string why;
+  return TableSubsetMatch(records, grid, min_zncc, compare, nodes, summary, &why) ? 0 : HostFail(why.c_str());
+}
+
+int f3d_subset_match_layout(size_t width, size_t height, size_t depth, int step, int window, f3d_subset_match_grid* grid)
+{
+  g_host_error.clear();
+  if (!grid) return HostFail("f3d_subset_match_layout: null argument");
+  std::string why;
+  return LayoutSubsetMatch(width, height, depth, step, window, grid, &why) ? 0 : HostFail(why.c_str());
+}
+
+int f3d_flow_subset_match(f3d_flow flow, int step, int window, int model, int start, int max_iterations, double tolerance, double reach,
+                          double min_zncc, f3d_subset_match_grid* grid, f3d_subset_match_info* info, f3d_subset_match_summary* summary)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_subset_match: null driver");
+  OpticalFlowE::SubsetMatchParams p;
+  p.step = step;
+  p.window = window;
+  p.model = model;
+  p.start = start;
+  p.max_iterations = max_iterations;
+  p.tolerance = tolerance;
+  p.reach = reach;
+  p.min_zncc = min_zncc;
+  if (!flow->driver.SubsetMatch(p, info, summary)) return HostFail(flow->driver.InitialFlowError().c_str());
+  if (grid) *grid = flow->driver.SubsetMatchGrid();
+  return 0;
+}
+
+int f3d_flow_subset_match_rows(f3d_flow flow, size_t capacity, f3d_subset_match_record* records, f3d_subset_match_node* nodes)
+{
+  g_host_error.clear();
+  if (!flow) return HostFail("f3d_flow_subset_match_rows: null driver");
+  const std::vector<f3d_subset_match_node>& rows = flow->driver.SubsetMatchNodes();
+  if (rows.empty()) return HostFail("f3d_flow_subset_match_rows: no node table is held (f3d_flow_subset_match first)");
+  if (rows.size() > capacity) return HostFail("f3d_flow_subset_match_rows: the table has more nodes than there is room for");
+  if (records) std::memcpy(static_cast<void*>(records), flow->driver.SubsetMatchRecords().data(), rows.size() * sizeof(f3d_subset_match_record));
+  if (nodes) std::memcpy(static_cast<void*>(nodes), rows.data(), rows.size() * sizeof(f3d_subset_match_node));
+  return 0;
 }
 
 int f3d_flow_block_match(f3d_flow flow, int step, int window, int rx, int ry, int rz, size_t bins, const float* range, const int* centre,

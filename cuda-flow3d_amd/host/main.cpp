@@ -41,6 +41,13 @@
 // shift, the offset, the ZNCC, the status and the counts of candidates), one line (nodes ok / low / flat / edge / none, the median and
 // the largest |shift|), then the node vectors go through the median test on the node grid, are expanded over the volume and start
 // the pair's solve; the initial flow: line follows.  --block-match-only (one pair) stops after the table.
+// --subset-match (resident driver, pairs in order) measures every pair a second time after its solve, independently of the flow (DESIGN.md
+// 30): on a grid of nodes --subset-step apart (default 16), the displacement and, for --subset-model affine (the default; or
+// translation), its gradient that carry the subset of radius --subset-window (default 8) of the first frame onto the second, by at
+// most --subset-iterations (default 20) Gauss-Newton steps down to --subset-tolerance (default 1e-3), started from --subset-start
+// flow (the default: the solved flow at the nodes), block-match (the table of --block-match) or zero.  <tag>_subset.csv has the node
+// table; one line gives the nodes per status, the median ZNCC and the rms, median and p95 of |flow - subset| over the nodes that
+// ended ok with a ZNCC of at least --subset-min-zncc (default 0.8).
 // --warm-start starts pair k >= 1 from the flow of pair k-1 as it stands (steady motion); the pairs stay the consecutive ones.
 // --total makes pair k frame 0 -> frame k+1, solved directly and started from the result of pair k-1: the other route to the
 // displacement from frame 0, which --cumulative composes from the consecutive pairs with one interpolation per step.  The flow of a
@@ -166,6 +173,8 @@ static void Usage()
               "              [--concurrent N] [--cumulative] [--initial-flow U V W] [--warm-start | --total]\n"
               "              [--block-match [--block-match-step S] [--block-match-window W] [--block-match-search R | RX:RY:RZ]\n"
               "               [--block-match-min-zncc T] [--block-match-only]]\n"
+              "              [--subset-match [--subset-step S] [--subset-window W] [--subset-model translation|affine]\n"
+              "               [--subset-iterations N] [--subset-tolerance T] [--subset-min-zncc Z] [--subset-start flow|block-match|zero]]\n"
               "              [--strain vol,e,eq] [--principal val,shear,dir1,dir3]\n"
               "              [--rotation angle,vector,stretch] [--inverse] [--match warped,zncc,rmsd [--match-radius R]]\n"
               "              [--window-strain vol,e,eq,grad [--window-radius R] [--window-min-count K]]\n"
@@ -198,6 +207,9 @@ int main(int argc, char** argv)
   std::vector<std::string> initial_files;
   bool block_match = false, block_match_only = false, block_match_sub_given = false;  // --block-match and its options
   OpticalFlowE::BlockMatchParams block_match_params;
+  bool subset_match = false, subset_sub_given = false;  // --subset-match and its options
+  OpticalFlowE::SubsetMatchParams subset_params;
+  subset_params.start = OpticalFlowE::kSubsetFlow;
   size_t concurrent = 1;
   unsigned strain_fields = 0;     // --strain: F3D_STRAIN_* groups
   unsigned wstrain_fields = 0;    // --window-strain: F3D_STRAIN_* groups and F3D_WSTRAIN_G
@@ -337,6 +349,42 @@ int main(int argc, char** argv)
       block_match_params.min_zncc = std::strtod(argv[++i], &rest);
       if (rest == argv[i] || *rest || std::isnan(block_match_params.min_zncc)) { Usage(); return 64; }
       block_match_sub_given = true;
+    }
+    else if (a == "--subset-match") subset_match = true;
+    else if (a == "--subset-step" || a == "--subset-window" || a == "--subset-iterations") {
+      need(1);
+      char* rest = nullptr;
+      const long n = std::strtol(argv[++i], &rest, 10);
+      const long most = a == "--subset-step" ? 1 << 20 : (a == "--subset-window" ? F3D_SUBSET_MATCH_MAX_WINDOW : F3D_SUBSET_MATCH_MAX_ITERATIONS);
+      if (rest == argv[i] || *rest || n < 1 || n > most) { Usage(); return 64; }
+      (a == "--subset-step" ? subset_params.step : (a == "--subset-window" ? subset_params.window : subset_params.max_iterations)) =
+          static_cast<int>(n);
+      subset_sub_given = true;
+    }
+    else if (a == "--subset-tolerance" || a == "--subset-min-zncc") {
+      need(1);
+      char* rest = nullptr;
+      const double v = std::strtod(argv[++i], &rest);
+      if (rest == argv[i] || *rest || std::isnan(v) || (a == "--subset-tolerance" && !(v > 0.0))) { Usage(); return 64; }
+      (a == "--subset-tolerance" ? subset_params.tolerance : subset_params.min_zncc) = v;
+      subset_sub_given = true;
+    }
+    else if (a == "--subset-model") {
+      need(1);
+      const std::string v = argv[++i];
+      if (v == "translation") subset_params.model = F3D_SUBSET_TRANSLATION;
+      else if (v == "affine") subset_params.model = F3D_SUBSET_AFFINE;
+      else { Usage(); return 64; }
+      subset_sub_given = true;
+    }
+    else if (a == "--subset-start") {
+      need(1);
+      const std::string v = argv[++i];
+      if (v == "flow") subset_params.start = OpticalFlowE::kSubsetFlow;
+      else if (v == "block-match") subset_params.start = OpticalFlowE::kSubsetNodes;
+      else if (v == "zero") subset_params.start = OpticalFlowE::kSubsetZero;
+      else { Usage(); return 64; }
+      subset_sub_given = true;
     }
     else if (a == "--inverse") inverse = true;
     else if (a == "--strain") {
@@ -750,6 +798,30 @@ int main(int argc, char** argv)
     if (!why && f3d_block_match_layout(width, height, depth, block_match_params.step, block_match_params.window, block_match_params.radius[0],
                                        block_match_params.radius[1], block_match_params.radius[2], &laid)) {
       layout_error = std::string("--block-match: ") + f3d_host_last_error();
+      why = layout_error.c_str();
+    }
+    if (why) {
+      std::printf("%s\n", why);
+      Usage();
+      return 64;
+    }
+  }
+  // --subset-match: all refusals before any device is touched
+  if (subset_sub_given && !subset_match) {
+    std::printf("--subset-step, -window, -model, -iterations, -tolerance, -min-zncc and -start need --subset-match\n");
+    Usage();
+    return 64;
+  }
+  if (subset_match) {
+    const char* why = nullptr;
+    if (use_partial_gpu || concurrent > 1) why = "--subset-match needs the resident driver: it cannot be combined with --partial or --concurrent N > 1";
+    else if (subset_params.start == OpticalFlowE::kSubsetNodes && (!block_match || block_match_only))
+      why = "--subset-start block-match needs --block-match (without --block-match-only)";
+    else if (block_match_only) why = "--subset-match runs after the pair's solve, which --block-match-only leaves out";
+    std::string layout_error;
+    f3d_subset_match_grid laid;
+    if (!why && f3d_subset_match_layout(width, height, depth, subset_params.step, subset_params.window, &laid)) {
+      layout_error = std::string("--subset-match: ") + f3d_host_last_error();
       why = layout_error.c_str();
     }
     if (why) {
@@ -1929,6 +2001,36 @@ int main(int argc, char** argv)
     return 0;
   };
 
+  // --subset-match: the node table of the resident pair, measured beside the flow the driver holds, into <tag>_subset.csv, and one
+  // line about it
+  auto subset_of_pair = [&](size_t k) {
+    f3d_subset_match_summary sum = {};
+    if (!optical_flow_e.SubsetMatch(subset_params, nullptr, &sum)) {
+      std::printf("Error: %s\n", optical_flow_e.InitialFlowError().c_str());
+      return 3;
+    }
+    const std::string tag = pairs > 1 ? prefix + "_" + std::to_string(k) : prefix;
+    std::FILE* csv = std::fopen((tag + "_subset.csv").c_str(), "w");
+    if (!csv) {
+      std::printf("Error: cannot write %s_subset.csv\n", tag.c_str());
+      return 2;
+    }
+    static const char* const kStatus[] = {"ok", "nan", "flat", "flat_target", "singular", "outside", "lost", "not_converged", "no_start", "low"};
+    std::fprintf(csv, "x,y,z,status,iterations,zncc,u,v,w,ux,uy,uz,vx,vy,vz,wx,wy,wz,diff_u,diff_v,diff_w\n");
+    for (const f3d_subset_match_node& r : optical_flow_e.SubsetMatchNodes()) {
+      std::fprintf(csv, "%d,%d,%d,%s,%d,%.17g,%.9g,%.9g,%.9g", r.position[0], r.position[1], r.position[2], kStatus[r.status], r.iterations, r.zncc,
+                   r.u, r.v, r.w);
+      for (float g : r.grad) std::fprintf(csv, ",%.9g", g);
+      std::fprintf(csv, ",%.9g,%.9g,%.9g\n", r.diff[0], r.diff[1], r.diff[2]);
+    }
+    std::fclose(csv);
+    std::printf("subset match: %llu nodes", sum.nodes);
+    for (int s = 0; s < F3D_SUBSET_NODE_STATUS_COUNT; ++s) std::printf(", %llu %s", sum.status[s], kStatus[s]);
+    std::printf(", median zncc %.4f, |flow - subset| over %llu nodes: rms %.4f, median %.4f, p95 %.4f\n", sum.median_zncc, sum.compared, sum.rms,
+                sum.median, sum.p95);
+    return 0;
+  };
+
   if (pairs == 1) {
     if (!synthetic && !load(frame_1, files[1])) return 2;
     optical_flow_e.UploadResidentFrames(frame_0, frame_1);
@@ -1951,6 +2053,8 @@ int main(int argc, char** argv)
     if (const int status = stats_of_frame_0()) return status;
     optical_flow_e.DownloadFlow(flow_u, flow_v, flow_w);
     write_pair(0, flow_u, flow_v, flow_w);
+    if (subset_match)
+      if (const int status = subset_of_pair(0)) return status;
     if (cumulative) {
       if (!optical_flow_e.ResetTrajectory() || !optical_flow_e.ComposeTrajectory() ||
           !optical_flow_e.DownloadTrajectory(disp[0], disp[1], disp[2], nullptr))
@@ -2096,6 +2200,9 @@ int main(int argc, char** argv)
         if (const int status = stats_of_frame_0()) return status;
       if (print_stats) report();
       std::printf("pair %zu of %zu: %.3f s on the device\n", k + 1, pairs, optical_flow_e.LastDeviceSeconds());
+      // the driver still holds the flow and the pair's two frames stay in their slots: the upload beside this solve went elsewhere
+      if (subset_match)
+        if (const int status = subset_of_pair(k)) return status;
       if (!optical_flow_e.TakeResult(taken)) return 3;
       for (int i = 0; i < 3; ++i)
         CheckDeviceError(f3d_copy_planes_d2h_on(down, host_flow[k & 1][i].DataPtr(), width, height, width, height, depth, taken[i],

@@ -17,6 +17,7 @@
 #include "label_field.h"
 #include "label_shape.h"
 #include "motion_fit.h"
+#include "subset_match.h"
 
 // Declared weak: the host library keeps loading against a device library that lacks the entry (the address is then null and the
 // trajectory calls fail with a message instead of the whole library failing to load).
@@ -26,6 +27,9 @@ extern "C" int f3d_compose_flow(f3d_devptr acc_u, f3d_devptr acc_v, f3d_devptr a
 extern "C" int f3d_block_match(f3d_devptr a, f3d_devptr b, float lo, float hi, size_t bins, size_t width, size_t height, size_t depth,
                                const f3d_block_match_grid* grid, const int* centre, f3d_block_match_record* records,
                                f3d_block_match_info* info) __attribute__((weak));
+extern "C" int f3d_subset_match(f3d_devptr a, f3d_devptr b, size_t width, size_t height, size_t depth, const f3d_subset_match_grid* grid,
+                                int model, const double* start, int max_iterations, double tolerance, double reach,
+                                f3d_subset_match_record* records, f3d_subset_match_info* info) __attribute__((weak));
 extern "C" int f3d_expand_nodes(const float* u, const float* v, const float* w, int ox, int oy, int oz, int step, int nx, int ny, int nz,
                                 f3d_devptr out_u, f3d_devptr out_v, f3d_devptr out_w, size_t width, size_t height, size_t depth)
     __attribute__((weak));
@@ -831,6 +835,85 @@ bool OpticalFlowE::SetInitialFromNodes(f3d_validate_stats* validated, f3d_initia
                  initial_.Check(CheckDeviceError(f3d_initial_flow(initial_.ptr[0], initial_.ptr[1], initial_.ptr[2], initial_.ptr[0],
                                                                   initial_.ptr[1], initial_.ptr[2], c.width, c.height, c.depth, info)));
   return initial_set_;
+}
+
+// ---- subset correlation on the resident pair ------------------------------------------------------------------------
+
+bool OpticalFlowE::SubsetMatch(const SubsetMatchParams& params, f3d_subset_match_info* info, f3d_subset_match_summary* summary)
+{
+  initial_.error.clear();
+  if (!initialized_) return initial_.Fail("the driver was not initialized");
+  if (!f3d_subset_match) return initial_.Fail("the device library has no f3d_subset_match (subset correlation of two frames)");
+  if (!resident_frame_[0] || !resident_frame_[1])
+    return initial_.Fail("no frames on the device (AllocateResidentFrames and UploadResidentFrames first)");
+  if (params.start != kSubsetZero && params.start != kSubsetNodes && params.start != kSubsetFlow)
+    return initial_.Fail("subset correlation: the start is zero, the node table or the flow");
+  if (params.start == kSubsetNodes && match_nodes_.empty()) return initial_.Fail("no node table is held (BlockMatch first)");
+  if (params.start == kSubsetFlow && !result_flow_[0]) return initial_.Fail("no flow is held on the device (ComputeFlowResident first)");
+  const f3d_size4 c = Container();
+  f3d_subset_match_grid grid;
+  std::string why;
+  if (!LayoutSubsetMatch(c.width, c.height, c.depth, params.step, params.window, &grid, &why)) return initial_.Fail(why.c_str());
+  const size_t nx = grid.nx, ny = grid.ny, nz = grid.nz, nodes = nx * ny * nz;
+
+  // the held flow at the node voxels: one plane per node plane and component
+  std::vector<float> at_nodes[3];
+  if (result_flow_[0]) {
+    std::vector<float> plane(c.width * c.height);
+    for (int i = 0; i < 3; ++i) {
+      at_nodes[i].resize(nodes);
+      for (size_t k = 0; k < nz; ++k) {
+        const size_t z = static_cast<size_t>(grid.oz) + k * grid.step;
+        if (!initial_.Check(CheckDeviceError(f3d_copy3d_d2h(plane.data(), c.width, c.height, 1, result_flow_[i], c.pitch, c.height, z))))
+          return false;
+        for (size_t j = 0; j < ny; ++j)
+          for (size_t n = 0; n < nx; ++n)
+            at_nodes[i][(k * ny + j) * nx + n] = plane[(grid.oy + j * grid.step) * c.width + grid.ox + n * grid.step];
+      }
+    }
+  }
+  std::vector<double> start;
+  if (params.start != kSubsetZero) {
+    start.assign(nodes * 12, 0.0);
+    const f3d_block_match_grid& m = match_grid_;
+    auto nearest = [](int x, int origin, int step, int count) {  // the node nearest to x, the lower of two equally near
+      const int below = x <= origin ? 0 : (x - origin) / step;
+      const int i = below >= count - 1 ? count - 1 : ((x - origin) - below * step) * 2 > step ? below + 1 : below;
+      return static_cast<size_t>(i);
+    };
+    size_t at = 0;
+    for (size_t k = 0; k < nz; ++k)
+      for (size_t j = 0; j < ny; ++j)
+        for (size_t n = 0; n < nx; ++n, ++at) {
+          float v[3];
+          if (params.start == kSubsetFlow) {
+            for (int i = 0; i < 3; ++i) v[i] = at_nodes[i][at];
+          } else {
+            const size_t from = (nearest(grid.oz + static_cast<int>(k) * grid.step, m.oz, m.step, m.nz) * m.ny +
+                                 nearest(grid.oy + static_cast<int>(j) * grid.step, m.oy, m.step, m.ny)) * m.nx +
+                                nearest(grid.ox + static_cast<int>(n) * grid.step, m.ox, m.step, m.nx);
+            v[0] = match_nodes_[from].u;
+            v[1] = match_nodes_[from].v;
+            v[2] = match_nodes_[from].w;
+          }
+          for (int i = 0; i < 3; ++i) start[12 * at + 4 * i] = static_cast<double>(v[i]);
+        }
+  }
+  if (!initial_.Check(CheckDeviceError(f3d_set_container(&c)))) return false;
+  std::vector<f3d_subset_match_record> records(nodes);
+  std::vector<f3d_subset_match_node> rows(nodes);
+  const double reach = params.reach > 0.0 ? params.reach : static_cast<double>(params.window);
+  if (!initial_.Check(CheckDeviceError(f3d_subset_match(resident_frame_[0], resident_frame_[1], c.width, c.height, c.depth, &grid, params.model,
+                                                        start.empty() ? nullptr : start.data(), params.max_iterations, params.tolerance,
+                                                        reach, records.data(), info))))
+    return false;
+  const float* compare[3] = {at_nodes[0].data(), at_nodes[1].data(), at_nodes[2].data()};
+  if (!TableSubsetMatch(records.data(), &grid, params.min_zncc, result_flow_[0] ? compare : nullptr, rows.data(), summary, &why))
+    return initial_.Fail(why.c_str());
+  subset_grid_ = grid;
+  subset_records_.swap(records);
+  subset_nodes_.swap(rows);
+  return true;
 }
 
 // ---- derived fields of a displacement: strain, principal strain, inverse, match quality -------------------------------------------

@@ -193,6 +193,22 @@ class OpticalFlowE : public OpticalFlowBase {
   const std::vector<f3d_block_match_record>& BlockMatchRecords() const { return match_records_; }
   const std::vector<f3d_block_match_node>& BlockMatchNodes() const { return match_nodes_; }
   bool SetInitialFromNodes(f3d_validate_stats* validated, f3d_initial_info* info);
+  // Subset correlation on the resident pair (include/f3d_subset_match.h): f3d_subset_match on the grid
+  // f3d_subset_match_layout lays, on the library stream, then f3d_subset_match_table.  The start translations come from `start`
+  // (the start gradients are zero): kSubsetZero; kSubsetNodes, the block-match table the driver holds, each subset node taking the
+  // vector of the block-match node nearest to it per axis (the lower of two equally near), which is NaN unless that node is ok or
+  // edge; kSubsetFlow, the held flow read at the node voxels.  Whenever a flow is held, its values at the node voxels are the
+  // comparison of the table.  The records, the rows and the grid stay with the driver.  False with InitialFlowError() set.
+  enum SubsetStart { kSubsetZero = 0, kSubsetNodes = 1, kSubsetFlow = 2 };
+  struct SubsetMatchParams {
+    int step = 16, window = 8, model = F3D_SUBSET_AFFINE, max_iterations = 20, start = kSubsetZero;
+    double tolerance = 1e-3, reach = 0.0;  // reach 0: the window radius
+    double min_zncc = 0.8;
+  };
+  bool SubsetMatch(const SubsetMatchParams& params, f3d_subset_match_info* info, f3d_subset_match_summary* summary);
+  const f3d_subset_match_grid& SubsetMatchGrid() const { return subset_grid_; }
+  const std::vector<f3d_subset_match_record>& SubsetMatchRecords() const { return subset_records_; }
+  const std::vector<f3d_subset_match_node>& SubsetMatchNodes() const { return subset_nodes_; }
   // The three compute calls started from the initial flow that is held (use_initial) or, with use_initial false, exactly as their
   // namesakes above; false with InitialFlowError() set when use_initial is asked for and none is held.
   bool ComputeFlow(Data3D& frame_0, Data3D& frame_1, Data3D& flow_u, Data3D& flow_v, Data3D& flow_w, OperationParameters& params,
@@ -351,6 +367,9 @@ class OpticalFlowE : public OpticalFlowBase {
   f3d_block_match_grid match_grid_ = {};  // of the last BlockMatch; match_nodes_ empty: none yet
   std::vector<f3d_block_match_record> match_records_;
   std::vector<f3d_block_match_node> match_nodes_;
+  f3d_subset_match_grid subset_grid_ = {};  // of the last SubsetMatch; subset_nodes_ empty: none yet
+  std::vector<f3d_subset_match_record> subset_records_;
+  std::vector<f3d_subset_match_node> subset_nodes_;
   FieldSet derived_[kDerivedCount];
   // the gradient of kWindowPrincipal and kWindowPolar (G00 .. G22), never downloaded
   DevicePtr window_gradient_[9] = {};

@@ -16,6 +16,7 @@
 
 #include "f3d.h"
 #include "f3d_block_match.h"
+#include "f3d_subset_match.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -622,6 +623,61 @@ int f3d_flow_block_match(f3d_flow flow, int step, int window, int rx, int ry, in
                          f3d_block_match_summary* summary);
 int f3d_flow_block_match_rows(f3d_flow flow, size_t capacity, f3d_block_match_record* records, f3d_block_match_node* nodes);
 int f3d_flow_initial_from_nodes(f3d_flow flow, f3d_validate_stats* validated, f3d_initial_info* info);
+
+/* The table of the records of f3d_subset_match (include/f3d_subset_match.h): one row per node.  Host code, no device
+ * needed.  status is the record's, but a record that is OK with not zncc >= min_zncc is F3D_SUBSET_NODE_LOW.  position, iterations
+ * and zncc are the node's and the record's.  u, v, w = (float)p[0], p[4], p[8] and grad = (float) of ux, uy, uz, vx, ..., wz when
+ * the status is OK, NaN otherwise.  compare (nullable) points to three float32 arrays of nx ny nz node values, a displacement to hold
+ * against: diff[k] = (float)((double)compare[k][node] - (double)(u, v, w)[k]), NaN without compare.
+ * Summary: status[] counts the rows per status; median_zncc is over the records that are OK (before the LOW test); compared counts
+ * the OK rows whose three differences are not NaN, and over their lengths sqrt((d0 d0 + d1 d1) + d2 d2), binary64, every operation
+ * rounded on its own: rms = sqrt((the squares added in node order) / compared), median and p95.  Of m sorted values the median is
+ * the one at (m - 1) / 2 and the 95 % quantile the one at (95 m + 99) / 100 - 1 (integer arithmetic); NaN when m = 0.
+ * Returns non-zero (f3d_host_last_error() set, nothing written) for a null records, grid or nodes, a grid f3d_subset_match refuses
+ * on its own numbers (step, counts, window; a node below 0 or beyond 2^30), or a NaN min_zncc. */
+#define F3D_SUBSET_NODE_LOW 9
+#define F3D_SUBSET_NODE_STATUS_COUNT 10
+typedef struct f3d_subset_match_node {
+  int position[3];
+  int status;
+  int iterations;
+  int reserved; /* 0 */
+  double zncc;
+  float u, v, w;
+  float grad[9];
+  float diff[3];
+  int reserved2; /* 0 */
+} f3d_subset_match_node;
+typedef struct f3d_subset_match_summary {
+  unsigned long long nodes;
+  unsigned long long status[F3D_SUBSET_NODE_STATUS_COUNT]; /* they add up to nodes */
+  unsigned long long compared;
+  double median_zncc;
+  double rms, median, p95; /* of |compare - subset| */
+} f3d_subset_match_summary;
+/* The grid subset correlation lays over a width x height x depth volume, as f3d_block_match_layout does with one voxel more to each
+ * face (the central differences): with reach = window + 1 and room = n - 1 - 2 reach per axis of n voxels, the first node lies at
+ * reach + (room % step) / 2 and there are (n - 1 - reach - first) / step + 1 of them.  Non-zero (nothing written) for a null grid, a
+ * step below 1, a window outside 1 .. 8, a window that leaves the volume, or more than 2^22 nodes. */
+int f3d_subset_match_layout(size_t width, size_t height, size_t depth, int step, int window, f3d_subset_match_grid* grid);
+int f3d_subset_match_table(const f3d_subset_match_record* records, const f3d_subset_match_grid* grid, double min_zncc,
+                           const float* const* compare /* nullable: three arrays */, f3d_subset_match_node* nodes /* nx ny nz entries */,
+                           f3d_subset_match_summary* summary /* nullable */);
+/* Subset correlation on the pair the driver holds (f3d_flow_upload): f3d_subset_match_layout over the driver's volume,
+ * f3d_subset_match of the resident frames 0 and 1 on the library stream, then f3d_subset_match_table.  start says where the start
+ * translations come from (the start gradients are zero): F3D_SUBSET_START_ZERO; F3D_SUBSET_START_NODES, the block-match table the
+ * driver holds (f3d_flow_block_match first), each subset node taking u, v, w of the block-match node nearest to it per axis (the
+ * lower of two equally near), NaN unless that node is ok or edge; F3D_SUBSET_START_FLOW, the held flow read at the node voxels.
+ * Whenever the driver holds a flow, its values at the node voxels are the table's comparison.  reach 0 means the window radius.
+ * grid, info, summary are nullable.  The records and rows stay with the driver; f3d_flow_subset_match_rows copies them out (each
+ * nullable, room for `capacity` nodes).  A device library without f3d_subset_match still loads; then the call fails with a
+ * message naming it. */
+#define F3D_SUBSET_START_ZERO 0
+#define F3D_SUBSET_START_NODES 1
+#define F3D_SUBSET_START_FLOW 2
+int f3d_flow_subset_match(f3d_flow flow, int step, int window, int model, int start, int max_iterations, double tolerance, double reach,
+                          double min_zncc, f3d_subset_match_grid* grid, f3d_subset_match_info* info, f3d_subset_match_summary* summary);
+int f3d_flow_subset_match_rows(f3d_flow flow, size_t capacity, f3d_subset_match_record* records, f3d_subset_match_node* nodes);
 /* message of this thread's last call that failed in the host library itself; f3d_last_error() when there is none */
 const char* f3d_host_last_error(void);
 int f3d_flow_destroy(f3d_flow flow);
